@@ -8,6 +8,8 @@ oracle timed beside it.
     python bench.py --gpus N --steps K --warmup W     # N > 1: starts N rank processes itself (torch.distributed.run), or
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # ... is started by a launcher, one rank per GPU
+    python bench.py --steps K --dump-outputs DIR      # also writes the last timed step's results as DIR/<name>.npy (fixed
+                                                      # seeds: the same arguments give the same inputs, build against build)
 
 A step = zero_grad -> forward -> KLDiv -> backward -> (RCCL all-reduce of the flat gradient arena, in two buckets overlapped
 with the early stages' backward) -> fused AdamW over one B=64 batch per rank, inputs resident in HBM, replayed from hipGraphs
@@ -50,7 +52,27 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying captured hipGraphs")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32-storage legs (training step and Grad-CAM sweep of the parity-grade path)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, log-probabilities) and the parameters "
+                         "and BatchNorm statistics it left behind as DIR/<name>.npy (float32; rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(path, loss, out, model):
+    """The timed path's results after its last step, copied to the host: the (loss, log-probabilities) pair the step returns and
+    the model state it updated in place (every parameter and floating-point buffer).  2.0 M parameters: ~8 MB in all."""
+    arrays = {"loss": loss, "log_probs": out}
+    arrays.update(("param." + n, p) for n, p in model.named_parameters())
+    arrays.update(("buffer." + n, b) for n, b in model.named_buffers() if b.is_floating_point())
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(path, exist_ok=True)
+    import numpy as np
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def conv_work(bx, dtype_bytes):
@@ -266,12 +288,14 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, out = step()
     sync()
     if world > 1:
         dist.barrier()
     elapsed = all_max(time.perf_counter() - t0)
     loss_val = float(loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, out, model)      # before anything below steps the model again
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
 

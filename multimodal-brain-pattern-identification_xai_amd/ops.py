@@ -163,6 +163,9 @@ _SEED = {}
 
 def seed_state(device, lane: str = "spec") -> torch.Tensor:
     """Dropout counter of a (device, lane); the EEG branch has its own lane because it runs on its own stream."""
+    if device.type != "cuda":
+        # refused before anything is cached or launched: the seed kernels would otherwise dereference host memory
+        raise RuntimeError(f"brainxai: dropout seeds live on the GPU (got {device}); this package has no CPU path")
     key = (device.index if device.index is not None else torch.cuda.current_device(), lane)
     st = _SEED.get(key)
     if st is None:

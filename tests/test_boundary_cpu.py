@@ -4,6 +4,7 @@ import ctypes
 import json
 import os
 import re
+from types import SimpleNamespace
 
 import pytest
 import torch
@@ -62,12 +63,27 @@ def test_state_dict_layout_matches_reference():
     assert sum(p.numel() for p in nets["MultimodalModel(bench)"].parameters()) == 2025074
 
 
-def test_product_refuses_cpu_tensors():
+def test_product_refuses_cpu_tensors(monkeypatch):
+    """...before any library entry point is reached: on a machine with a GPU a launcher handed host pointers would fault the device.
+    The library is replaced by a recorder (nothing reaches the real one), and device and stream lookups succeed as they do where
+    a GPU is, so that the check means the same on a machine without one."""
+    reached = []
+
+    class Recorder:
+        def __getattr__(self, name):
+            def call(*args):
+                reached.append(name)
+                raise RuntimeError(f"{name} called")
+            return call
+    monkeypatch.setattr(_lib, "load", lambda: Recorder())
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: SimpleNamespace(cuda_stream=0))
     net = brainxai.build_multimodal(19, 2000, 4)
     with pytest.raises(RuntimeError, match="GPU|CUDA|cuda"):
         net(torch.zeros(1, 1, 19, 2000), torch.zeros(1, 4, 32, 64))
     with pytest.raises(RuntimeError):
         brainxai.stack_eeg(torch.zeros(1, 10000, 19))
+    assert reached == [], f"library entry points reached with CPU tensors: {reached}"
 
 
 def test_product_does_not_import_oracle():
