@@ -308,6 +308,25 @@ int bx_eeg_features_fwd(const bxEegDesc* d, const bxEegParams* p, const float* x
 int bx_eeg_features_bwd(const bxEegDesc* d, const bxEegParams* p, const float* x, const float* dfeat,
                         const uint64_t* seed, const void* saved, const bxEegGrads* g, float* dx,
                         void* workspace, size_t workspace_bytes, bxStream stream);
+/* Byte offsets, inside the saved arena of the tuned family (F1=8, D=2, F2=16, K2=16, K1 <= 64, Chans <= 64, T <= 15000), of the
+ * depthwise output dmap fp32 [B,F1*D,T] and the separable output smap fp32 [B,F2,T/P1] (both before their BatchNorm).
+ * BX_EUNSUPPORTED for any other geometry. */
+int bx_eeg_saved_layout(const bxEegDesc* d, size_t* off_dmap, size_t* off_smap);
+
+/* Grad-CAM on the EEGNet branch (canonical Grad-CAM; target = the module whose output a forward hook would see). */
+enum { BX_EEG_CAM_CONV1 = 0, BX_EEG_CAM_DEPTHWISE = 1, BX_EEG_CAM_SEPARABLE = 2 };
+/* 0 = unsupported (geometry outside the tuned family, maps_per_act outside [1,64], unknown target). */
+size_t bx_eeg_gradcam_workspace(const bxEegDesc* d, int maps_per_act, int target);
+/* saved: the arena of bx_eeg_features_fwd of the same x in evaluation mode (d->training = 0).  dfeat fp32 [B*nm, F2*T2]: the
+ * gradient of each map's class score with respect to feat (nm = maps_per_act maps per sample, map = sample * nm + class).
+ * Outputs (fp32; cam ReLU'd iff relu, raw the pre-ReLU map and may be NULL, weights may be NULL):
+ *   BX_EEG_CAM_CONV1:     cam / raw [B*nm, Chans, T],  weights [B*nm, F1]   (reads x fp32 [B,1,Chans,T]; needs the workspace)
+ *   BX_EEG_CAM_DEPTHWISE: cam / raw [B*nm, T],         weights [B*nm, F1*D]
+ *   BX_EEG_CAM_SEPARABLE: cam / raw [B*nm, T/P1],      weights [B*nm, F2]
+ * BX_EUNSUPPORTED (before touching any pointer) for a geometry outside the tuned family. */
+int bx_eeg_gradcam(const bxEegDesc* d, const bxEegParams* p, const float* x, const void* saved, const float* dfeat,
+                   int maps_per_act, int target, int relu, float* cam, float* raw, float* weights, void* workspace,
+                   size_t workspace_bytes, bxStream stream);
 
 /* ---- EEGNetAttentionDeep head (M:136-235, Attention M:109-134): everything after EEGNet's block 2 ----------
  * feat fp32 [B, F2*T2] (bx_eeg_features_fwd's output for the same input; the class's dropout2 is applied there)

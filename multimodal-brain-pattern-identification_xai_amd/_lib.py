@@ -17,6 +17,7 @@ BX_ALGO_AUTO, BX_ALGO_DIRECT, BX_ALGO_MFMA = 0, 1, 2
 BX_EPI_RELU = 1
 BX_EPI_MASK_BITS = 2
 BX_TAIL_SYNC_WORDS = 8192
+BX_EEG_CAM_CONV1, BX_EEG_CAM_DEPTHWISE, BX_EEG_CAM_SEPARABLE = 0, 1, 2
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -112,6 +113,9 @@ SIGNATURES = {
     "bx_eeg_workspace": (sz, [P(EegDesc)]),
     "bx_eeg_features_fwd": (i32, [P(EegDesc), P(EegParams), vp, vp, vp, vp, vp, sz, vp]),
     "bx_eeg_features_bwd": (i32, [P(EegDesc), P(EegParams), vp, vp, vp, vp, P(EegGrads), vp, vp, sz, vp]),
+    "bx_eeg_saved_layout": (i32, [P(EegDesc), P(sz), P(sz)]),
+    "bx_eeg_gradcam_workspace": (sz, [P(EegDesc), i32, i32]),
+    "bx_eeg_gradcam": (i32, [P(EegDesc), P(EegParams), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "bx_eeg_deep_saved_bytes": (sz, [P(EegDeepDesc)]),
     "bx_eeg_deep_workspace": (sz, [P(EegDeepDesc)]),
     "bx_eeg_deep_fwd": (i32, [P(EegDeepDesc), P(EegDeepParams), vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -1,0 +1,304 @@
+// Grad-CAM on the EEG branch (EEGNet blocks 1-2, reference models.py:271-285) in evaluation mode, from the arena that
+// bx_eeg_features_fwd saved for the same input: the depthwise output dmap [B,16,T], the separable output smap [B,16,T1] and the
+// three BatchNorms' scale s / shift h.  phi = dy_c/dfeat [F2,T2] per map (map m = sample * nm + class).  Per map:
+//   Gs[o,t]  = s3[o] ELU'(s3[o] smap[o,t] + h3[o]) phi[o,t/P2] / P2          (t < T2*P2, else 0)
+//   Gp1[q,t] = sum_o sum_j ws[o,q,j] Gs[o,t-j+7]                              (K2 = 16 'same': left pad 7)
+//   Gd[q,t]  = s2[q] ELU'(s2[q] dmap[q,t] + h2[q]) Gp1[q,t/P1] / P1           (t < T1*P1, else 0)
+// separableConv: w[o] = mean_t Gs[o,t], map = sum_o w[o] smap[o]
+// depthwiseConv: w[q] = mean_t Gd[q,t], map = sum_q w[q] dmap[q]
+// conv1:         w[f] = s1[f]/(Chans T) sum_{q in f} (sum_ch wd[q,ch]) (sum_t Gd[q,t]); BatchNorm1 is affine in evaluation mode, so
+//                sum_f w[f] conv1_f(x) is ONE K1-tap filter kappa = sum_f w[f] k1[f] over the input: the [B,F1,Chans,T] conv1
+//                output is never formed.
+// Only sum_t Gd[q,t] is needed, and it folds the pooling: sum_t Gd[q,t] = sum_t1 Gp1[q,t1] (s2[q]/P1) sum_p ELU'(..dmap[q,P1 t1+p]..).
+#include "eeg_internal.h"
+
+#define CAM_TT 256           // pooled time steps per tile of k_eeg_cam_back (one per thread)
+#define CAM_GP (CAM_TT + 16) // Gs tile row: index i <-> t = t0 - 8 + i (i < CAM_TT + 15 is read)
+#define CAM1_TT 1024         // time steps per workgroup of k_eeg_cam_conv1 (4 per thread)
+#define CAM_MAX_NM 64        // maps per sample (classes) one call serves
+
+// 16 per-thread sums -> out[k] = scale * block total (fixed order: DPP wave sums, then the four waves in order).  256 threads.
+__device__ __forceinline__ void cam_block_sum16(const float (&acc)[16], float* red, float* out, float scale) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const float s = wave_sum(acc[k]);
+    if (lane == 0) red[wave * 16 + k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    const int k = threadIdx.x;
+    out[k] = ((red[k] + red[16 + k]) + (red[32 + k] + red[48 + k])) * scale;
+  }
+  __syncthreads();
+}
+
+// separableConv target: one workgroup per map.
+__global__ __launch_bounds__(256) void k_eeg_cam_sep(const float* __restrict__ smap, EegStats st, const float* __restrict__ dfeat,
+                                                     float* __restrict__ cam, float* __restrict__ raw, float* __restrict__ wout, EegGeom g,
+                                                     int nm, int relu) {
+  __shared__ float red[64], sw[16], ssc[16], ssh[16];
+  const int m = blockIdx.x, b = m / nm, tid = threadIdx.x;
+  if (tid < 16) { ssc[tid] = st.sc3[tid]; ssh[tid] = st.sh3[tid]; }
+  __syncthreads();
+  const int T1 = g.T1, T2 = g.T2, P2 = g.P2, TP = T2 * P2;
+  const float* sb = smap + (size_t)b * 16 * T1;
+  const float* phi = dfeat + (size_t)m * 16 * T2;
+  float acc[16];
+#pragma unroll
+  for (int o = 0; o < 16; ++o) acc[o] = 0.f;
+  for (int t = tid; t < TP; t += 256) {
+    const int tq = t / P2;
+#pragma unroll
+    for (int o = 0; o < 16; ++o) {
+      const float a = ssc[o], z = fmaf(a, sb[(size_t)o * T1 + t], ssh[o]);
+      acc[o] = fmaf(z > 0.f ? a : a * expf(z), phi[o * T2 + tq], acc[o]);
+    }
+  }
+  cam_block_sum16(acc, red, sw, 1.f / ((float)P2 * (float)T1));
+  if (wout && tid < 16) wout[(size_t)m * 16 + tid] = sw[tid];
+  for (int t = tid; t < T1; t += 256) {
+    float s = 0.f;
+#pragma unroll
+    for (int o = 0; o < 16; ++o) s = fmaf(sw[o], sb[(size_t)o * T1 + t], s);
+    if (raw) raw[(size_t)m * T1 + t] = s;
+    cam[(size_t)m * T1 + t] = relu ? fmaxf(s, 0.f) : s;
+  }
+}
+
+// depthwiseConv (TGT 1) and conv1 (TGT 0) targets: one workgroup per map.  The pooled axis is walked in tiles of CAM_TT steps: the
+// tile's Gs (plus the 15-step halo of the 16-tap transposed convolution) is formed in LDS, a thread forms Gp1[0..15] of its step
+// (wave-uniform 16-byte weight reads: one Gs read + 4 weight reads per 16 FMAs) and folds it with the pooled ELU' of dmap into its
+// running sum_t Gd.  Depthwise target: a second pass writes the map; conv1 target: writes w[f] and the combined kernel kappa.
+template <int TGT>
+__global__ __launch_bounds__(256) void k_eeg_cam_back(const float* __restrict__ dmap, const float* __restrict__ smap, EegStats st,
+                                                      const float* __restrict__ dfeat, const float* __restrict__ ws, const float* __restrict__ wd,
+                                                      const float* __restrict__ w1, float* __restrict__ cam, float* __restrict__ raw,
+                                                      float* __restrict__ wout, float* __restrict__ kappa, int K1p, EegGeom g, int nm, int relu) {
+  __shared__ __attribute__((aligned(16))) float sW[16 * 16 * 16];   // [o][j][q] <- separableConv.weight [o][q][1][j]
+  __shared__ float sG[16 * CAM_GP];
+  __shared__ float red[64], sS[16], sc[4][16], swf[16];              // sc: s3, h3, s2, h2
+  const int m = blockIdx.x, b = m / nm, tid = threadIdx.x;
+  lds_fill<16>(sW, 4096, [&](int i) { const int q = i & 15, j = (i >> 4) & 15, o = i >> 8; return ws[(o * 16 + q) * 16 + j]; });
+  if (tid < 16) { sc[0][tid] = st.sc3[tid]; sc[1][tid] = st.sh3[tid]; sc[2][tid] = st.sc2[tid]; sc[3][tid] = st.sh2[tid]; }
+  const int T = g.T, T1 = g.T1, T2 = g.T2, P1 = g.P1, P2 = g.P2, TP2 = T2 * P2;
+  const float* sb = smap + (size_t)b * 16 * T1;
+  const float* db = dmap + (size_t)b * 16 * T;
+  const float* phi = dfeat + (size_t)m * 16 * T2;
+  const float inv_p2 = 1.f / (float)P2, inv_p1 = 1.f / (float)P1;
+  const bool vec4 = P1 == 4 && T % 4 == 0;                             // dmap rows 16-byte aligned (the arena region is)
+  float accS[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) accS[q] = 0.f;
+  for (int t0 = 0; t0 < T1; t0 += CAM_TT) {
+    __syncthreads();                // first trip: sW / sc staged; later trips: the previous tile's readers are done
+    // 16 * CAM_GP = 17 * 256: all 17 of a thread's smap / phi loads are issued before the first use (clamped, then masked)
+    lds_fill<17>(sG, 16 * CAM_GP, [&](int i) {
+      const int o = i / CAM_GP, k = i - o * CAM_GP, t = t0 - 8 + k;
+      const bool ok = t >= 0 && t < TP2 && k < CAM_TT + 15;
+      const int tc = ok ? t : 0;
+      const float a = sc[0][o], z = fmaf(a, sb[(size_t)o * T1 + tc], sc[1][o]);
+      const float v = (z > 0.f ? a : a * expf(z)) * phi[o * T2 + tc / P2] * inv_p2;
+      return ok ? v : 0.f;
+    });
+    const int t = t0 + tid;
+    // this step's 16 x P1 dmap values, requested before the FMA loop below (one 16-byte load per row when P1 = 4)
+    float e2[16];
+    if (t < T1) {
+      if (vec4) {
+        float4 dv[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) dv[q] = *reinterpret_cast<const float4*>(db + (size_t)q * T + (size_t)t * 4);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float a = sc[2][q], h = sc[3][q];
+          const float d4[4] = {dv[q].x, dv[q].y, dv[q].z, dv[q].w};
+          float e = 0.f;
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            const float z = fmaf(a, d4[p], h);
+            e += z > 0.f ? 1.f : expf(z);
+          }
+          e2[q] = e * a * inv_p1;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float a = sc[2][q], h = sc[3][q];
+          const float* dr = db + (size_t)q * T + (size_t)t * P1;
+          float e = 0.f;
+          for (int p = 0; p < P1; ++p) {
+            const float z = fmaf(a, dr[p], h);
+            e += z > 0.f ? 1.f : expf(z);
+          }
+          e2[q] = e * a * inv_p1;
+        }
+      }
+    }
+    __syncthreads();
+    if (t < T1) {
+      float gp[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) gp[q] = 0.f;
+      for (int o = 0; o < 16; ++o) {
+        const float* gr = sG + o * CAM_GP + tid;                      // gr[15 - j] <-> Gs[o, t - j + 7]
+        const float4* wr = reinterpret_cast<const float4*>(sW + o * 256);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const float gv = gr[15 - j];
+#pragma unroll
+          for (int qq = 0; qq < 4; ++qq) {
+            const float4 w4 = wr[j * 4 + qq];
+            gp[4 * qq + 0] = fmaf(w4.x, gv, gp[4 * qq + 0]);
+            gp[4 * qq + 1] = fmaf(w4.y, gv, gp[4 * qq + 1]);
+            gp[4 * qq + 2] = fmaf(w4.z, gv, gp[4 * qq + 2]);
+            gp[4 * qq + 3] = fmaf(w4.w, gv, gp[4 * qq + 3]);
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 16; ++q) accS[q] = fmaf(gp[q], e2[q], accS[q]);
+    }
+  }
+  __syncthreads();
+  cam_block_sum16(accS, red, sS, 1.f);                                  // sS[q] = sum_t Gd[q,t]
+  if (TGT == 1) {
+    if (tid < 16) {
+      swf[tid] = sS[tid] / (float)T;
+      if (wout) wout[(size_t)m * 16 + tid] = swf[tid];
+    }
+    __syncthreads();
+    for (int t = tid; t < T; t += 256) {
+      float s = 0.f;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) s = fmaf(swf[q], db[(size_t)q * T + t], s);
+      if (raw) raw[(size_t)m * T + t] = s;
+      cam[(size_t)m * T + t] = relu ? fmaxf(s, 0.f) : s;
+    }
+  } else {
+    const int Ch = g.Ch, D = g.D;
+    if (tid < g.F1) {
+      const int f = tid;
+      float s = 0.f;
+      for (int d = 0; d < D; ++d) {
+        const int q = f * D + d;
+        float c = 0.f;
+        for (int ch = 0; ch < Ch; ++ch) c += wd[(size_t)q * Ch + ch];
+        s = fmaf(c, sS[q], s);
+      }
+      swf[f] = st.sc1[f] * s / ((float)Ch * (float)T);
+      if (wout) wout[(size_t)m * g.F1 + f] = swf[f];
+    }
+    __syncthreads();
+    for (int j = tid; j < K1p; j += 256) {
+      float k = 0.f;
+      if (j < g.K1)
+        for (int f = 0; f < g.F1; ++f) k = fmaf(swf[f], w1[(size_t)f * g.K1 + j], k);
+      kappa[(size_t)m * K1p + j] = k;                                   // zero beyond K1: the FIR below runs K1p taps
+    }
+  }
+}
+
+// conv1 map: raw[m,ch,t] = sum_j kappa[m,j] x[b,ch,t+j-padl1] for the nm maps of sample b.  grid (T / CAM1_TT, Chans, B): the
+// x row tile plus its K1p+4 halo is read into LDS once and serves every map; a thread produces 4 consecutive steps with a sliding
+// window (one 16-byte LDS read and one wave-uniform 16-byte kappa read per 16 FMAs) and writes them with one 16-byte store.
+__global__ __launch_bounds__(256) void k_eeg_cam_conv1(const float* __restrict__ x, const float* __restrict__ kappa, float* __restrict__ cam,
+                                                       float* __restrict__ raw, int Ch, int T, int K1p, int padl, int nm, int relu, int vec) {
+  extern __shared__ __attribute__((aligned(16))) float sx[];          // [CAM1_TT + K1p + 4]: sx[k] <-> x[t0 - padl + k] (0 outside [0, T))
+  const int t0 = blockIdx.x * CAM1_TT, ch = blockIdx.y, b = blockIdx.z;
+  const float* xr = x + ((size_t)b * Ch + ch) * T;
+  lds_fill<5>(sx, CAM1_TT + K1p + 4, [&](int k) { const int t = t0 - padl + k; return (t >= 0 && t < T) ? xr[t] : 0.f; });
+  __syncthreads();
+  const int tl = 4 * threadIdx.x, tt = t0 + tl;
+  if (tt >= T) return;
+  for (int mm = 0; mm < nm; ++mm) {
+    const size_t m = (size_t)b * nm + mm;
+    const float* kp = kappa + m * K1p;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    float4 cur = *reinterpret_cast<const float4*>(sx + tl);
+    for (int j0 = 0; j0 < K1p; j0 += 4) {
+      const float4 nxt = *reinterpret_cast<const float4*>(sx + tl + j0 + 4);
+      const float4 k4 = *reinterpret_cast<const float4*>(kp + j0);
+      const float win[8] = {cur.x, cur.y, cur.z, cur.w, nxt.x, nxt.y, nxt.z, nxt.w};
+      const float kk[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fmaf(kk[u], win[u + i], acc[i]);
+      cur = nxt;
+    }
+    const size_t o = (m * Ch + ch) * T + tt;
+    if (vec && tt + 3 < T) {
+      if (raw) *reinterpret_cast<float4*>(raw + o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      if (relu) for (int i = 0; i < 4; ++i) acc[i] = fmaxf(acc[i], 0.f);
+      *reinterpret_cast<float4*>(cam + o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+      for (int i = 0; i < 4 && tt + i < T; ++i) {
+        if (raw) raw[o + i] = acc[i];
+        cam[o + i] = relu ? fmaxf(acc[i], 0.f) : acc[i];
+      }
+    }
+  }
+}
+
+static int cam_k1p(const EegGeom& g) { return (g.K1 + 3) / 4 * 4; }
+
+extern "C" size_t bx_eeg_gradcam_workspace(const bxEegDesc* d, int maps_per_act, int target) {
+  EegGeom g;
+  if (!d || !eeg_tuned(d, &g) || maps_per_act < 1 || maps_per_act > CAM_MAX_NM || target < BX_EEG_CAM_CONV1 || target > BX_EEG_CAM_SEPARABLE)
+    return 0;
+  return bx_align_up((size_t)g.B * maps_per_act * cam_k1p(g) * sizeof(float), 256);   // conv1 target: the combined kernels kappa
+}
+
+extern "C" int bx_eeg_saved_layout(const bxEegDesc* d, size_t* off_dmap, size_t* off_smap) {
+  BX_REQUIRE(d && off_dmap && off_smap, "bx_eeg_saved_layout: null pointer");
+  EegGeom g;
+  if (!eeg_tuned(d, &g)) BX_FAIL(BX_EUNSUPPORTED, "bx_eeg_saved_layout: EEG geometry outside the tuned family");
+  *off_dmap = g.off_d;
+  *off_smap = g.off_s;
+  return BX_OK;
+}
+
+extern "C" int bx_eeg_gradcam(const bxEegDesc* d, const bxEegParams* p, const float* x, const void* saved, const float* dfeat, int maps_per_act,
+                              int target, int relu, float* cam, float* raw, float* weights, void* workspace, size_t workspace_bytes,
+                              bxStream stream) {
+  BX_REQUIRE(d, "bx_eeg_gradcam: null descriptor");
+  EegGeom g;
+  if (!eeg_tuned(d, &g))
+    BX_FAIL(BX_EUNSUPPORTED, "bx_eeg_gradcam: EEG geometry outside the tuned family (needs F1=8, D=2, F2=16, K2=16, kernLength <= %d, "
+            "Chans <= %d, T <= %d)", EEG_MAXK, EEG_MAXCH, EEG_MAXT);
+  BX_REQUIRE(p && p->sep_w && p->dw_w && p->conv1_w && saved && dfeat && cam, "bx_eeg_gradcam: null pointer");
+  BX_REQUIRE(target >= BX_EEG_CAM_CONV1 && target <= BX_EEG_CAM_SEPARABLE, "bx_eeg_gradcam: unknown target %d", target);
+  BX_REQUIRE(!d->training, "bx_eeg_gradcam: needs the arena of an evaluation-mode forward (training = 0)");
+  BX_REQUIRE(maps_per_act >= 1 && maps_per_act <= CAM_MAX_NM, "bx_eeg_gradcam: maps_per_act %d outside [1, %d]", maps_per_act, CAM_MAX_NM);
+  BX_REQUIRE(g.B <= 65535 && (long long)g.B * maps_per_act <= (1ll << 30), "bx_eeg_gradcam: batch %d too large", g.B);
+  hipStream_t s = (hipStream_t)stream;
+  const EegStats st = eeg_stats(g, const_cast<void*>(saved));
+  const float* dmap = (const float*)((const char*)saved + g.off_d);
+  const float* smap = (const float*)((const char*)saved + g.off_s);
+  const int n_maps = g.B * maps_per_act;
+  if (target == BX_EEG_CAM_SEPARABLE) {
+    hipLaunchKernelGGL(k_eeg_cam_sep, dim3(n_maps), dim3(256), 0, s, smap, st, dfeat, cam, raw, weights, g, maps_per_act, relu ? 1 : 0);
+    BX_CHECK_LAUNCH("bx_eeg_gradcam (separableConv)");
+    return BX_OK;
+  }
+  if (target == BX_EEG_CAM_DEPTHWISE) {
+    hipLaunchKernelGGL(k_eeg_cam_back<1>, dim3(n_maps), dim3(256), 0, s, dmap, smap, st, dfeat, p->sep_w, p->dw_w, p->conv1_w, cam, raw, weights,
+                       (float*)nullptr, 0, g, maps_per_act, relu ? 1 : 0);
+    BX_CHECK_LAUNCH("bx_eeg_gradcam (depthwiseConv)");
+    return BX_OK;
+  }
+  BX_REQUIRE(x, "bx_eeg_gradcam: the conv1 target reads the input x");
+  const size_t need = bx_eeg_gradcam_workspace(d, maps_per_act, target);
+  if (!workspace || workspace_bytes < need) BX_FAIL(BX_EWORKSPACE, "bx_eeg_gradcam: workspace %zu < %zu", workspace_bytes, need);
+  const int K1p = cam_k1p(g);
+  float* kappa = (float*)workspace;
+  hipLaunchKernelGGL(k_eeg_cam_back<0>, dim3(n_maps), dim3(256), 0, s, dmap, smap, st, dfeat, p->sep_w, p->dw_w, p->conv1_w, cam, raw, weights,
+                     kappa, K1p, g, maps_per_act, relu ? 1 : 0);
+  BX_CHECK_LAUNCH("bx_eeg_gradcam (conv1 weights)");
+  const int vec = g.T % 4 == 0 && ((uintptr_t)cam & 15) == 0 && ((uintptr_t)raw & 15) == 0;
+  hipLaunchKernelGGL(k_eeg_cam_conv1, dim3(bx_ceil_div(g.T, CAM1_TT), g.Ch, g.B), dim3(256), (size_t)(CAM1_TT + K1p + 4) * sizeof(float), s, x, kappa,
+                     cam, raw, g.Ch, g.T, K1p, g.padl1, maps_per_act, relu ? 1 : 0, vec);
+  BX_CHECK_LAUNCH("bx_eeg_gradcam (conv1 map)");
+  return BX_OK;
+}

@@ -9,6 +9,7 @@
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 import re
 
 import numpy as np
@@ -76,6 +77,89 @@ def resize_bilinear(maps: torch.Tensor, size) -> torch.Tensor:
 
 
 _TARGET = re.compile(r"^(?:spectrogram_model\.)?block([1-5])(?:\.conv([1-3]))?$")
+_EEG_TARGETS = {"conv1": L.BX_EEG_CAM_CONV1, "depthwiseConv": L.BX_EEG_CAM_DEPTHWISE, "separableConv": L.BX_EEG_CAM_SEPARABLE}
+_EEG_TARGET = re.compile(r"^(?:eeg_model\.)?(" + "|".join(_EEG_TARGETS) + r")$")
+
+
+def _eeg_head(em, f):
+    """The EEG branch after block 2 on the features f (EEGNet: dense + LogSoftmax; EEGNetAttentionDeep: its head)."""
+    if hasattr(em, "head"):
+        return em.head(f)
+    if f.shape[1] != em.dense.in_features:
+        raise RuntimeError(f"EEGNet: {f.shape[1]} features but dense expects {em.dense.in_features} (Samples mismatch)")
+    return ops.LinearLsmFn.apply(f, em.dense.weight, em.dense.bias)
+
+
+def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_parts):
+    """Grad-CAM at an EEGNet block-1/2 convolution (explain.grad_cam).  The EEG branch runs forward once without autograd, keeping
+    its saved arena; the rest of the model runs on a detached feature leaf, autograd gives dy_c/dfeat for each class seed; then ONE
+    bx_eeg_gradcam call does the backward to the target and the channel reduce (and for conv1 the combined-kernel FIR over x)."""
+    from .models import EEGNet, EEGNetAttentionDeep
+    multimodal = hasattr(model, "eeg_model")
+    em = model.eeg_model if multimodal else model
+    if not isinstance(em, (EEGNet, EEGNetAttentionDeep)):
+        raise ValueError(f"EEG Grad-CAM needs an EEGNet / EEGNetAttentionDeep branch, got {type(em).__name__}")
+    if multimodal and spec is None:
+        raise ValueError("EEG Grad-CAM on a MultimodalModel needs the spectrogram input too")
+    if class_idx is None:
+        modes = [-1]
+    elif isinstance(class_idx, str):
+        if class_idx != "all":
+            raise ValueError(class_idx)
+        modes = None                                     # every class, once the output width is known
+    else:
+        modes = [int(class_idx)]
+    target = _EEG_TARGETS[layer]
+    lib = L.load()
+    g = em._geom
+    B, T = eeg.shape[0], eeg.shape[-1]
+    n_cls = model.fc2.out_features if multimodal else (em.dense2.out_features if hasattr(em, "dense2") else em.dense.out_features)
+    nm = n_cls if modes is None else 1
+    probe = L.EegDesc(B, eeg.shape[-2], T, g.F1, g.D, g.F2, g.K1, g.K2, g.P1, g.P2, 0, 1e-5, 0.1, 0.0, 0, L.BX_F32, 0, -1.0)
+    if lib.bx_eeg_gradcam_workspace(C.byref(probe), nm, target) == 0:
+        raise ValueError(f"EEG Grad-CAM supports the tuned EEGNet family only: F1=8, D=2, F2=16, K2=16, kernLength <= 64, Chans <= 64, "
+                         f"T <= 15000, at most 64 classes (got F1={g.F1}, D={g.D}, F2={g.F2}, kernLength={g.K1}, Chans={eeg.shape[-2]}, "
+                         f"T={T}, {nm} maps per sample)")
+    with _eval_frozen(model):
+        with torch.no_grad():
+            feat, saved, desc, params, x = ops.eeg_features_keep(em, eeg)
+            s_out = model.spectrogram_model(spec) if multimodal else None
+        f = feat.detach().requires_grad_(True)
+        with torch.enable_grad():
+            out = _eeg_head(em, f)
+            if multimodal:
+                out = ops.FusionHeadFn.apply(out, s_out, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
+        seeds = [_class_seed(out, c) for c in (range(out.shape[1]) if modes is None else modes)]
+        grads = [torch.autograd.grad(out, f, grad_outputs=sd, retain_graph=i + 1 < len(seeds))[0] for i, sd in enumerate(seeds)]
+        dfeat = (torch.stack(grads, dim=1).reshape(B * nm, -1) if nm > 1 else grads[0]).contiguous()
+        Ch, T1 = desc.Chans, T // g.P1
+        shape1, nw = {L.BX_EEG_CAM_CONV1: ((Ch, T), g.F1), L.BX_EEG_CAM_DEPTHWISE: ((1, T), g.F1 * g.D),
+                      L.BX_EEG_CAM_SEPARABLE: ((1, T1), g.F2)}[target]
+        dev = feat.device
+        cam = torch.empty(B * nm, *shape1, dtype=torch.float32, device=dev)
+        raw = torch.empty_like(cam) if (return_parts and relu) else None
+        wts = torch.empty(B * nm, nw, dtype=torch.float32, device=dev) if return_parts else None
+        ws = ops.workspace(lib.bx_eeg_gradcam_workspace(C.byref(desc), nm, target), dev)
+        L.check(lib.bx_eeg_gradcam(C.byref(desc), C.byref(params), _p(x), _p(saved), _p(dfeat), nm, target, 1 if relu else 0, _p(cam),
+                                   _p(raw), _p(wts), _p(ws), ws.numel(), _stream()), "bx_eeg_gradcam")
+        if raw is None:
+            raw = cam
+        A = None
+        if return_parts and target != L.BX_EEG_CAM_CONV1:
+            off_d, off_s = C.c_size_t(0), C.c_size_t(0)
+            L.check(lib.bx_eeg_saved_layout(C.byref(desc), C.byref(off_d), C.byref(off_s)), "bx_eeg_saved_layout")
+            if target == L.BX_EEG_CAM_DEPTHWISE:
+                A = saved[off_d.value:off_d.value + B * g.F1 * g.D * T * 4].view(torch.float32).reshape(B, g.F1 * g.D, 1, T).clone()
+            else:
+                A = saved[off_s.value:off_s.value + B * g.F2 * T1 * 4].view(torch.float32).reshape(B, g.F2, 1, T1).clone()
+        if upsample and target == L.BX_EEG_CAM_SEPARABLE:
+            cam = resize_bilinear(cam.reshape(B * nm, 1, T1), (1, T))
+    stacked = isinstance(class_idx, str)
+    def shape(t):
+        return t.reshape(B, nm, *t.shape[1:]) if stacked else t
+    if return_parts:
+        return shape(cam), shape(raw), shape(wts), A, out.detach()
+    return shape(cam)
 
 
 def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_parts):
@@ -292,13 +376,32 @@ def grad_cam(model, eeg, spec, target_layer="spectrogram_model.block5", class_id
     cam[b] = ReLU(sum_k w[b,k] A[b,k]); optionally bilinear-upsampled to the spectrogram's H x W.
 
     target_layer: 'spectrogram_model.blockN' (stage output) or 'spectrogram_model.blockN.convK'
-                  (that convolution's pre-ReLU output, i.e. what a hook on the reference's nn.Conv2d sees).
+                  (that convolution's pre-ReLU output, i.e. what a hook on the reference's nn.Conv2d sees);
+                  or an EEG-branch convolution (its output, before its BatchNorm; 'eeg_model.' is optional, and a
+                  stand-alone EEGNet / EEGNetAttentionDeep is called as grad_cam(net, eeg, None, 'conv1')):
+                    'eeg_model.conv1'          -> electrode x time maps [B, Chans, T]
+                    'eeg_model.depthwiseConv'  -> [B, 1, T]
+                    'eeg_model.separableConv'  -> [B, 1, T//4]; upsample=True resizes it to [B, 1, T] (bilinear)
+                  The conv1 and depthwiseConv maps are at input resolution already: `upsample` leaves them as they are.
+                  EEG targets need the tuned EEGNet family (F1=8, D=2, F2=16, kernLength <= 64, Chans <= 64,
+                  T <= 15000); other geometries raise ValueError.
     class_idx:    None -> each sample's arg-max class; int -> that class; 'all' -> every class, output
                   gains a class axis [B, n_classes, H, W].
+    return_parts: (cam, raw, weights, A, out).  For EEG targets weights is [B(, n_classes), channels of the target]
+                  and A the target's activation [B, channels, 1, time] -- None for conv1, whose [B, 8, Chans, T]
+                  output is never formed (in evaluation mode its map is one combined 1-D filter over the input).
+    The model's training mode and every parameter's requires_grad are restored on return.
     """
+    me = _EEG_TARGET.match(target_layer)
+    if me:
+        return _grad_cam_eeg(model, eeg, spec, me.group(1), class_idx, upsample, relu, return_parts)
+    if target_layer.startswith("eeg_model."):
+        raise ValueError(f"unsupported EEG Grad-CAM target {target_layer!r}; use one of "
+                         + ", ".join(f"'eeg_model.{k}'" for k in _EEG_TARGETS))
     m = _TARGET.match(target_layer)
     if not m:
-        raise ValueError(f"unsupported Grad-CAM target {target_layer!r}; use 'spectrogram_model.blockN[.convK]'")
+        raise ValueError(f"unsupported Grad-CAM target {target_layer!r}; use 'spectrogram_model.blockN[.convK]' or one of "
+                         + ", ".join(f"'eeg_model.{k}'" for k in _EEG_TARGETS))
     spec_model = model.spectrogram_model if hasattr(model, "spectrogram_model") else model
     blk = getattr(spec_model, f"block{m.group(1)}")
     conv_k = int(m.group(2)) if m.group(2) else 0

@@ -182,6 +182,10 @@ class EEGNet(nn.Module):
         self.salt = 100 | (0x80000000 if dropoutType == "Dropout2d" else 0)     # bit 31: channel-wise mask (nn.Dropout2d)
 
     def features(self, x, seed=None):
+        return ops.EegFeaturesFn.apply(*self._features_args(x, seed))
+
+    def _features_args(self, x, seed=None):
+        """The arguments of ops.EegFeaturesFn for input x (also what ops.eeg_features_keep launches with)."""
         if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != self.Chans:
             raise RuntimeError(f"EEGNet expected [B,1,{self.Chans},T], got {tuple(x.shape)}")
         g = self._geom
@@ -192,8 +196,8 @@ class EEGNet(nn.Module):
                               grad_mode=torch.is_grad_enabled())      # (inside an autograd Function's forward grad mode always reads False)
         bufs = (bn1.running_mean, bn1.running_var, bn1.num_batches_tracked, bn2.running_mean, bn2.running_var,
                 bn2.num_batches_tracked, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked)
-        return ops.EegFeaturesFn.apply(x, self.conv1.weight, bn1.weight, bn1.bias, self.depthwiseConv.weight, bn2.weight, bn2.bias,
-                                       self.separableConv.weight, bn3.weight, bn3.bias, bufs, cfg)
+        return (x, self.conv1.weight, bn1.weight, bn1.bias, self.depthwiseConv.weight, bn2.weight, bn2.bias,
+                self.separableConv.weight, bn3.weight, bn3.bias, bufs, cfg)
 
     def forward(self, x):
         feat = self.features(x)
@@ -260,6 +264,10 @@ class EEGNetAttentionDeep(nn.Module):
 
     def features(self, x):
         """Block 1-2 output after dropout2, flattened [B, F2 * (T//32)] (same kernels as EEGNet.features)."""
+        return ops.EegFeaturesFn.apply(*self._features_args(x))
+
+    def _features_args(self, x):
+        """The arguments of ops.EegFeaturesFn for input x (also what ops.eeg_features_keep launches with)."""
         if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != self.Chans:
             raise RuntimeError(f"EEGNetAttentionDeep expected [B,1,{self.Chans},T], got {tuple(x.shape)}")
         g = self._geom
@@ -271,11 +279,14 @@ class EEGNetAttentionDeep(nn.Module):
                               grad_mode=torch.is_grad_enabled())
         bufs = (bn1.running_mean, bn1.running_var, bn1.num_batches_tracked, bn2.running_mean, bn2.running_var,
                 bn2.num_batches_tracked, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked)
-        return ops.EegFeaturesFn.apply(x, self.conv1.weight, bn1.weight, bn1.bias, self.depthwiseConv.weight, bn2.weight, bn2.bias,
-                                       self.separableConv.weight, bn3.weight, bn3.bias, bufs, cfg)
+        return (x, self.conv1.weight, bn1.weight, bn1.bias, self.depthwiseConv.weight, bn2.weight, bn2.bias,
+                self.separableConv.weight, bn3.weight, bn3.bias, bufs, cfg)
 
     def forward(self, x):
-        feat = self.features(x)
+        return self.head(self.features(x))
+
+    def head(self, feat):
+        """Everything after block 2 (conv2 ... LogSoftmax) on the flattened block-2 features [B, F2 * (T//32)]."""
         g, bn4, att = self._geom, self.batchnorm4, self.attention_layer
         T2 = feat.shape[1] // g.F2
         if g.F3 * (T2 // g.P3) != self.dense1.in_features:

@@ -896,41 +896,58 @@ class KLDivFn(torch.autograd.Function):
         return out, None, None, None
 
 
+def _eeg_forward(x, c1w, bn1w, bn1b, dww, bn2w, bn2b, sepw, bn3w, bn3b, bufs, cfg, needs_input_grad):
+    """One bx_eeg_features_fwd launch (EegFeaturesFn.forward and eeg_features_keep): returns (x as read, feat, saved arena, desc,
+    params, seed).  ``needs_input_grad``: autograd's flags for (x, the nine parameters)."""
+    lib = L.load()
+    _require_gpu(x, "eeg input")
+    B, _, Ch, T = x.shape
+    x = x.contiguous().float()
+    # collapsed front end (no conv1 output tensor).  Training: only when nobody can ask for the input's gradient.  Evaluation
+    # mode (BatchNorm1 a fixed affine map): whenever no PARAMETER needs a gradient -- inference, Grad-CAM sweeps, saliency /
+    # integrated-gradients passes (the input gradient has a collapsed form too)
+    params_need_grad = getattr(cfg, "grad_mode", True) and any(needs_input_grad[1:10])      # under no_grad nobody does
+    collapse = 1 if EEG_COLLAPSE and ((cfg.training and not needs_input_grad[0]) or
+                                      (not cfg.training and not params_need_grad)) else 0
+    desc = L.EegDesc(B, Ch, T, cfg.F1, cfg.D, cfg.F2, cfg.K1, cfg.K2, cfg.P1, cfg.P2, 1 if cfg.training else 0, cfg.eps, cfg.momentum,
+                     float(cfg.dropout_p), cfg.salt, bx_dtype(cfg.dtype), collapse, float(getattr(cfg, "dropout_p2", -1.0)))
+    if INPUT_SLOTS and collapse and not cfg.training and not torch.is_grad_enabled() and cfg.K1 == 64:
+        desc.x_slot = _take_slot(x)                      # a graph input read through its device slot (GradCamSweep)
+    nsaved = lib.bx_eeg_saved_bytes(C.byref(desc))
+    if nsaved == 0:
+        raise RuntimeError("brainxai: EEGNet geometry outside the kernels' range (F1*D, F2 <= 1024, kernel lengths <= 4096, tensors below 2^31 elements)")
+    saved = torch.empty(nsaved, dtype=torch.uint8, device=x.device)
+    ws = workspace(lib.bx_eeg_workspace(C.byref(desc)), x.device)
+    params = L.EegParams(_p(c1w), _p(bn1w), _p(bn1b), _p(bufs[0]), _p(bufs[1]), _p(bufs[2]), _p(dww), _p(bn2w), _p(bn2b), _p(bufs[3]),
+                         _p(bufs[4]), _p(bufs[5]), _p(sepw), _p(bn3w), _p(bn3b), _p(bufs[6]), _p(bufs[7]), _p(bufs[8]))
+    T2 = (T // cfg.P1) // cfg.P2
+    feat = torch.empty(B, cfg.F2 * T2, dtype=torch.float32, device=x.device)
+    seed = None
+    if cfg.training and (cfg.dropout_p > 0 or getattr(cfg, "dropout_p2", 0.0) > 0):
+        seed = getattr(cfg, "seed", None)
+        if seed is None:
+            seed = next_seed(x.device, "eeg")
+    L.check(lib.bx_eeg_features_fwd(C.byref(desc), C.byref(params), _p(x), _p(seed), _p(feat), _p(saved), _p(ws), ws.numel(), _stream()),
+            "bx_eeg_features_fwd")
+    return x, feat, saved, desc, params, seed
+
+
+def eeg_features_keep(model, x):
+    """EEGNet / EEGNetAttentionDeep blocks 1-2 without autograd, keeping what the launch saved: returns (feat, saved arena, desc,
+    params, x as read) -- the arena holds the depthwise and separable outputs and the BatchNorm scale / shift (bx_eeg_saved_layout)
+    that Grad-CAM on the EEG branch reads.  The model's mode decides the path, as in ``model.features``."""
+    args = model._features_args(x)
+    x, feat, saved, desc, params, _ = _eeg_forward(*args, needs_input_grad=(False,) * 10)
+    return feat, saved, desc, params, x
+
+
 class EegFeaturesFn(torch.autograd.Function):
     """EEGNet up to Flatten (reference models.py:271-285). x fp32 [B,1,Chans,T] -> feat fp32 [B, F2*(T//32)]."""
 
     @staticmethod
     def forward(ctx, x, c1w, bn1w, bn1b, dww, bn2w, bn2b, sepw, bn3w, bn3b, bufs, cfg):
-        lib = L.load()
-        _require_gpu(x, "eeg input")
-        B, _, Ch, T = x.shape
-        x = x.contiguous().float()
-        # collapsed front end (no conv1 output tensor).  Training: only when nobody can ask for the input's gradient.  Evaluation
-        # mode (BatchNorm1 a fixed affine map): whenever no PARAMETER needs a gradient -- inference, Grad-CAM sweeps, saliency /
-        # integrated-gradients passes (the input gradient has a collapsed form too)
-        params_need_grad = getattr(cfg, "grad_mode", True) and any(ctx.needs_input_grad[1:10])      # under no_grad nobody does
-        collapse = 1 if EEG_COLLAPSE and ((cfg.training and not ctx.needs_input_grad[0]) or
-                                          (not cfg.training and not params_need_grad)) else 0
-        desc = L.EegDesc(B, Ch, T, cfg.F1, cfg.D, cfg.F2, cfg.K1, cfg.K2, cfg.P1, cfg.P2, 1 if cfg.training else 0, cfg.eps, cfg.momentum,
-                         float(cfg.dropout_p), cfg.salt, bx_dtype(cfg.dtype), collapse, float(getattr(cfg, "dropout_p2", -1.0)))
-        if INPUT_SLOTS and collapse and not cfg.training and not torch.is_grad_enabled() and cfg.K1 == 64:
-            desc.x_slot = _take_slot(x)                      # a graph input read through its device slot (GradCamSweep)
-        nsaved = lib.bx_eeg_saved_bytes(C.byref(desc))
-        if nsaved == 0:
-            raise RuntimeError("brainxai: EEGNet geometry outside the kernels' range (F1*D, F2 <= 1024, kernel lengths <= 4096, tensors below 2^31 elements)")
-        saved = torch.empty(nsaved, dtype=torch.uint8, device=x.device)
-        ws = workspace(lib.bx_eeg_workspace(C.byref(desc)), x.device)
-        params = L.EegParams(_p(c1w), _p(bn1w), _p(bn1b), _p(bufs[0]), _p(bufs[1]), _p(bufs[2]), _p(dww), _p(bn2w), _p(bn2b), _p(bufs[3]),
-                             _p(bufs[4]), _p(bufs[5]), _p(sepw), _p(bn3w), _p(bn3b), _p(bufs[6]), _p(bufs[7]), _p(bufs[8]))
-        T2 = (T // cfg.P1) // cfg.P2
-        feat = torch.empty(B, cfg.F2 * T2, dtype=torch.float32, device=x.device)
-        seed = None
-        if cfg.training and (cfg.dropout_p > 0 or getattr(cfg, "dropout_p2", 0.0) > 0):
-            seed = getattr(cfg, "seed", None)
-            if seed is None:
-                seed = next_seed(x.device, "eeg")
-        L.check(lib.bx_eeg_features_fwd(C.byref(desc), C.byref(params), _p(x), _p(seed), _p(feat), _p(saved), _p(ws), ws.numel(), _stream()),
-                "bx_eeg_features_fwd")
+        x, feat, saved, desc, params, seed = _eeg_forward(x, c1w, bn1w, bn1b, dww, bn2w, bn2b, sepw, bn3w, bn3b, bufs, cfg,
+                                                          ctx.needs_input_grad)
         ctx.desc, ctx.params, ctx.seed, ctx.bufs = desc, params, seed, bufs
         ctx.save_for_backward(x, saved, c1w, bn1w, bn1b, dww, bn2w, bn2b, sepw, bn3w, bn3b)
         return feat
