@@ -195,8 +195,8 @@ int bx_set_tree_max_rows(int rows);
  * workgroup of the apply kernel sums the producer's partial rows itself, in one fixed order, so no finalize launch (k_bn_finalize /
  * k_tail_bwd_mid) and no atomics are needed.  mask: bit 0 = backward passes, bit 1 = forward passes; default 3 (or the environment
  * variable BX_TAIL_FOLD at first use); a pass is folded only while rows x C stays small (the backward reduction launches
- * BX_TAIL_FOLD_RC / C rows, default 8192 / C; the forward folds when its producer wrote at most BX_TAIL_FOLD_RC_FWD / C rows,
- * default 16384 / C -- the late stages).  Results do not depend on the choice beyond the rounding of double-precision sums. */
+ * 8192 / C rows; the forward folds when its producer wrote at most 32768 / C rows -- the late stages).  Results do not depend
+ * on the choice beyond the rounding of double-precision sums. */
 int bx_set_tail_fold(int mask);
 /* conv3 + tail forward in two launches (bf16 storage, MFMA-capable C; otherwise BX_EUNSUPPORTED and the caller uses
  * bx_conv3x3 + bx_block_tail_fwd): y3 = relu(conv3x3(y2, w3) + b3) is stored for backward, and conv3's epilogue also

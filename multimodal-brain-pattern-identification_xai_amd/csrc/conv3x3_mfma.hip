@@ -799,10 +799,11 @@ __global__ __launch_bounds__(256) void k_conv_mfma_c(const bf16_t* __restrict__ 
 // workgroup and relies on occupancy alone to hide it).
 // Launch bound: the block-1 instantiation <16,1,32> (HBM-bound, five launches per training step) allocated 108 + 24 registers, four
 // over the limit for four workgroups per CU; bounded, the compiler finds 122 without spilling: 1.560 -> 1.547 ms/step (same box).
-// DL (round 2, CK <= 16 where the staged tile is linear in the thread index): halos go from HBM straight into one of THREE LDS
-// images, two tiles ahead (buffer_load ... lds: no registers hold them -- 95 instead of 122 -- no LDS write instructions, one barrier
-// per tile instead of two); out-of-image lanes load zeros through the same out-of-range offsets.  Not faster (see the launcher).
-template <int CK, int NC, int TW, bool POOL = false, bool C8 = false, bool DL = false>
+// The block-1 kernels are bound by instruction issue -- LDS reads, MFMA and epilogue arithmetic of four waves per SIMD (SQ counters:
+// VALU 35 %, MFMA 12 % of the SIMD cycles plus one LDS read per MFMA) -- not by the latency of their input loads: a form that filled
+// three LDS halo images by direct-to-LDS loads two tiles ahead (95 registers instead of 122) was bit-identical and not faster
+// (1.534-1.538 vs 1.532-1.536 ms/step same box; one tile ahead: 1.539-1.542).
+template <int CK, int NC, int TW, bool POOL = false, bool C8 = false>
 __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4 : 1) void k_conv_mfma_p(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const float* __restrict__ bias,
     const bf16_t* __restrict__ mask_src, const bf16_t* __restrict__ addend, bf16_t* __restrict__ y,
     int H, int W, int Co, int relu, int tiles_x, int tiles_y, int ntiles, uint32_t x_bytes, BxConvPoolEpi pe, WgradRedJob red, int nred) {
@@ -833,8 +834,7 @@ __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4
     hpx[k] = p % HWID - 1;
     hrel[k] = (uint32_t)(((p / HWID - 1) * W + (p % HWID - 1)) * CK + c * 8) * 2u;
   }
-  constexpr int IMG_BYTES = NR * 256 * 16;        // DL: one LDS image (thread-linear, padded to whole waves)
-  auto fetch = [&](int tile, int img = 0) {
+  auto fetch = [&](int tile) {
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
     const int y0 = ty * TH, x0 = tx * TW;
     const uint32_t tbase = (uint32_t)(((b * H + y0) * W + x0) * CK) * 2u;        // bytes; < 2^31 (checked by the launcher)
@@ -842,13 +842,8 @@ __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4
     for (int k = 0; k < NR; ++k) {
       const bool ok = (unsigned)(y0 + hpy[k]) < (unsigned)H && (unsigned)(x0 + hpx[k]) < (unsigned)W;
       const uint32_t off = ok ? tbase + hrel[k] : 0x80000000u;
-      if constexpr (DL) {      // lane l of this wave lands at (wave base of trip k) + 16 l
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (__attribute__((address_space(3))) void*)(lds + img * IMG_BYTES + (k * 256 + wave * 64) * 16), 16,
-                                                 (int)off, 0, 0, 0);
-      } else {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xres, off, 0, 0);
-        rv[k] = make_uint4(v.x, v.y, v.z, v.w);
-      }
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xres, off, 0, 0);
+      rv[k] = make_uint4(v.x, v.y, v.z, v.w);
     }
   };
   const uint32_t y_bytes = (uint32_t)((size_t)(ntiles / (tiles_x * tiles_y)) * H * W * Co * 2);
@@ -864,7 +859,6 @@ __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4
   for (int n = 0; n < NC; ++n)
     bz[n] = bias && ch_ok ? *reinterpret_cast<const float4*>(bias + co_base + n * 16 + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
   if (first_tile < ntiles) fetch(first_tile);
-  if constexpr (DL) { if (first_tile + tile_stride < ntiles) fetch(first_tile + tile_stride, 1); }      // two tiles ahead, three images
   // pooled form: statistics accumulate over the workgroup's tiles in registers; one reduction-tree row per workgroup at the end
   float st[2][NC][4];
   __amdgpu_buffer_rsrc_t pres = yres;
@@ -876,21 +870,9 @@ __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4
 #pragma unroll
       for (int r = 0; r < 4; ++r) st[0][n][r] = st[1][n][r] = 0.f;
   }
-  int it = 0;
-  for (int tile = first_tile; tile < ntiles; tile += tile_stride, ++it) {
+  for (int tile = first_tile; tile < ntiles; tile += tile_stride) {
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
     const int y0 = ty * TH, x0 = tx * TW;
-    const char* cur = lds;
-    if constexpr (DL) {
-      // this wave's loads of the tile have landed (vmcnt counts in issue order: only the previous tile's MP*NC output stores, issued
-      // after them, may still be in flight), then everybody's; the other image was last read before this barrier
-      static_assert(MP * NC + NR <= 15, "vmcnt immediate");
-      if (tile + tile_stride < ntiles) __builtin_amdgcn_s_waitcnt(0x0F70 | (MP * NC + NR));    // + the NR loads of the tile after this one
-      else __builtin_amdgcn_s_waitcnt(0x0F70 | (MP * NC));
-      __syncthreads();
-      cur = lds + (it % 3) * IMG_BYTES;
-      if (tile + 2 * tile_stride < ntiles) fetch(tile + 2 * tile_stride, (it + 2) % 3);
-    } else {
     __syncthreads();                          // previous tile's fragment reads are done
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
@@ -902,7 +884,6 @@ __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4
     }
     __syncthreads();
     if (tile + tile_stride < ntiles) fetch(tile + tile_stride);
-    }
     f32x4 acc[MP][NC];
 #pragma unroll
     for (int i = 0; i < MP; ++i)
@@ -930,7 +911,7 @@ __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4
       for (int i = 0; i < MP; ++i) {
         const int t = wave * MP + i;
         const int p = (t / TPR + dy) * HWID + (t % TPR) * 16 + li + dx;
-        bf16x8 bv = *reinterpret_cast<const bf16x8*>(cur + p * CKB + 16 * lds_chunk<CK>(c, p));
+        bf16x8 bv = *reinterpret_cast<const bf16x8*>(lds + p * CKB + 16 * lds_chunk<CK>(c, p));
         if (!valid) bv = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int n = 0; n < NC; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s % 3][n], bv, acc[i][n], 0, 0, 0);
@@ -1295,9 +1276,8 @@ __global__ __launch_bounds__(256, C1 <= 32 ? 4 : 2) void k_conv12b_mfma(const bf
   }
 }
 extern "C" int bx_conv3x3_pair_supported(int C0_p, int C1, int C2, int dtype) {
-  static const int second = getenv("BX_CONV_PAIR2") ? atoi(getenv("BX_CONV_PAIR2")) : 2;       // 0 = stage 1 only, 1 = stages 1-2, 2 = stages 1-3
-  return dtype == BX_BF16 && ((C0_p == 8 && C1 == 16 && C2 == 16) || (second >= 1 && C0_p == 16 && C1 == 32 && C2 == 32) ||
-                              (second >= 2 && C0_p == 32 && C1 == 64 && C2 == 64));
+  return dtype == BX_BF16 && ((C0_p == 8 && C1 == 16 && C2 == 16) || (C0_p == 16 && C1 == 32 && C2 == 32) ||
+                              (C0_p == 32 && C1 == 64 && C2 == 64));
 }
 extern "C" int bx_conv3x3_pair(const void* x, const void* packed1_mfma, const float* bias1, const void* packed2_mfma, const float* bias2,
                                void* y1, void* y2, unsigned char* mask1, unsigned char* mask2, int B, int H, int W, int C0_p, int C1, int C2,
@@ -1310,7 +1290,9 @@ extern "C" int bx_conv3x3_pair(const void* x, const void* packed1_mfma, const fl
   const int tiles_x = (W + 31) / 32, tiles_y = (H + 7) / 8;
   const long long ntiles = (long long)tiles_x * tiles_y * B;
   BX_REQUIRE(ntiles < (1ll << 31), "bx_conv3x3_pair: too many tiles");
-  static const int gx_cap = getenv("BX_CONV12_GX") ? atoi(getenv("BX_CONV12_GX")) : 2048;      // sweep knob (workgroups of the stage-1 pair kernel)
+  // workgroups of the stage-1 pair kernel (each walks tiles); 1024 / 4096 / 8192 (= one tile each) measured no difference beyond
+  // run-to-run noise (1.529-1.545 ms/step)
+  constexpr int gx_cap = 2048;
   const int gx = ntiles < gx_cap ? (int)ntiles : gx_cap;
   if (C1 >= 32) {
     const size_t lds2 = (size_t)12 * 36 * C0_p * 2 + (size_t)10 * 34 * C1 * 2;
@@ -1340,137 +1322,6 @@ extern "C" int bx_conv3x3_pair(const void* x, const void* packed1_mfma, const fl
     hipLaunchKernelGGL((k_conv12_mfma<false>), dim3((unsigned)gx), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)packed1_mfma, bias1,
                        (const bf16_t*)packed2_mfma, bias2, (bf16_t*)nullptr, (bf16_t*)y2, (unsigned char*)nullptr, (unsigned char*)nullptr, H, W, tiles_x, tiles_y, (int)ntiles, xb);
   BX_CHECK_LAUNCH("bx_conv3x3_pair");
-  return BX_OK;
-}
-
-// K-split variant for Ci >= 64 (the MFMA-bound late stages, where maps are small and a workgroup-per-tile kernel is a
-// serial chain stage -> 18*nchunk K-steps -> epilogue on too few workgroups).  A workgroup owns 4 x 16 pixels x 64 output
-// channels; ALL input chunks of its (4+2) x (16+2) halo sit in LDS at once and wave w takes K-steps w, w+4, w+8, ...
-// (a K-step = 32 of the 9*Ci reduction elements), so each wave's dependency chain is a quarter as long and every weight
-// fragment is loaded by exactly one wave.  The four partial accumulators meet in LDS (one barrier); wave r then finishes
-// pixel row r (bias / ReLU / mask / addend epilogue, 8-byte NHWC stores).
-template <int NCHUNK>
-__global__ __launch_bounds__(256) void k_conv_mfma_ks(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const float* __restrict__ bias,
-    const bf16_t* __restrict__ mask_src, const bf16_t* __restrict__ addend, bf16_t* __restrict__ y,
-    int H, int W, int Co, int relu, int tiles_x, int tiles_y) {
-  constexpr int CK = 64, TH = 4, TW = 16, HWID = TW + 2, HH = TH + 2, NPIX = HH * HWID, CKB = CK * 2, NCH = CK / 8, KS = 18, NC = 4;
-  constexpr int Ci = CK * NCHUNK, KTOT = KS * NCHUNK;
-  constexpr int NU = NPIX * NCH * NCHUNK, NR = (NU + 255) / 256;
-  constexpr int CHUNK_BYTES = NPIX * CKB;
-  extern __shared__ __attribute__((aligned(16))) char lds[];      // max(NCHUNK * CHUNK_BYTES, 64 KiB reduce buffer)
-  const int bid = blockIdx.x;
-  const int tx = bid % tiles_x, ty = (bid / tiles_x) % tiles_y, b = bid / (tiles_x * tiles_y);
-  const int y0 = ty * TH, x0 = tx * TW, co_base = blockIdx.y * (NC * 16);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
-
-  {  // stage every chunk of the halo tile: all loads first, then the LDS writes
-    uint4 rv[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int u = threadIdx.x + k * 256;
-      const int c = u % NCH, p = (u / NCH) % NPIX, ch = u / (NCH * NPIX);
-      const int iy = y0 + p / HWID - 1, ix = x0 + p % HWID - 1;
-      rv[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (u < NU && iy >= 0 && iy < H && ix >= 0 && ix < W)
-        rv[k] = *reinterpret_cast<const uint4*>(x + (((size_t)b * H + iy) * W + ix) * Ci + ch * CK + c * 8);
-    }
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int u = threadIdx.x + k * 256;
-      if (u < NU) {
-        const int c = u % NCH, p = (u / NCH) % NPIX, ch = u / (NCH * NPIX);
-        *reinterpret_cast<uint4*>(lds + ch * CHUNK_BYTES + p * CKB + 16 * lds_chunk<CK>(c, p)) = rv[k];
-      }
-    }
-  }
-  f32x4 acc[TH][NC];
-#pragma unroll
-  for (int i = 0; i < TH; ++i)
-#pragma unroll
-    for (int n = 0; n < NC; ++n) acc[i][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  bf16x8 a[3][NC];
-  auto load_a = [&](int ks, bf16x8 (&dst)[NC]) {      // packed layout [chunk][s][Co][32] == [ks][Co][32]
-#pragma unroll
-    for (int n = 0; n < NC; ++n)
-      dst[n] = *reinterpret_cast<const bf16x8*>(wp + ((size_t)ks * Co + co_base + n * 16 + li) * 32 + 8 * g);
-  };
-  constexpr int NIT = (KTOT + 3) / 4;                  // K-steps per wave (the last one may be empty for some waves)
-  load_a(wave, a[0]);
-  if (NIT > 1 && wave + 4 < KTOT) load_a(wave + 4, a[1]);
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int ks = wave + 4 * it;
-    if (it + 2 < NIT && ks + 8 < KTOT) load_a(ks + 8, a[(it + 2) % 3]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (ks < KTOT) {
-      const int chunk = ks / KS, s = ks % KS;
-      const int tap = s >> 1, c = (s & 1) * 4 + g;
-      const int dy = tap / 3, dx = tap - 3 * dy;
-      const char* base = lds + chunk * CHUNK_BYTES;
-#pragma unroll
-      for (int i = 0; i < TH; ++i) {
-        const int p = (i + dy) * HWID + li + dx;
-        const bf16x8 bv = *reinterpret_cast<const bf16x8*>(base + p * CKB + 16 * lds_chunk<CK>(c, p));
-#pragma unroll
-        for (int n = 0; n < NC; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[it % 3][n], bv, acc[i][n], 0, 0, 0);
-      }
-    }
-  }
-  // cross-wave reduction: red[wave][row i][n][reg r][lane]
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int i = 0; i < TH; ++i)
-#pragma unroll
-    for (int n = 0; n < NC; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[(((wave * TH + i) * NC + n) * 4 + r) * 64 + lane] = acc[i][n][r];
-  __syncthreads();
-  const int i = wave;                                   // this wave finishes pixel row i
-  const int oy = y0 + i, ox = x0 + li;
-  if (oy >= H || ox >= W) return;
-#pragma unroll
-  for (int n = 0; n < NC; ++n) {
-    const int co = co_base + n * 16 + 4 * g;
-    const size_t o = (((size_t)b * H + oy) * W + ox) * Co + co;
-    const float4 bz = bias ? *reinterpret_cast<const float4*>(bias + co) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float v[4] = {bz.x, bz.y, bz.z, bz.w};
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] += red[(((w * TH + i) * NC + n) * 4 + r) * 64 + lane];
-    if (relu) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-    }
-    if (mask_src) {
-      const uint2 mk = *reinterpret_cast<const uint2*>(mask_src + o);
-      const uint32_t mm[4] = {mk.x & 0xffffu, mk.x >> 16, mk.y & 0xffffu, mk.y >> 16};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = (mm[r] != 0u && mm[r] < 0x8000u) ? v[r] : 0.f;
-    }
-    if (addend) {
-      const uint2 a2 = *reinterpret_cast<const uint2*>(addend + o);
-      v[0] += __uint_as_float(a2.x << 16); v[1] += __uint_as_float(a2.x & 0xffff0000u);
-      v[2] += __uint_as_float(a2.y << 16); v[3] += __uint_as_float(a2.y & 0xffff0000u);
-    }
-    uint2 out;
-    out.x = pack2bf(v[0], v[1]);
-    out.y = pack2bf(v[2], v[3]);
-    *reinterpret_cast<uint2*>(y + o) = out;
-  }
-}
-template <int NCHUNK>
-static int launch_conv_ks(const void* x, const void* wp, const float* bias, const void* mask, const void* addend, void* y,
-                          int B, int H, int W, int Co, int relu, hipStream_t s) {
-  const int tiles_x = (W + 15) / 16, tiles_y = (H + 3) / 4;
-  size_t lds = (size_t)NCHUNK * 6 * 18 * 128;
-  if (lds < 65536) lds = 65536;
-  dim3 grid((unsigned)(tiles_x * tiles_y * B), (unsigned)(Co / 64));
-  hipLaunchKernelGGL((k_conv_mfma_ks<NCHUNK>), grid, dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)wp, bias, (const bf16_t*)mask,
-                     (const bf16_t*)addend, (bf16_t*)y, H, W, Co, relu, tiles_x, tiles_y);
-  BX_CHECK_LAUNCH("bx_conv3x3(mfma k-split)");
   return BX_OK;
 }
 
@@ -1522,8 +1373,9 @@ static int launch_conv(const void* x, const void* wp, const float* bias, const v
   }
   if constexpr (CK <= 32) if (Ci == CK) {
     const int ntiles = tiles_x * tiles_y * B, ygroups = Co / (16 * NC);
-    static const int pgx = getenv("BX_CONV_PGX") ? atoi(getenv("BX_CONV_PGX")) : 2048;
-    static const int pmin = getenv("BX_CONV_PMIN") ? atoi(getenv("BX_CONV_PMIN")) : 4;
+    // workgroups of the persistent kernel, tiles per workgroup from which it is used; swept on the training step (same box, ms/step):
+    // 2048 / 4 1.559-1.564; 1024 / 2 1.595, 512 / 4 1.583, 1024 / 4 1.570, 512 / 2 1.578
+    constexpr int pgx = 2048, pmin = 4;
     int gx = pgx / ygroups;                        // ~8 workgroups per CU in total, each walking ntiles/gx tiles
     if (gx > ntiles) gx = ntiles;
     if (ntiles >= pmin * gx && (size_t)B * H * W * CK * 2 < ((size_t)1 << 31)) {       // 32-bit byte offsets in the halo fetch
@@ -1538,20 +1390,6 @@ static int launch_conv(const void* x, const void* wp, const float* bias, const v
           return BX_OK;
         }
       }
-      if constexpr (CK <= 16 && NC == 1) {
-        // Measured (same box, training step): 1.534-1.538 ms with it (two images, one tile ahead: 1.539-1.542) against 1.532-1.536
-        // without -- the block-1 kernels are bound by instruction issue (LDS reads + MFMA + epilogue arithmetic of four waves per
-        // SIMD), not by the latency of their input loads; opt-in (BX_CONV_DLDS=1), results bit-identical.
-        static const bool use_dl = getenv("BX_CONV_DLDS") != nullptr;
-        if (use_dl) {                          // three thread-linear LDS images filled by direct-to-LDS loads, two tiles ahead
-          const size_t lds_dl = (size_t)3 * ((10 * (TW + 2) * (CK / 8) + 255) / 256) * 256 * 16;
-          hipLaunchKernelGGL((k_conv_mfma_p<CK, NC, TW, false, false, true>), dim3((unsigned)(gx + nred), (unsigned)ygroups), dim3(256),
-                             lds_dl < 4096 ? 4096 : lds_dl, s, (const bf16_t*)x, (const bf16_t*)wp, bias, (const bf16_t*)mask, (const bf16_t*)addend,
-                             (bf16_t*)y, H, W, Co, relu, tiles_x, tiles_y, ntiles, (uint32_t)((size_t)B * H * W * CK * 2), none, rj, nred);
-          BX_CHECK_LAUNCH("bx_conv3x3(mfma persistent, direct-to-LDS)");
-          return BX_OK;
-        }
-      }
       hipLaunchKernelGGL((k_conv_mfma_p<CK, NC, TW>), dim3((unsigned)(gx + nred), (unsigned)ygroups), dim3(256), lds, s, (const bf16_t*)x,
                          (const bf16_t*)wp, bias, (const bf16_t*)mask, (const bf16_t*)addend, (bf16_t*)y, H, W, Co, relu, tiles_x, tiles_y, ntiles,
                          (uint32_t)((size_t)B * H * W * CK * 2), none, rj, nred);
@@ -1561,11 +1399,9 @@ static int launch_conv(const void* x, const void* wp, const float* bias, const v
   }
   // two-image tiles where one 8 x 16 tile IS the image and the layer is wide (stage 5, 256 output channels): measured at B=64
   // 21.0 -> 15.6 us (256->256 forward), 21.7 -> 16.5 (its dgrad), 11.9 -> 9.9 (128->256 forward); every other shape got slower
-  // with IMGS = 2 or 4 (fewer, longer workgroups), see DESIGN section 6.  BX_CONV_IMGS=1|2 overrides for sweeps.
+  // with IMGS = 2 or 4 (fewer, longer workgroups), see DESIGN section 6.
   if constexpr (CK == 64) {
-    static const int imgs_env = getenv("BX_CONV_IMGS") ? atoi(getenv("BX_CONV_IMGS")) : 0;
-    const bool two = imgs_env ? imgs_env == 2 : (tiles_x * tiles_y == 1 && Co >= 256);
-    if (two && B % 2 == 0) {
+    if (tiles_x * tiles_y == 1 && Co >= 256 && B % 2 == 0) {
       const size_t lds2 = lds * 2;
       static bool attr_done = false;
       if (lds2 > 64 * 1024 && !attr_done) {
@@ -1606,21 +1442,18 @@ static int launch_conv(const void* x, const void* wp, const float* bias, const v
     }
     BX_FAIL(BX_EUNSUPPORTED, "bx_conv3x3(pooled): needs at least 16 input channels");
   }
-  if constexpr (CK == 64 && NC % 2 == 0) {
-    static const bool w22 = !(getenv("BX_CONV_W22") && atoi(getenv("BX_CONV_W22")) == 0);     // 2 x 2 wave grid (see k_conv_mfma)
-    if (w22) {
-      hipLaunchKernelGGL((k_conv_mfma<CK, NC, TW, 1, false, false, true>), grid, dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)wp, bias,
-                         (const bf16_t*)mask, (const bf16_t*)addend, (bf16_t*)y, H, W, Ci, Co, relu, tiles_x, tiles_y, (uint32_t)((size_t)B * H * W * Ci * 2), none, rj, nred);
-      BX_CHECK_LAUNCH("bx_conv3x3(mfma, 2 x 2 waves)");
-      return BX_OK;
-    }
+  if constexpr (CK == 64 && NC % 2 == 0) {         // 2 x 2 wave grid (see k_conv_mfma)
+    hipLaunchKernelGGL((k_conv_mfma<CK, NC, TW, 1, false, false, true>), grid, dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)wp, bias,
+                       (const bf16_t*)mask, (const bf16_t*)addend, (bf16_t*)y, H, W, Ci, Co, relu, tiles_x, tiles_y, (uint32_t)((size_t)B * H * W * Ci * 2), none, rj, nred);
+    BX_CHECK_LAUNCH("bx_conv3x3(mfma, 2 x 2 waves)");
+  } else {
+    hipLaunchKernelGGL((k_conv_mfma<CK, NC, TW>), grid, dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)wp, bias,
+                       (const bf16_t*)mask, (const bf16_t*)addend, (bf16_t*)y, H, W, Ci, Co, relu, tiles_x, tiles_y, (uint32_t)((size_t)B * H * W * Ci * 2), none, rj, nred);
+    BX_CHECK_LAUNCH("bx_conv3x3(mfma)");
   }
-  hipLaunchKernelGGL((k_conv_mfma<CK, NC, TW>), grid, dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)wp, bias,
-                     (const bf16_t*)mask, (const bf16_t*)addend, (bf16_t*)y, H, W, Ci, Co, relu, tiles_x, tiles_y, (uint32_t)((size_t)B * H * W * Ci * 2), none, rj, nred);
-  BX_CHECK_LAUNCH("bx_conv3x3(mfma)");
   return BX_OK;
 }
-// channel-split kernel for Ci % 64 == 0, Co % 64 == 0 (BX_CONV_C=0 keeps the pixel-split kernels)
+// channel-split kernel for Ci % 64 == 0, Co % 64 == 0
 template <int NCW, int TW, int IMGS>
 static int launch_conv_c(const void* x, const void* wp, const float* bias, const void* mask, const void* addend, void* y,
                          int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe) {
@@ -1660,13 +1493,12 @@ static int launch_conv_c(const void* x, const void* wp, const float* bias, const
 // returns -1 when the channel-split kernel does not apply.  Measured at B=64 against the pixel-split kernels (us, forward / data gradient):
 //   16x32 128->128  14.1 / 17.5  vs 15.3 / 17.1      8x16 128->256  8.5 / 13.2 vs 9.6 / 12.4      8x16 256->256  13.6 / 15.0 vs 15.4 / 16.3
 //   32x64  64->64   18.3 / 24.8  vs 18.5 / 21.8     16x32  64->128  9.9 / 14.2 vs 10.2 / 10.5
-// so: forward (and pooled) layers with Co >= 128, data gradients only at 256 -> 256.  BX_CONV_C=0 never, 2 wherever it applies.
+// so: forward (and pooled) layers with Co >= 128, data gradients only at 256 -> 256.
 static int try_conv_c(const void* x, const void* wp, const float* bias, const void* mask, const void* addend, void* y,
                       int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe) {
-  static const int mode = getenv("BX_CONV_C") ? atoi(getenv("BX_CONV_C")) : 1;
-  if (!mode || Ci % 64 || Co % 64) return -1;
+  if (Ci % 64 || Co % 64) return -1;
   const bool dgrad = mask || addend;
-  if (mode == 1 && (dgrad ? (Ci < 256 || Co < 256) : Co < 128)) return -1;
+  if (dgrad ? (Ci < 256 || Co < 256) : Co < 128) return -1;
   if (W <= 16) {
     const long long wgs = (long long)((H + 7) / 8) * B * (Co / 64);
     if (B % 2 == 0 && wgs / 2 >= 256) return launch_conv_c<1, 16, 2>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe);
@@ -1680,9 +1512,10 @@ template <int CK, int NC>
 static int launch_conv_tw(const void* x, const void* wp, const float* bias, const void* mask, const void* addend, void* y,
                           int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe = nullptr, const WgradRedJob* red = nullptr) {
   // 8x32 tiles wherever the map is wide enough: a workgroup re-reads its whole weight slab from L2 per pixel tile, so
-  // twice the pixels per tile halves the dominant L2 traffic of the late stages (measured: 16x32 maps 22.4 -> 17.3 us)
-  static const int tw16_ck = getenv("BX_CONV_TW16_CK") ? atoi(getenv("BX_CONV_TW16_CK")) : 0;     // sweep knob: 8 x 16 tiles for layers with this chunk size
-  if (W <= 16 || (tw16_ck && (tw16_ck & CK))) return launch_conv<CK, NC, 16>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe, red);
+  // twice the pixels per tile halves the dominant L2 traffic of the late stages (measured: 16x32 maps 22.4 -> 17.3 us).  8x16 tiles
+  // for the wide maps of one chunk size as well, training step (ms/step): chunk 32 / 16 / 8 / 64 1.556 / 1.560 / 1.547 / 1.575
+  // against 1.542 with none
+  if (W <= 16) return launch_conv<CK, NC, 16>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe, red);
   return launch_conv<CK, NC, 32>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe, red);
 }
 template <int CK>
@@ -1691,7 +1524,7 @@ static int launch_conv_nc(const void* x, const void* wp, const float* bias, cons
   // output channels per workgroup: 64 while that still launches >= 512 workgroups, else 32 (keeps two per CU in flight)
   const int tw = W <= 16 ? 16 : 32;
   const long long tiles = (long long)((W + tw - 1) / tw) * ((H + 7) / 8) * B;
-  static const long long nc4_min = getenv("BX_CONV_NC4_MIN") ? atoll(getenv("BX_CONV_NC4_MIN")) : 512;
+  constexpr long long nc4_min = 512;           // training step (ms/step): 256 1.744, 512 1.738, 1024 1.745, never 1.750
   if (Co % 64 == 0 && tiles * (Co / 64) >= nc4_min) return launch_conv_tw<CK, 4>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe, red);
   if (Co % 32 == 0) return launch_conv_tw<CK, 2>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe, red);
   return launch_conv_tw<CK, 1>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe, red);
@@ -1706,13 +1539,6 @@ int bx_conv3x3_mfma_launch(const void* x, const void* packed_mfma, const float* 
   if (carry && carry->valid) { job = wgrad_job_from(carry, true); red = &job; carry->valid = 0; }
   // the kernels address activations with 32-bit byte offsets through buffer resources
   BX_REQUIRE((size_t)B * H * W * (Ci > Co ? Ci : Co) * 2 < ((size_t)1 << 31), "bx_conv3x3(mfma): an activation tensor of 2 GiB or more is not supported (B=%d H=%d W=%d)", B, H, W);
-  // K-split variant: measured equal to the tile-per-workgroup kernel on MI355X (round 1: fwd +8 %, dgrad -3 %), so it is
-  // opt-in (BX_KSPLIT=1) until its main loop gets LDS double buffering
-  if (!red && Co % 64 == 0 && getenv("BX_KSPLIT")) {
-    if (Ci == 64)  return launch_conv_ks<1>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Co, relu, s);
-    if (Ci == 128) return launch_conv_ks<2>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Co, relu, s);
-    if (Ci == 256) return launch_conv_ks<4>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Co, relu, s);
-  }
   if (!red) {
     const int rc = try_conv_c(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr);
     if (rc >= 0) return rc;
@@ -2035,22 +1861,16 @@ extern "C" int bx_debug_wgrad_stamps(unsigned long long* host_out) {
 #else
 #define BX_STAMP(i) do { } while (0)
 #endif
-// DL (round 3): the tiles go from HBM / L2 straight into one of THREE LDS images, two tiles ahead (buffer_load ... lds: no staging
-// registers, no LDS write instructions, one barrier per tile).  The in-kernel stamps showed the register-staged loop at one exposed
-// global-load latency per tile (2500 cycles per 8 x 16 tile for 4 x 144 cycles of MFMA, 4500 per 8 x 32 tile): with one tile ahead and
-// two workgroups per CU there is nothing else to run while a load is in flight.  A lane's 16 bytes land at (wave base) + 16 lane, so
-// the swizzle moves to the SOURCE side: LDS slot L = 4 p + c' of pixel p takes channel unit c = ((c' >> 1) ^ (px >> 3)) << 1 | (c' & 1)
-// -- the image is byte for byte what stage() writes.  TH = 4 with 32-wide tiles keeps three images at 74 KB (two workgroups per CU).
-// SHIFT (round 3): the loop is bound by LDS READ bandwidth, not by latency (which is why DL did not pay: 2 workgroups x 4 waves x 20
+// Shifted fragments (round 3): the loop is bound by LDS READ bandwidth, not by latency (2 workgroups x 4 waves x 20
 // ds_read_b64_tr_b16 x 512 bytes per K-step = 2560 cycles per pair of tiles at 128 bytes/clk -- exactly the stamps).  The nine tap
 // fragments of a K-step are three shifted windows per tile row: a lane's 8 pixels of tap dx are pixels dx .. dx + 7 of the 10 it would
 // read for dx = 0 .. 2 together.  So each row is read ONCE as 12 pixels (three transposing reads) and the dx = 1 / 2 fragments are
 // built in registers (dword re-indexing and four v_alignbit): 9 + 2 reads per K-step instead of 18 + 2.
-template <int TW, int OCC, int DEPTH, int TH = 8, bool DL = false, bool SHIFT = true>
+template <int TW, int OCC>
 __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dz, float* __restrict__ partial,
     int H, int W, int Ci_p, int Co, int tiles_x, int tiles_y, int ntiles, int tiles_per_split, int nsplit, int ytiles, int ztiles,
     WgradRedJob prev, int nred) {
-  constexpr int HWID = TW + 2, HH = TH + 2, CIT = 32, COT = 32, XB = 64, ZB = 64;
+  constexpr int TH = 8, HWID = TW + 2, HH = TH + 2, CIT = 32, COT = 32, XB = 64, ZB = 64;
   constexpr int KSTEPS = TH * TW / 32, ROWS_PER_STEP = 32 / TW;   // TW = 32: one tile row per K-step; TW = 16: two
   constexpr int XS_BYTES = HH * HWID * XB;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -2083,9 +1903,7 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
   const int t_end = t_begin + tiles_per_split < ntiles ? t_begin + tiles_per_split : ntiles;
   constexpr int NXU = HH * HWID * (CIT / 8), NZU = TH * TW * (COT / 8);
   constexpr int NX = (NXU + 255) / 256, NZ = (NZU + 255) / 256;
-  constexpr int IMG_BYTES = (NX + NZ) * 256 * 16;                // DL: one LDS image = x units padded to whole waves, then the dZ units
-  if constexpr (DL) zs = lds + NX * 256 * 16;
-  uint4 rxa[DL ? 1 : NX], rza[DL ? 1 : NZ], rxb[DL ? 1 : NX], rzb[DL ? 1 : NZ];        // two tiles in flight (OCC = 3 leaves the registers): fetch distance 2
+  uint4 xreg[NX], zreg[NZ];                                      // the next tile, staged in registers
   const int nimg = ntiles / (tiles_x * tiles_y);
   const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (uint32_t)((size_t)nimg * H * W * Ci_p * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t zres = __builtin_amdgcn_make_buffer_rsrc((void*)dz, 0, (uint32_t)((size_t)nimg * H * W * Co * 2), 0x00020000);
@@ -2094,8 +1912,7 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
 #pragma unroll
   for (int k = 0; k < NX; ++k) {
     const int u = threadIdx.x + k * 256;
-    const int p = u / (CIT / 8), px = p % HWID;
-    const int cu = u % (CIT / 8), c = DL ? (((((cu >> 1) ^ (px >> 3)) & 1) << 1) | (cu & 1)) : cu;     // DL: u is the LDS slot
+    const int p = u / (CIT / 8), px = p % HWID, c = u % (CIT / 8);
     const bool live = u < NXU && ci0 + c * 8 < Ci_p;
     xpp[k] = ((live ? p / HWID - 1 : -20000) << 16) | ((px - 1) & 0xffff);
     xrel[k] = (uint32_t)((((p / HWID - 1) * W + (px - 1)) * Ci_p + ci0 + c * 8) * 2);
@@ -2103,30 +1920,10 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
 #pragma unroll
   for (int k = 0; k < NZ; ++k) {
     const int u = threadIdx.x + k * 256;
-    const int p = u / (COT / 8), px = p % TW;
-    const int cu = u % (COT / 8), c = DL ? (((((cu >> 1) ^ (px >> 3)) & 1) << 1) | (cu & 1)) : cu;
+    const int p = u / (COT / 8), px = p % TW, c = u % (COT / 8);
     zpp[k] = ((u < NZU ? p / TW : 20000) << 16) | px;
     zrel[k] = (uint32_t)((((p / TW) * W + px) * Co + co0 + c * 8) * 2);
   }
-  auto fetch_lds = [&](int tile, int img) {                    // DL: lane l of wave w lands at image + (k * 256 + w * 64 + l) * 16
-    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int y0 = ty * TH, x0 = tx * TW;
-    const uint32_t pix0 = (uint32_t)((b * H + y0) * W + x0);
-    const uint32_t xb = pix0 * (uint32_t)(Ci_p * 2), zb = pix0 * (uint32_t)(Co * 2);
-    char* base = lds + img * IMG_BYTES + wave * 64 * 16;
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      const bool ok = (unsigned)(y0 + (xpp[k] >> 16)) < (unsigned)H && (unsigned)(x0 + (int)(short)(xpp[k] & 0xffff)) < (unsigned)W;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (__attribute__((address_space(3))) void*)(base + k * 256 * 16), 16,
-                                               (int)(ok ? xb + xrel[k] : 0x80000000u), 0, 0, 0);
-    }
-#pragma unroll
-    for (int k = 0; k < NZ; ++k) {
-      const bool ok = (unsigned)(y0 + (zpp[k] >> 16)) < (unsigned)H && (unsigned)(x0 + (zpp[k] & 0xffff)) < (unsigned)W;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(zres, (__attribute__((address_space(3))) void*)(base + (NX + k) * 256 * 16), 16,
-                                               (int)(ok ? zb + zrel[k] : 0x80000000u), 0, 0, 0);
-    }
-  };
   auto fetch = [&](int tile, uint4 (&rx)[NX], uint4 (&rz)[NZ]) {
     const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
     const int y0 = ty * TH, x0 = tx * TW;
@@ -2146,6 +1943,8 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
     }
   };
   // per-lane read addresses: pixel kp = 8g + 4h + q of a K-step (h = the two 4-row halves of a transposing read pair)
+  // (only xbase[h][0] is read -- the loop builds the dx = 1, 2 fragments in registers -- but dropping the dx = 1, 2 entries changes
+  // how the compiler schedules the 32-wide instantiation, so the array keeps its full form)
   int xbase[2][3], zbase[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -2172,8 +1971,7 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
   // The K-steps of a staged tile with the operand fragments of step k+1 requested BEFORE the nine MFMAs of step k.  Written
   // as plain "read, then use" the compiler waits for each fragment right before its MFMA: the in-kernel stamps (tools/
   // wgrad_stamps.py) showed 560 cycles per K-step for 144 cycles of MFMA -- nine exposed LDS latencies.
-  int img_off = 0;                                               // DL: byte offset of the image being consumed
-  int xbase2;                                                    // SHIFT: pixels 8 .. 11 past the lane group's first (third transposing read)
+  int xbase2;                                                    // pixels 8 .. 11 past the lane group's first (third transposing read)
   {
     const int kp = 8 * g + q;
     const int r = TW == 32 ? 0 : (kp >> 4), c = (TW == 32 ? kp : (kp & 15)) + 8;
@@ -2181,27 +1979,18 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
   }
   auto load_frags = [&](int ks, bf16x8 (&a)[9], bf16x8& b) {
     const int r0 = ks * ROWS_PER_STEP;
-    b = tr_read8(zs + img_off, zbase[0] + r0 * TW * ZB, zbase[1] + r0 * TW * ZB);
-    if constexpr (SHIFT) {
+    b = tr_read8(zs, zbase[0] + r0 * TW * ZB, zbase[1] + r0 * TW * ZB);
 #pragma unroll
-      for (int dy = 0; dy < 3; ++dy) {
-        const int ro = (r0 + dy) * HWID * XB;
-        const char* xi = xs + img_off;
-        const u32x2 p0 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xi + xbase[0][0] + ro)));
-        const u32x2 p1 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xi + xbase[1][0] + ro)));
-        const u32x2 p2 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xi + xbase2 + ro)));
-        const uint32_t d0 = p0.x, d1 = p0.y, d2 = p1.x, d3 = p1.y, d4 = p2.x;       // pixel pairs (0,1) (2,3) (4,5) (6,7) (8,9)
-        a[dy * 3 + 0] = __builtin_bit_cast(bf16x8, (u32x4){d0, d1, d2, d3});
-        a[dy * 3 + 1] = __builtin_bit_cast(bf16x8, (u32x4){__builtin_amdgcn_alignbit(d1, d0, 16), __builtin_amdgcn_alignbit(d2, d1, 16),
-                                                           __builtin_amdgcn_alignbit(d3, d2, 16), __builtin_amdgcn_alignbit(d4, d3, 16)});
-        a[dy * 3 + 2] = __builtin_bit_cast(bf16x8, (u32x4){d1, d2, d3, d4});
-      }
-    } else {
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int dy = tap / 3, dx = tap % 3;
-        a[tap] = tr_read8(xs + img_off, xbase[0][dx] + (r0 + dy) * HWID * XB, xbase[1][dx] + (r0 + dy) * HWID * XB);
-      }
+    for (int dy = 0; dy < 3; ++dy) {
+      const int ro = (r0 + dy) * HWID * XB;
+      const u32x2 p0 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xs + xbase[0][0] + ro)));
+      const u32x2 p1 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xs + xbase[1][0] + ro)));
+      const u32x2 p2 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xs + xbase2 + ro)));
+      const uint32_t d0 = p0.x, d1 = p0.y, d2 = p1.x, d3 = p1.y, d4 = p2.x;       // pixel pairs (0,1) (2,3) (4,5) (6,7) (8,9)
+      a[dy * 3 + 0] = __builtin_bit_cast(bf16x8, (u32x4){d0, d1, d2, d3});
+      a[dy * 3 + 1] = __builtin_bit_cast(bf16x8, (u32x4){__builtin_amdgcn_alignbit(d1, d0, 16), __builtin_amdgcn_alignbit(d2, d1, 16),
+                                                         __builtin_amdgcn_alignbit(d3, d2, 16), __builtin_amdgcn_alignbit(d4, d3, 16)});
+      a[dy * 3 + 2] = __builtin_bit_cast(bf16x8, (u32x4){d1, d2, d3, d4});
     }
   };
   auto mma = [&](const bf16x8 (&a)[9], const bf16x8& b) {
@@ -2223,51 +2012,15 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
       if (ks + 1 < KSTEPS) mma(a1, b1);
     }
   };
-  if constexpr (DL) {
-    static_assert(NX + NZ <= 15, "vmcnt immediate");
-    if (t_begin < t_end) fetch_lds(t_begin, 0);
-    if (t_begin + 1 < t_end) fetch_lds(t_begin + 1, 1);
-    int it = 0;
-    for (int tile = t_begin; tile < t_end; ++tile, ++it) {
-      // this wave's loads of `tile` have landed (vmcnt counts in issue order: only the NX + NZ loads of the tile after it may still be
-      // in flight), then everybody's; the image about to be refilled was last read before this barrier
-      if (tile + 1 < t_end) __builtin_amdgcn_s_waitcnt(0x0F70 | (NX + NZ));
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
-      __syncthreads();
-      if (tile == t_begin) BX_STAMP(1);
-      if (tile + 2 < t_end) fetch_lds(tile + 2, (it + 2) % 3);
-      img_off = (it % 3) * IMG_BYTES;
-      compute();
-      if (tile - t_begin < 4) BX_STAMP(2 + tile - t_begin);
-    }
-  } else if (DEPTH == 2) {                                       // two tiles in flight (needs the 256-register budget of OCC = 2)
-    if (t_begin < t_end) fetch(t_begin, rxa, rza);
-    if (t_begin + 1 < t_end) fetch(t_begin + 1, rxb, rzb);
-    for (int tile = t_begin; tile < t_end; tile += 2) {
-      __syncthreads();
-      stage(rxa, rza);
-      __syncthreads();
-      if (tile + 2 < t_end) fetch(tile + 2, rxa, rza);
-      compute();
-      if (tile + 1 < t_end) {
-        __syncthreads();
-        stage(rxb, rzb);
-        __syncthreads();
-        if (tile + 3 < t_end) fetch(tile + 3, rxb, rzb);
-        compute();
-      }
-    }
-  } else {
-    if (t_begin < t_end) fetch(t_begin, rxa, rza);
-    for (int tile = t_begin; tile < t_end; ++tile) {
-      __syncthreads();
-      stage(rxa, rza);
-      __syncthreads();
-      if (tile == t_begin) BX_STAMP(1);
-      if (tile + 1 < t_end) fetch(tile + 1, rxa, rza);
-      compute();
-      if (tile - t_begin < 4) BX_STAMP(2 + tile - t_begin);
-    }
+  if (t_begin < t_end) fetch(t_begin, xreg, zreg);
+  for (int tile = t_begin; tile < t_end; ++tile) {
+    __syncthreads();
+    stage(xreg, zreg);
+    __syncthreads();
+    if (tile == t_begin) BX_STAMP(1);
+    if (tile + 1 < t_end) fetch(tile + 1, xreg, zreg);
+    compute();
+    if (tile - t_begin < 4) BX_STAMP(2 + tile - t_begin);
   }
   // ---- the partial: fragment order [tile = tap*4 + m*2 + n][lane][reg], exactly what k_wgrad_mfma writes (same reduce kernel)
   constexpr int NT = 36;
@@ -2286,30 +2039,19 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
   BX_STAMP(6);
 }
 
-struct WgradPlan { int ma, nb, tw, th, tiles_x, tiles_y, ntiles, ytiles, ztiles, nsplit, tps; size_t lds; };
-// tile-owner kernel with direct-to-LDS tiles (k_wgrad_own<.., DL>): BX_WGRAD_DL=1; default is the register-staged loop
-static bool wgrad_own_dl() {
-  static const bool v = getenv("BX_WGRAD_DL") && atoi(getenv("BX_WGRAD_DL")) != 0;     // opt-in: measured slower (1.501 vs 1.476 ms/step)
-  return v;
-}
-static bool wgrad_own_on() {
-  static const bool v = !(getenv("BX_WGRAD_OWN") && atoi(getenv("BX_WGRAD_OWN")) == 0);
-  return v;
-}
+struct WgradPlan { int ma, nb, tw, tiles_x, tiles_y, ntiles, ytiles, ztiles, nsplit, tps; size_t lds; };
 static WgradPlan wgrad_plan(int B, int H, int W, int Ci_p, int Co) {
   WgradPlan p;
   p.ma = Ci_p >= 32 ? 2 : 1;
   p.nb = Co >= 32 ? 2 : 1;
   p.tw = W <= 16 ? 16 : 32;
-  // 4-row tiles for the direct-to-LDS form of the tile-owner kernel at 32-wide tiles (three LDS images, two workgroups per CU)
-  p.th = (p.ma == 2 && p.nb == 2 && p.tw == 32 && wgrad_own_on() && wgrad_own_dl()) ? 4 : 8;
-  p.tiles_x = (W + p.tw - 1) / p.tw; p.tiles_y = (H + p.th - 1) / p.th; p.ntiles = p.tiles_x * p.tiles_y * B;
+  p.tiles_x = (W + p.tw - 1) / p.tw; p.tiles_y = (H + 7) / 8; p.ntiles = p.tiles_x * p.tiles_y * B;
   p.ytiles = (Ci_p + 16 * p.ma - 1) / (16 * p.ma); p.ztiles = Co / (16 * p.nb);
   // two rounds of 256 workgroups for every tile shape: with the partial sum riding in the next layer's launch, more (smaller)
-  // splits only add partial traffic (sweep of BX_WGRAD_WANT on the training step: 384 1.789, 512 1.733, 576 1.745, 768 1.870,
+  // splits only add partial traffic (sweep of the workgroup count on the training step: 384 1.789, 512 1.733, 576 1.745, 768 1.870,
   // 1024 1.882 ms; the lighter tiles used to run at 1024)
-  static const int want_env = getenv("BX_WGRAD_WANT") ? atoi(getenv("BX_WGRAD_WANT")) : 0;
-  int want = (want_env ? want_env : 512) / (p.ytiles * p.ztiles);
+  constexpr int want_wgs = 512;
+  int want = want_wgs / (p.ytiles * p.ztiles);
   if (want < 1) want = 1;
   if (want > p.ntiles) want = p.ntiles;
   p.tps = (p.ntiles + want - 1) / want;
@@ -2375,53 +2117,28 @@ int bx_wgrad_mfma_launch(const void* x, const void* dz, float* dw, float* db, in
     prev = wgrad_job_from(pending, true);
     zextra = (prev.nblocks + p.nsplit * p.ytiles - 1) / (p.nsplit * p.ytiles);
   }
-  const bool own = wgrad_own_on();
-  if (own && p.ma == 2 && p.nb == 2) {
+  if (p.ma == 2 && p.nb == 2) {
     // tile-owner kernel (k_wgrad_own): 1-D grid = [reduce-role workgroups, padded to a multiple of 8][8 XCD lanes x slots]
     const int nred = pending && pending->valid ? (prev.nblocks + 7) / 8 * 8 : 0;
     const int ranges8 = (p.nsplit + 7) / 8;                           // pixel ranges per XCD lane
     const int nwg = nred + ranges8 * 8 * p.ytiles * p.ztiles;
-    const size_t lds = (size_t)10 * (p.tw + 2) * 64 + (size_t)8 * p.tw * 64;
-    // two workgroups per CU (256-register budget: 36 accumulators + two fragment sets of 40 + 40 staging registers); BX_WGRAD_DEPTH=2
-    // keeps two tiles in flight instead of one
-    static const int depth = getenv("BX_WGRAD_DEPTH") ? atoi(getenv("BX_WGRAD_DEPTH")) : 1;
-    static const bool shift = !(getenv("BX_WGRAD_SHIFT") && atoi(getenv("BX_WGRAD_SHIFT")) == 0);      // (the third read of the last halo row reaches 128 bytes past the x tile: lds + 256)
-    if (wgrad_own_dl()) {
-      // three LDS images of (x halo units + dZ units, each padded to whole 256-lane trips) x 16 bytes
-      const int nxu = (p.th + 2) * (p.tw + 2) * 4, nzu = p.th * p.tw * 4;
-      const size_t lds_dl = (size_t)3 * ((nxu + 255) / 256 + (nzu + 255) / 256) * 256 * 16;
-      static bool attr16 = false, attr32 = false;
-      if (p.tw == 16) {
-        if (!attr16 && lds_dl > 64 * 1024) {
-          if (hipFuncSetAttribute((const void*)k_wgrad_own<16, 2, 1, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dl) != hipSuccess)
-            BX_FAIL(BX_EHIP, "bx_conv3x3_wgrad(mfma): cannot reserve %zu bytes of LDS", lds_dl);
-          attr16 = true;
-        }
-        hipLaunchKernelGGL((k_wgrad_own<16, 2, 1, 8, true>), dim3(nwg), dim3(256), lds_dl, s, (const bf16_t*)x, (const bf16_t*)dz, part, H, W,
-                           Ci_p, Co, p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.nsplit, p.ytiles, p.ztiles, prev, nred);
-      } else {
-        if (!attr32 && lds_dl > 64 * 1024) {
-          if (hipFuncSetAttribute((const void*)k_wgrad_own<32, 2, 1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dl) != hipSuccess)
-            BX_FAIL(BX_EHIP, "bx_conv3x3_wgrad(mfma): cannot reserve %zu bytes of LDS", lds_dl);
-          attr32 = true;
-        }
-        hipLaunchKernelGGL((k_wgrad_own<32, 2, 1, 4, true>), dim3(nwg), dim3(256), lds_dl, s, (const bf16_t*)x, (const bf16_t*)dz, part, H, W,
-                           Ci_p, Co, p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.nsplit, p.ytiles, p.ztiles, prev, nred);
-      }
-    } else
-#define BX_OWN(TW_, D_, SH_) hipLaunchKernelGGL((k_wgrad_own<TW_, 2, D_, 8, false, SH_>), dim3(nwg), dim3(256), lds + 256, s, (const bf16_t*)x, \
-                                           (const bf16_t*)dz, part, H, W, Ci_p, Co, p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.nsplit, p.ytiles, p.ztiles, prev, nred)
-    if (p.tw == 16) { if (depth == 2) BX_OWN(16, 2, false); else if (shift) BX_OWN(16, 1, true); else BX_OWN(16, 1, false); }
-    else            { if (depth == 2) BX_OWN(32, 2, false); else if (shift) BX_OWN(32, 1, true); else BX_OWN(32, 1, false); }
-#undef BX_OWN
-  } else
+    // two workgroups per CU (256-register budget: 36 accumulators + two fragment sets of 40 + 40 staging registers); the third
+    // read of the last halo row reaches 128 bytes past the x tile: lds + 256
+    const size_t lds = (size_t)10 * (p.tw + 2) * 64 + (size_t)8 * p.tw * 64 + 256;
+    if (p.tw == 16)
+      hipLaunchKernelGGL((k_wgrad_own<16, 2>), dim3(nwg), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)dz, part, H, W, Ci_p, Co,
+                         p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.nsplit, p.ytiles, p.ztiles, prev, nred);
+    else
+      hipLaunchKernelGGL((k_wgrad_own<32, 2>), dim3(nwg), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)dz, part, H, W, Ci_p, Co,
+                         p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.nsplit, p.ytiles, p.ztiles, prev, nred);
+  } else {
 #define BX_WG(MA_, NB_) do { if (p.tw == 16) launch_wgrad<MA_, NB_, 16>(p, x, dz, part, H, W, Ci_p, Co, prev, zextra, s); \
                              else launch_wgrad<MA_, NB_, 32>(p, x, dz, part, H, W, Ci_p, Co, prev, zextra, s); } while (0)
-  { if (p.ma == 1 && p.nb == 1) BX_WG(1, 1);
-  else if (p.ma == 1 && p.nb == 2) BX_WG(1, 2);
-  else if (p.ma == 2 && p.nb == 1) BX_WG(2, 1);
-  else BX_WG(2, 2); }
+    if (p.ma == 1 && p.nb == 1) BX_WG(1, 1);
+    else if (p.ma == 1) BX_WG(1, 2);
+    else BX_WG(2, 1);
 #undef BX_WG
+  }
   BX_CHECK_LAUNCH("bx_conv3x3_wgrad(mfma)");
   bxWgradPending cur;
   cur.partial = part; cur.dw = dw; cur.db = db; cur.nsplit = p.nsplit; cur.Cin = Cin; cur.Co = Co; cur.ma = p.ma; cur.nb = p.nb;

@@ -301,20 +301,14 @@ static int launch_split(const float* x, const bf16_t* wp, const float* bias, con
   if (lds > 64 * 1024) {
     static bool attr_done = false;
     if (!attr_done) {
-      if (hipFuncSetAttribute((const void*)k_conv_split<CK, NC, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_conv_split<CK, NC, TW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)k_conv_split<CK, NC, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         BX_FAIL(BX_EHIP, "bx_conv3x3(split): cannot reserve %zu bytes of LDS", lds);
       attr_done = true;
     }
   }
-  static const bool w22 = !(getenv("BX_SPLIT_W22") && atoi(getenv("BX_SPLIT_W22")) == 0);      // 0: the pixel-split wave mapping (A/B sweeps)
   dim3 grid((unsigned)(tiles_x * tiles_y * B), (unsigned)(Co / (16 * NC)));
-  if (w22)
-    hipLaunchKernelGGL((k_conv_split<CK, NC, TW>), grid, dim3(256), lds, s, x, wp, (uint32_t)split_image_elems(Ci, Co), bias, mask, addend, y,
-                       H, W, Ci, Co, relu, tiles_x, tiles_y, (uint32_t)((size_t)B * H * W * Ci * 4), (uint32_t)((size_t)B * H * W * Co * 4));
-  else
-    hipLaunchKernelGGL((k_conv_split<CK, NC, TW, false>), grid, dim3(256), lds, s, x, wp, (uint32_t)split_image_elems(Ci, Co), bias, mask, addend, y,
-                       H, W, Ci, Co, relu, tiles_x, tiles_y, (uint32_t)((size_t)B * H * W * Ci * 4), (uint32_t)((size_t)B * H * W * Co * 4));
+  hipLaunchKernelGGL((k_conv_split<CK, NC, TW>), grid, dim3(256), lds, s, x, wp, (uint32_t)split_image_elems(Ci, Co), bias, mask, addend, y,
+                     H, W, Ci, Co, relu, tiles_x, tiles_y, (uint32_t)((size_t)B * H * W * Ci * 4), (uint32_t)((size_t)B * H * W * Co * 4));
   BX_CHECK_LAUNCH("bx_conv3x3(split mfma)");
   return BX_OK;
 }
@@ -323,7 +317,7 @@ static int launch_split_nc(const float* x, const bf16_t* wp, const float* bias, 
                            int B, int H, int W, int Ci, int Co, int relu, hipStream_t s) {
   // output channels per workgroup: 64 while that still launches >= 512 workgroups, else 32, else 16
   const long long tiles = (long long)((W + TW - 1) / TW) * ((H + 7) / 8) * B;
-  static const long long nc4_min = getenv("BX_SPLIT_NC4_MIN") ? atoll(getenv("BX_SPLIT_NC4_MIN")) : 512;
+  constexpr long long nc4_min = 512;
   if (Co % 64 == 0 && tiles * (Co / 64) >= nc4_min) return launch_split<CK, 4, TW>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s);
   if (Co % 32 == 0) return launch_split<CK, 2, TW>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s);
   return launch_split<CK, 1, TW>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s);
@@ -609,8 +603,8 @@ static WsplitPlan wsplit_plan(int B, int H, int W, int Ci_p, int Co) {
   p.nb = Co >= 32 ? 2 : 1;
   p.tiles_x = (W + 15) / 16; p.tiles_y = (H + 7) / 8; p.ntiles = p.tiles_x * p.tiles_y * B;
   p.ytiles = (Ci_p + 16 * p.ma - 1) / (16 * p.ma); p.ztiles = Co / (16 * p.nb);
-  static const int want_env = getenv("BX_WSPLIT_WANT") ? atoi(getenv("BX_WSPLIT_WANT")) : 0;
-  int want = (want_env ? want_env : 1024) / (p.ytiles * p.ztiles);
+  constexpr int want_wgs = 1024;
+  int want = want_wgs / (p.ytiles * p.ztiles);
   if (want < 1) want = 1;
   if (want > p.ntiles) want = p.ntiles;
   p.tps = (p.ntiles + want - 1) / want;

@@ -460,14 +460,11 @@ extern "C" int bx_eeg_features_fwd(const bxEegDesc* d, const bxEegParams* p, con
   }
   dim3 gsep(bx_ceil_div(g.T1, SEP_TT), g.B);
   {
-    // outputs per wave: split the 16 outputs over 2 or 4 workgroups while that is what it takes to give every CU one (BX_EEG_SEP_NO overrides)
-    static const int no_env = getenv("BX_EEG_SEP_NO") ? atoi(getenv("BX_EEG_SEP_NO")) : 0;
+    // outputs per wave: split the 16 outputs over 2 workgroups while that is what it takes to give every CU one
     const long long wgs = (long long)gsep.x * gsep.y;
     // measured at B = 64, T1 = 500 (training step, same box): NO = 4 1.483 ms, 2 1.479, 1 1.486 (one 4-byte weight read per 4 FMAs)
-    const int no = no_env == 1 || no_env == 2 || no_env == 4 ? no_env : wgs >= 512 ? 4 : 2;
-    if (no == 4) hipLaunchKernelGGL(k_eeg_sep<4>, gsep, dim3(256), 0, s, p1, p->sep_w, smap, part, g, tr);
-    else if (no == 2) hipLaunchKernelGGL(k_eeg_sep<2>, dim3(gsep.x, gsep.y, 2), dim3(256), 0, s, p1, p->sep_w, smap, part, g, tr);
-    else hipLaunchKernelGGL(k_eeg_sep<1>, dim3(gsep.x, gsep.y, 4), dim3(256), 0, s, p1, p->sep_w, smap, part, g, tr);
+    if (wgs >= 512) hipLaunchKernelGGL(k_eeg_sep<4>, gsep, dim3(256), 0, s, p1, p->sep_w, smap, part, g, tr);
+    else hipLaunchKernelGGL(k_eeg_sep<2>, dim3(gsep.x, gsep.y, 2), dim3(256), 0, s, p1, p->sep_w, smap, part, g, tr);
   }
   BX_CHECK_LAUNCH("eeg sepconv");
   if (tr && (bx_tail_fold_mask() & 2) && g.F2 == 16 && (long long)gsep.x * gsep.y * 16 <= 8192)
@@ -1041,10 +1038,8 @@ extern "C" int bx_eeg_features_bwd(const bxEegDesc* d, const bxEegParams* p, con
   BX_CHECK_LAUNCH("eeg bn3 bwd finalize");
   // separable conv (the BatchNorm3 backward apply rides in its staging)
   {
-    // the two halves of the kernel in separate workgroups while that is what gives every CU two (BX_EEG_SEPB_SPLIT=0|1 overrides);
-    // B = 64: 27.0 -> 24.0 us
-    static const int split_env = getenv("BX_EEG_SEPB_SPLIT") ? atoi(getenv("BX_EEG_SEPB_SPLIT")) : -1;
-    const bool split = split_env >= 0 ? split_env != 0 : g.B * 4 < 1024;
+    // the two halves of the kernel in separate workgroups while that is what gives every CU two; B = 64: 27.0 -> 24.0 us
+    const bool split = g.B * 4 < 1024;
     const size_t tile = (size_t)16 * eeg_sepb_pitch(g.T1);
     const size_t lds = (split ? (tile + (tile > 4096 ? tile : 4096)) : (2 * tile + 4096)) * sizeof(float);
     BX_REQUIRE(lds <= 160 * 1024, "bx_eeg_features_bwd: T/P1 too long for the LDS tile (%zu bytes)", lds);
@@ -1079,9 +1074,7 @@ extern "C" int bx_eeg_features_bwd(const bxEegDesc* d, const bxEegParams* p, con
   if (eeg_collapsed(d)) {
     // gradients of conv1 / BatchNorm1 / depthwise from C = g (*) x, G = sum g and the saved (R, S): eeg_collapse.hip
     BX_REQUIRE(!dx, "bx_eeg_features_bwd: the collapsed front end (bxEegDesc.collapse) has no input gradient; clear the flag when x needs one");
-    static const int want_split = getenv("BX_EEGC_NSPLIT") ? atoi(getenv("BX_EEGC_NSPLIT")) : EEGC_MAX_SPLIT;
-    int nsplit = want_split < 1 ? 1 : want_split > EEGC_MAX_SPLIT ? EEGC_MAX_SPLIT : want_split;
-    if (nsplit > g.B) nsplit = g.B;
+    const int nsplit = g.B < EEGC_MAX_SPLIT ? g.B : EEGC_MAX_SPLIT;
     float* cpart = w1part;
     float* ep = rpart;
     float* gpart = rpart + (size_t)g.Ch * 520;

@@ -27,11 +27,10 @@
 // role r (blockIdx.x < EC_NR): rows w, w + EC_NR, ...; a thread takes 4 consecutive samples and keeps the 67-sample window in
 //   registers: 4 x 64 products per 17 aligned 16-byte LDS reads.  One partial row [65] per workgroup.
 // role e: rows e, e + EC_NE, ...; wave rg takes every 4th of them; see below.
-template <int ROLE>      // 0: both roles in one launch; 1 / 2: one role only (profiling: BX_EEGC_SPLIT_STATS=1)
 __global__ __launch_bounds__(256) void k_eegc_stats(const float* __restrict__ x, float* __restrict__ rpart, float* __restrict__ epart, int nrows, int T) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int blk = ROLE == 2 ? (int)blockIdx.x + EC_NR : (int)blockIdx.x;
+  const int blk = (int)blockIdx.x;
   if (blk < EC_NR) {
     // lag sums straight from global memory: a thread takes 4 consecutive samples and requests its 68-sample window as 17
     // 16-byte buffer loads, all in flight together (past the row: zeros); neighbouring threads' windows overlap in L1.  No LDS
@@ -596,18 +595,11 @@ int bx_eegc_forward(const float* x, const float* w1, const float* wd, const floa
   const size_t lds = lds_r > lds_e ? lds_r : lds_e;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)k_eegc_stats<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void*)k_eegc_stats<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void*)k_eegc_stats<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return -1;
+    if (hipFuncSetAttribute((const void*)k_eegc_stats, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return -1;
     attr = true;
   }
   if (lds > 150 * 1024) return -2;
-  static const bool split_roles = getenv("BX_EEGC_SPLIT_STATS") != nullptr;
-  if (split_roles) {
-    hipLaunchKernelGGL(k_eegc_stats<1>, dim3(EC_NR), dim3(256), lds_r, s, x, rpart, epart, B * Ch, T);
-    hipLaunchKernelGGL(k_eegc_stats<2>, dim3(EC_NE), dim3(256), lds_e, s, x, rpart, epart, B * Ch, T);
-  } else
-    hipLaunchKernelGGL(k_eegc_stats<0>, dim3(EC_NR + EC_NE), dim3(256), lds, s, x, rpart, epart, B * Ch, T);
+  hipLaunchKernelGGL(k_eegc_stats, dim3(EC_NR + EC_NE), dim3(256), lds, s, x, rpart, epart, B * Ch, T);
   hipLaunchKernelGGL(k_eegc_finalize1, dim3(1), dim3(1024), 0, s, rpart, epart, w1, gamma, beta, rmean, rvar, nbt, momentum, eps,
                      (double)B * Ch * T, mean1, inv1, sc1, sh1, RS);
   dim3 grid((unsigned)((T + EC_TC - 1) / EC_TC), (unsigned)B);

@@ -10,7 +10,7 @@
 #include "bx_common.h"
 
 #define TAIL_MAX_GROUPS 128         // BxStatTree: bx_stat_tree_shape never makes more groups
-#define TAIL_MAX_BLOCKS 2048        // layout bound of the partial buffers; the launch cap is tail_block_cap()
+#define TAIL_MAX_BLOCKS 2048        // layout bound of the partial buffers; the launch cap is TAIL_BLOCK_CAP
 
 struct TailGeom {
   int B, H, W, Ho, Wo, C, Cin_p, ncg, slots;
@@ -30,17 +30,15 @@ static int make_geom(const bxTailDesc* d, TailGeom* g) {
   return 0;
 }
 // kernels without per-workgroup partials take one pixel group per workgroup (no serial grid-stride trips)
-static int tail_block_cap() {          // workgroups of the statistics / reduction passes (BX_TAIL_BLOCKS, default 512)
-  static const int cap = [] { const char* e = getenv("BX_TAIL_BLOCKS"); int v = e ? atoi(e) : 512; return v < 1 ? 1 : v > TAIL_MAX_BLOCKS ? TAIL_MAX_BLOCKS : v; }();
-  return cap;
-}
+// workgroups of the statistics / reduction passes; training step (ms/step): 256 1.729, 512 1.731, 1024 1.753, 2048 1.775
+constexpr int TAIL_BLOCK_CAP = 512;
 static int tail_blocks_all(const TailGeom& g) {
   long long nb = (g.npool + g.slots - 1) / g.slots;
   return (int)(nb > 65535 ? 65535 : nb);
 }
 static int tail_blocks(const TailGeom& g) {
   long long nb = (g.npool + g.slots - 1) / g.slots;
-  return (int)(nb > tail_block_cap() ? tail_block_cap() : nb);
+  return (int)(nb > TAIL_BLOCK_CAP ? TAIL_BLOCK_CAP : nb);
 }
 
 // pooled-pixel index -> (sample, row, column) with 32-bit unsigned divisions (the launchers check B*H*W < 2^31): the
@@ -306,8 +304,8 @@ extern "C" int bx_set_tree_max_rows(int rows) {
   return BX_OK;
 }
 // Folded finalizes (consumer-side sums, bx_rows_total): BX_TAIL_FOLD bit 0 = backward (no k_tail_bwd_mid), bit 1 = forward (no
-// k_bn_finalize); default 3.  BX_TAIL_FOLD_RC bounds rows x C of a folded pass (the backward reduction role launches that many rows,
-// the forward folds only when its producer wrote no more), BX_TAIL_FOLD_GRID caps the consuming kernel's workgroups (each re-reads the rows).
+// k_bn_finalize); default 3.  TAIL_FOLD_RC_BWD / _FWD bound rows x C of a folded pass (the backward reduction role launches that many
+// rows, the forward folds only when its producer wrote no more), TAIL_FOLD_GRID caps the consuming kernel's workgroups (each re-reads the rows).
 static int g_tail_fold = -1;
 static int tail_fold() {
   if (g_tail_fold < 0) { const char* e = getenv("BX_TAIL_FOLD"); g_tail_fold = e ? atoi(e) & 3 : 3; }
@@ -319,17 +317,11 @@ extern "C" int bx_set_tail_fold(int mask) {
   g_tail_fold = mask;
   return BX_OK;
 }
-static int tail_fold_rc(bool fwd) {
-  static const int rc_b = getenv("BX_TAIL_FOLD_RC") ? atoi(getenv("BX_TAIL_FOLD_RC")) : 8192;
-  static const int rc_f = getenv("BX_TAIL_FOLD_RC_FWD") ? atoi(getenv("BX_TAIL_FOLD_RC_FWD")) : 32768;   // (16384 and 32768 measure the same; 32768 also folds stage 3: one launch fewer)
-  return fwd ? rc_f : rc_b;
-}
-static int tail_fold_grid() {
-  static const int v = getenv("BX_TAIL_FOLD_GRID") ? atoi(getenv("BX_TAIL_FOLD_GRID")) : 512;       // measured: 512 1.498 ms, 1024 1.500, 4096 1.514
-  return v < 1 ? 1 : v;
-}
+constexpr int TAIL_FOLD_RC_BWD = 8192;      // measured: 2048 1.523 ms, 4096 1.498, 8192 1.498, 16384 1.505
+constexpr int TAIL_FOLD_RC_FWD = 32768;     // (16384 and 32768 measure the same; 32768 also folds stage 3: one launch fewer)
+constexpr int TAIL_FOLD_GRID = 512;         // measured: 512 1.498 ms, 1024 1.500, 4096 1.514
 static bool tail_fold_ok(const TailGeom& g) { return g.C <= 256 && bx_rows_total_ok(g.C); }
-static int tail_fold_rows(int C) { const int r = tail_fold_rc(false) / C; return r < 16 ? 16 : r > TAIL_MAX_BLOCKS ? TAIL_MAX_BLOCKS : r; }
+static int tail_fold_rows(int C) { const int r = TAIL_FOLD_RC_BWD / C; return r < 16 ? 16 : r > TAIL_MAX_BLOCKS ? TAIL_MAX_BLOCKS : r; }
 // rows of forward partial sums: the pooling kernel writes at most TAIL_MAX_BLOCKS, conv3's pooled epilogue one per 8 x 16 (or larger) tile
 static size_t tail_rows_cap(const bxTailDesc* d) {
   const size_t conv_rows = (size_t)d->B * ((d->H + 7) / 8) * ((d->W + 15) / 16);
@@ -394,7 +386,7 @@ extern "C" int bx_block_tail_fwd(const bxTailDesc* d, const void* y3, const void
                        w1x1, Cin, wT, tree, fin));
   BX_CHECK_LAUNCH("bx_block_tail_fwd(pool)");
   // folded finalize: the apply kernel's workgroups sum the partial rows themselves (no k_bn_finalize launch)
-  const bool fold = d->training && !in_launch && (tail_fold() & 2) && tail_fold_ok(g) && (long long)nblk * g.C <= tail_fold_rc(true);
+  const bool fold = d->training && !in_launch && (tail_fold() & 2) && tail_fold_ok(g) && (long long)nblk * g.C <= TAIL_FOLD_RC_FWD;
   TailFwdPro pro = {};
   if (fold)
     pro = TailFwdPro{partials, nblk, BxBnFinalize{bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, d->momentum, d->eps, scale, shift,
@@ -405,7 +397,7 @@ extern "C" int bx_block_tail_fwd(const bxTailDesc* d, const void* y3, const void
     BX_CHECK_LAUNCH("bx_block_tail_fwd(finalize)");
   }
   const bool ev = !d->training;
-  const int napply = fold && tail_blocks_all(g) > tail_fold_grid() ? tail_fold_grid() : tail_blocks_all(g);
+  const int napply = fold && tail_blocks_all(g) > TAIL_FOLD_GRID ? TAIL_FOLD_GRID : tail_blocks_all(g);
   BX_DISPATCH_DTYPE(d->dtype, T,
     hipLaunchKernelGGL((k_tail_apply<T, 8>), dim3(napply), dim3(256), xs_bytes, s, (const T*)pooled, (const T*)x, wT, Cin, b1x1,
                        scale, shift, seed, p, d->salt, (T*)out, g, ev ? bn_weight : (const float*)nullptr, bn_bias, (const float*)running_mean,
@@ -459,7 +451,7 @@ extern "C" int bx_block_conv3_tail_fwd(const bxTailDesc* d, const void* y2, cons
   // few partial rows (the late stages: one per 8 x 32 tile or per image): the apply kernel's workgroups sum them themselves
   // (and at most 1 024 rows: stage 1's 2 048 rows x 16 channels fit the rows x C bound, but its apply kernel -- HBM-bound, 4 096 one-trip
   // workgroups -- loses more under the 512-workgroup cap of a folded consumer (23 -> 33 us) than the 8 us finalize launch costs)
-  const bool fold = d->training && !pe.tree.cnt && (tail_fold() & 2) && tail_fold_ok(g) && (long long)pe.tree.nrows * g.C <= tail_fold_rc(true)
+  const bool fold = d->training && !pe.tree.cnt && (tail_fold() & 2) && tail_fold_ok(g) && (long long)pe.tree.nrows * g.C <= TAIL_FOLD_RC_FWD
                     && pe.tree.nrows <= 1024;
   TailFwdPro pro = {};
   if (fold) pro = TailFwdPro{partials, pe.tree.nrows, pe.fin};
@@ -470,7 +462,7 @@ extern "C" int bx_block_conv3_tail_fwd(const bxTailDesc* d, const void* y2, cons
   }
   const float p = d->training ? d->dropout_p : 0.f;
   const bool ev = !d->training;
-  const int napply = fold && tail_blocks_all(g) > tail_fold_grid() ? tail_fold_grid() : tail_blocks_all(g);
+  const int napply = fold && tail_blocks_all(g) > TAIL_FOLD_GRID ? TAIL_FOLD_GRID : tail_blocks_all(g);
   hipLaunchKernelGGL((k_tail_apply<bf16_t, 8>), dim3(napply), dim3(256), xs_bytes, s, (const bf16_t*)pooled, (const bf16_t*)x, wT, Cin, b1x1,
                      scale, shift, seed, p, d->salt, (bf16_t*)out, g, ev ? bn_weight : (const float*)nullptr, bn_bias, (const float*)running_mean,
                      (const float*)running_var, d->eps, save_mean, save_invstd, pro);
@@ -1110,8 +1102,7 @@ extern "C" int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const vo
 
   // ---- front: reduction | w1x1 weight-gradient partials | skip input gradient
   const bool even = (g.H % 2 == 0) && (g.W % 2 == 0);
-  static const int no_mfma = getenv("BX_SKIP_NO_MFMA") ? atoi(getenv("BX_SKIP_NO_MFMA")) : 0;
-  const int mf = (dx_skip && !no_mfma && d->dtype == BX_BF16 && g.C % 32 == 0 && (g.Cin_p == 16 || g.Cin_p == 32 || g.Cin_p == 64 || g.Cin_p == 128))
+  const int mf = (dx_skip && d->dtype == BX_BF16 && g.C % 32 == 0 && (g.Cin_p == 16 || g.Cin_p == 32 || g.Cin_p == 64 || g.Cin_p == 128))
                  ? g.Cin_p : 0;
   const bool wbig = mf >= 64 && g.C % 64 == 0;                 // 64 x 64 weight-gradient tiles (kernel: MF >= 64)
   BX_REQUIRE(mf < 64 || wbig, "bx_block_tail_bwd: C must be a multiple of 64 when Cin_p >= 64");
@@ -1120,11 +1111,11 @@ extern "C" int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const vo
     // up to ~4096 workgroups in total; partial buffer = nchunk * C * Cin_p floats <= 2048*256 + 64*C*Cin_p (workspace formula)
     const int otiles = wg_y * wg_z;
     nchunk = (int)((g.npool + 63) / 64);
-    // one output tile (first stage): 1 024 chunks of eight 64-pixel trips; more, shorter chunks do not help (BX_TAIL_W1_CAP sweep:
+    // one output tile (first stage): 1 024 chunks of eight 64-pixel trips; more, shorter chunks do not help (sweep of that cap:
     // 1024 1.472, 2048 1.474, 4096 1.479 ms/step) -- the role is bound by its per-trip work, not by the chain of trips.  Role times at
     // stage 1, measured by launching the front kernel with one role at a time: BN reduction 16.9 us, this role 28.4 -> 23.5 us with
     // the transposed tiles, together 36.8 -> 33.8 us.
-    static const int cap1 = getenv("BX_TAIL_W1_CAP") ? atoi(getenv("BX_TAIL_W1_CAP")) : 1024;
+    constexpr int cap1 = 1024;
     int cap = otiles == 1 ? cap1 : 4096 / otiles;
     if (cap < 64) cap = 64;
     while ((size_t)cap * g.C * g.Cin_p > (size_t)2048 * 256 + (size_t)64 * g.C * g.Cin_p) cap /= 2;
@@ -1138,7 +1129,7 @@ extern "C" int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const vo
   const int n_w = nchunk * wg_y * wg_z;
   const size_t front_lds = (dx_skip && !mf) ? (size_t)64 * g.Cin_p * sizeof(float) : 0;
   const bool in_launch = d->sync && 256 % g.C == 0 && nblk <= bx_tree_max_rows();
-  // folded finalize: the reduction role writes few rows (rows x C <= BX_TAIL_FOLD_RC), every apply workgroup sums them itself
+  // folded finalize: the reduction role writes few rows (rows x C <= TAIL_FOLD_RC_BWD), every apply workgroup sums them itself
   const bool fold = !in_launch && (tail_fold() & 1) && tail_fold_ok(g);
   const int nred = fold && nblk > tail_fold_rows(g.C) ? tail_fold_rows(g.C) : nblk;
   BxStatTree tree = {};
@@ -1173,7 +1164,7 @@ extern "C" int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const vo
   TailWsum wsum = {};
   TailBwdPro pro = {};
   int n_sum256 = 0;
-  const int napply = fold && tail_blocks_all(g) > tail_fold_grid() ? tail_fold_grid() : tail_blocks_all(g);
+  const int napply = fold && tail_blocks_all(g) > TAIL_FOLD_GRID ? TAIL_FOLD_GRID : tail_blocks_all(g);
   if (fold) {
     pro = TailBwdPro{partials, nred, TailBwdFin{bn_weight, save_invstd, coef, d_bn_weight, d_bn_bias, d_b1x1, (double)g.npool, d->training}};
     if (d_w1x1) {

@@ -337,18 +337,7 @@ class MultimodalModel(nn.Module):
                 sf = sm.features(spectrogram_data, seed=ss, cut=cut, packed=packed)
             return ops.MultimodalHeadFn.apply(sf.permute(0, 2, 3, 1), ef, sm.fc.weight, sm.fc.bias, em.dense.weight, em.dense.bias,
                                               self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
-        if ops.OVERLAP and eeg_data.is_cuda and ops.CONV_PROFILE is None:
-            # the EEG branch (small, latency-bound kernels) runs on a side stream beside the spectrogram branch; autograd
-            # replays each branch's backward on the stream its forward ran on, so the backward overlaps too
-            cur = torch.cuda.current_stream()
-            side = ops.side_stream("eeg", eeg_data.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                e = self.eeg_model(eeg_data)
-            s = self.spectrogram_model(spectrogram_data)
-            cur.wait_stream(side)
-            e.record_stream(cur)
-        elif self._fusable():
+        if self._fusable():
             # one launch for GAP+fc, dense and the fusion head (same arithmetic as the three separate ops below)
             em, sm = self.eeg_model, self.spectrogram_model
             ss = se = packed = None

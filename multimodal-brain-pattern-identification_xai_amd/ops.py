@@ -18,13 +18,7 @@ CONV_ALGO = L.BX_ALGO_AUTO        # module-level switch used by tests to force t
 WGRAD_ALGO = L.BX_ALGO_AUTO
 CONV_PROFILE = None               # bench.py sets a list: every conv launch appends (kind, start_event, end_event, meta); meta =
                                   # (form, B, H, W, Ci, Co) with form "conv" | "pair" (two layers, Co = both widths) | "conv3+pool"
-# Multi-stream overlap (most kernels of this model are latency-bound and leave CUs idle): weight-gradient kernels run
-# on a side stream beside the data-gradient chain, the EEG branch beside the spectrogram branch.  join_side_streams()
-# must run before anything consumes the gradients (FlatAdamW.step / DataParallel.sync_gradients do it).
-# Measured on MI355X (round 1): +2 % under hipGraph replay, -10 % when launching eagerly (host-side stream switches),
-# so it is OFF by default; BX_OVERLAP=1 turns it on.
 import os as _os
-OVERLAP = _os.environ.get("BX_OVERLAP", "0") == "1"
 # The EEG branch on a side stream beside the spectrogram branch (one fork / join per direction; round 3).  BX_OVERLAP_EEG: 0 = never,
 # 1 (default) = inside captured hipGraphs (GraphedTrainStep, GradCamSweep: two parallel chains of the graph), 2 = also when launching
 # eagerly (host-side stream switches make that slower than the serial order).  Same kernels, same arithmetic: the overlapped step
@@ -68,27 +62,12 @@ def side_stream(name: str, device) -> "torch.cuda.Stream":
 
 
 def join_side_streams(device=None):
+    """The current stream waits for every side stream.  Must run before anything consumes the gradients (the EEG branch's
+    backward may still run on its side stream): FlatAdamW.gather_grads and DataParallel.sync_gradients do it."""
     cur = torch.cuda.current_stream()
     for (name, idx), st in _SIDE.items():
         if device is None or idx == (device.index if device.index is not None else torch.cuda.current_device()):
             cur.wait_stream(st)
-
-
-_JOIN_QUEUED = [False]
-
-
-def _join_after_backward():
-    """Queue ONE engine callback per backward pass: when autograd finishes, the caller's stream waits for the side
-    streams, so `p.grad` is safe to read right after `loss.backward()` returns (eager users, torch optimizers)."""
-    if _JOIN_QUEUED[0]:
-        return
-
-    def _cb():
-        _JOIN_QUEUED[0] = False
-        join_side_streams()
-
-    _JOIN_QUEUED[0] = True
-    torch.autograd.Variable._execution_engine.queue_callback(_cb)
 
 
 class _Timed:
@@ -701,18 +680,8 @@ class BlockFn(torch.autograd.Function):
         bss = (b1, b2, b3)
         grads_w, grads_b = [None] * 3, [None] * 3
         dz = dz3
-        use_side = OVERLAP and need_w and CONV_PROFILE is None
-        side = side_stream("wgrad", x.device) if use_side else None
-        if use_side:
-            _join_after_backward()
         for k in (2, 1, 0):
-            if need_w and side is not None:
-                # dW/db of this layer only feed the optimizer: compute them beside the data-gradient chain
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    grads_w[k], grads_b[k] = _wgrad(acts[k], dz, wts[k], bss[k])
-                dz.record_stream(side); acts[k].record_stream(side)
-            elif need_w:
+            if need_w:
                 grads_w[k], grads_b[k] = _wgrad(acts[k], dz, wts[k], bss[k], chain=True)
             packed = cfg.prepacked.get(cfg.pack_base + k, True) if cfg.prepacked is not None else None
             if k > 0:
@@ -722,8 +691,8 @@ class BlockFn(torch.autograd.Function):
                 if cfg.preact == k:
                     cfg.capture["grad"] = dz
             elif need_dx:
-                dz = _conv(dz, packed or _pack(wts[0], flip=True, dtype=dt), None, None, dx_skip, False, dt, carry=need_w and side is None)
-        if need_w and side is None:
+                dz = _conv(dz, packed or _pack(wts[0], flip=True, dtype=dt), None, None, dx_skip, False, dt, carry=need_w)
+        if need_w:
             wgrad_flush(x.device)                           # conv1's partial sum: nothing may be pending when the gradients are returned
         dx = dz if need_dx else None
         if not need_bn:

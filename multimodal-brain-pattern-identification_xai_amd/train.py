@@ -118,8 +118,8 @@ class FlatAdamW(torch.optim.Optimizer):
         """Make the gradient arena hold the gradients of parameters [first, last) (default: all); a no-op for slices the
         kernels wrote, zero for parameters that received no gradient."""
         if self.is_cuda:
-            ops.join_side_streams(self.flat_g.device)      # weight-gradient kernels may still run on the side stream
-            ops.wgrad_flush(self.flat_g.device)            # normally done by backward's end callback; no-op then
+            ops.join_side_streams(self.flat_g.device)      # the EEG branch's backward may still run on its side stream
+            ops.wgrad_flush(self.flat_g.device)            # normally done at the end of each Block's backward; no-op then
         base = self.flat_g.data_ptr()
         last = len(self.params) if last is None else last
         for p, off in zip(self.params[first:last], self.offsets[first:last]):
@@ -253,7 +253,7 @@ class DataParallel(nn.Module):
             flat = optimizer.flat_g
         else:
             if torch.cuda.is_available():
-                ops.join_side_streams()
+                ops.join_side_streams()                    # the EEG branch's backward may still run on its side stream
             grads = [p.grad for p in self.module.parameters() if p.grad is not None]
             flat = torch.cat([g.reshape(-1) for g in grads])
         if flat.is_cuda:
