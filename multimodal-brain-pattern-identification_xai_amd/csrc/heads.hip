@@ -380,7 +380,7 @@ __device__ __forceinline__ float mmh_wave_dot(const float* __restrict__ wrow, co
   return wave_sum(acc);
 }
 
-// FAST (2N <= 12, N <= 8, K <= 1024, C <= 1024): every weight a thread will need is loaded into registers at kernel start,
+// FAST (2N <= 12, i.e. N <= 6, K <= 1024, C <= 1024: three [dense ; fc] rows per wave, 12 fc1 entries per thread): every weight a thread will need is loaded into registers at kernel start,
 // together with the feature loads, so the chain gap -> logits -> hidden -> logits costs one memory round trip instead of six.
 template <typename T, bool FAST>
 __global__ __launch_bounds__(256) void k_mm_head_fwd(const T* __restrict__ feat, const float* __restrict__ ef, const float* __restrict__ fcw,

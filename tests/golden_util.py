@@ -53,7 +53,7 @@ def grad_close(got, want, tol, label="", floor=0.0, flips=None):
     err = float(d.max() / scale)
     frac = float((d > tol * scale).double().mean())
     REPORT.append((label, err, frac))
-    if err > tol:
+    if not err <= tol:          # (a NaN anywhere makes err NaN, which `err > tol` would let through)
         hint = ""
         if flips:
             hint = (f"; the forward under test flipped {len(flips)} activation decision(s) against the exact forward ({describe_flips(flips)}): "

@@ -47,6 +47,29 @@ def test_error_convention_without_gpu():
     assert lib.bx_eeg_workspace(ctypes.byref(e)) > 0
 
 
+@pytest.mark.parametrize("n", [1, 2, 3, 6, 7, 8, 16, 17, 32, 33])
+def test_head_route_by_class_count(n):
+    """MultimodalModel takes the fused head up to 16 classes (fc1 width 128 * 2N <= 4096) and the three separate heads from 17
+    on; EEGNetAttentionDeep's head holds at most 16 classes (bx_eeg_deep_saved_bytes: 0 = unsupported, checked before a launch)."""
+    net = brainxai.build_multimodal(19, 2000, 4, num_classes=n)
+    assert net.fc2.out_features == net.eeg_model.dense.out_features == net.spectrogram_model.fc.out_features == n
+    assert net.fc1.in_features == 2 * n
+    assert net._fusable() == (n <= 16)
+    deep = brainxai.EEGNetAttentionDeep(n, Chans=19, Samples=2000)
+    g = deep._geom
+    d = _lib.EegDeepDesc(2, 2000 // (g.P1 * g.P2), g.F2, g.F3, g.K3, g.P3, deep.dense1.out_features, deep.dense2.out_features, 0, 1e-5,
+                         0.1, 0.0, 0)
+    assert (_lib.load().bx_eeg_deep_saved_bytes(ctypes.byref(d)) > 0) == (n <= 16)
+
+
+def test_grad_close_fails_on_nan():
+    """a NaN in the result (an unguarded 0 * log 0, say) makes the max error NaN, which must fail, not pass, the comparison"""
+    from tests.golden_util import grad_close
+    with pytest.raises(AssertionError, match="nan"):
+        grad_close(torch.tensor([1.0, float("nan")]), torch.tensor([1.0, 2.0]), 1e-3, label="nan")
+    assert grad_close(torch.tensor([1.0, 2.0]), torch.tensor([1.0, 2.0]), 1e-3) == 0.0
+
+
 def test_state_dict_layout_matches_reference():
     man = json.load(open(os.path.join(GOLDEN, "state_dict_manifest.json")))
     nets = {"Block(4,16)": brainxai.Block(4, 16), "Spectrogram_Model": brainxai.Spectrogram_Model(6),
