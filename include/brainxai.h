@@ -143,6 +143,20 @@ int bx_conv3x3_wgrad_finish(bxWgradPending* pending, bxStream stream);
 int bx_conv3x3_carry(const void* x, const float* packed_f32, const void* packed_mfma, const float* bias,
                      const void* relu_mask_src, const void* addend, void* y, int B, int H, int W, int Ci, int Co,
                      int dtype, int flags, int algo, bxWgradPending* pending, bxStream stream);
+/* Stage 1's backward, bf16 storage: the data AND weight gradient of a 16 -> 16 conv3x3 layer in one pass over dz (one kernel).
+ *   dz [B,H,W,16] = dZ_L, xl [B,H,W,16] = X_L = relu(z_{L-1}) (the layer's input), packed_flip = bx_conv3x3_pack's data-gradient
+ *   operand (transpose_flip) of W_L.
+ *   dzo != NULL, x0 == NULL: dzo = conv(dz, flipped W_L) * (xl > 0) -- bit-identical to bx_conv3x3 with that mask -- and
+ *     dw / db [16,16,3,3] / [16] = bx_conv3x3_wgrad(xl, dz) up to fp32 reassociation.  Chained like bx_conv3x3_wgrad_chained: a valid
+ *     *pending is summed by this launch and overwritten with dw / db's partials (pending == NULL: they are summed right away).
+ *   dzo == NULL, x0 != NULL (the stage's conv2, block input without a gradient): the masked data gradient dZ_{L-1} is not stored;
+ *     instead dw0 / db0 [16,Cin0,3,3] / [16] = bx_conv3x3_wgrad(x0, dZ_{L-1}) with x0 [B,H,W,8] the padded block input (Cin0 <= 8
+ *     logical channels).  Both weight gradients are summed by one reduce launch that follows; *pending is invalid on return.
+ *   workspace: bx_conv3x3_bwd_fused_workspace(B, H, W, x0 != NULL) bytes, not the one holding valid pending partials. */
+size_t bx_conv3x3_bwd_fused_workspace(int B, int H, int W, int with_w1);
+int bx_conv3x3_bwd_fused(const void* dz, const void* xl, const void* packed_flip, void* dzo, const void* x0, float* dw, float* db,
+                         float* dw0, float* db0, int B, int H, int W, int Cin0, void* workspace, size_t workspace_bytes,
+                         bxWgradPending* pending, bxStream stream);
 
 /* Measurement hook: the next bx_block_conv3_tail_fwd call of this host thread records the two hipEvent_t (created by the caller,
  * timing enabled) immediately before and after its convolution kernel on the call's stream -- bench.py times the fused conv3 +

@@ -91,6 +91,8 @@ SIGNATURES = {
     "bx_conv3x3_wgrad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "bx_conv3x3_wgrad_chained": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, P(WgradPending), vp]),
     "bx_conv3x3_wgrad_finish": (i32, [P(WgradPending), vp]),
+    "bx_conv3x3_bwd_fused_workspace": (sz, [i32, i32, i32, i32]),
+    "bx_conv3x3_bwd_fused": (i32, [vp] * 9 + [i32] * 4 + [vp, sz, P(WgradPending), vp]),
     "bx_block_tail_workspace": (sz, [P(TailDesc)]),
     "bx_block_tail_fwd": (i32, [P(TailDesc), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "bx_set_tree_max_rows": (i32, [i32]),

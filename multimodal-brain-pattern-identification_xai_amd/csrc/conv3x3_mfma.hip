@@ -1622,9 +1622,12 @@ __device__ __forceinline__ void wgrad_reduce3_body(const WgradRedJob& jb, int bi
     }
   }
 }
-__global__ __launch_bounds__(256) void k_wgrad_reduce3(WgradRedJob jb) {
+// jb2: a second job in the same launch (workgroups from jb.nblocks on; nblocks == 0: none) -- the two weight gradients of
+// stage 1's fused conv2 backward (k_conv_mfma_bwd<true>)
+__global__ __launch_bounds__(256) void k_wgrad_reduce3(WgradRedJob jb, WgradRedJob jb2) {
   __shared__ float4 sm[256];
-  wgrad_reduce3_body(jb, blockIdx.x, sm);
+  if ((int)blockIdx.x < jb.nblocks) wgrad_reduce3_body(jb, blockIdx.x, sm);
+  else wgrad_reduce3_body(jb2, (int)blockIdx.x - jb.nblocks, sm);
 }
 
 // ================================================================================================
@@ -2095,8 +2098,8 @@ static WgradRedJob wgrad_job_from(const bxWgradPending* pd, bool chained) {
 }
 int bx_wgrad_mfma_finish(bxWgradPending* pd, hipStream_t s) {
   if (!pd || !pd->valid) return BX_OK;
-  const WgradRedJob jb = wgrad_job_from(pd, false);
-  hipLaunchKernelGGL(k_wgrad_reduce3, dim3(jb.nblocks), dim3(256), 0, s, jb);
+  const WgradRedJob jb = wgrad_job_from(pd, false), none = {};
+  hipLaunchKernelGGL(k_wgrad_reduce3, dim3(jb.nblocks), dim3(256), 0, s, jb, none);
   pd->valid = 0;
   BX_CHECK_LAUNCH("bx_conv3x3_wgrad(mfma reduce)");
   return BX_OK;
@@ -2145,4 +2148,295 @@ int bx_wgrad_mfma_launch(const void* x, const void* dz, float* dw, float* db, in
   cur.ztiles = p.ztiles; cur.nfrag4 = p.ytiles * p.ztiles * 9 * p.ma * p.nb * 64; cur.valid = 1;
   if (pending) { *pending = cur; return BX_OK; }
   return bx_wgrad_mfma_finish(&cur, s);
+}
+
+// ================================================================================================
+// Stage 1's backward (k_conv_mfma_bwd): the data AND the weight gradient of a 16 -> 16 layer in one pass over dZ.
+//   The two kernels this replaces (k_conv_mfma_p<16,1,32> data gradient, k_wgrad_mfma<1,1,32> weight gradient) are bound by HBM bytes
+//   at 128 x 256, and each read dZ_L on its own; the data gradient also read the ReLU bits of X_L = relu(z_{L-1}) that the weight
+//   gradient's operand X_L carries anyway.  Here a workgroup stages, per 8 x 32 tile, the 10 x 34 halos of dZ_L and X_L in LDS
+//   ([pixel][16 ch] bf16, 32 bytes a pixel: the layout of k_conv_mfma_p's CK = 16 halo and of k_wgrad_mfma's x tile alike) and
+//   - data gradient: k_conv_mfma_p's main loop and epilogue operation for operation (same K order, same packed flipped weights), masked
+//     by (X_L > 0) read from the staged X_L centre -- the decision relu_bits stored -- so dZ_{L-1} is bit-identical;
+//   - weight gradient: k_wgrad_mfma's K-steps on the centre of the same dZ_L image (transposing reads; row stride 34 pixels instead
+//     of 32) against the X_L halo, 9 accumulator tiles per wave across the workgroup's contiguous tile range, bias sums from the
+//     dZ fragments; partials in k_wgrad_mfma's fragment order (split = workgroup), so k_wgrad_reduce3 and the chaining apply.
+//   W1 (conv2 of the stage, block input without a gradient): dZ_{L-1} (= dZ1) is not stored.  The masked tile, rounded to bf16 as
+//   it would have been stored, goes to LDS pixel-major and conv1's weight gradient accumulates against the halo of the 8-channel
+//   padded block input x0 (staged as 16 channels, the upper 8 zero): dZ1 never makes its 2 x 67 MB round trip through HBM.
+//   Each wave's weight-gradient K-steps are the tile rows its own data-gradient tiles cover (rows 2w, 2w + 1), so a wave reads only
+//   dZ1 rows it wrote itself (in-order LDS, no barrier).
+//   A pending weight-gradient sum rides in the first `nred` workgroups, as in the convolution launches.
+__device__ __forceinline__ void wgrad_store_1x1(f32x4 (&acc)[9], float bsum, float* __restrict__ out, char* lds) {
+  // k_wgrad_mfma's cross-wave reduce-scatter (fixed order) for MA = NB = 1, then the fragments and the 16 bias sums
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  constexpr int NT = 9, SLOTS = 3;
+  float4* red4 = reinterpret_cast<float4*>(lds);       // [4 writers][SLOTS][64]
+  __syncthreads();
+#pragma unroll
+  for (int s = 1; s < 4; ++s) {
+    const int dst = (wave + s) & 3, src = (wave - s) & 3;
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+      if ((i & 3) == dst) red4[(wave * SLOTS + i / 4) * 64 + lane] = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+      if ((i & 3) == wave) {
+        const float4 v = red4[(src * SLOTS + i / 4) * 64 + lane];
+        acc[i][0] += v.x; acc[i][1] += v.y; acc[i][2] += v.z; acc[i][3] += v.w;
+      }
+    __syncthreads();
+  }
+  float4* out4 = reinterpret_cast<float4*>(out);
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+    if ((i & 3) == wave) out4[i * 64 + lane] = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+  float* red = reinterpret_cast<float*>(lds);
+  float v = bsum;
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  if (lane < 16) red[wave * 16 + lane] = v;
+  __syncthreads();
+  if (threadIdx.x < 16) out[NT * 256 + threadIdx.x] = red[threadIdx.x] + red[16 + threadIdx.x] + red[32 + threadIdx.x] + red[48 + threadIdx.x];
+}
+
+template <bool W1>
+__global__ __launch_bounds__(256, 2) void k_conv_mfma_bwd(const bf16_t* __restrict__ dz, const bf16_t* __restrict__ xl, const bf16_t* __restrict__ wp,
+    const bf16_t* __restrict__ x0, bf16_t* __restrict__ dzo, float* __restrict__ partial, int H, int W, int tiles_x, int tiles_y, int ntiles,
+    int tps, int nsplit, uint32_t act_bytes, WgradRedJob red, int nred) {
+  constexpr int TH = 8, TW = 32, HWID = TW + 2, HH = TH + 2, PB = 32, KS = 5, MP = TH * TW / 64, TPR = TW / 16;
+  constexpr int NU = HH * HWID * 2, NR = (NU + 255) / 256;           // 16-byte units of a 16-channel halo
+  constexpr int NU0 = HH * HWID, NR0 = (NU0 + 255) / 256;            // ... of the 8-channel x0 halo
+  constexpr int IMG = HH * HWID * PB;
+  constexpr int PER_SPLIT = 9 * 256 + 16;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  if ((int)blockIdx.x < nred) {
+    if ((int)blockIdx.x < red.nblocks) wgrad_reduce3_body(red, (int)blockIdx.x, reinterpret_cast<float4*>(lds));
+    return;
+  }
+  const int split = (int)blockIdx.x - nred;
+  char* zs = lds;                    // dZ_L halo
+  char* xs = lds + IMG;              // X_L halo
+  char* x0s = lds + 2 * IMG;         // W1: x0 halo (16-channel records, upper half zero)
+  char* d1s = lds + 3 * IMG;         // W1: dZ_{L-1} tile [8 x 32][16 ch]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
+  const int q = li >> 2, pc = li & 3;
+  const __amdgpu_buffer_rsrc_t zres = __builtin_amdgcn_make_buffer_rsrc((void*)dz, 0, act_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)xl, 0, act_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t x0res = __builtin_amdgcn_make_buffer_rsrc((void*)(W1 ? x0 : xl), 0, W1 ? act_bytes / 2 : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t yres = __builtin_amdgcn_make_buffer_rsrc((void*)(W1 ? xl : dzo), 0, W1 ? 0u : act_bytes, 0x00020000);
+  int hpy[NR], hpx[NR];
+  uint32_t hrel[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const int u = threadIdx.x + k * 256;
+    const int p = u / 2, c = u % 2;
+    hpy[k] = u < NU ? p / HWID - 1 : -100000;
+    hpx[k] = p % HWID - 1;
+    hrel[k] = (uint32_t)(((p / HWID - 1) * W + (p % HWID - 1)) * 16 + c * 8) * 2u;
+  }
+  int h0y[NR0], h0x[NR0];
+  uint32_t h0rel[NR0];
+#pragma unroll
+  for (int k = 0; k < NR0; ++k) {
+    const int p = threadIdx.x + k * 256;
+    h0y[k] = p < NU0 ? p / HWID - 1 : -100000;
+    h0x[k] = p % HWID - 1;
+    h0rel[k] = (uint32_t)(((p / HWID - 1) * W + (p % HWID - 1)) * 8) * 2u;
+  }
+  uint4 rz[NR], rx[NR], r0[W1 ? NR0 : 1];
+  auto fetch = [&](int tile) {
+    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
+    const int y0 = ty * TH, xo = tx * TW;
+    const uint32_t pix0 = (uint32_t)((b * H + y0) * W + xo);
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const bool ok = (unsigned)(y0 + hpy[k]) < (unsigned)H && (unsigned)(xo + hpx[k]) < (unsigned)W;
+      const uint32_t off = ok ? pix0 * 32u + hrel[k] : 0x80000000u;
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(zres, off, 0, 0);
+      const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(xres, off, 0, 0);
+      rz[k] = make_uint4(v.x, v.y, v.z, v.w);
+      rx[k] = make_uint4(w.x, w.y, w.z, w.w);
+    }
+    if constexpr (W1) {
+#pragma unroll
+      for (int k = 0; k < NR0; ++k) {
+        const bool ok = (unsigned)(y0 + h0y[k]) < (unsigned)H && (unsigned)(xo + h0x[k]) < (unsigned)W;
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(x0res, ok ? pix0 * 16u + h0rel[k] : 0x80000000u, 0, 0);
+        r0[k] = make_uint4(v.x, v.y, v.z, v.w);
+      }
+    }
+  };
+  if constexpr (W1) {
+    for (int p = threadIdx.x; p < NU0; p += 256) *reinterpret_cast<uint4*>(x0s + p * PB + 16) = make_uint4(0u, 0u, 0u, 0u);
+  }
+  f32x4 aw[9], aw1[W1 ? 9 : 1];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) aw[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < (W1 ? 9 : 1); ++t) aw1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f, bsum1 = 0.f;
+  const int t_begin = split * tps;
+  const int t_end = t_begin + tps < ntiles ? t_begin + tps : ntiles;
+  if (t_begin < t_end) fetch(t_begin);
+  for (int tile = t_begin; tile < t_end; ++tile) {
+    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
+    const int y0 = ty * TH, xo = tx * TW;
+    __syncthreads();                          // previous tile's reads are done
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int u = threadIdx.x + k * 256;
+      if (u < NU) {
+        *reinterpret_cast<uint4*>(zs + u * 16) = rz[k];
+        *reinterpret_cast<uint4*>(xs + u * 16) = rx[k];
+      }
+    }
+    if constexpr (W1) {
+#pragma unroll
+      for (int k = 0; k < NR0; ++k) {
+        const int p = threadIdx.x + k * 256;
+        if (p < NU0) *reinterpret_cast<uint4*>(x0s + p * PB) = r0[k];
+      }
+    }
+    __syncthreads();
+    if (tile + 1 < t_end) fetch(tile + 1);
+    // ---- data gradient (k_conv_mfma_p<16, 1, 32>'s loop)
+    f32x4 acc[MP];
+#pragma unroll
+    for (int i = 0; i < MP; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bf16x8 a[3];
+    auto load_a = [&](int s, bf16x8& dst) { dst = *reinterpret_cast<const bf16x8*>(wp + ((size_t)s * 16 + li) * 32 + 8 * g); };
+    load_a(0, a[0]);
+    load_a(1, a[1]);
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      if (s + 2 < KS) load_a(s + 2, a[(s + 2) % 3]);
+      __builtin_amdgcn_sched_barrier(0);
+      const int q0 = s * 32 + 8 * g;
+      int tap = q0 / 16;
+      const int c = (q0 % 16) / 8;
+      const bool valid = tap < 9;
+      if (!valid) tap = 0;
+      const int dy = tap / 3, dx = tap - 3 * dy;
+#pragma unroll
+      for (int i = 0; i < MP; ++i) {
+        const int t = wave * MP + i;
+        const int p = (t / TPR + dy) * HWID + (t % TPR) * 16 + li + dx;
+        bf16x8 bv = *reinterpret_cast<const bf16x8*>(zs + p * PB + 16 * c);
+        if (!valid) bv = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s % 3], bv, acc[i], 0, 0, 0);
+      }
+    }
+    // epilogue: v = acc + 0 (no bias), masked by (X_L > 0) of the staged centre, rounded to bf16
+#pragma unroll
+    for (int i = 0; i < MP; ++i) {
+      const int t = wave * MP + i;
+      const int r = t / TPR, col = (t % TPR) * 16 + li;
+      const u32x2 m = *reinterpret_cast<const u32x2*>(xs + ((r + 1) * HWID + col + 1) * PB + 8 * g);
+      const uint32_t mm[4] = {m.x & 0xffffu, m.x >> 16, m.y & 0xffffu, m.y >> 16};
+      float v[4] = {acc[i][0] + 0.f, acc[i][1] + 0.f, acc[i][2] + 0.f, acc[i][3] + 0.f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = (mm[j] != 0u && mm[j] < 0x8000u) ? v[j] : 0.f;
+      const u32x2 out = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+      if constexpr (W1) {
+        *reinterpret_cast<u32x2*>(d1s + (r * TW + col) * PB + 8 * g) = out;       // out-of-image pixels: X_L = 0 there, so 0
+      } else {
+        const bool inb = y0 + r < H && xo + col < W;
+        const uint32_t off = inb ? (uint32_t)((((b * H + y0 + r) * W + xo + col) * 16 + 4 * g) * 2) : 0x80000000u;
+        __builtin_amdgcn_raw_buffer_store_b64(out, yres, off, 0, 0);
+      }
+    }
+    // ---- weight gradient(s) (k_wgrad_mfma<1, 1, 32>'s K-steps): rows 2w, 2w + 1 of the tile.  The scheduling barriers keep the
+    //      phases apart: interleaved, their operand reads outlive the 256-register budget of two workgroups per CU.
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      __builtin_amdgcn_sched_barrier(0);
+      const int row = wave * 2 + ks;
+      const int col0 = 8 * g + q, col1 = 8 * g + 4 + q;
+      const bf16x8 bfr = tr_read8(zs, ((row + 1) * HWID + col0 + 1) * PB + 8 * pc, ((row + 1) * HWID + col1 + 1) * PB + 8 * pc);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) bsum += __uint_as_float(((uint32_t)(unsigned short)bfr[j]) << 16);
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int dy = tap / 3, dx = tap % 3;
+        const bf16x8 afr = tr_read8(xs, ((row + dy) * HWID + col0 + dx) * PB + 8 * pc, ((row + dy) * HWID + col1 + dx) * PB + 8 * pc);
+        aw[tap] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr, aw[tap], 0, 0, 0);
+      }
+      if constexpr (W1) {
+        __builtin_amdgcn_sched_barrier(0);
+        const bf16x8 bf1 = tr_read8(d1s, (row * TW + col0) * PB + 8 * pc, (row * TW + col1) * PB + 8 * pc);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) bsum1 += __uint_as_float(((uint32_t)(unsigned short)bf1[j]) << 16);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+          const int dy = tap / 3, dx = tap % 3;
+          const bf16x8 afr = tr_read8(x0s, ((row + dy) * HWID + col0 + dx) * PB + 8 * pc, ((row + dy) * HWID + col1 + dx) * PB + 8 * pc);
+          aw1[tap] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bf1, aw1[tap], 0, 0, 0);
+        }
+      }
+    }
+  }
+  wgrad_store_1x1(aw, bsum, partial + (size_t)split * PER_SPLIT, lds);
+  if constexpr (W1) wgrad_store_1x1(aw1, bsum1, partial + ((size_t)nsplit + split) * PER_SPLIT, lds);
+}
+
+struct FusedBwdPlan { int tiles_x, tiles_y, ntiles, tps, nsplit; };
+static FusedBwdPlan fused_bwd_plan(int B, int H, int W) {
+  FusedBwdPlan p;
+  p.tiles_x = (W + 31) / 32; p.tiles_y = (H + 7) / 8; p.ntiles = p.tiles_x * p.tiles_y * B;
+  // two workgroups per CU (k_wgrad_mfma's split count for this shape)
+  constexpr int want_wgs = 512;
+  const int want = want_wgs < p.ntiles ? want_wgs : p.ntiles;
+  p.tps = (p.ntiles + want - 1) / want;
+  p.nsplit = (p.ntiles + p.tps - 1) / p.tps;
+  return p;
+}
+extern "C" size_t bx_conv3x3_bwd_fused_workspace(int B, int H, int W, int with_w1) {
+  const FusedBwdPlan p = fused_bwd_plan(B, H, W);
+  return (size_t)p.nsplit * (9 * 256 + 16) * sizeof(float) * (with_w1 ? 2 : 1);
+}
+extern "C" int bx_conv3x3_bwd_fused(const void* dz, const void* xl, const void* packed_flip, void* dzo, const void* x0, float* dw, float* db,
+                                    float* dw0, float* db0, int B, int H, int W, int Cin0, void* ws, size_t ws_bytes, bxWgradPending* pending,
+                                    bxStream stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const bool w1 = x0 != nullptr;
+  BX_REQUIRE(dz && xl && packed_flip && dw && db && ws && B > 0 && H > 0 && W > 0, "bx_conv3x3_bwd_fused: bad arguments");
+  BX_REQUIRE(w1 ? (!dzo && dw0 && db0 && Cin0 > 0 && Cin0 <= 8) : (dzo && !dw0 && !db0),
+             "bx_conv3x3_bwd_fused: either dzo (data gradient stored) or x0 with dw0 / db0 (conv1's weight gradient, 1..8 input channels)");
+  BX_REQUIRE((size_t)B * H * W * 16 * 2 < ((size_t)1 << 31), "bx_conv3x3_bwd_fused: an activation tensor of 2 GiB or more is not supported");
+  const FusedBwdPlan p = fused_bwd_plan(B, H, W);
+  const size_t need = bx_conv3x3_bwd_fused_workspace(B, H, W, w1);
+  BX_REQUIRE(ws_bytes >= need, "bx_conv3x3_bwd_fused: workspace %zu < %zu", ws_bytes, need);
+  BX_REQUIRE(!pending || !pending->valid || pending->partial != ws, "bx_conv3x3_bwd_fused: the pending partials live in this call's workspace");
+  WgradRedJob prev = {};
+  int nred = 0;
+  if (pending && pending->valid) { prev = wgrad_job_from(pending, true); nred = prev.nblocks; pending->valid = 0; }
+  constexpr int IMG = 10 * 34 * 32;
+  const size_t lds = w1 ? (size_t)3 * IMG + 8 * 32 * 32 : (size_t)2 * IMG;        // >= the 12 KiB of the final reduce-scatter
+  const uint32_t act_bytes = (uint32_t)((size_t)B * H * W * 16 * 2);
+  float* part = (float*)ws;
+  if (w1)
+    hipLaunchKernelGGL((k_conv_mfma_bwd<true>), dim3((unsigned)(p.nsplit + nred)), dim3(256), lds, s, (const bf16_t*)dz, (const bf16_t*)xl,
+                       (const bf16_t*)packed_flip, (const bf16_t*)x0, (bf16_t*)nullptr, part, H, W, p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.nsplit,
+                       act_bytes, prev, nred);
+  else
+    hipLaunchKernelGGL((k_conv_mfma_bwd<false>), dim3((unsigned)(p.nsplit + nred)), dim3(256), lds, s, (const bf16_t*)dz, (const bf16_t*)xl,
+                       (const bf16_t*)packed_flip, (const bf16_t*)nullptr, (bf16_t*)dzo, part, H, W, p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.nsplit,
+                       act_bytes, prev, nred);
+  BX_CHECK_LAUNCH("bx_conv3x3_bwd_fused");
+  bxWgradPending cur = {};
+  cur.partial = part; cur.dw = dw; cur.db = db; cur.nsplit = p.nsplit; cur.Cin = 16; cur.Co = 16; cur.ma = 1; cur.nb = 1;
+  cur.ztiles = 1; cur.nfrag4 = 9 * 64; cur.valid = 1;
+  if (!w1) {
+    if (pending) { *pending = cur; return BX_OK; }
+    return bx_wgrad_mfma_finish(&cur, s);
+  }
+  // both weight gradients of the W1 form in ONE reduce launch; the chain ends here
+  bxWgradPending cur0 = cur;
+  cur0.partial = part + (size_t)p.nsplit * (9 * 256 + 16); cur0.dw = dw0; cur0.db = db0; cur0.Cin = Cin0;
+  const WgradRedJob j1 = wgrad_job_from(&cur, false), j0 = wgrad_job_from(&cur0, false);
+  hipLaunchKernelGGL(k_wgrad_reduce3, dim3((unsigned)(j1.nblocks + j0.nblocks)), dim3(256), 0, s, j1, j0);
+  BX_CHECK_LAUNCH("bx_conv3x3_bwd_fused(reduce)");
+  return BX_OK;
 }

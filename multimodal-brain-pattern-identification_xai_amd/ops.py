@@ -544,6 +544,39 @@ def _wgrad(x, dz, w: torch.Tensor, b: torch.Tensor, chain: bool = False):
     return dw, db
 
 
+def _bwd_fused(dz, xl, packed, w, b, x0, w0, b0):
+    """Stage 1's fused backward of one 16 -> 16 layer (bx_conv3x3_bwd_fused): dZ_{L-1} (None when x0 is given) and dW / db chained
+    like _wgrad's; with x0 (the padded block input) also conv1's dW0 / db0, summed together with dW / db before it returns."""
+    lib = L.load()
+    B, H, W, _ = dz.shape
+    st = _wg_chain_state(dz.device)
+    if st.pend.valid and st.stream != _stream():
+        wgrad_flush(dz.device)
+    need = lib.bx_conv3x3_bwd_fused_workspace(B, H, W, 1 if x0 is not None else 0)
+    buf = st.ring[st.slot]
+    if buf is None or buf.numel() < need:
+        if buf is not None:
+            st.retired.append(buf)                          # never freed: see _wgrad
+        big = max([int(need), 1 << 20] + [t.numel() for t in st.ring if t is not None])
+        buf = torch.empty(big, dtype=torch.uint8, device=dz.device)
+        st.ring[st.slot] = buf
+    st.stream = _stream()
+    dw, db = new_grad(w), new_grad(b)
+    dw0, db0 = (new_grad(w0), new_grad(b0)) if x0 is not None else (None, None)
+    dzo = torch.empty_like(dz) if x0 is None else None
+    if packed[1] is None or packed[4] != "bf16":
+        raise RuntimeError("brainxai: the fused stage-1 backward needs the bf16 MFMA data-gradient operand")
+    with _Timed("dgrad", ("conv", B, H, W, 16, 16)):
+        L.check(lib.bx_conv3x3_bwd_fused(_p(dz), _p(xl), _p(packed[1]), _p(dzo), _p(x0), _p(dw), _p(db), _p(dw0), _p(db0), B, H, W,
+                                         w0.shape[1], _p(buf), buf.numel(), C.byref(st.pend), st.stream), "bx_conv3x3_bwd_fused")
+    if x0 is None:
+        st.keep = (buf, dw, db)
+        st.slot ^= 1
+    else:
+        st.keep = None
+    return dw, db, dzo, (dw0, db0)
+
+
 def _tail_desc(x, shape, dt, cfg, route=None) -> L.TailDesc:
     B, H, W, Cc = shape
     return L.TailDesc(B, H, W, x.shape[3], Cc, L.BX_POOL_MAX if cfg.pool == "max" else L.BX_POOL_AVG, 1 if cfg.training else 0,
@@ -571,6 +604,7 @@ class BlockFn(torch.autograd.Function):
         packed3 = None
         first = 0
         masks = None
+        fuse_bwd = False
         # stage 1 (8 padded input channels -> 16 -> 16, bf16): conv1 and conv2 in one launch, conv1's output kept in LDS and written
         # out only when a backward pass (or a debugging hook) will read it
         if (CONV_PAIR and dt == torch.bfloat16 and CONV_ALGO != L.BX_ALGO_DIRECT and cfg.preact not in (1, 2)
@@ -583,7 +617,11 @@ class BlockFn(torch.autograd.Function):
                 need_y1 = cfg.keep is not None or (getattr(cfg, "grad_mode", True) and any(ctx.needs_input_grad[:11]))
                 y1 = torch.empty(B, H, W, w1.shape[0], dtype=dt, device=x.device) if need_y1 else None
                 y2 = torch.empty(B, H, W, w2.shape[0], dtype=dt, device=x.device)
-                if need_y1 and MASK_BITS and w1.shape[0] <= 32:     # the ReLU decisions of y1 / y2 as bits for the data gradients (1/8 of the
+                # the backward takes conv3's and conv2's data and weight gradients in one pass each (bx_conv3x3_bwd_fused), which
+                # reads the ReLU decisions off y1 / y2 themselves: no mask bits then
+                fuse_bwd = (need_y1 and cfg.keep is None and WGRAD_ALGO != L.BX_ALGO_DIRECT and x.shape[3] == 8
+                            and tuple(w2.shape[:2]) == (16, 16) and tuple(w3.shape[:2]) == (16, 16) and any(ctx.needs_input_grad[1:11]))
+                if need_y1 and MASK_BITS and w1.shape[0] <= 32 and not fuse_bwd:     # the ReLU decisions of y1 / y2 as bits for the data gradients (1/8 of the
                     # bytes; stages 1-2: the later stages' data gradients are not bound by those bytes and read the activations)
                     masks = (torch.empty(B, H, W, w1.shape[0] // 4, dtype=torch.uint8, device=x.device),
                              torch.empty(B, H, W, w2.shape[0] // 4, dtype=torch.uint8, device=x.device))
@@ -643,6 +681,7 @@ class BlockFn(torch.autograd.Function):
                                           _p(seed), _p(pooled), _p(out), _p(mean), _p(invstd), _p(ws), ws.numel(), _stream()), "bx_block_tail_fwd")
         ctx.cfg, ctx.desc, ctx.seed = cfg, desc, seed
         ctx.masks = masks                                   # (plain attributes: uint8 side outputs of the pair launch, never differentiated)
+        ctx.fuse_bwd = fuse_bwd
         ctx.route, ctx.y3_shape = route, (B, H, W, Cc)
         ctx.save_for_backward(x, acts[1], acts[2], y3 if y3 is not None else x.new_empty(0), pooled, mean, invstd, w1, b1, w2, b2, w3, b3,
                               bnw, bnb, w11, b11)
@@ -680,7 +719,19 @@ class BlockFn(torch.autograd.Function):
         bss = (b1, b2, b3)
         grads_w, grads_b = [None] * 3, [None] * 3
         dz = dz3
-        for k in (2, 1, 0):
+        layers = (2, 1, 0)
+        if ctx.fuse_bwd and need_w:
+            # stage 1: conv3's and conv2's data and weight gradients in one pass over dZ each; when the block input needs no gradient,
+            # conv2's launch also takes conv1's weight gradient and dZ1 is never stored
+            for k in (2, 1):
+                packed = cfg.prepacked.get(cfg.pack_base + k, True) if cfg.prepacked is not None else None
+                w1_form = k == 1 and not need_dx
+                grads_w[k], grads_b[k], dz, g0 = _bwd_fused(dz, acts[k], packed or _pack(wts[k], flip=True, dtype=dt), wts[k], bss[k],
+                                                            x if w1_form else None, w1, b1)
+            if w1_form:
+                grads_w[0], grads_b[0] = g0
+            layers = () if w1_form else (0,)
+        for k in layers:
             if need_w:
                 grads_w[k], grads_b[k] = _wgrad(acts[k], dz, wts[k], bss[k], chain=True)
             packed = cfg.prepacked.get(cfg.pack_base + k, True) if cfg.prepacked is not None else None
