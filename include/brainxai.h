@@ -163,9 +163,9 @@ int bx_conv3x3_bwd_fused(const void* dz, const void* xl, const void* packed_flip
  * pool launch of the training step with it (events cannot bracket one kernel of a multi-launch call from outside).  One-shot. */
 int bx_profile_next_conv3(void* ev_start, void* ev_stop);
 
-/* ---- Block tail: 2x2 pool -> BatchNorm2d -> Dropout -> + conv1x1(bilinear(x))  (M:67-76) ------ */
+/* ---- Block tail: pool -> BatchNorm2d -> Dropout -> + conv1x1(bilinear(x))  (M:67-76) ----------- */
 typedef struct {
-  int B, H, W;          /* conv3 output resolution; pooled map is [B, H/2, W/2] (floor) */
+  int B, H, W;          /* conv3 output resolution; pooled map is [B, H/pool_h, W/pool_w] (floor) */
   int Cin_p;            /* channels of the block input x as stored (padded)            */
   int C;                /* block output channels                                        */
   int pool;             /* BX_POOL_MAX | BX_POOL_AVG                                    */
@@ -183,7 +183,10 @@ typedef struct {
                          * first maximum as ATen) or the positive ones (average pool).  That is all the backward needs of conv3's
                          * full-resolution output: bx_block_conv3_tail_fwd writes the nibbles (and may then be given y3 = NULL:
                          * the output is not stored), bx_block_tail_bwd reads them instead of y3 (which may be NULL).  1/16 of the
-                         * bytes of y3 in each direction.  bf16 fused path only; ignored by bx_block_tail_fwd. */
+                         * bytes of y3 in each direction.  bf16 fused path and 2x2 windows only; ignored by bx_block_tail_fwd. */
+  int pool_h, pool_w;   /* pooling window = stride (no padding, floor); 0 means 2, the reference's 2x2.  Windows other than 2x2 run
+                         * the general pooling and routing kernels: bx_block_conv3_tail_fwd returns BX_EUNSUPPORTED for them,
+                         * bx_block_tail_route_bytes returns 0, and bx_block_tail_bwd needs y3 (route NULL). */
 } bxTailDesc;
 size_t bx_block_tail_route_bytes(const bxTailDesc* d);
 #define BX_TAIL_SYNC_WORDS 8192
@@ -192,7 +195,7 @@ size_t bx_block_tail_route_bytes(const bxTailDesc* d);
 size_t bx_block_tail_workspace(const bxTailDesc* d);
 /* y3: conv3 output [B,H,W,C]; x: block input [B,H,W,Cin_p]; w1x1 fp32 [C][Cin] OIHW(1x1), Cin logical;
  * bn_* fp32 [C]; num_batches_tracked int64[1]; seed uint64[1] (device, may be NULL if dropout_p==0).
- * Outputs: pooled [B,H/2,W/2,C] (pre-BN, kept for backward), out [B,H/2,W/2,C],
+ * Outputs: pooled [B,Ho,Wo,C] (pre-BN, kept for backward), out [B,Ho,Wo,C] (Ho = H/pool_h, Wo = W/pool_w),
  * save_mean/save_invstd fp32 [C] (statistics actually used). */
 int bx_block_tail_fwd(const bxTailDesc* d, const void* y3, const void* x, const float* w1x1, int Cin,
                       const float* b1x1, const float* bn_weight, const float* bn_bias,
@@ -212,7 +215,7 @@ int bx_set_tree_max_rows(int rows);
  * 8192 / C rows; the forward folds when its producer wrote at most 32768 / C rows -- the late stages).  Results do not depend
  * on the choice beyond the rounding of double-precision sums. */
 int bx_set_tail_fold(int mask);
-/* conv3 + tail forward in two launches (bf16 storage, MFMA-capable C; otherwise BX_EUNSUPPORTED and the caller uses
+/* conv3 + tail forward in two launches (bf16 storage, MFMA-capable C, 2x2 window; otherwise BX_EUNSUPPORTED and the caller uses
  * bx_conv3x3 + bx_block_tail_fwd): y3 = relu(conv3x3(y2, w3) + b3) is stored for backward, and conv3's epilogue also
  * writes pooled = pool2x2(y3) and the batch statistics, so the pool never re-reads y3 from HBM.  w3_mfma is conv3's
  * MFMA operand from bx_conv3x3_pack (flip 0).  Same workspace size and the same
@@ -222,8 +225,9 @@ int bx_block_conv3_tail_fwd(const bxTailDesc* d, const void* y2, const void* w3_
                             const float* bn_bias, float* running_mean, float* running_var, int64_t* num_batches_tracked,
                             const uint64_t* seed, void* pooled, void* out, float* save_mean, float* save_invstd,
                             void* workspace, size_t workspace_bytes, bxStream stream);
-/* Backward of the tail.  dout [B,H/2,W/2,C].  Produces
- *   dz3 [B,H,W,C]: gradient w.r.t. conv3's pre-activation (pool backward AND conv3's ReLU mask applied),
+/* Backward of the tail.  dout [B,Ho,Wo,C].  Produces
+ *   dz3 [B,H,W,C]: gradient w.r.t. conv3's pre-activation (pool backward AND conv3's ReLU mask applied; zero in the rows and
+ *                  columns the floor-pool drops),
  *   dx_skip [B,H,W,Cin_p] (may be NULL): gradient reaching the block input through the skip path,
  *   d_bn_weight, d_bn_bias, d_w1x1 [C][Cin], d_b1x1 (fp32, overwritten). */
 int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const void* y3, const void* x, const void* pooled,

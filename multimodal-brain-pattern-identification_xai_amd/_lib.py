@@ -24,7 +24,8 @@ vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_flo
 
 class TailDesc(C.Structure):
     _fields_ = [("B", i32), ("H", i32), ("W", i32), ("Cin_p", i32), ("C", i32), ("pool", i32), ("training", i32),
-                ("eps", f32), ("momentum", f32), ("dropout_p", f32), ("salt", u32), ("dtype", i32), ("sync", vp), ("route", vp)]
+                ("eps", f32), ("momentum", f32), ("dropout_p", f32), ("salt", u32), ("dtype", i32), ("sync", vp), ("route", vp),
+                ("pool_h", i32), ("pool_w", i32)]          # pooling window; 0 = 2 (descriptors built without them stay 2x2)
 
 
 class EegDesc(C.Structure):

@@ -1,6 +1,9 @@
-// Block tail: 2x2 pool -> BatchNorm2d -> Dropout -> + conv1x1(bilinear_half(x)), forward and backward,
-// over channels-last activations.  Replaces reference root/src/models/models.py:67-76 (Block.forward after
-// the three convolutions) and its autograd backward.
+// Block tail: pool -> BatchNorm2d -> Dropout -> + conv1x1(bilinear(x)), forward and backward, over channels-last
+// activations.  Replaces reference root/src/models/models.py:67-76 (Block.forward after the three convolutions) and its
+// autograd backward.  The pool is max or average over non-overlapping pool_h x pool_w windows (stride = window, floor);
+// the reference's 2x2 window has the tuned kernels (k_pool_stats, k_tail_bwd_apply, the fused conv3 epilogue, the even
+// skip shortcut), any other window the general pair k_pool_stats_win / k_tail_bwd_apply_win around the same BN apply,
+// reductions and skip kernels.
 //
 // Thread layout shared by the pixel-wise kernels: a thread owns 8 consecutive channels of one pooled
 // pixel; a 256-thread workgroup covers `slots = 256 / (C/8)` pixels at a time and grid-strides.
@@ -18,8 +21,14 @@ struct TailGeom {
   float sy, sx;  // bilinear scales H/Ho, W/Wo (float, as ATen computes them)
 };
 
+// pooling window of a descriptor (0 = the reference's 2)
+static int tail_ph(const bxTailDesc* d) { return d->pool_h ? d->pool_h : 2; }
+static int tail_pw(const bxTailDesc* d) { return d->pool_w ? d->pool_w : 2; }
+static bool tail_2x2(const bxTailDesc* d) { return tail_ph(d) == 2 && tail_pw(d) == 2; }
+
 static int make_geom(const bxTailDesc* d, TailGeom* g) {
-  g->B = d->B; g->H = d->H; g->W = d->W; g->Ho = d->H / 2; g->Wo = d->W / 2; g->C = d->C; g->Cin_p = d->Cin_p;
+  if (tail_ph(d) < 1 || tail_pw(d) < 1) return -5;
+  g->B = d->B; g->H = d->H; g->W = d->W; g->Ho = d->H / tail_ph(d); g->Wo = d->W / tail_pw(d); g->C = d->C; g->Cin_p = d->Cin_p;
   if (d->B <= 0 || g->Ho <= 0 || g->Wo <= 0) return -1;
   if (d->C % 8 || d->C > 256 || 256 % (d->C / 8)) return -2;
   if (d->Cin_p % 8 || d->Cin_p <= 0) return -3;
@@ -70,6 +79,35 @@ __device__ __forceinline__ void block_channel_reduce(float (*vals)[8], float* ld
 }
 
 // ------------------------------------------------------------------------------------------------
+// The general-window kernels share these pieces through helpers; the tuned 2x2 kernels keep their own inline copies (compiled
+// through the helpers their instruction schedules change).
+// wT[ci][c] = W1x1[c][ci] (zero rows for padded inputs): read by k_tail_apply.  Each workgroup of a pooling pass transposes a slice.
+__device__ __forceinline__ void tail_transpose_w1x1(const float* __restrict__ w1x1, int Cin, float* __restrict__ wT, const TailGeom& g) {
+  const int nw = g.Cin_p * g.C, per = (nw + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = (int)blockIdx.x * per, cnt = nw - lo < per ? nw - lo : per;
+  if (cnt > 0)
+    lds_fill<4>(wT + lo, cnt, [&](int k) { const int i = lo + k, ci = i / g.C, c = i % g.C; return ci < Cin ? w1x1[(size_t)c * Cin + ci] : 0.f; });
+}
+
+// end of a pooling pass: this workgroup's per-channel (sum, sumsq) go to its partial row, or (stat tree) the last workgroup to
+// arrive finalizes the batch statistics (no k_bn_finalize launch)
+__device__ __forceinline__ void pool_stats_publish(float (*acc)[8], float* lds, float* partials, const TailGeom& g, const BxStatTree& tree,
+                                                   const BxBnFinalize& fin) {
+  float red[2];
+  block_channel_reduce<2>(acc, lds, g.C, g.ncg, g.slots, red);
+  if (tree.cnt) {
+    double tot[2];
+    __syncthreads();                                    // block_channel_reduce's LDS reads are done
+    if (bx_stat_tree_arrive<2>(tree, 0, 0, blockIdx.x, red, tot, reinterpret_cast<char*>(lds)) && (int)threadIdx.x < g.C)
+      bx_bn_finalize_channel(threadIdx.x, tot[0], tot[1], fin);
+    return;
+  }
+  if ((int)threadIdx.x < g.C) {
+    partials[((size_t)blockIdx.x * 2 + 0) * g.C + threadIdx.x] = red[0];
+    partials[((size_t)blockIdx.x * 2 + 1) * g.C + threadIdx.x] = red[1];
+  }
+}
+
 // forward 1: pooled = pool2x2(y3) (stored, needed again by backward) + per-workgroup (sum, sumsq)
 template <typename T>
 __global__ __launch_bounds__(256) void k_pool_stats(const T* __restrict__ y3, T* __restrict__ pooled, float* partials,
@@ -137,6 +175,58 @@ __global__ __launch_bounds__(256) void k_pool_stats(const T* __restrict__ y3, T*
     partials[((size_t)blockIdx.x * 2 + 0) * g.C + threadIdx.x] = red[0];
     partials[((size_t)blockIdx.x * 2 + 1) * g.C + threadIdx.x] = red[1];
   }
+}
+
+// forward 1 for any other window (ph x pw, stride = window, floor): the same outputs as k_pool_stats.  A thread owns 8 channels of one
+// pooled pixel per trip and walks its window in row-major order, four 16-byte loads in flight.  The maximum is the window's largest
+// value (which element is first matters only to the backward); the average sums in fp32 in row-major order and divides by ph * pw,
+// as ATen does.
+template <typename T>
+__global__ __launch_bounds__(256) void k_pool_stats_win(const T* __restrict__ y3, T* __restrict__ pooled, float* partials, TailGeom g,
+                                                         int ph, int pw, int pool, int want_stats, const float* __restrict__ w1x1, int Cin,
+                                                         float* __restrict__ wT, BxStatTree tree, BxBnFinalize fin) {
+  __shared__ __attribute__((aligned(16))) float lds[2048];
+  tail_transpose_w1x1(w1x1, Cin, wT, g);
+  const int cg = threadIdx.x % g.ncg, slot = threadIdx.x / g.ncg;
+  const int area = ph * pw;
+  float acc[2][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[0][j] = acc[1][j] = 0.f;
+  const long long stride = (long long)gridDim.x * g.slots;
+  for (long long pp = (long long)blockIdx.x * g.slots + slot; pp < g.npool; pp += stride) {
+    int ox, oy, b;
+    px_decode(pp, g.Wo, g.Ho, ox, oy, b);
+    const size_t base = (((size_t)b * g.H + (size_t)ph * oy) * g.W + (size_t)pw * ox) * g.C + cg * 8;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = pool == BX_POOL_MAX ? -INFINITY : 0.f;
+    for (int q0 = 0; q0 < area; q0 += 4) {
+      float w[4][8];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {                    // (clamped index past the window's end: loaded, never used)
+        const int q = q0 + u < area ? q0 + u : q0, r = q / pw;
+        ld8(y3, base + ((size_t)r * g.W + (q - r * pw)) * g.C, w[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (q0 + u < area)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = pool == BX_POOL_MAX ? fmaxf(v[j], w[u][j]) : v[j] + w[u][j];
+    }
+    if (pool != BX_POOL_MAX)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = v[j] / (float)area;
+    st8(pooled, (size_t)pp * g.C + cg * 8, v);
+    if (want_stats) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {          // statistics of the values as stored (bf16-rounded if bf16)
+        const float q = round_as(pooled, v[j]);
+        acc[0][j] += q; acc[1][j] += q * q;
+      }
+    }
+  }
+  if (!want_stats) return;
+  pool_stats_publish(acc, lds, partials, g, tree, fin);
 }
 
 // 8 consecutive elements held in their storage form (a load issued early costs 4 registers for bf16, not 8)
@@ -329,17 +419,17 @@ static size_t tail_rows_cap(const bxTailDesc* d) {
 }
 extern "C" size_t bx_block_tail_route_bytes(const bxTailDesc* d) {
   TailGeom g;
-  if (!d || make_geom(d, &g)) return 0;
+  if (!d || make_geom(d, &g) || !tail_2x2(d)) return 0;
   return (size_t)g.npool * g.C / 2;                       // C % 8 == 0: a thread's 8 channels are one 32-bit word
 }
 extern "C" size_t bx_block_tail_workspace(const bxTailDesc* d) {
   TailGeom g;
   if (!d || make_geom(d, &g)) return 0;
-  const size_t Ho = d->H / 2, Wo = d->W / 2;
+  const size_t Ho = g.Ho, Wo = g.Wo;
   size_t fwd = ((size_t)tail_rows_cap(d) * 2 + 2) * d->C * sizeof(float) + (size_t)d->Cin_p * d->C * sizeof(float)
              + (size_t)TAIL_MAX_GROUPS * 2 * d->C * sizeof(double);                                  // reduction-tree group sums
   size_t bwd = ((size_t)TAIL_MAX_BLOCKS * 3 + 3) * d->C * sizeof(float)                 // partials + coefficients
-             + bx_align_up((size_t)d->B * Ho * Wo * d->Cin_p * sizeof(float), 256)       // dXs (half-res, fp32)
+             + bx_align_up((size_t)d->B * Ho * Wo * d->Cin_p * sizeof(float), 256)       // dXs (pooled resolution, fp32)
              + (size_t)2048 * 256 * sizeof(float) + (size_t)65 * d->C * d->Cin_p * sizeof(float);   // conv1x1 weight-grad partials (+1 slab for compaction)
   return bx_align_up(fwd > bwd ? fwd : bwd, 256) + (size_t)TAIL_MAX_GROUPS * 3 * d->C * sizeof(double);    // + backward reduction-tree group sums
 }
@@ -354,7 +444,8 @@ extern "C" int bx_block_tail_fwd(const bxTailDesc* d, const void* y3, const void
   BX_DTYPE_OK(d->dtype);
   TailGeom g;
   const int ge = make_geom(d, &g);
-  BX_REQUIRE(ge == 0, "bx_block_tail_fwd: unsupported geometry (code %d): need C%%8==0, C<=256, 256%%(C/8)==0, Cin_p%%8==0, H,W>=2", ge);
+  BX_REQUIRE(ge == 0, "bx_block_tail_fwd: unsupported geometry (code %d): need C%%8==0, C<=256, 256%%(C/8)==0, Cin_p%%8==0, "
+             "pool_h, pool_w >= 0, H >= pool_h, W >= pool_w", ge);
   BX_REQUIRE(Cin > 0 && Cin <= d->Cin_p, "bx_block_tail_fwd: Cin=%d exceeds Cin_p=%d", Cin, d->Cin_p);
   BX_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "bx_block_tail_fwd: dropout_p must be in [0,1)");
   BX_REQUIRE(d->dropout_p == 0.f || !d->training || seed, "bx_block_tail_fwd: dropout needs a device seed");
@@ -381,9 +472,15 @@ extern "C" int bx_block_tail_fwd(const bxTailDesc* d, const void* y3, const void
     fin = BxBnFinalize{bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, d->momentum, d->eps, scale, shift, save_mean, save_invstd,
                        (double)g.npool};
   }
-  BX_DISPATCH_DTYPE(d->dtype, T,
-    hipLaunchKernelGGL((k_pool_stats<T>), dim3(nblk), dim3(256), 0, s, (const T*)y3, (T*)pooled, partials, g, d->pool, d->training,
-                       w1x1, Cin, wT, tree, fin));
+  if (tail_2x2(d)) {
+    BX_DISPATCH_DTYPE(d->dtype, T,
+      hipLaunchKernelGGL((k_pool_stats<T>), dim3(nblk), dim3(256), 0, s, (const T*)y3, (T*)pooled, partials, g, d->pool, d->training,
+                         w1x1, Cin, wT, tree, fin));
+  } else {
+    BX_DISPATCH_DTYPE(d->dtype, T,
+      hipLaunchKernelGGL((k_pool_stats_win<T>), dim3(nblk), dim3(256), 0, s, (const T*)y3, (T*)pooled, partials, g, tail_ph(d), tail_pw(d),
+                         d->pool, d->training, w1x1, Cin, wT, tree, fin));
+  }
   BX_CHECK_LAUNCH("bx_block_tail_fwd(pool)");
   // folded finalize: the apply kernel's workgroups sum the partial rows themselves (no k_bn_finalize launch)
   const bool fold = d->training && !in_launch && (tail_fold() & 2) && tail_fold_ok(g) && (long long)nblk * g.C <= TAIL_FOLD_RC_FWD;
@@ -418,6 +515,8 @@ extern "C" int bx_block_conv3_tail_fwd(const bxTailDesc* d, const void* y2, cons
              && save_invstd, "bx_block_conv3_tail_fwd: null pointer");            // (y3 may be NULL: conv3's output is then not stored)
   if (d->dtype != BX_BF16 || !bx_conv3x3_mfma_supported(d->C, d->C, d->dtype) || d->C < 16)
     BX_FAIL(BX_EUNSUPPORTED, "bx_block_conv3_tail_fwd: needs bf16 storage and an MFMA-capable channel count (C=%d dtype=%d)", d->C, d->dtype);
+  if (!tail_2x2(d))
+    BX_FAIL(BX_EUNSUPPORTED, "bx_block_conv3_tail_fwd: the fused epilogue pools 2x2 windows only (pool %dx%d)", tail_ph(d), tail_pw(d));
   TailGeom g;
   const int ge = make_geom(d, &g);
   BX_REQUIRE(ge == 0, "bx_block_conv3_tail_fwd: unsupported geometry (code %d)", ge);
@@ -577,6 +676,38 @@ struct TailWsum { const float* wpart; float* dw; int nchunk, Cin, S, n_apply; };
 // itself (bx_rows_total) and derives the three coefficients, workgroup 0 writes the parameter gradients
 struct TailBwdPro { const float* rows; int nrows; TailBwdFin fin; };
 
+// this thread's 8 channels of the BN-backward coefficients (folded form: summed from the reduction role's rows first) and statistics
+__device__ __forceinline__ void tail_bwd_coefs(const TailGeom& g, int cg, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                               const float* __restrict__ coef, const TailBwdPro& pro, float (&mu)[8], float (&is)[8],
+                                               float (&a)[8], float (&k1)[8], float (&k2)[8]) {
+  if (pro.rows) {
+    __shared__ __attribute__((aligned(8))) double sp[BX_ROWS_TOTAL_LDS(3) / 8];
+    __shared__ float cf[3][256];
+    bx_rows_total<3>(pro.rows, pro.nrows, g.C, sp);
+    if ((int)threadIdx.x < g.C) {
+      const int c = threadIdx.x;
+      const double st[3] = {sp[c], sp[g.C + c], sp[2 * g.C + c]};
+      const TailBwdFin& f = pro.fin;
+      cf[0][c] = f.gamma[c] * f.invstd[c];
+      cf[1][c] = f.training ? (float)(st[0] / f.count) : 0.f;
+      cf[2][c] = f.training ? (float)(st[1] / f.count) : 0.f;
+      if (blockIdx.x == 0) tail_bwd_finalize_channel(c, g.C, st, f);       // parameter gradients (+ the coefficients, for inspection)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = cg * 8 + j;
+      mu[j] = mean[c]; is[j] = invstd[c]; a[j] = cf[0][c]; k1[j] = cf[1][c]; k2[j] = cf[2][c];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = cg * 8 + j;
+      mu[j] = mean[c]; is[j] = invstd[c]; a[j] = coef[c]; k1[j] = coef[g.C + c]; k2[j] = coef[2 * g.C + c];
+    }
+  }
+}
+
 // apply: dP = a*(dD - k1 - xhat*k2); route through the 2x2 pool and conv3's ReLU to full resolution
 template <typename T>
 __global__ __launch_bounds__(256) void k_tail_bwd_apply(const T* __restrict__ dout, const T* __restrict__ pooled, const T* __restrict__ y3,
@@ -686,7 +817,86 @@ __global__ __launch_bounds__(256) void k_tail_bwd_apply(const T* __restrict__ do
   }
 }
 
-// dXs[p][ci] = sum_c W1x1[c][ci] * dOut[p][c]   (half resolution, fp32).  One (pixel, CIV input channels) unit per
+// apply for any other window (ph x pw, stride = window, floor): dP as above, routed from the stored y3.  Max: to the first maximum of
+// the window in row-major order (ATen), if positive (conv3's ReLU); average: dP / (ph * pw) to every positive element.  The rows and
+// columns the floor-pool never covers (at most ph - 1 / pw - 1) are written by the last window row / column, as zeros.
+template <typename T>
+__global__ __launch_bounds__(256) void k_tail_bwd_apply_win(const T* __restrict__ dout, const T* __restrict__ pooled, const T* __restrict__ y3,
+    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ coef,
+    const uint64_t* __restrict__ seed, float dropout_p, uint32_t salt, int pool, T* __restrict__ dz3, TailGeom g, int ph, int pw,
+    TailWsum ws, TailBwdPro pro) {
+  if (ws.n_apply && (int)blockIdx.x >= ws.n_apply) {            // extra workgroups: the 1x1 weight-gradient sum rides here
+    __shared__ float sm[256];
+    w1x1_sum_group(ws.wpart, ws.dw, ws.nchunk, g.C, ws.Cin, g.Cin_p, ws.S, (int)blockIdx.x - ws.n_apply, threadIdx.x, sm);
+    return;
+  }
+  const int cg = threadIdx.x % g.ncg, slot = threadIdx.x / g.ncg;
+  const uint64_t sd = (dropout_p > 0.f && seed) ? seed[0] : 0;
+  const float inv_keep = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
+  float mu[8], is[8], a[8], k1[8], k2[8];
+  tail_bwd_coefs(g, cg, mean, invstd, coef, pro, mu, is, a, k1, k2);
+  const int area = ph * pw;
+  const long long pstep = (long long)(ws.n_apply ? ws.n_apply : (int)gridDim.x) * g.slots;
+  for (long long pp = (long long)blockIdx.x * g.slots + slot; pp < g.npool; pp += pstep) {
+    int ox, oy, b;
+    px_decode(pp, g.Wo, g.Ho, ox, oy, b);
+    float go[8], pv[8], dp[8];
+    ld8(dout, (size_t)pp * g.C + cg * 8, go); ld8(pooled, (size_t)pp * g.C + cg * 8, pv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float dd = go[j];
+      if (dropout_p > 0.f) dd *= bx_dropout_scale(sd, salt, (uint64_t)pp * g.C + cg * 8 + j, dropout_p, inv_keep);
+      dp[j] = a[j] * (dd - k1[j] - (pv[j] - mu[j]) * is[j] * k2[j]);
+    }
+    const size_t base = (((size_t)b * g.H + (size_t)ph * oy) * g.W + (size_t)pw * ox) * g.C + cg * 8;
+    const int nr = oy == g.Ho - 1 ? g.H - ph * oy : ph, nc = ox == g.Wo - 1 ? g.W - pw * ox : pw;   // + the uncovered remainder
+    if (pool == BX_POOL_MAX) {
+      float m[8];
+      int arg[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { m[j] = -INFINITY; arg[j] = 0; }
+      for (int q0 = 0; q0 < area; q0 += 4) {
+        float w[4][8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                  // (clamped index past the window's end: loaded, never used)
+          const int q = q0 + u < area ? q0 + u : q0, r = q / pw;
+          ld8(y3, base + ((size_t)r * g.W + (q - r * pw)) * g.C, w[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (q0 + u < area)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              if (w[u][j] > m[j]) { m[j] = w[u][j]; arg[j] = q0 + u; }     // first maximum in row-major order
+      }
+      for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+          const int q = r < ph && c < pw ? r * pw + c : -1;
+          float o[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = (q == arg[j] && m[j] > 0.f) ? dp[j] : 0.f;
+          st8(dz3, base + ((size_t)r * g.W + c) * g.C, o);
+        }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dp[j] = dp[j] / (float)area;
+      for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+          const size_t e = base + ((size_t)r * g.W + c) * g.C;
+          float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          if (r < ph && c < pw) {
+            float v[8];
+            ld8(y3, e, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = v[j] > 0.f ? dp[j] : 0.f;
+          }
+          st8(dz3, e, o);
+        }
+    }
+  }
+}
+
+// dXs[p][ci] = sum_c W1x1[c][ci] * dOut[p][c]   (pooled resolution, fp32).  One (pixel, CIV input channels) unit per
 // thread (CIV = 8, or 4 when the map is so small that 8 would leave most CUs without a workgroup); the weight matrix
 // streams through LDS in 64-output-channel slabs ([c][Cin_p], zero padded), dOut comes straight from global as 16-byte vectors.
 template <typename T, int CIV>
@@ -1088,6 +1298,8 @@ extern "C" int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const vo
   TailGeom g;
   const int ge = make_geom(d, &g);
   BX_REQUIRE(ge == 0, "bx_block_tail_bwd: unsupported geometry (code %d)", ge);
+  const bool w22 = tail_2x2(d);
+  BX_REQUIRE(w22 || (y3 && !d->route), "bx_block_tail_bwd: a %dx%d window needs y3 (route nibbles are 2x2 only)", tail_ph(d), tail_pw(d));
   BX_REQUIRE(Cin > 0 && Cin <= d->Cin_p, "bx_block_tail_bwd: Cin=%d exceeds Cin_p=%d", Cin, d->Cin_p);
   BX_REQUIRE(d->C % 16 == 0, "bx_block_tail_bwd: C must be a multiple of 16");
   const size_t need = bx_block_tail_workspace(d);
@@ -1101,7 +1313,7 @@ extern "C" int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const vo
   float* wpart = (float*)((char*)dxs + bx_align_up((size_t)g.npool * g.Cin_p * sizeof(float), 256));
 
   // ---- front: reduction | w1x1 weight-gradient partials | skip input gradient
-  const bool even = (g.H % 2 == 0) && (g.W % 2 == 0);
+  const bool even = w22 && (g.H % 2 == 0) && (g.W % 2 == 0);       // skip input gradient written directly as the 2x2 mean's transpose
   const int mf = (dx_skip && d->dtype == BX_BF16 && g.C % 32 == 0 && (g.Cin_p == 16 || g.Cin_p == 32 || g.Cin_p == 64 || g.Cin_p == 128))
                  ? g.Cin_p : 0;
   const bool wbig = mf >= 64 && g.C % 64 == 0;                 // 64 x 64 weight-gradient tiles (kernel: MF >= 64)
@@ -1181,9 +1393,15 @@ extern "C" int bx_block_tail_bwd(const bxTailDesc* d, const void* dout, const vo
     n_sum256 = bx_ceil_div(n_sum_elems, 256 / S);
     wsum = TailWsum{wpart, d_w1x1, nchunk, Cin, S, napply};
   }
-  BX_DISPATCH_DTYPE(d->dtype, T,
-    hipLaunchKernelGGL((k_tail_bwd_apply<T>), dim3(napply + n_sum256), dim3(256), 0, s, (const T*)dout, (const T*)pooled, (const T*)y3,
-                       save_mean, save_invstd, coef, seed, p, d->salt, d->pool, (T*)dz3, g, wsum, pro, (const uint32_t*)d->route));
+  if (w22) {
+    BX_DISPATCH_DTYPE(d->dtype, T,
+      hipLaunchKernelGGL((k_tail_bwd_apply<T>), dim3(napply + n_sum256), dim3(256), 0, s, (const T*)dout, (const T*)pooled, (const T*)y3,
+                         save_mean, save_invstd, coef, seed, p, d->salt, d->pool, (T*)dz3, g, wsum, pro, (const uint32_t*)d->route));
+  } else {
+    BX_DISPATCH_DTYPE(d->dtype, T,
+      hipLaunchKernelGGL((k_tail_bwd_apply_win<T>), dim3(napply + n_sum256), dim3(256), 0, s, (const T*)dout, (const T*)pooled, (const T*)y3,
+                         save_mean, save_invstd, coef, seed, p, d->salt, d->pool, (T*)dz3, g, tail_ph(d), tail_pw(d), wsum, pro));
+  }
   BX_CHECK_LAUNCH("bx_block_tail_bwd(apply)");
   if (dx_skip) {
     if (!even) {

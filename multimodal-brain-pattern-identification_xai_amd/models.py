@@ -11,6 +11,7 @@ activation storage type; parameters, statistics and gradients stay float32.
 """
 from __future__ import annotations
 
+import numbers
 from types import SimpleNamespace
 
 import torch
@@ -27,13 +28,23 @@ def _is_internal(x: torch.Tensor, dtype: torch.dtype) -> bool:
             and x.permute(0, 2, 3, 1).is_contiguous())
 
 
+def _pool_window(pool_size) -> tuple:
+    """(ph, pw) of a Block's ``pool_size``: an int k means (k, k), else a pair of positive ints (window = stride, as in the reference)"""
+    def is_int(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    win = (pool_size, pool_size) if is_int(pool_size) else tuple(pool_size) if isinstance(pool_size, (tuple, list)) else None
+    if win is None or len(win) != 2 or not all(is_int(v) and v > 0 for v in win):
+        raise ValueError(f"brainxai Block: pool_size must be a positive int or a pair of positive ints, got {pool_size!r}")
+    return int(win[0]), int(win[1])
+
+
 class Block(nn.Module):
-    """relu(conv3x3) x3 -> 2x2 pool -> BatchNorm -> Dropout -> + conv1x1(bilinear(x))  (reference models.py:42-77)."""
+    """relu(conv3x3) x3 -> pool -> BatchNorm -> Dropout -> + conv1x1(bilinear(x))  (reference models.py:42-77).
+    ``pool_size`` is any non-overlapping window (int k or (ph, pw)); the reference's 2x2 runs the tuned kernels."""
 
     def __init__(self, in_channels, out_channels, pool_type="max", pool_size=(2, 2), dropout_p=0.5):
         super().__init__()
-        if tuple(pool_size) != (2, 2) if not isinstance(pool_size, int) else pool_size != 2:
-            raise ValueError("brainxai Block: only the reference's 2x2 pooling is implemented")
+        self.pool_window = _pool_window(pool_size)
         if pool_type not in ("max", "avg"):
             raise ValueError(f"pool_type must be 'max' or 'avg', got {pool_type!r}")
         self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)
@@ -69,10 +80,11 @@ class Block(nn.Module):
             if x.dim() != 4 or x.shape[1] != self.in_channels:
                 raise RuntimeError(f"Block expected [B,{self.in_channels},H,W], got {tuple(x.shape)}")
             xi = ops.InputLayout.apply(x, dt)
-        if xi.shape[1] < 2 or xi.shape[2] < 2:
-            raise RuntimeError("Block needs H, W >= 2")
+        ph, pw = self.pool_window
+        if xi.shape[1] < ph or xi.shape[2] < pw:
+            raise RuntimeError("Block needs H, W >= 2" if (ph, pw) == (2, 2) else f"Block needs H >= {ph} and W >= {pw} (pool_size {ph}x{pw})")
         bn = self.bn
-        cfg = ops.block_cfg(pool=self.pool_type, training=self.training, dropout_p=self.dropout.p if self.training else 0.0,
+        cfg = ops.block_cfg(pool=self.pool_type, pool_size=self.pool_window, training=self.training, dropout_p=self.dropout.p if self.training else 0.0,
                             eps=bn.eps, momentum=0.1 if bn.momentum is None else bn.momentum, salt=self.salt,
                             preact=self._preact, capture=self._capture, prepacked=self._prepacked, pack_base=self._pack_base, seed=self._seed,
                             keep=self._keep, sync=self._sync_words(xi.device), grad_mode=torch.is_grad_enabled())

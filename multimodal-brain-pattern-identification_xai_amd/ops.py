@@ -580,13 +580,13 @@ def _bwd_fused(dz, xl, packed, w, b, x0, w0, b0):
 def _tail_desc(x, shape, dt, cfg, route=None) -> L.TailDesc:
     B, H, W, Cc = shape
     return L.TailDesc(B, H, W, x.shape[3], Cc, L.BX_POOL_MAX if cfg.pool == "max" else L.BX_POOL_AVG, 1 if cfg.training else 0,
-                      cfg.eps, cfg.momentum, float(cfg.dropout_p), cfg.salt, bx_dtype(dt), _p(cfg.sync), _p(route))
+                      cfg.eps, cfg.momentum, float(cfg.dropout_p), cfg.salt, bx_dtype(dt), _p(cfg.sync), _p(route), *cfg.pool_size)
 
 
 class BlockFn(torch.autograd.Function):
     """relu(conv3x3) x3 -> pool -> BN -> dropout -> + conv1x1(bilinear(x))   (reference models.py:62-77).
 
-    x: NHWC [B,H,W,Cin_p].  Returns NHWC [B,H/2,W/2,C].  With cfg.preact = k in {1,2,3} the k-th conv's
+    x: NHWC [B,H,W,Cin_p].  Returns NHWC [B,H/ph,W/pw,C] for the window (ph, pw) = cfg.pool_size.  With cfg.preact = k in {1,2,3} the k-th conv's
     PRE-ReLU output (what a hook on ``blockN.convK`` would see) is kept in cfg.capture["act"] and the
     gradient reaching it during backward in cfg.capture["grad"] (attribution targets inside a stage).
     """
@@ -599,8 +599,10 @@ class BlockFn(torch.autograd.Function):
         acts, pre = [x], None
         B, H, W, _ = x.shape
         Cc = w3.shape[0]
-        # conv3 with the pool and the batch statistics in its epilogue (two launches for conv3 + tail instead of four)
-        fused = FUSE_POOL and dt == torch.bfloat16 and CONV_ALGO != L.BX_ALGO_DIRECT and cfg.preact != 3 and Cc >= 16
+        ph, pw = cfg.pool_size
+        # conv3 with the pool and the batch statistics in its epilogue (two launches for conv3 + tail instead of four; 2x2 windows)
+        fused = (FUSE_POOL and dt == torch.bfloat16 and CONV_ALGO != L.BX_ALGO_DIRECT and cfg.preact != 3 and Cc >= 16
+                 and (ph, pw) == (2, 2))
         packed3 = None
         first = 0
         masks = None
@@ -648,7 +650,7 @@ class BlockFn(torch.autograd.Function):
         seed = None
         if cfg.training and cfg.dropout_p > 0:
             seed = cfg.seed if cfg.seed is not None else next_seed(x.device)       # the model hands one seed to all stages (salts differ)
-        pooled = torch.empty(B, H // 2, W // 2, Cc, dtype=dt, device=x.device)
+        pooled = torch.empty(B, H // ph, W // pw, Cc, dtype=dt, device=x.device)
         out = torch.empty_like(pooled)
         mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
@@ -1072,7 +1074,7 @@ class AttentionFn(torch.autograd.Function):
 
 
 def block_cfg(**kw) -> SimpleNamespace:
-    base = dict(pool="max", training=False, dropout_p=0.0, eps=1e-5, momentum=0.1, salt=0, preact=0, capture=None,
+    base = dict(pool="max", pool_size=(2, 2), training=False, dropout_p=0.0, eps=1e-5, momentum=0.1, salt=0, preact=0, capture=None,
                 prepacked=None, pack_base=0, seed=None, keep=None, sync=None)
     base.update(kw)
     return SimpleNamespace(**base)
