@@ -345,6 +345,14 @@ size_t bx_eeg_gradcam_workspace(const bxEegDesc* d, int maps_per_act, int target
 int bx_eeg_gradcam(const bxEegDesc* d, const bxEegParams* p, const float* x, const void* saved, const float* dfeat,
                    int maps_per_act, int target, int relu, float* cam, float* raw, float* weights, void* workspace,
                    size_t workspace_bytes, bxStream stream);
+/* The same for every class-activation method (BX_CAM_*, see "attribution" below); bx_eeg_gradcam = method BX_CAM_GRADCAM.  The
+ * spatial axes are (Chans, T) for conv1, T for depthwiseConv and T/P1 for separableConv; A is the target's output (for conv1 the
+ * 'same'-padded, bias-free conv1 of x, never stored), G its gradient formed per element from dfeat.  weights must be NULL for
+ * BX_CAM_LAYERCAM.  The workspace of a method may be larger than Grad-CAM's: size it with bx_eeg_cam_workspace. */
+size_t bx_eeg_cam_workspace(const bxEegDesc* d, int maps_per_act, int target, int method);
+int bx_eeg_cam(const bxEegDesc* d, const bxEegParams* p, const float* x, const void* saved, const float* dfeat,
+               int maps_per_act, int target, int method, int relu, float* cam, float* raw, float* weights, void* workspace,
+               size_t workspace_bytes, bxStream stream);
 
 /* ---- EEGNetAttentionDeep head (M:136-235, Attention M:109-134): everything after EEGNet's block 2 ----------
  * feat fp32 [B, F2*T2] (bx_eeg_features_fwd's output for the same input; the class's dropout2 is applied there)
@@ -400,6 +408,17 @@ int bx_attention_bwd(const float* dout, const float* dattn, const float* x, cons
  * sample sharing one activation).  cam fp32 [n_maps,HW]; weights_out fp32 [n_maps,C] may be NULL. */
 int bx_gradcam_reduce(const void* A, const void* G, float* cam, float* weights_out, int n_maps, int maps_per_act,
                       int HW, int C, int relu, int dtype, bxStream stream);
+/* Class-activation methods.  A[k,s]: the target's activation (channel k, position s), G = dy_c/dA, eps = 1e-6:
+ *   BX_CAM_GRADCAM     w[k] = mean_s G[k,s];                                         raw[s] = sum_k w[k] A[k,s]
+ *   BX_CAM_GRADCAM_PP  S[k] = sum_s A[k,s];  alpha[k,s] = G^2 / (2 G^2 + S[k] G^3 + eps), 0 where G == 0;
+ *                      w[k] = sum_s max(G[k,s], 0) alpha[k,s]  (a sum, not a mean);   raw[s] = sum_k w[k] A[k,s]
+ *   BX_CAM_LAYERCAM    raw[s] = sum_k max(G[k,s], 0) A[k,s]   (no channel weights: weights_out must be NULL)
+ * cam = relu ? max(raw, 0) : raw; no normalisation.  Arithmetic is fp32 after the load for both storage types; fixed-order
+ * sums, no atomics.  An unknown method, or Layer-CAM with non-NULL weights_out, returns BX_EINVAL. */
+enum { BX_CAM_GRADCAM = 0, BX_CAM_GRADCAM_PP = 1, BX_CAM_LAYERCAM = 2 };
+/* bx_gradcam_reduce for any method, same layouts and channel rule; bx_gradcam_reduce = method BX_CAM_GRADCAM. */
+int bx_cam_reduce(const void* A, const void* G, float* cam, float* weights_out, int n_maps, int maps_per_act, int HW, int C,
+                  int method, int relu, int dtype, bxStream stream);
 /* Grad-CAM at the last stage of the multimodal model in one launch (canonical definition; the reference ships none, SURVEY fact
  * 3; heads = models.py:103-106 and XAI_Multimodality.py:1095-1105).  A: stage output NHWC [B,HW,C] (dtype); eeg_logp fp32 [B,N]
  * (EEG branch's log-probs); fc_* = Spectrogram_Model.fc, w1/b1 = fc1 [Hd,2N], w2/b2 = fc2 [N,Hd].  class_mode -2: every class
@@ -415,6 +434,17 @@ int bx_gradcam_head_sweep(const void* A, const float* eeg_feat, const float* den
                           const float* fc_b, const float* w1, const float* b1, const float* w2, const float* b2, float* out_logp,
                           float* maps, int B, int h, int w, int C, int N, int Hd, int H, int W, int class_mode, int relu, int dtype,
                           bxStream stream);
+/* bx_gradcam_head / bx_gradcam_head_sweep for any method (the old entry points are method BX_CAM_GRADCAM).  At the last stage
+ * G[k,s] = w[k] (the Grad-CAM weight) at every position and S[k] = HW gap[k], so a method only transforms the channel weights
+ * before the same channel reduce:  Layer-CAM w'[k] = max(w[k], 0);  Grad-CAM++ w'[k] = w[k] > 0 ? HW w^3 / (2 w^2 + S w^3 + eps) : 0.
+ * weights_out receives w' (the Grad-CAM++ w of the definition above) and must be NULL for Layer-CAM. */
+int bx_cam_head(const void* A, const float* eeg_logp, const float* fc_w, const float* fc_b, const float* w1, const float* b1,
+                const float* w2, const float* b2, float* out_logp, float* cam, float* raw, float* weights_out, int B, int HW,
+                int C, int N, int Hd, int class_mode, int method, int relu, int dtype, bxStream stream);
+int bx_cam_head_sweep(const void* A, const float* eeg_feat, const float* dense_w, const float* dense_b, int Fe, const float* fc_w,
+                      const float* fc_b, const float* w1, const float* b1, const float* w2, const float* b2, float* out_logp,
+                      float* maps, int B, int h, int w, int C, int N, int Hd, int H, int W, int class_mode, int method, int relu,
+                      int dtype, bxStream stream);
 /* Bilinear resize (align_corners=False) of fp32 maps [N,h,w] -> [N,H,W]  (F.interpolate). */
 int bx_resize_bilinear(const float* src, float* dst, int N, int h, int w, int H, int W, bxStream stream);
 /* Saliency reduce (NB:3121-3129): out[b,p] = scale * max_c |g[b,p,c]|, g NHWC `dtype` (first C of Cs). */

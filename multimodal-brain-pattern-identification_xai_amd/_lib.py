@@ -18,6 +18,7 @@ BX_EPI_RELU = 1
 BX_EPI_MASK_BITS = 2
 BX_TAIL_SYNC_WORDS = 8192
 BX_EEG_CAM_CONV1, BX_EEG_CAM_DEPTHWISE, BX_EEG_CAM_SEPARABLE = 0, 1, 2
+BX_CAM_GRADCAM, BX_CAM_GRADCAM_PP, BX_CAM_LAYERCAM = 0, 1, 2
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -119,6 +120,8 @@ SIGNATURES = {
     "bx_eeg_saved_layout": (i32, [P(EegDesc), P(sz), P(sz)]),
     "bx_eeg_gradcam_workspace": (sz, [P(EegDesc), i32, i32]),
     "bx_eeg_gradcam": (i32, [P(EegDesc), P(EegParams), vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "bx_eeg_cam_workspace": (sz, [P(EegDesc), i32, i32, i32]),
+    "bx_eeg_cam": (i32, [P(EegDesc), P(EegParams), vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "bx_eeg_deep_saved_bytes": (sz, [P(EegDeepDesc)]),
     "bx_eeg_deep_workspace": (sz, [P(EegDeepDesc)]),
     "bx_eeg_deep_fwd": (i32, [P(EegDeepDesc), P(EegDeepParams), vp, vp, vp, vp, vp, vp, sz, vp]),
@@ -129,6 +132,9 @@ SIGNATURES = {
     "bx_gradcam_reduce": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "bx_gradcam_head": (i32, [vp] * 12 + [i32] * 8 + [vp]),
     "bx_gradcam_head_sweep": (i32, [vp] * 4 + [i32] + [vp] * 8 + [i32] * 11 + [vp]),
+    "bx_cam_reduce": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "bx_cam_head": (i32, [vp] * 12 + [i32] * 9 + [vp]),
+    "bx_cam_head_sweep": (i32, [vp] * 4 + [i32] + [vp] * 8 + [i32] * 12 + [vp]),
     "bx_resize_bilinear": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "bx_saliency_reduce": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "bx_axpby": (i32, [vp, vp, sz, f32, f32, vp]),

@@ -1,5 +1,6 @@
 // Attribution reduce kernels and the EEG stacker.
 //   bx_gradcam_reduce : canonical Grad-CAM channel reduce (the reference has no Grad-CAM)
+//   bx_cam_reduce     : the same for Grad-CAM++ and Layer-CAM (bx_cam_head*: the last-stage form of all three methods)
 //   bx_resize_bilinear: F.interpolate(mode='bilinear', align_corners=False) of the maps
 //   bx_saliency_reduce: spec.grad.abs().max(dim=1)   reference XAI_Multimodality.py:3128-3129
 //   bx_eeg_stack_iir  : _EEGTransformer.transform     reference root/src/data/dataset.py:73-104,125-131
@@ -51,17 +52,108 @@ __global__ __launch_bounds__(256) void k_gradcam(const T* __restrict__ A, const 
   }
 }
 
+// Grad-CAM++ and Layer-CAM channel reduce (bx_cam_reduce; its method 0 launches k_gradcam above).  One workgroup per map.
+//   Grad-CAM++  phase 0: S[c] = sum_p A[p][c] -- k_gradcam's column sum, over A (each of an activation's maps_per_act maps forms it
+//                        again: its second and later reads of A come from L2, and the reduce needs no workspace);
+//               phase 1: w[c] = sum_p campp_term(G[p][c], S[c]), the same column sum over G;  then raw[p] = sum_c w[c] A[p][c].
+//   Layer-CAM   raw[p] = sum_c max(G[p][c], 0) A[p][c]: one streaming pass over A and G.
+// The position reduce puts a position's channels on min(C/8, 64) neighbouring lanes (16-byte loads along C) and 64 / that many
+// positions on a wave, four position groups per trip, segmented butterfly sum (fixed order: the result does not vary from run to run).
+template <typename T, typename F>
+__device__ __forceinline__ void cam_colsum(const T* x, int HW, int C, float* part, float* dst, F f) {
+  const int ncg = C / 8, slots = 256 / ncg, cg = threadIdx.x % ncg, slot = threadIdx.x / ncg;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int p0 = slot; p0 < HW; p0 += 4 * slots) {        // four 16-byte loads in flight per trip (clamped index, masked add)
+    float v[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { const int p = p0 + u * slots; ld8(x, (size_t)(p < HW ? p : HW - 1) * C + cg * 8, v[u]); }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += p0 + u * slots < HW ? f(v[u][j], cg * 8 + j) : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[slot * C + cg * 8 + j] = acc[j];
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float s = 0.f;
+    for (int sl = 0; sl < slots; ++sl) s += part[sl * C + c];
+    dst[c] = s;
+  }
+  __syncthreads();
+}
+
+template <typename T, int METHOD>
+__global__ __launch_bounds__(256) void k_cam(const T* __restrict__ A, const T* __restrict__ G, float* __restrict__ cam,
+                                             float* __restrict__ wout, int HW, int C, int maps_per_act, int relu) {
+  extern __shared__ float sm[];  // Grad-CAM++: part[2048] | S[C] | w[C]
+  const int m = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const T* g = G + (size_t)m * HW * C;
+  const T* a = A + (size_t)(m / maps_per_act) * HW * C;
+  float* w = sm + 2048 + C;
+  if constexpr (METHOD == BX_CAM_GRADCAM_PP) {
+    float* S = sm + 2048;
+    cam_colsum(a, HW, C, sm, S, [](float v, int) { return v; });
+    cam_colsum(g, HW, C, sm, w, [&](float v, int c) { return campp_term(v, S[c]); });
+    if (wout)
+      for (int c = threadIdx.x; c < C; c += 256) wout[(size_t)m * C + c] = w[c];
+  }
+  const int lpp = C / 8 < 64 ? C / 8 : 64, ppw = 64 / lpp, sub = lane / lpp, cg = lane - sub * lpp;
+  const int ngrp = (HW + ppw - 1) / ppw;                  // position groups; wave takes groups wave, wave + 4, ...
+  for (int g0 = wave; g0 < ngrp; g0 += 16) {
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = cg * 8; c0 < C; c0 += 512) {
+      float av[4][8], gv[4][8];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int p = (g0 + 4 * u) * ppw + sub;
+        const size_t i = (size_t)(p < HW ? p : HW - 1) * C + c0;
+        ld8(a, i, av[u]);
+        if constexpr (METHOD == BX_CAM_LAYERCAM) ld8(g, i, gv[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[u] = fmaf(METHOD == BX_CAM_LAYERCAM ? fmaxf(gv[u][j], 0.f) : w[c0 + j], av[u][j], s[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      for (int o = lpp >> 1; o > 0; o >>= 1) s[u] += __shfl_xor(s[u], o, 64);
+      const int p = (g0 + 4 * u) * ppw + sub;
+      if (cg == 0 && g0 + 4 * u < ngrp && p < HW) cam[(size_t)m * HW + p] = relu ? fmaxf(s[u], 0.f) : s[u];
+    }
+  }
+}
+
+extern "C" int bx_cam_reduce(const void* A, const void* G, float* cam, float* weights_out, int n_maps, int maps_per_act, int HW, int C,
+                             int method, int relu, int dtype, bxStream stream) {
+  const char* who = method == BX_CAM_GRADCAM ? "bx_gradcam_reduce" : "bx_cam_reduce";
+  BX_REQUIRE(method >= BX_CAM_GRADCAM && method <= BX_CAM_LAYERCAM, "%s: unknown method %d (0 = Grad-CAM, 1 = Grad-CAM++, 2 = Layer-CAM)", who, method);
+  BX_REQUIRE(method != BX_CAM_LAYERCAM || !weights_out, "%s: Layer-CAM has no channel weights (weights_out must be NULL)", who);
+  BX_DTYPE_OK(dtype);
+  BX_REQUIRE(A && G && cam && n_maps > 0 && HW > 0 && maps_per_act > 0 && n_maps % maps_per_act == 0, "%s: bad arguments", who);
+  BX_REQUIRE(C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0, "%s: C=%d must be 8*2^k, <= 2048", who, C);
+  hipStream_t s = (hipStream_t)stream;
+  if (method == BX_CAM_GRADCAM) {
+    const size_t lds = ((size_t)(256 / (C / 8)) * C + C) * sizeof(float);
+    BX_DISPATCH_DTYPE(dtype, T,
+      hipLaunchKernelGGL((k_gradcam<T>), dim3(n_maps), dim3(256), lds, s, (const T*)A, (const T*)G, cam, weights_out, HW, C, maps_per_act, relu));
+  } else if (method == BX_CAM_GRADCAM_PP) {
+    const size_t lds = ((size_t)2048 + 2 * C) * sizeof(float);
+    BX_DISPATCH_DTYPE(dtype, T,
+      hipLaunchKernelGGL((k_cam<T, BX_CAM_GRADCAM_PP>), dim3(n_maps), dim3(256), lds, s, (const T*)A, (const T*)G, cam, weights_out, HW, C,
+                         maps_per_act, relu));
+  } else {
+    BX_DISPATCH_DTYPE(dtype, T,
+      hipLaunchKernelGGL((k_cam<T, BX_CAM_LAYERCAM>), dim3(n_maps), dim3(256), 0, s, (const T*)A, (const T*)G, cam, (float*)nullptr, HW, C,
+                         maps_per_act, relu));
+  }
+  BX_CHECK_LAUNCH(who);
+  return BX_OK;
+}
 extern "C" int bx_gradcam_reduce(const void* A, const void* G, float* cam, float* weights_out, int n_maps, int maps_per_act,
                                  int HW, int C, int relu, int dtype, bxStream stream) {
-  BX_DTYPE_OK(dtype);
-  BX_REQUIRE(A && G && cam && n_maps > 0 && HW > 0 && maps_per_act > 0 && n_maps % maps_per_act == 0, "bx_gradcam_reduce: bad arguments");
-  BX_REQUIRE(C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0, "bx_gradcam_reduce: C=%d must be 8*2^k, <= 2048", C);
-  const size_t lds = ((size_t)(256 / (C / 8)) * C + C) * sizeof(float);
-  BX_DISPATCH_DTYPE(dtype, T,
-    hipLaunchKernelGGL((k_gradcam<T>), dim3(n_maps), dim3(256), lds, (hipStream_t)stream, (const T*)A, (const T*)G, cam, weights_out,
-                       HW, C, maps_per_act, relu));
-  BX_CHECK_LAUNCH("bx_gradcam_reduce");
-  return BX_OK;
+  return bx_cam_reduce(A, G, cam, weights_out, n_maps, maps_per_act, HW, C, BX_CAM_GRADCAM, relu, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -74,7 +166,7 @@ extern "C" int bx_gradcam_reduce(const void* A, const void* G, float* cam, float
 // Sweep form (bx_gradcam_head_sweep; GcExtra.ef / .up non-null): the EEG branch's dense layer + LogSoftmax (a launch of its own per
 // batch otherwise) and the bilinear up-sampling of the finished map (a second launch and a round trip of the small maps) run here too.
 struct GcExtra { const float* ef; const float* dw; const float* db; int Fe; float* up; int h, w, H, W; };
-template <typename T>
+template <typename T, int METHOD = BX_CAM_GRADCAM>
 __global__ __launch_bounds__(256) void k_gradcam_head(const T* __restrict__ A, const float* __restrict__ e_lp, const float* __restrict__ fcw,
                                                        const float* __restrict__ fcb, const float* __restrict__ w1, const float* __restrict__ b1,
                                                        const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ out_lp,
@@ -246,6 +338,11 @@ __global__ __launch_bounds__(256) void k_gradcam_head(const T* __restrict__ A, c
         for (int u = 0; u < 8; ++u) acc = n0 + u < N ? fmaf(wv[u], dz[n0 + u], acc) : acc;
       }
       acc *= inv_hw;
+      if constexpr (METHOD == BX_CAM_LAYERCAM) {          // (the gradient is acc at every position, and S[k] = HW gap[k])
+        acc = fmaxf(acc, 0.f);
+      } else if constexpr (METHOD == BX_CAM_GRADCAM_PP) {
+        acc = (float)HW * campp_term(acc, (float)HW * gap[k]);
+      }
       w[k] = acc;
       if (wdst) wdst[k] = acc;
     }
@@ -346,41 +443,62 @@ __global__ __launch_bounds__(256) void k_gradcam_head(const T* __restrict__ A, c
   }
 }
 
+#define BX_CAM_HEAD_LAUNCH(METHOD, ...) do { switch (METHOD) {                                                                  \
+  case BX_CAM_GRADCAM:    BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_gradcam_head<T>), __VA_ARGS__)); break;                        \
+  case BX_CAM_GRADCAM_PP: BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_gradcam_head<T, BX_CAM_GRADCAM_PP>), __VA_ARGS__)); break;     \
+  default:                BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_gradcam_head<T, BX_CAM_LAYERCAM>), __VA_ARGS__)); break; } } while (0)
+
+extern "C" int bx_cam_head(const void* A, const float* eeg_logp, const float* fc_w, const float* fc_b, const float* w1, const float* b1,
+                           const float* w2, const float* b2, float* out_logp, float* cam, float* raw, float* weights_out, int B, int HW,
+                           int C, int N, int Hd, int class_mode, int method, int relu, int dtype, bxStream stream) {
+  const char* who = method == BX_CAM_GRADCAM ? "bx_gradcam_head" : "bx_cam_head";
+  BX_REQUIRE(method >= BX_CAM_GRADCAM && method <= BX_CAM_LAYERCAM, "%s: unknown method %d (0 = Grad-CAM, 1 = Grad-CAM++, 2 = Layer-CAM)", who, method);
+  BX_REQUIRE(method != BX_CAM_LAYERCAM || !weights_out, "%s: Layer-CAM has no channel weights (weights_out must be NULL)", who);
+  BX_DTYPE_OK(dtype);
+  BX_REQUIRE(A && eeg_logp && fc_w && fc_b && w1 && b1 && w2 && b2 && cam, "%s: null pointer", who);
+  BX_REQUIRE(B > 0 && HW > 0 && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0 && N > 0 && N <= 64 && Hd > 0 && Hd <= 4096,
+             "%s: unsupported sizes (C=%d must be 8*2^k <= 2048, N=%d <= 64, Hd=%d <= 4096)", who, C, N, Hd);
+  BX_REQUIRE(class_mode >= -2 && class_mode < N, "%s: class %d out of range", who, class_mode);
+  const size_t lds = ((size_t)2 * C + 2 * Hd + 5 * N + (size_t)(256 / (C / 8)) * C) * sizeof(float);
+  const GcExtra none = {nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0};
+  BX_CAM_HEAD_LAUNCH(method, dim3(B, class_mode == -2 ? N : 1), dim3(256), lds, (hipStream_t)stream, (const T*)A, eeg_logp, fc_w, fc_b, w1, b1,
+                     w2, b2, out_logp, cam, raw, weights_out, HW, C, N, Hd, class_mode, relu, none);
+  BX_CHECK_LAUNCH(who);
+  return BX_OK;
+}
 extern "C" int bx_gradcam_head(const void* A, const float* eeg_logp, const float* fc_w, const float* fc_b, const float* w1, const float* b1,
                                const float* w2, const float* b2, float* out_logp, float* cam, float* raw, float* weights_out, int B, int HW,
                                int C, int N, int Hd, int class_mode, int relu, int dtype, bxStream stream) {
+  return bx_cam_head(A, eeg_logp, fc_w, fc_b, w1, b1, w2, b2, out_logp, cam, raw, weights_out, B, HW, C, N, Hd, class_mode, BX_CAM_GRADCAM,
+                     relu, dtype, stream);
+}
+extern "C" int bx_cam_head_sweep(const void* A, const float* eeg_feat, const float* dense_w, const float* dense_b, int Fe, const float* fc_w,
+                                 const float* fc_b, const float* w1, const float* b1, const float* w2, const float* b2, float* out_logp,
+                                 float* maps, int B, int h, int w, int C, int N, int Hd, int H, int W, int class_mode, int method, int relu,
+                                 int dtype, bxStream stream) {
+  const char* who = method == BX_CAM_GRADCAM ? "bx_gradcam_head_sweep" : "bx_cam_head_sweep";
+  BX_REQUIRE(method >= BX_CAM_GRADCAM && method <= BX_CAM_LAYERCAM, "%s: unknown method %d (0 = Grad-CAM, 1 = Grad-CAM++, 2 = Layer-CAM)", who, method);
   BX_DTYPE_OK(dtype);
-  BX_REQUIRE(A && eeg_logp && fc_w && fc_b && w1 && b1 && w2 && b2 && cam, "bx_gradcam_head: null pointer");
-  BX_REQUIRE(B > 0 && HW > 0 && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0 && N > 0 && N <= 64 && Hd > 0 && Hd <= 4096,
-             "bx_gradcam_head: unsupported sizes (C=%d must be 8*2^k <= 2048, N=%d <= 64, Hd=%d <= 4096)", C, N, Hd);
-  BX_REQUIRE(class_mode >= -2 && class_mode < N, "bx_gradcam_head: class %d out of range", class_mode);
-  const size_t lds = ((size_t)2 * C + 2 * Hd + 5 * N + (size_t)(256 / (C / 8)) * C) * sizeof(float);
-  const GcExtra none = {nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0};
-  BX_DISPATCH_DTYPE(dtype, T,
-    hipLaunchKernelGGL((k_gradcam_head<T>), dim3(B, class_mode == -2 ? N : 1), dim3(256), lds, (hipStream_t)stream, (const T*)A, eeg_logp, fc_w, fc_b, w1, b1, w2, b2,
-                       out_logp, cam, raw, weights_out, HW, C, N, Hd, class_mode, relu, none));
-  BX_CHECK_LAUNCH("bx_gradcam_head");
+  BX_REQUIRE(A && eeg_feat && dense_w && dense_b && fc_w && fc_b && w1 && b1 && w2 && b2 && maps, "%s: null pointer", who);
+  const int HW = h * w;
+  BX_REQUIRE(B > 0 && h > 0 && w > 0 && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0 && N > 0 && N <= 64 && Hd > 0 && Hd <= 4096 && Fe > 0,
+             "%s: unsupported sizes (C=%d must be 8*2^k <= 2048, N=%d <= 64, Hd=%d <= 4096)", who, C, N, Hd);
+  BX_REQUIRE(H > 0 && W > 0 && W % 4 == 0 && ((uintptr_t)maps & 15) == 0, "%s: W must be a multiple of 4 and maps 16-byte aligned", who);
+  BX_REQUIRE(class_mode >= -2 && class_mode < N, "%s: class %d out of range", who, class_mode);
+  const size_t lds = ((size_t)2 * C + 2 * Hd + 5 * N + (size_t)(256 / (C / 8)) * C + HW) * sizeof(float);
+  BX_REQUIRE(lds <= 64 * 1024, "%s: stage output of %d positions x %d channels does not fit the workgroup's LDS", who, HW, C);
+  const GcExtra ex = {eeg_feat, dense_w, dense_b, Fe, maps, h, w, H, W};
+  BX_CAM_HEAD_LAUNCH(method, dim3(B, class_mode == -2 ? N : 1), dim3(256), lds, (hipStream_t)stream, (const T*)A, (const float*)nullptr, fc_w,
+                     fc_b, w1, b1, w2, b2, out_logp, (float*)nullptr, (float*)nullptr, (float*)nullptr, HW, C, N, Hd, class_mode, relu, ex);
+  BX_CHECK_LAUNCH(who);
   return BX_OK;
 }
 extern "C" int bx_gradcam_head_sweep(const void* A, const float* eeg_feat, const float* dense_w, const float* dense_b, int Fe, const float* fc_w,
                                      const float* fc_b, const float* w1, const float* b1, const float* w2, const float* b2, float* out_logp,
                                      float* maps, int B, int h, int w, int C, int N, int Hd, int H, int W, int class_mode, int relu, int dtype,
                                      bxStream stream) {
-  BX_DTYPE_OK(dtype);
-  BX_REQUIRE(A && eeg_feat && dense_w && dense_b && fc_w && fc_b && w1 && b1 && w2 && b2 && maps, "bx_gradcam_head_sweep: null pointer");
-  const int HW = h * w;
-  BX_REQUIRE(B > 0 && h > 0 && w > 0 && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0 && N > 0 && N <= 64 && Hd > 0 && Hd <= 4096 && Fe > 0,
-             "bx_gradcam_head_sweep: unsupported sizes (C=%d must be 8*2^k <= 2048, N=%d <= 64, Hd=%d <= 4096)", C, N, Hd);
-  BX_REQUIRE(H > 0 && W > 0 && W % 4 == 0 && ((uintptr_t)maps & 15) == 0, "bx_gradcam_head_sweep: W must be a multiple of 4 and maps 16-byte aligned");
-  BX_REQUIRE(class_mode >= -2 && class_mode < N, "bx_gradcam_head_sweep: class %d out of range", class_mode);
-  const size_t lds = ((size_t)2 * C + 2 * Hd + 5 * N + (size_t)(256 / (C / 8)) * C + HW) * sizeof(float);
-  BX_REQUIRE(lds <= 64 * 1024, "bx_gradcam_head_sweep: stage output of %d positions x %d channels does not fit the workgroup's LDS", HW, C);
-  const GcExtra ex = {eeg_feat, dense_w, dense_b, Fe, maps, h, w, H, W};
-  BX_DISPATCH_DTYPE(dtype, T,
-    hipLaunchKernelGGL((k_gradcam_head<T>), dim3(B, class_mode == -2 ? N : 1), dim3(256), lds, (hipStream_t)stream, (const T*)A, (const float*)nullptr, fc_w,
-                       fc_b, w1, b1, w2, b2, out_logp, (float*)nullptr, (float*)nullptr, (float*)nullptr, HW, C, N, Hd, class_mode, relu, ex));
-  BX_CHECK_LAUNCH("bx_gradcam_head_sweep");
-  return BX_OK;
+  return bx_cam_head_sweep(A, eeg_feat, dense_w, dense_b, Fe, fc_w, fc_b, w1, b1, w2, b2, out_logp, maps, B, h, w, C, N, Hd, H, W, class_mode,
+                           BX_CAM_GRADCAM, relu, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -128,6 +128,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(bx_lane(v, 0), bx_lane(v, 16)), fmaxf(bx_lane(v, 32), bx_lane(v, 48)));
 }
 
+// Grad-CAM++ (include/brainxai.h, BX_CAM_GRADCAM_PP): one position's share of the channel weight, max(g, 0) * alpha(g, S) with
+// alpha = g^2 / (2 g^2 + S g^3 + eps) and alpha = 0 where g == 0; S = sum_s A[k, s] of the channel
+#define BX_CAM_EPS 1e-6f
+__device__ __forceinline__ float campp_term(float g, float S) {
+  const float g2 = g * g, g3 = g2 * g;
+  return g > 0.f ? g3 / (2.f * g2 + S * g3 + BX_CAM_EPS) : 0.f;
+}
+
 // LogSoftmax backward for one row, dz_n = dy_n - softmax_n * sum_j dy_j, evaluated WITHOUT its cancellation:
 //     dz_n = dy_n * (sum_{j != n} p_j)  -  p_n * (sum_{j != n} dy_j),      p = exp(logp).
 // The textbook form computes (1 - p_n) by subtraction; with a one-hot seed on a confident sample (saliency / Grad-CAM of the

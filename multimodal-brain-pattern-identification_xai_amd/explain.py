@@ -2,7 +2,8 @@
 
 * ``grad_cam``                -- canonical Grad-CAM (the reference ships none): forward,
                                  backward from the class score to the target layer only, then the fused
-                                 activation x gradient channel-reduce kernel (bx_gradcam_reduce).
+                                 activation x gradient channel-reduce kernel (bx_cam_reduce); method=
+                                 'gradcam++' / 'layercam' for Grad-CAM++ and Layer-CAM at every target.
 * ``saliency`` / ``generate_saliency_maps`` -- reference XAI_Multimodality.py:3101-3133.
 * ``integrated_gradients``    -- Captum-default semantics (imported but never called by the reference, NB:51).
 """
@@ -56,13 +57,22 @@ def _class_seed(out: torch.Tensor, class_mode: int, rows=None) -> torch.Tensor:
     return seed
 
 
-def _reduce(A_nhwc, G_nhwc, maps_per_act, relu):
+_METHODS = {"gradcam": L.BX_CAM_GRADCAM, "gradcam++": L.BX_CAM_GRADCAM_PP, "layercam": L.BX_CAM_LAYERCAM}
+
+
+def _method_code(method):
+    if method not in _METHODS:
+        raise ValueError(f"unknown class-activation method {method!r}; use one of " + ", ".join(f"'{k}'" for k in _METHODS))
+    return _METHODS[method]
+
+
+def _reduce(A_nhwc, G_nhwc, maps_per_act, relu, method=L.BX_CAM_GRADCAM):
     lib = L.load()
     n_maps, h, w, c = G_nhwc.shape
     cam = torch.empty(n_maps, h, w, dtype=torch.float32, device=G_nhwc.device)
-    wts = torch.empty(n_maps, c, dtype=torch.float32, device=G_nhwc.device)
-    L.check(lib.bx_gradcam_reduce(_p(A_nhwc), _p(G_nhwc), _p(cam), _p(wts), n_maps, maps_per_act, h * w, c, 1 if relu else 0,
-                                  ops.bx_dtype(A_nhwc.dtype), _stream()), "bx_gradcam_reduce")
+    wts = None if method == L.BX_CAM_LAYERCAM else torch.empty(n_maps, c, dtype=torch.float32, device=G_nhwc.device)
+    L.check(lib.bx_cam_reduce(_p(A_nhwc), _p(G_nhwc), _p(cam), _p(wts), n_maps, maps_per_act, h * w, c, method, 1 if relu else 0,
+                              ops.bx_dtype(A_nhwc.dtype), _stream()), "bx_cam_reduce")
     return cam, wts
 
 
@@ -90,10 +100,11 @@ def _eeg_head(em, f):
     return ops.LinearLsmFn.apply(f, em.dense.weight, em.dense.bias)
 
 
-def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_parts):
-    """Grad-CAM at an EEGNet block-1/2 convolution (explain.grad_cam).  The EEG branch runs forward once without autograd, keeping
-    its saved arena; the rest of the model runs on a detached feature leaf, autograd gives dy_c/dfeat for each class seed; then ONE
-    bx_eeg_gradcam call does the backward to the target and the channel reduce (and for conv1 the combined-kernel FIR over x)."""
+def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_parts, method=L.BX_CAM_GRADCAM):
+    """Grad-CAM (or Grad-CAM++ / Layer-CAM) at an EEGNet block-1/2 convolution (explain.grad_cam).  The EEG branch runs forward once
+    without autograd, keeping its saved arena; the rest of the model runs on a detached feature leaf, autograd gives dy_c/dfeat for
+    each class seed; then ONE bx_eeg_cam call does the backward to the target and the reduce of the method (and for conv1 the FIR
+    over x)."""
     from .models import EEGNet, EEGNetAttentionDeep
     multimodal = hasattr(model, "eeg_model")
     em = model.eeg_model if multimodal else model
@@ -116,7 +127,7 @@ def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_par
     n_cls = model.fc2.out_features if multimodal else (em.dense2.out_features if hasattr(em, "dense2") else em.dense.out_features)
     nm = n_cls if modes is None else 1
     probe = L.EegDesc(B, eeg.shape[-2], T, g.F1, g.D, g.F2, g.K1, g.K2, g.P1, g.P2, 0, 1e-5, 0.1, 0.0, 0, L.BX_F32, 0, -1.0)
-    if lib.bx_eeg_gradcam_workspace(C.byref(probe), nm, target) == 0:
+    if lib.bx_eeg_cam_workspace(C.byref(probe), nm, target, method) == 0:
         raise ValueError(f"EEG Grad-CAM supports the tuned EEGNet family only: F1=8, D=2, F2=16, K2=16, kernLength <= 64, Chans <= 64, "
                          f"T <= 15000, at most 64 classes (got F1={g.F1}, D={g.D}, F2={g.F2}, kernLength={g.K1}, Chans={eeg.shape[-2]}, "
                          f"T={T}, {nm} maps per sample)")
@@ -138,10 +149,10 @@ def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_par
         dev = feat.device
         cam = torch.empty(B * nm, *shape1, dtype=torch.float32, device=dev)
         raw = torch.empty_like(cam) if (return_parts and relu) else None
-        wts = torch.empty(B * nm, nw, dtype=torch.float32, device=dev) if return_parts else None
-        ws = ops.workspace(lib.bx_eeg_gradcam_workspace(C.byref(desc), nm, target), dev)
-        L.check(lib.bx_eeg_gradcam(C.byref(desc), C.byref(params), _p(x), _p(saved), _p(dfeat), nm, target, 1 if relu else 0, _p(cam),
-                                   _p(raw), _p(wts), _p(ws), ws.numel(), _stream()), "bx_eeg_gradcam")
+        wts = torch.empty(B * nm, nw, dtype=torch.float32, device=dev) if return_parts and method != L.BX_CAM_LAYERCAM else None
+        ws = ops.workspace(lib.bx_eeg_cam_workspace(C.byref(desc), nm, target, method), dev)
+        L.check(lib.bx_eeg_cam(C.byref(desc), C.byref(params), _p(x), _p(saved), _p(dfeat), nm, target, method, 1 if relu else 0,
+                               _p(cam), _p(raw), _p(wts), _p(ws), ws.numel(), _stream()), "bx_eeg_cam")
         if raw is None:
             raw = cam
         A = None
@@ -158,14 +169,14 @@ def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_par
     def shape(t):
         return t.reshape(B, nm, *t.shape[1:]) if stacked else t
     if return_parts:
-        return shape(cam), shape(raw), shape(wts), A, out.detach()
+        return shape(cam), shape(raw), None if wts is None else shape(wts), A, out.detach()
     return shape(cam)
 
 
-def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_parts):
+def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_parts, method=L.BX_CAM_GRADCAM):
     """Default target (the last stage feeds the heads directly): no autograd and no framework arithmetic at all.  The two
-    branches run forward, then ONE launch (bx_gradcam_head) does both heads forward, their backward for every requested class
-    and the activation x gradient channel reduce; a second launch upsamples the maps."""
+    branches run forward, then ONE launch (bx_cam_head) does both heads forward, their backward for every requested class
+    and the method's channel reduce; a second launch upsamples the maps."""
     lib = L.load()
     sm = model.spectrogram_model
     if class_idx is None:
@@ -193,10 +204,10 @@ def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_par
             lds_floats = 2 * C + 2 * Hd + 5 * N + (256 // (C // 8)) * C + h * w
             if lds_floats * 4 <= 64 * 1024:
                 maps = torch.empty(B * nm, H, W, dtype=torch.float32, device=A.device)
-                L.check(lib.bx_gradcam_head_sweep(_p(A), _p(ef), _p(em.dense.weight), _p(em.dense.bias), ef.shape[1], _p(sm.fc.weight),
-                                                  _p(sm.fc.bias), _p(model.fc1.weight), _p(model.fc1.bias), _p(model.fc2.weight),
-                                                  _p(model.fc2.bias), None, _p(maps), B, h, w, C, N, Hd, H, W, mode, 1 if relu else 0,
-                                                  ops.bx_dtype(A.dtype), _stream()), "bx_gradcam_head_sweep")
+                L.check(lib.bx_cam_head_sweep(_p(A), _p(ef), _p(em.dense.weight), _p(em.dense.bias), ef.shape[1], _p(sm.fc.weight),
+                                              _p(sm.fc.bias), _p(model.fc1.weight), _p(model.fc1.bias), _p(model.fc2.weight),
+                                              _p(model.fc2.bias), None, _p(maps), B, h, w, C, N, Hd, H, W, mode, method, 1 if relu else 0,
+                                              ops.bx_dtype(A.dtype), _stream()), "bx_cam_head_sweep")
                 return maps.reshape(B, nm, H, W) if isinstance(class_idx, str) else maps
             e = ops.LinearLsmFn.apply(ef, em.dense.weight, em.dense.bias).contiguous()
         else:
@@ -209,16 +220,16 @@ def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_par
         out = torch.empty(B, N, dtype=torch.float32, device=dev)
         cam = torch.empty(B * nm, h, w, dtype=torch.float32, device=dev)
         raw = torch.empty_like(cam) if return_parts else None
-        wts = torch.empty(B * nm, C, dtype=torch.float32, device=dev) if return_parts else None
-        L.check(lib.bx_gradcam_head(_p(A), _p(e), _p(sm.fc.weight), _p(sm.fc.bias), _p(model.fc1.weight), _p(model.fc1.bias),
-                                    _p(model.fc2.weight), _p(model.fc2.bias), _p(out), _p(cam), _p(raw), _p(wts), B, h * w, C, N, Hd, mode,
-                                    1 if relu else 0, ops.bx_dtype(A.dtype), _stream()), "bx_gradcam_head")
+        wts = torch.empty(B * nm, C, dtype=torch.float32, device=dev) if return_parts and method != L.BX_CAM_LAYERCAM else None
+        L.check(lib.bx_cam_head(_p(A), _p(e), _p(sm.fc.weight), _p(sm.fc.bias), _p(model.fc1.weight), _p(model.fc1.bias),
+                                _p(model.fc2.weight), _p(model.fc2.bias), _p(out), _p(cam), _p(raw), _p(wts), B, h * w, C, N, Hd, mode,
+                                method, 1 if relu else 0, ops.bx_dtype(A.dtype), _stream()), "bx_cam_head")
         if upsample:
             cam = resize_bilinear(cam, spec.shape[-2:])
     stacked = isinstance(class_idx, str)
     shape = (lambda t: t.reshape(B, nm, *t.shape[1:])) if stacked else (lambda t: t)
     if return_parts:
-        return shape(cam), shape(raw), shape(wts), A, out
+        return shape(cam), shape(raw), None if wts is None else shape(wts), A, out
     return shape(cam)
 
 
@@ -227,7 +238,8 @@ class GradCamSweep:
     10 000 samples, all classes).  The launches of `grad_cam` are captured once per batch shape on static input buffers (the
     ragged last batch of a sweep gets its own capture the first time it is seen); a call copies the batch in and replays them,
     so the sweep runs at GPU speed instead of at the host's launch rate.  The returned tensor is that graph's static output
-    buffer: clone it if it must outlive the next call with the same shape.
+    buffer: clone it if it must outlive the next call with the same shape.  ``method`` is that of `grad_cam` ('gradcam',
+    'gradcam++', 'layercam'); a replay runs the eager call's launches, so its maps equal ``grad_cam(..., method=method)``.
 
     The captured launches hold no weight-packing jobs: a call re-packs first when a parameter changed since the last pack -- as far
     as torch's version counters and this library's own optimizer kernels can tell.  A parameter rewritten through a ``.data`` view
@@ -238,10 +250,11 @@ class GradCamSweep:
             maps = sweep(eeg, spec)          # [B, 6, H, W]
     """
 
-    def __init__(self, model, eeg, spec, class_idx="all", upsample=True, relu=True):
+    def __init__(self, model, eeg, spec, class_idx="all", upsample=True, relu=True, method="gradcam"):
+        code = _method_code(method)
         if not (eeg.is_cuda and spec.is_cuda):
             raise RuntimeError("brainxai.GradCamSweep needs CUDA tensors; there is no CPU path")
-        self.model, self.args = model, (class_idx, upsample, relu)
+        self.model, self.args = model, (class_idx, upsample, relu, code)
         self._graphs = {}
         self._capture(eeg, spec)
 
@@ -255,7 +268,7 @@ class GradCamSweep:
 
     def _capture(self, eeg, spec):
         model = self.model
-        class_idx, upsample, relu = self.args
+        class_idx, upsample, relu, method = self.args
         s_eeg, s_spec = eeg.detach().clone().contiguous(), spec.detach().clone().contiguous()
         # The kernels that read the raw batch take its address from a device slot (ops.INPUT_SLOTS): a replay on the caller's own
         # fp32 tensors costs one 16-byte store instead of two copies (43 MB per batch of 64 at the bench shape, ~20 us).  Inputs in
@@ -273,12 +286,12 @@ class GradCamSweep:
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
                     for _ in range(2):                   # allocate workspaces / pack tables on the capture stream
-                        _grad_cam_last_stage(model, s_eeg, s_spec, class_idx, upsample, relu, False)
+                        _grad_cam_last_stage(model, s_eeg, s_spec, class_idx, upsample, relu, False, method)
                 torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    out = _grad_cam_last_stage(model, s_eeg, s_spec, class_idx, upsample, relu, False)
+                    out = _grad_cam_last_stage(model, s_eeg, s_spec, class_idx, upsample, relu, False, method)
         finally:
             model.train(was_training)
             used = (False, False)
@@ -369,11 +382,20 @@ def sharded_sweep(fn, n_samples, batch_size, fetch, rank=None, world=None, gathe
 
 
 def grad_cam(model, eeg, spec, target_layer="spectrogram_model.block5", class_idx=None, upsample=True, relu=True,
-             return_parts=False):
+             return_parts=False, method="gradcam"):
     """Grad-CAM heat-maps of ``model(eeg, spec)``.
 
     score y_c = the model's output log-probability of class c;  w[b,k] = mean_hw dy_c/dA[b,k];
     cam[b] = ReLU(sum_k w[b,k] A[b,k]); optionally bilinear-upsampled to the spectrogram's H x W.
+
+    method:       'gradcam' (above), 'gradcam++' or 'layercam'.  With A[k,s] the target's activation (channel k, position s
+                  over the axes Grad-CAM averages), G = dy_c/dA and eps = 1e-6:
+                    'gradcam++': S_k = sum_s A[k,s];  alpha[k,s] = G^2 / (2 G^2 + S_k G^3 + eps), 0 where G == 0;
+                                 w_k = sum_s max(G[k,s], 0) alpha[k,s] (a sum, not a mean);  raw[s] = sum_k w_k A[k,s]
+                                 (Chattopadhyay et al., WACV 2018, eq. 19)
+                    'layercam':  raw[s] = sum_k max(G[k,s], 0) A[k,s]   (Jiang et al., TIP 2021)
+                  cam = ReLU(raw) if relu, then the same optional up-sampling; no normalisation.  Every target, class_idx form
+                  and option below works with every method.
 
     target_layer: 'spectrogram_model.blockN' (stage output) or 'spectrogram_model.blockN.convK'
                   (that convolution's pre-ReLU output, i.e. what a hook on the reference's nn.Conv2d sees);
@@ -390,11 +412,14 @@ def grad_cam(model, eeg, spec, target_layer="spectrogram_model.block5", class_id
     return_parts: (cam, raw, weights, A, out).  For EEG targets weights is [B(, n_classes), channels of the target]
                   and A the target's activation [B, channels, 1, time] -- None for conv1, whose [B, 8, Chans, T]
                   output is never formed (in evaluation mode its map is one combined 1-D filter over the input).
+                  weights holds w_k of the method: the Grad-CAM++ w_k for 'gradcam++', and None for 'layercam', whose
+                  weights vary with the position.
     The model's training mode and every parameter's requires_grad are restored on return.
     """
+    code = _method_code(method)
     me = _EEG_TARGET.match(target_layer)
     if me:
-        return _grad_cam_eeg(model, eeg, spec, me.group(1), class_idx, upsample, relu, return_parts)
+        return _grad_cam_eeg(model, eeg, spec, me.group(1), class_idx, upsample, relu, return_parts, code)
     if target_layer.startswith("eeg_model."):
         raise ValueError(f"unsupported EEG Grad-CAM target {target_layer!r}; use one of "
                          + ", ".join(f"'eeg_model.{k}'" for k in _EEG_TARGETS))
@@ -409,7 +434,7 @@ def grad_cam(model, eeg, spec, target_layer="spectrogram_model.block5", class_id
         was_training = model.training
         model.eval()
         try:
-            return _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_parts)
+            return _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_parts, code)
         finally:
             model.train(was_training)
     with _eval_frozen(model):
@@ -451,15 +476,15 @@ def grad_cam(model, eeg, spec, target_layer="spectrogram_model.block5", class_id
         nm = len(grads)
         # map index = sample * nm + class
         G = torch.stack(grads, dim=1).reshape(B * nm, *grads[0].shape[1:]) if nm > 1 else grads[0]
-        cam, wts = _reduce(A, G, nm, relu=relu)
-        raw = _reduce(A, G, nm, relu=False)[0] if (return_parts and relu) else cam
+        cam, wts = _reduce(A, G, nm, relu, code)
+        raw = _reduce(A, G, nm, False, code)[0] if (return_parts and relu) else cam
         if upsample:
             cam = resize_bilinear(cam, spec.shape[-2:])
     stacked = isinstance(class_idx, str)
     def shape(t):
         return t.reshape(B, nm, *t.shape[1:]) if stacked else t
     if return_parts:
-        return shape(cam), shape(raw), shape(wts), A, out.detach()
+        return shape(cam), shape(raw), None if wts is None else shape(wts), A, out.detach()
     return shape(cam)
 
 
