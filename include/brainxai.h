@@ -537,6 +537,32 @@ int bx_sumsq(const float* x, size_t n, float* out, bxStream stream);
  * channels-last layout [N,H,W,Cp] (dtype; channels C..Cp-1 zero) = torchvision ToTensor with scale 1/255; row-wise softmax. */
 int bx_u8_to_nhwc(const unsigned char* src, void* dst, int N, int H, int W, int C, int Cp, float scale, int dtype, bxStream stream);
 int bx_softmax_rows(const float* x, float* y, int rows, int N, bxStream stream);
+/* ---- LIME for images (lime 0.2.0.1 LimeImageExplainer.explain_instance, XAI_Multimodality.py:1658-1670): everything after the
+ * segmentation.  Limits of all four entry points: 1 <= S <= 1024 segments (labels 0..S-1), 1 <= C <= 4 image channels (Cp = 8),
+ * K <= 32 classes, N >= 2 samples; refused with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+/* Fudged colours (hide_color=None): colours u8 [B,S,C] = per (segment, channel) mean of img u8 [B,H,W,C] over segments i32 [B,H,W],
+ * exact 64-bit integer sum and count, double(sum) / count truncated -- bit for bit numpy's mean + astype(uint8).  A label without
+ * pixels gets 0 (the Python layer refuses such label maps). */
+int bx_lime_segment_mean(const unsigned char* img, const int* segments, unsigned char* colours, int B, int H, int W, int C, int S,
+                         bxStream stream);
+/* Rows n0 .. n0+n-1 of every image's neighbourhood, x [B*n, H, W, Cp] (dtype; image-major): pixel p of sample j is the image where
+ * Z u8 [B,N,S] has Z[b, n0+j, segments[p]] != 0 and colours[b, segments[p]] elsewhere, as (float)u8 * (float)(1/255) -- what
+ * bx_u8_to_nhwc gives for the perturbed uint8 image, which is never built; channels C..Cp-1 zero. */
+int bx_lime_perturb(const unsigned char* img, const int* segments, const unsigned char* colours, const unsigned char* Z, void* x,
+                    int B, int H, int W, int C, int Cp, int S, int N, int n0, int n, int dtype, bxStream stream);
+/* Weighted ridge surrogate per image and label, fp64, fixed summation order (identical bits run to run).  Z u8 [B,N,S] masks,
+ * P fp32 [B,N,K] class probabilities, labels i32 [B,nl] classes to explain, used i32 [B,S_used] feature subset (NULL: all,
+ * S_used = S).  weights[b,n] = sqrt(exp(-d^2 / kernel_width^2)), d = 1 - sqrt(sum_s Z[b,n,s] / S) (cosine distance to the all-ones
+ * row 0); then sklearn's Ridge(alpha, fit_intercept=True).fit(Z[:, used], P[:, label], sample_weight=weights): coef fp64
+ * [B,nl,S_used] (in the order of `used`), intercept, score (weighted R^2) and local_pred (prediction for row 0) fp64 [B,nl].
+ * workspace: bx_lime_fit_workspace bytes (0 for refused shapes), 8-byte aligned. */
+size_t bx_lime_fit_workspace(int B, int N, int S, int S_used, int K, int nl);
+int bx_lime_fit(const unsigned char* Z, const float* P, const int* labels, const int* used, int B, int N, int S, int S_used, int K, int nl,
+                double alpha, double kernel_width, void* workspace, size_t workspace_bytes, double* coef, double* intercept, double* score,
+                double* local_pred, double* weights, bxStream stream);
+/* Per-pixel heat map fp32 [B,nl,H,W]: map[b,l,p] = (float)coef[b,l,j] where used[b,j] == segments[b,p], 0 for unused features. */
+int bx_lime_weight_map(const double* coef, const int* used, const int* segments, float* map, int B, int nl, int H, int W, int S,
+                       int S_used, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

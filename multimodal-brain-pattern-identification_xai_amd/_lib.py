@@ -160,6 +160,11 @@ SIGNATURES = {
     "bx_sumsq": (i32, [vp, sz, vp, vp]),
     "bx_u8_to_nhwc": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
     "bx_softmax_rows": (i32, [vp, vp, i32, i32, vp]),
+    "bx_lime_segment_mean": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "bx_lime_perturb": (i32, [vp] * 5 + [i32] * 10 + [vp]),
+    "bx_lime_fit_workspace": (sz, [i32] * 6),
+    "bx_lime_fit": (i32, [vp] * 4 + [i32] * 6 + [C.c_double, C.c_double, vp, sz] + [vp] * 5 + [vp]),
+    "bx_lime_weight_map": (i32, [vp] * 4 + [i32] * 6 + [vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

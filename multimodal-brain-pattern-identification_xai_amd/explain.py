@@ -6,6 +6,9 @@
                                  'gradcam++' / 'layercam' for Grad-CAM++ and Layer-CAM at every target.
 * ``saliency`` / ``generate_saliency_maps`` -- reference XAI_Multimodality.py:3101-3133.
 * ``integrated_gradients``    -- Captum-default semantics (imported but never called by the reference, NB:51).
+* ``lime_image``              -- LIME for images as lime 0.2.0.1's explain_instance defines it (reference
+                                 XAI_Multimodality.py:1658-1670): perturbed batch, forward passes and the weighted
+                                 ridge surrogate on the GPU (bx_lime_*); ``predict_fn`` is its callback alone.
 """
 from __future__ import annotations
 
@@ -662,3 +665,254 @@ def predict_fn(images, model, device=None, max_batch=256):
     finally:
         model.train(was_training)
     return torch.cat(out).numpy()
+
+
+# ------------------------------------------------------------------------------------------------
+# LIME for images (lime 0.2.0.1, LimeImageExplainer.explain_instance; reference XAI_Multimodality.py:1658-1670)
+_LIME_MAX_S, _LIME_MAX_C, _LIME_MAX_K = 1024, 4, 32
+_LIME_SELECTIONS = ("auto", "none", "highest_weights")
+
+
+def grid_segments(H, W, rows, cols):
+    """Label map [H, W] (int32) of rows x cols time-by-frequency tiles, label = row * cols + col; tile heights (widths) differ by at
+    most one pixel when H (W) is not divisible.  The built-in segmentation for spectrograms; ``lime_image`` takes any label map."""
+    H, W, rows, cols = int(H), int(W), int(rows), int(cols)
+    if not (1 <= rows <= H and 1 <= cols <= W):
+        raise ValueError(f"grid_segments: need 1 <= rows <= H and 1 <= cols <= W, got H={H} W={W} rows={rows} cols={cols}")
+    r = (np.arange(H, dtype=np.int64) * rows) // H
+    c = (np.arange(W, dtype=np.int64) * cols) // W
+    return (r[:, None] * cols + c[None, :]).astype(np.int32)
+
+
+class LimeExplanation:
+    """What ``lime_image`` returns for one image, with the attribute names of lime's ImageExplanation: ``image``, ``segments``,
+    ``top_labels``, ``local_exp`` {label: [(feature, weight), ...] by descending |weight|}, ``intercept``, ``score``, ``local_pred``
+    {label: float}; plus ``weights`` [N] (kernel weights), ``masks`` [N, S] uint8, ``probs`` (device tensor [N, K])."""
+
+    def __init__(self, image, segments):
+        self.image, self.segments = image, segments
+        self.top_labels = None
+        self.local_exp, self.intercept, self.score, self.local_pred = {}, {}, {}, {}
+        self.weights = self.masks = self.probs = None
+        self._seg_dev, self._coef_dev, self._used_dev = None, {}, {}
+
+    def heatmap(self, label):
+        """Device tensor [H, W] fp32: the surrogate's weight of each pixel's segment (0 for features the fit did not use)."""
+        if label not in self._coef_dev:
+            raise KeyError("Label not in explanation")
+        coef, used, seg = self._coef_dev[label], self._used_dev[label], self._seg_dev
+        H, W = seg.shape
+        out = torch.empty(H, W, dtype=torch.float32, device=seg.device)
+        with torch.cuda.device(seg.device):
+            L.check(L.load().bx_lime_weight_map(_p(coef), _p(used), _p(seg), _p(out), 1, 1, H, W, self.masks.shape[1], coef.numel(), _stream()),
+                    "bx_lime_weight_map")
+        return out
+
+    def get_image_and_mask(self, label, positive_only=True, negative_only=False, hide_rest=False, num_features=5, min_weight=0.0):
+        """lime's ImageExplanation.get_image_and_mask (host numpy: presentation).  Returns (image, mask)."""
+        if label not in self.local_exp:
+            raise KeyError("Label not in explanation")
+        if positive_only and negative_only:
+            raise ValueError("Positive_only and negative_only cannot be true at the same time.")
+        segments, image, exp = self.segments, self.image, self.local_exp[label]
+        mask = np.zeros(segments.shape, segments.dtype)
+        temp = np.zeros(image.shape) if hide_rest else image.copy()
+        if positive_only or negative_only:
+            if positive_only:
+                fs = [f for f, w in exp if w > 0 and w > min_weight][:num_features]
+            else:
+                fs = [f for f, w in exp if w < 0 and abs(w) > min_weight][:num_features]
+            for f in fs:
+                temp[segments == f] = image[segments == f].copy()
+                mask[segments == f] = 1
+            return temp, mask
+        for f, w in exp[:num_features]:
+            if abs(w) < min_weight:
+                continue
+            c = 0 if w < 0 else 1
+            mask[segments == f] = -1 if w < 0 else 1
+            temp[segments == f] = image[segments == f].copy()
+            temp[segments == f, c] = np.max(image)
+        return temp, mask
+
+
+def _lime_colours_host(img, seg, S, hide_color):
+    """The fudged colour table u8 [B,S,C] where the package's arithmetic is float (a float image: segment means over the float
+    values, truncated; hide_color: the given colour), or None for a uint8 image with hide_color=None (bx_lime_segment_mean)."""
+    B, Cc = img.shape[0], img.shape[3]
+    if hide_color is not None:
+        return np.broadcast_to(np.broadcast_to(np.asarray(hide_color, dtype=np.float64), (Cc,)).astype(np.uint8), (B, S, Cc))
+    if img.dtype == np.uint8:
+        return None
+    out = np.empty((B, S, Cc), dtype=np.uint8)
+    for b in range(B):
+        for s in range(S):
+            out[b, s] = np.array([np.mean(img[b][seg[b] == s][:, c]) for c in range(Cc)]).astype(np.uint8)
+    return out
+
+
+def _lime_fit(Z, P, labels, used, alpha, kernel_width):
+    """bx_lime_fit on device tensors: Z u8 [B,N,S], P f32 [B,N,K], labels i32 [B,nl], used i32 [B,S'] or None."""
+    lib = L.load()
+    B, N, S = Z.shape
+    K, nl = P.shape[2], labels.shape[1]
+    Sp = S if used is None else used.shape[1]
+    dev = Z.device
+    f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)
+    coef, icpt, score, pred, wts = f64(B, nl, Sp), f64(B, nl), f64(B, nl), f64(B, nl), f64(B, N)
+    nbytes = lib.bx_lime_fit_workspace(B, N, S, Sp, K, nl)
+    if nbytes == 0:
+        L.check(-1, "bx_lime_fit_workspace")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    L.check(lib.bx_lime_fit(_p(Z), _p(P), _p(labels), _p(used), B, N, S, Sp, K, nl, float(alpha), float(kernel_width), _p(ws), nbytes,
+                            _p(coef), _p(icpt), _p(score), _p(pred), _p(wts), _stream()), "bx_lime_fit")
+    return coef, icpt, score, pred, wts
+
+
+def lime_image(model, image, segments, *, labels=None, top_labels=5, hide_color=None, num_features=100000, num_samples=1000,
+               feature_selection="auto", kernel_width=0.25, alpha=1.0, seed=0, masks=None, max_batch=256, device=None):
+    """LIME for images as lime 0.2.0.1's ``LimeImageExplainer.explain_instance`` defines it (the reference's call:
+    XAI_Multimodality.py:1658-1670), with the perturbed batch, the forward passes and the weighted ridge surrogate on the GPU.
+
+    image: numpy array or tensor [H,W,C] (C <= 4), or a batch [B,H,W,C] with ``segments`` [B,H,W] (a list of explanations comes back;
+    the images share N and S and draw their masks from one ``RandomState(seed)`` stream in image order).  uint8 images run wholly on
+    the device.  Float arrays holding 0..255 (what the package hands its callback) are accepted: kept pixels are truncated as
+    ``predict_fn`` does, and their fudged colours -- S x C segment means over the float values, then truncated, as the package
+    computes them -- are taken on the HOST with numpy and uploaded as the colour table.
+    segments: integer label map with labels exactly 0..S-1 (S <= 1024); ``grid_segments`` builds tiles, skimage output passes as is.
+    model: ``Spectrogram_Model`` or a ``MultimodalModel`` (through ``forward_spectrogram``), on the GPU; it runs in eval mode and gets
+    its training flag back; nothing needs a gradient.
+    masks: optional Z [N,S] / [B,N,S] of 0/1 replacing the draw (row 0 is set to ones; ``seed`` is then unused).
+    labels: classes to explain; None = the ``top_labels`` most probable classes of the unperturbed image.
+    hide_color: None = a hidden segment shows its own per-channel mean; otherwise that colour (a number or one per channel).
+    feature_selection: 'none', 'highest_weights' or 'auto' (= 'highest_weights' for num_features > 6, which uses every feature when
+    num_features >= S).  Semantics per step: DESIGN.md section 1, row G.  Returns a ``LimeExplanation`` (a list for a batch)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    if feature_selection not in _LIME_SELECTIONS:
+        raise ValueError(f"lime_image: feature_selection {feature_selection!r} is not supported; use one of "
+                         + ", ".join(f"'{s}'" for s in _LIME_SELECTIONS) + " ('forward_selection' and 'lasso_path' are not built)")
+    num_features, N = int(num_features), int(num_samples)
+    if feature_selection == "auto":
+        if num_features <= 6:
+            raise ValueError("lime_image: feature_selection='auto' with num_features <= 6 means 'forward_selection', which is not "
+                             "supported; use 'none' or 'highest_weights'")
+        feature_selection = "highest_weights"
+    if num_features < 1:
+        raise ValueError(f"lime_image: num_features = {num_features} < 1")
+    if N < 2:
+        raise ValueError(f"lime_image: num_samples = {N} < 2")
+    if int(max_batch) < 1:
+        raise ValueError(f"lime_image: max_batch = {max_batch} < 1")
+    if not (float(kernel_width) > 0 and float(alpha) > 0):
+        raise ValueError("lime_image: kernel_width and alpha must be positive")
+    img = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+    seg = segments.detach().cpu().numpy() if isinstance(segments, torch.Tensor) else np.asarray(segments)
+    single = img.ndim == 3
+    if single:
+        img, seg = img[None], seg[None] if seg.ndim == 2 else seg
+    if img.ndim != 4 or seg.ndim != 3 or seg.shape != img.shape[:3]:
+        raise ValueError(f"lime_image: image {tuple(np.shape(image))} and segments {tuple(np.shape(segments))} do not match "
+                         "([H,W,C] with [H,W], or [B,H,W,C] with [B,H,W])")
+    B, H, W, Cc = img.shape
+    if not 1 <= Cc <= _LIME_MAX_C:
+        raise ValueError(f"lime_image: {Cc} channels, supported 1..{_LIME_MAX_C}")
+    if not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError(f"lime_image: segments must be an integer label map, got {seg.dtype}")
+    if seg.min() < 0:
+        raise ValueError("lime_image: negative label in segments")
+    S = int(seg.max()) + 1
+    if S > _LIME_MAX_S:
+        raise ValueError(f"lime_image: {S} segments, supported 1..{_LIME_MAX_S}")
+    for b in range(B):
+        if np.unique(seg[b]).size != S:
+            raise ValueError(f"lime_image: segments{'' if single else f'[{b}]'} must use every label 0..{S - 1} (features are indexed by label)")
+    fwd = model.forward_spectrogram if hasattr(model, "forward_spectrogram") else model
+    net = model.spectrogram_model if hasattr(model, "spectrogram_model") else model
+    K = int(net.fc.out_features)
+    if K > _LIME_MAX_K:
+        raise ValueError(f"lime_image: {K} classes, supported up to {_LIME_MAX_K}")
+    if labels is not None:
+        labels = [int(k) for k in labels]
+        if not labels or len(labels) > K or any(not 0 <= k < K for k in labels):
+            raise ValueError(f"lime_image: labels {labels} outside [0, {K})")
+    elif not 1 <= int(top_labels):
+        raise ValueError(f"lime_image: top_labels = {top_labels} < 1")
+    if masks is not None:
+        Zh = np.asarray(masks.detach().cpu().numpy() if isinstance(masks, torch.Tensor) else masks)
+        if Zh.ndim == 2:
+            Zh = Zh[None]
+        if Zh.shape != (B, N, S) or not np.isin(Zh, (0, 1)).all():
+            raise ValueError(f"lime_image: masks must be 0/1 of shape [{'' if single else 'B, '}num_samples, S] = {(B, N, S)}, got {Zh.shape}")
+        Zh = Zh.astype(np.uint8)
+    else:
+        rs = np.random.RandomState(seed)
+        Zh = np.stack([rs.randint(0, 2, N * S).reshape(N, S) for _ in range(B)]).astype(np.uint8)
+    Zh[:, 0, :] = 1
+    device = torch.device(device) if device is not None else next(model.parameters()).device
+    if device.type != "cuda":
+        raise RuntimeError("brainxai.lime_image: the model must live on the GPU; there is no CPU path")
+    colours_h = _lime_colours_host(img, seg, S, hide_color)
+    img_u8 = np.ascontiguousarray(img.astype(np.uint8))
+
+    lib = L.load()
+    dt = getattr(net, "compute_dtype", torch.float32)
+    img_d = torch.from_numpy(img_u8).to(device)
+    seg_d = torch.from_numpy(np.ascontiguousarray(seg.astype(np.int32))).to(device)
+    Z_d = torch.from_numpy(Zh).to(device)
+    P = torch.empty(B, N, K, dtype=torch.float32, device=device)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.cuda.device(device), torch.no_grad():
+            if colours_h is None:
+                col_d = torch.empty(B, S, Cc, dtype=torch.uint8, device=device)
+                L.check(lib.bx_lime_segment_mean(_p(img_d), _p(seg_d), _p(col_d), B, H, W, Cc, S, _stream()), "bx_lime_segment_mean")
+            else:
+                col_d = torch.from_numpy(np.ascontiguousarray(colours_h)).to(device)
+            for b in range(B):                                     # the chunks of one image are the chunks predict_fn would run
+                for n0 in range(0, N, int(max_batch)):
+                    n = min(int(max_batch), N - n0)
+                    x = torch.empty(n, H, W, ops.pad8(Cc), dtype=dt, device=device)
+                    L.check(lib.bx_lime_perturb(_p(img_d[b]), _p(seg_d[b]), _p(col_d[b]), _p(Z_d[b]), _p(x), 1, H, W, Cc, ops.pad8(Cc), S, N, n0, n,
+                                                ops.bx_dtype(dt), _stream()), "bx_lime_perturb")
+                    logp = fwd(x.permute(0, 3, 1, 2)).float().contiguous()
+                    L.check(lib.bx_softmax_rows(_p(logp), _p(P[b, n0:n0 + n]), n, K, _stream()), "bx_softmax_rows")
+            # ---- labels: the K probabilities of each unperturbed image are all that is read back before the fit ----
+            if labels is None:
+                p0 = P[:, 0, :].cpu().numpy()
+                t = min(int(top_labels), K)
+                lab_h = np.stack([np.argsort(p0[b])[-t:][::-1] for b in range(B)]).astype(np.int32)
+            else:
+                lab_h = np.tile(np.asarray(labels, dtype=np.int32), (B, 1))
+            nl = lab_h.shape[1]
+            lab_d = torch.from_numpy(np.ascontiguousarray(lab_h)).to(device)
+            if feature_selection == "none" or num_features >= S:
+                coef, icpt, score, pred, wts = _lime_fit(Z_d, P, lab_d, None, alpha, kernel_width)
+                fits = [(coef[:, l], None, icpt[:, l], score[:, l], pred[:, l]) for l in range(nl)]
+            else:                                                  # 'highest_weights': first fit at alpha = 0.01 picks the features per label
+                coef0 = _lime_fit(Z_d, P, lab_d, None, 0.01, kernel_width)[0].cpu().numpy()
+                fits = []
+                for l in range(nl):
+                    used_h = np.stack([np.argsort(-np.abs(coef0[b, l] * Zh[b, 0]), kind="stable")[:num_features] for b in range(B)])
+                    used_d = torch.from_numpy(np.ascontiguousarray(used_h.astype(np.int32))).to(device)
+                    coef, icpt, score, pred, wts = _lime_fit(Z_d, P, lab_d[:, l:l + 1].contiguous(), used_d, alpha, kernel_width)
+                    fits.append((coef[:, 0], used_d, icpt[:, 0], score[:, 0], pred[:, 0]))
+    finally:
+        model.train(was_training)
+    wts_h = wts.cpu().numpy()
+    host = [(c.cpu().numpy(), None if u is None else u.cpu().numpy(), i.cpu().numpy(), s.cpu().numpy(), p.cpu().numpy()) for c, u, i, s, p in fits]
+    out = []
+    for b in range(B):
+        e = LimeExplanation(img[b], seg[b])
+        e.top_labels = None if labels is not None else [int(k) for k in lab_h[b]]
+        e.weights, e.masks, e.probs, e._seg_dev = wts_h[b], Zh[b], P[b], seg_d[b]
+        for l in range(nl):
+            k = int(lab_h[b, l])
+            c, u, i, s, p = host[l]
+            feats = np.arange(S) if u is None else u[b]
+            e.local_exp[k] = sorted(zip((int(f) for f in feats), (float(v) for v in c[b])), key=lambda fv: abs(fv[1]), reverse=True)
+            e.intercept[k], e.score[k], e.local_pred[k] = float(i[b]), float(s[b]), float(p[b])
+            e._coef_dev[k] = fits[l][0][b].contiguous()
+            e._used_dev[k] = None if fits[l][1] is None else fits[l][1][b].contiguous()
+        out.append(e)
+    return out[0] if single else out

@@ -698,11 +698,22 @@ def _run_epoch(model, loader, criterion, device, optimizer=None, ddp=None, unpac
 
 
 def train_and_validate_combined(model, train_loader, valid_loader, epochs, optimizer, criterion, device, checkpoint_dir,
-                                n=2, sample_spectrogram=None, async_checkpoint=False):
-    """Reference XAI_Multimodality.py:1579-1681 minus its LIME tail (CPU skimage; out of scope).
-    Batches are ``((eeg, spec), labels)``; returns (train_losses, valid_losses, train_accuracies, valid_accuracies)
-    and writes ``combined_checkpoint.pth.tar`` with the reference's dict layout each epoch (``async_checkpoint=True``:
-    through AsyncCheckpointer, the file of the last epoch is complete when the function returns)."""
+                                n=2, sample_spectrogram=None, async_checkpoint=False, explain_fn=None):
+    """Reference XAI_Multimodality.py:1579-1681.  Batches are ``((eeg, spec), labels)``; returns (train_losses, valid_losses,
+    train_accuracies, valid_accuracies) and writes ``combined_checkpoint.pth.tar`` with the reference's dict layout each epoch
+    (``async_checkpoint=True``: through AsyncCheckpointer, the file of the last epoch is complete when the function returns).
+
+    The reference's LIME tail (:1658-1670: every ``n`` epochs, ``explain_instance`` on ``sample_spectrogram``) runs when
+    ``explain_fn`` is given: with ``sample_spectrogram`` an image [H,W,C] or a pair ``(image, segments)`` (a bare image is cut into
+    ``grid_segments(H, W, 8, 8)``; the reference's skimage segmentation is not part of this package), every ``n``-th epoch calls
+    ``explain_fn(epoch, brainxai.lime_image(model, image, segments))`` after that epoch's checkpoint.  The explanation runs in
+    eval mode without gradients and leaves the training state alone.  With ``explain_fn=None`` both arguments are ignored."""
+    sample = None
+    if explain_fn is not None and sample_spectrogram is not None:
+        from .explain import grid_segments, lime_image
+        sample = tuple(sample_spectrogram) if isinstance(sample_spectrogram, (tuple, list)) else (sample_spectrogram, None)
+        if sample[1] is None:
+            sample = (sample[0], grid_segments(sample[0].shape[0], sample[0].shape[1], 8, 8))
     name = "combined_checkpoint.pth.tar"
     start, tr_l, va_l, tr_a, va_a = load_checkpoint(checkpoint_dir, name, model, optimizer)
     saver = AsyncCheckpointer(checkpoint_dir, name) if async_checkpoint else None
@@ -723,6 +734,8 @@ def train_and_validate_combined(model, train_loader, valid_loader, epochs, optim
             saver.save(state)
         else:
             save_checkpoint(state, checkpoint_dir, name)
+        if sample is not None and (epoch + 1) % n == 0:
+            explain_fn(epoch + 1, lime_image(model, sample[0], sample[1]))
     if saver is not None:
         saver.wait()
     return tr_l, va_l, tr_a, va_a
