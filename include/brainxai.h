@@ -563,6 +563,35 @@ int bx_lime_fit(const unsigned char* Z, const float* P, const int* labels, const
 /* Per-pixel heat map fp32 [B,nl,H,W]: map[b,l,p] = (float)coef[b,l,j] where used[b,j] == segments[b,p], 0 for unused features. */
 int bx_lime_weight_map(const double* coef, const int* used, const int* segments, float* map, int B, int nl, int H, int W, int S,
                        int S_used, bxStream stream);
+/* ---- Deletion / insertion curves (the causal metric of RISE, Petsiuk et al., BMVC 2018; the reference ships no faithfulness
+ * metric): score an attribution map by removing (deletion) or restoring (insertion) the input's cells in order of decreasing
+ * attribution, a fixed number `per` per step, and following the explained class.  A map has N cells per sample, 1 <= N < 2^20
+ * (refused with BX_EUNSUPPORTED above that, before any pointer is touched). */
+/* ranks i32 [B,N]: position of cell i in a stable descending sort of values fp32 [B,N] over the flat index, ties by ascending
+ * index: rank[b,i] = #{j : key[b,j] > key[b,i]} + #{j < i : key[b,j] == key[b,i]}, key = value with NaN counted as -inf and
+ * -0.0 equal to +0.0.  Exact and deterministic (per-row radix sort; no result depends on the order of an atomic).  Every row of
+ * ranks is a permutation of 0..N-1.  workspace: bx_rank_desc_workspace bytes (0 for refused shapes), 4-byte aligned. */
+size_t bx_rank_desc_workspace(int B, int N);
+int bx_rank_desc(const float* values, int* ranks, int B, int N, void* workspace, size_t workspace_bytes, bxStream stream);
+/* Perturbed spectrogram rows.  x fp32 NCHW [B,C,H,W], ranks i32 [B,H*W] (a cell is a pixel with all its channels) ->
+ * out [B*n, H, W, Cp] (dtype; sample-major: row b*n + j carries curve point i0 + j), channels C..Cp-1 zero, 1 <= C <= 4 (Cp = 8).
+ * With the cut k = min(H*W, (i0 + j) * per): deletion (insertion = 0) takes cells of rank < k from the baseline and the others from
+ * x, insertion the other way round.  Bit for bit bx_nchw_to_nhwc of that selection, which is never built.
+ * baseline fp32, by baseline_kind: 0 one value, 1 one value per channel [C], 2 a tensor of x's shape.
+ * Any number of points may sit at the clamped cut k = H*W (steps = 5 on 7 cells: per = 2, cuts 0 2 4 6 7 7); only the point index is
+ * bounded, i0 >= 0, n >= 1, i0 + n - 1 <= H*W.  One call's output stays below 2^32 bytes. */
+int bx_faith_perturb_spec(const float* x, const int* ranks, const float* baseline, int baseline_kind, void* out, int B, int C, int H,
+                          int W, int Cp, int per, int i0, int n, int insertion, int dtype, bxStream stream);
+/* Perturbed EEG rows.  x fp32 [B,1,Chans,T] -> out fp32 [B*n,1,Chans,T], same row order, cut and selection.  map_rows = Chans:
+ * ranks i32 [B,Chans*T], a cell is one electrode at one time step; map_rows = 1: ranks i32 [B,T], a cell is a time column across
+ * electrodes.  baseline_kind: 0 one value, 1 one value per electrode [Chans], 2 a tensor of x's shape. */
+int bx_faith_perturb_eeg(const float* x, const int* ranks, int map_rows, const float* baseline, int baseline_kind, float* out, int B,
+                         int Chans, int T, int per, int i0, int n, int insertion, bxStream stream);
+/* logp fp32 [B,P,K] (log-probabilities of the P = steps + 1 curve points), classes i32 [B] -> curve fp32 [B,P] =
+ * exp(logp[b,i,classes[b]]) (use_logprob: the log-probability itself) and auc fp64 [B] = (sum_i curve - curve[0]/2 - curve[P-1]/2)
+ * / (P - 1), RISE's trapezoid rule on the unit interval; the sum runs in fp64 over the stored fp32 points in index order, one
+ * thread per sample, so its bits do not depend on scheduling. */
+int bx_faith_curve(const float* logp, const int* classes, float* curve, double* auc, int B, int P, int K, int use_logprob, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

@@ -165,6 +165,11 @@ SIGNATURES = {
     "bx_lime_fit_workspace": (sz, [i32] * 6),
     "bx_lime_fit": (i32, [vp] * 4 + [i32] * 6 + [C.c_double, C.c_double, vp, sz] + [vp] * 5 + [vp]),
     "bx_lime_weight_map": (i32, [vp] * 4 + [i32] * 6 + [vp]),
+    "bx_rank_desc_workspace": (sz, [i32, i32]),
+    "bx_rank_desc": (i32, [vp, vp, i32, i32, vp, sz, vp]),
+    "bx_faith_perturb_spec": (i32, [vp, vp, vp, i32, vp] + [i32] * 10 + [vp]),
+    "bx_faith_perturb_eeg": (i32, [vp, vp, i32, vp, i32, vp] + [i32] * 7 + [vp]),
+    "bx_faith_curve": (i32, [vp] * 4 + [i32] * 4 + [vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

@@ -9,11 +9,16 @@
 * ``lime_image``              -- LIME for images as lime 0.2.0.1's explain_instance defines it (reference
                                  XAI_Multimodality.py:1658-1670): perturbed batch, forward passes and the weighted
                                  ridge surrogate on the GPU (bx_lime_*); ``predict_fn`` is its callback alone.
+* ``deletion_insertion``      -- deletion / insertion curves of any of those maps (the causal metric of RISE, Petsiuk et al.,
+                                 BMVC 2018; not in the reference): exact ranks (``attribution_ranks``, bx_rank_desc), perturbed
+                                 batches in the model's layout (bx_faith_perturb_*), forward passes, curves and areas (bx_faith_curve).
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
+import numbers
 import re
 
 import numpy as np
@@ -916,3 +921,254 @@ def lime_image(model, image, segments, *, labels=None, top_labels=5, hide_color=
             e._used_dev[k] = None if fits[l][1] is None else fits[l][1][b].contiguous()
         out.append(e)
     return out[0] if single else out
+
+
+# ------------------------------------------------------------------------------------------------
+# Deletion / insertion curves (the causal metric of RISE, Petsiuk et al., BMVC 2018): how faithful is an attribution map?
+_FAITH_MAX_N, _FAITH_MAX_C = (1 << 20) - 1, 4
+_FAITH_MODES, _FAITH_SCORES, _FAITH_INPUTS = ("both", "deletion", "insertion"), ("prob", "logprob"), ("spec", "eeg")
+
+FaithfulnessCurves = collections.namedtuple("FaithfulnessCurves", "deletion insertion deletion_auc insertion_auc classes fractions ranks")
+FaithfulnessCurves.__doc__ = """What ``deletion_insertion`` returns: ``deletion`` / ``insertion`` fp32 [B, steps+1] and ``deletion_auc`` /
+``insertion_auc`` fp64 [B] on the device (None for the mode that was not asked for), ``classes`` int64 [B] (device), ``fractions``
+fp64 [steps+1] = k_i / N (host) and ``ranks`` int32 [B, N] (device)."""
+
+
+def attribution_ranks(attribution):
+    """int32 [B, N] on the device: the position of every cell of ``attribution`` [B, ...] (N = the cells of one sample, flattened) in a
+    stable descending sort of its sample, ties by ascending flat index, NaN counted as -inf and -0.0 equal to +0.0 --
+    ``np.argsort(-key, kind="stable")`` inverted.  Exact; one launch chain (bx_rank_desc), no host round trip."""
+    if not isinstance(attribution, torch.Tensor) or attribution.dim() < 2:
+        raise ValueError("attribution_ranks: attribution must be a tensor [B, ...] with at least two axes")
+    B = int(attribution.shape[0])
+    N = attribution.numel() // B if B else 0
+    if B < 1 or not 1 <= N <= _FAITH_MAX_N:
+        raise ValueError(f"attribution_ranks: {N} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
+    if not attribution.is_cuda:
+        raise RuntimeError("brainxai.attribution_ranks: the attribution must live on the GPU; there is no CPU path")
+    lib = L.load()
+    a = attribution.detach().reshape(B, N).to(torch.float32).contiguous()
+    ranks = torch.empty(B, N, dtype=torch.int32, device=a.device)
+    nbytes = lib.bx_rank_desc_workspace(B, N)
+    if nbytes == 0:
+        L.check(-1, "bx_rank_desc_workspace")
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        L.check(lib.bx_rank_desc(_p(a), _p(ranks), B, N, _p(ws), nbytes, _stream()), "bx_rank_desc")
+    return ranks
+
+
+def _faith_chunks(B, P, max_rows):
+    """(b0, nb, i0, n): sample groups x windows of curve points with nb * n <= max_rows rows (one row when max_rows < 1); the rows of
+    a sample sit together, which is what lets the unchanged branch's output be repeated instead of recomputed."""
+    nb = max(1, min(B, max_rows))
+    n = max(1, max_rows // nb)
+    for b0 in range(0, B, nb):
+        for i0 in range(0, P, n):
+            yield b0, min(nb, B - b0), i0, min(n, P - i0)
+
+
+def _faith_perturb(x, ranks, base, kind, b0, nb, i0, n, per, insertion, dt, map_rows=None):
+    """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1, of the perturbed batch at curve points i0 + j.  x: fp32 [B,C,H,W] -> internal
+    layout [nb*n,H,W,8] in dt (bx_faith_perturb_spec), or with map_rows fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_faith_perturb_eeg)."""
+    lib = L.load()
+    xs, rs = x[b0:b0 + nb], ranks[b0:b0 + nb]
+    bs = base[b0:b0 + nb] if kind == 2 else base
+    if map_rows is None:
+        _, Cc, H, W = x.shape
+        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
+        L.check(lib.bx_faith_perturb_spec(_p(xs), _p(rs), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), per, i0, n, 1 if insertion else 0,
+                                          ops.bx_dtype(dt), _stream()), "bx_faith_perturb_spec")
+    else:
+        _, _, Chans, T = x.shape
+        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
+        L.check(lib.bx_faith_perturb_eeg(_p(xs), _p(rs), map_rows, _p(bs), kind, _p(out), nb, Chans, T, per, i0, n, 1 if insertion else 0, _stream()),
+                "bx_faith_perturb_eeg")
+    return out
+
+
+def _faith_baseline(baseline, x, per_len, what):
+    """-> (kind, fp32 host or device tensor): 0 one value, 1 one per channel / electrode, 2 a tensor of the input's shape."""
+    if isinstance(baseline, numbers.Real) and not isinstance(baseline, bool):
+        return 0, torch.tensor([float(baseline)], dtype=torch.float32)
+    try:
+        t = baseline.detach() if isinstance(baseline, torch.Tensor) else torch.as_tensor(np.asarray(baseline, dtype=np.float32))
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"deletion_insertion: baseline is neither a number, a sequence nor a tensor ({exc})") from None
+    if t.dim() == 0:
+        return 0, t.reshape(1)
+    if t.dim() == 1 and t.shape[0] == per_len:
+        return 1, t
+    if tuple(t.shape) == tuple(x.shape) or (x.shape[1] == 1 and tuple(t.shape) == (x.shape[0],) + tuple(x.shape[2:])):
+        return 2, t
+    raise ValueError(f"deletion_insertion: baseline of shape {tuple(t.shape)} is none of: a number, one value per {what} [{per_len}], "
+                     f"a tensor of the input's shape {tuple(x.shape)}")
+
+
+def deletion_insertion(model, eeg, spec, attribution, *, input="spec", mode="both", steps=32, baseline=0.0, class_idx=None, score="prob",
+                       max_batch=256):
+    """Deletion and insertion curves of an attribution map (the causal metric of RISE, Petsiuk et al., BMVC 2018).
+
+    The cells of the chosen input are ranked by decreasing attribution (``attribution_ranks``).  With per = ceil(N / steps), curve
+    point i (0..steps) has the cut k_i = min(N, i * per).  Deletion input at point i: cells of rank < k_i come from the baseline, the
+    others from the input; insertion: cells of rank < k_i come from the input, the others from the baseline.  Each curve follows
+    p_c = softmax probability of the explained class (score='logprob': its log-probability); its area is RISE's
+    (sum(curve) - curve[0]/2 - curve[-1]/2) / steps in fp64.  A faithful map gives a small deletion and a large insertion area.
+
+    input:       'spec': attribution [B,H,W], a cell is a pixel with all its channels (C <= 4); 'eeg': attribution [B,Chans,T] (a cell is
+                 one electrode at one time step) or [B,1,T] (a whole time column).  The outputs of grad_cam (int / None class),
+                 saliency, a channel-reduced IG result and LimeExplanation.heatmap(label)[None] fit as they are.
+    model:       a MultimodalModel; a stand-alone Spectrogram_Model (eeg=None, input='spec'); a stand-alone EEGNet /
+                 EEGNetAttentionDeep (spec=None, input='eeg') -- the convention of grad_cam.
+    baseline:    a number; one value per channel (spec) / electrode (eeg); or a tensor of the input's shape (a blurred copy, a
+                 per-sample mean: the package does not blur).
+    class_idx:   None = each sample's arg-max class on the unperturbed input; an int; or one class per sample (sequence / tensor [B]).
+    mode:        'both', 'deletion' or 'insertion'; the fields of the other mode are None.
+    max_batch:   rows (perturbed samples) per forward pass.
+    Forward-only: (steps + 1) * B evaluations per mode, in eval mode without autograd; the perturbed rows are written once, straight
+    in the model's layout (bx_faith_perturb_*), and weights are packed once for the whole pass.  In a MultimodalModel the branch
+    whose input does not change runs once per SAMPLE, not once per row, and its output is repeated into the fusion head: for
+    input='eeg' that removes almost all of the work (the spectrogram branch dominates), for input='spec' it saves little.
+    The training flag and every requires_grad are restored on return.  Returns ``FaithfulnessCurves``."""
+    return _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, baseline, class_idx, score, max_batch)
+
+
+def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, baseline, class_idx, score, max_batch, profile=None):
+    """``deletion_insertion`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'rank',
+    'perturb', 'forward', 'curve' -- device events around every phase of the pass (tools/faithfulness_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "deletion_insertion"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if mode not in _FAITH_MODES:
+        raise ValueError(f"{who}: unknown mode {mode!r}; use one of " + ", ".join(f"'{m}'" for m in _FAITH_MODES))
+    if score not in _FAITH_SCORES:
+        raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
+    steps, max_batch = int(steps), int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    x = spec if input == "spec" else eeg
+    if x is None:
+        raise ValueError(f"{who}: input={input!r} but that tensor is None")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
+        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
+    if not isinstance(attribution, torch.Tensor):
+        raise ValueError(f"{who}: attribution must be a tensor")
+    B = int(x.shape[0])
+    if input == "spec":
+        Cc, H, W = (int(v) for v in x.shape[1:])
+        if not 1 <= Cc <= _FAITH_MAX_C:
+            raise ValueError(f"{who}: {Cc} channels, supported 1..{_FAITH_MAX_C}")
+        if tuple(attribution.shape) != (B, H, W):
+            raise ValueError(f"{who}: wrong map shape {tuple(attribution.shape)} for input='spec'; expected [B,H,W] = {(B, H, W)}")
+        map_rows, N, per_len, what = None, H * W, Cc, "channel"
+    else:
+        Chans, T = int(x.shape[2]), int(x.shape[3])
+        if tuple(attribution.shape) == (B, Chans, T):
+            map_rows = Chans
+        elif tuple(attribution.shape) == (B, 1, T):
+            map_rows = 1
+        else:
+            raise ValueError(f"{who}: wrong map shape {tuple(attribution.shape)} for input='eeg'; expected [B,Chans,T] = {(B, Chans, T)} or "
+                             f"[B,1,T] = {(B, 1, T)}")
+        N, per_len, what = map_rows * T, Chans, "electrode"
+    if B < 1 or not 1 <= N <= _FAITH_MAX_N:
+        raise ValueError(f"{who}: {N} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
+    if not 1 <= steps <= N:
+        raise ValueError(f"{who}: steps = {steps} outside 1..N = {N}")
+    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
+    if multimodal:
+        other = eeg if input == "spec" else spec
+        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
+            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
+        K = int(model.fc2.out_features)
+    elif input == "spec":
+        if not (hasattr(model, "block1") and hasattr(model, "fc")):
+            raise ValueError(f"{who}: input='spec' needs a MultimodalModel or a Spectrogram_Model")
+        K = int(model.fc.out_features)
+    else:
+        if not hasattr(model, "depthwiseConv"):
+            raise ValueError(f"{who}: input='eeg' needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
+        K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
+    if class_idx is None:
+        cls_h = None
+    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
+        cls_h = [int(class_idx)] * B
+    elif isinstance(class_idx, str):
+        raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int or one class per sample")
+    else:
+        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
+        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
+            raise ValueError(f"{who}: class_idx must be None, an int or {B} integers (one class per sample)")
+        cls_h = [int(c) for c in cls_t.tolist()]
+    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
+        raise ValueError(f"{who}: class outside [0, {K})")
+    kind, base = _faith_baseline(baseline, x, per_len, what)
+    if not (x.is_cuda and attribution.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
+        raise RuntimeError(f"brainxai.{who}: the model, its inputs and the attribution must live on the GPU; there is no CPU path")
+
+    lib = L.load()
+    dev = x.device
+    P, per = steps + 1, -(-N // steps)
+    spec_net = model.spectrogram_model if multimodal else model
+    dt = getattr(spec_net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
+    # a pass addresses its largest activation with 32-bit byte offsets: stage 1's H x W x 16 channels, EEGNet's F1 x Chans x T
+    row_bytes = H * W * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * Chans * T * 4
+    max_rows = max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+
+    @contextlib.contextmanager
+    def lap(name):
+        if profile is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        profile.append((name, e0, e1))
+
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
+        xs = x.detach().to(torch.float32).contiguous()
+        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+        with lap("rank"):
+            ranks = attribution_ranks(attribution)
+        fixed = None
+        if multimodal:                                              # the branch whose input does not change: once per sample
+            with lap("forward"):
+                o = other.detach().to(torch.float32).contiguous()
+                fixed = (model.eeg_model(o) if input == "spec" else model.spectrogram_model(o)).float().contiguous()
+        logps = {}
+        for m in ("deletion", "insertion"):
+            if mode not in ("both", m):
+                continue
+            logp = torch.empty(B, P, K, dtype=torch.float32, device=dev)
+            for b0, nb, i0, n in _faith_chunks(B, P, max_rows):
+                with lap("perturb"):
+                    rows = _faith_perturb(xs, ranks, base, kind, b0, nb, i0, n, per, m == "insertion", dt, map_rows)
+                with lap("forward"):
+                    if input == "spec":
+                        out = spec_net(rows.permute(0, 3, 1, 2))     # a logical-NCHW view of the internal layout: no further copy
+                    else:
+                        out = (model.eeg_model if multimodal else model)(rows)
+                    if multimodal:
+                        rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0)
+                        e, s = (rep, out) if input == "spec" else (out, rep)
+                        out = ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
+                    logp[b0:b0 + nb, i0:i0 + n] = out.float().reshape(nb, n, K)
+            logps[m] = logp
+        unperturbed = logps["deletion"][:, 0] if "deletion" in logps else logps["insertion"][:, P - 1]
+        if cls_h is None:
+            classes = unperturbed.argmax(dim=1).to(torch.int32).contiguous()
+        else:
+            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
+        res = {}
+        with lap("curve"):
+            for m, logp in logps.items():
+                curve = torch.empty(B, P, dtype=torch.float32, device=dev)
+                auc = torch.empty(B, dtype=torch.float64, device=dev)
+                L.check(lib.bx_faith_curve(_p(logp), _p(classes), _p(curve), _p(auc), B, P, K, 1 if score == "logprob" else 0, _stream()),
+                        "bx_faith_curve")
+                res[m] = (curve, auc)
+    fractions = torch.tensor([min(N, i * per) / N for i in range(P)], dtype=torch.float64)
+    d, i = res.get("deletion", (None, None)), res.get("insertion", (None, None))
+    return FaithfulnessCurves(d[0], i[0], d[1], i[1], classes.long(), fractions, ranks)
