@@ -592,6 +592,42 @@ int bx_faith_perturb_eeg(const float* x, const int* ranks, int map_rows, const f
  * / (P - 1), RISE's trapezoid rule on the unit interval; the sum runs in fp64 over the stored fp32 points in index order, one
  * thread per sample, so its bits do not depend on scheduling. */
 int bx_faith_curve(const float* logp, const int* classes, float* curve, double* auc, int B, int P, int K, int use_logprob, bxStream stream);
+/* ---- RISE saliency (Petsiuk et al., BMVC 2018; the reference ships no black-box attribution of the EEG input): the map of an input
+ * is the average of N random smooth masks, each weighted by the class probability the model gives the input seen through it.
+ * Mask domain [Hm,Wm]: [H,W] of a spectrogram (one value for all channels of a pixel, 1 <= C <= 4), [Chans,T] of an EEG input or
+ * [1,T] (a time column across electrodes); Hm * Wm < 2^20.  Grid gh x gw with 1 <= gh <= min(32, Hm), 1 <= gw <= min(32, Wm); cell
+ * size ch = ceil(Hm / gh), cw = ceil(Wm / gw).  bits u8 [N,gh,gw] (non-zero = 1), shifts i32 [N,2] = (dy, dx) with 0 <= dy < ch,
+ * 0 <= dx < cw (values outside are clamped into the range); N < 2^24.
+ * Mask n is the crop [dy:dy+Hm, dx:dx+Wm] of the bilinear, align_corners=False up-sampling of bits[n] (as 0.0 / 1.0) from gh x gw to
+ * (gh+1) ch x (gw+1) cw.  Per axis, in fp32 and without fused multiply-adds, for the up-sampled coordinate u = y + dy (x + dx):
+ *     s = max(0, (u + 0.5) * (g / ((g + 1) c)) - 0.5),  i0 = min(int(s), g - 1),  i1 = min(i0 + 1, g - 1),  l = s - i0,
+ *     m = (1 - ly) * ((1 - lx) * b[y0][x0] + lx * b[y0][x1]) + ly * ((1 - lx) * b[y1][x0] + lx * b[y1][x1])
+ * (horizontal blend first, then vertical; the convention of bx_resize_bilinear).  Every m lies in [0, 1]; all-ones bits give exactly
+ * 1.0 and all-zero bits exactly 0.0.  No entry point but bx_rise_masks ever stores a mask: each recomputes m where it needs it from
+ * the bit rows staged in LDS.  Limits are refused with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+/* out fp32 [n,Hm,Wm]: masks n0 .. n0+n-1 (for tests, plots and callers who want them; n * Hm * Wm < 2^31). */
+int bx_rise_masks(const unsigned char* bits, const int* shifts, float* out, int N, int gh, int gw, int Hm, int Wm, int n0, int n,
+                  bxStream stream);
+/* Perturbed spectrogram rows.  x fp32 NCHW [B,C,H,W] -> out [B*n, H, W, Cp] (dtype; sample-major: row b*n + j is sample b seen
+ * through mask n0 + j), channels C..Cp-1 zero, Cp = 8: base + m * (x - base) evaluated in fp32 as written (three roundings), then
+ * stored as dtype -- bit for bit bx_nchw_to_nhwc of that tensor, which is never built.  baseline fp32, by baseline_kind as in
+ * bx_faith_perturb_spec: 0 one value, 1 one value per channel [C], 2 a tensor of x's shape.  One call's output stays below 2^32 bytes. */
+int bx_rise_perturb_spec(const float* x, const unsigned char* bits, const int* shifts, const float* baseline, int baseline_kind, void* out,
+                         int B, int C, int H, int W, int Cp, int N, int gh, int gw, int n0, int n, int dtype, bxStream stream);
+/* Perturbed EEG rows.  x fp32 [B,1,Chans,T] -> out fp32 [B*n,1,Chans,T], same row order and arithmetic.  map_rows = Chans: the mask
+ * domain is [Chans,T]; map_rows = 1: it is [1,T] and a column's value is applied to every electrode.  baseline_kind: 0 one value,
+ * 1 one value per electrode [Chans], 2 a tensor of x's shape. */
+int bx_rise_perturb_eeg(const float* x, const unsigned char* bits, const int* shifts, int map_rows, const float* baseline, int baseline_kind,
+                        float* out, int B, int Chans, int T, int N, int gh, int gw, int n0, int n, bxStream stream);
+/* The map.  P fp32 [B,N,K] class probabilities of sample b seen through mask n (K <= 32); classes i32 [B] (one map per sample, of
+ * that class) or NULL (a map for each of the K classes).  sal fp32 [B,Hm*Wm] or [B,K,Hm*Wm]:
+ *     sal[b,k,p] = (sum_n P[b,n,k] m_n(p)) / D(p),   D = N p1 (normalize = 0, the paper's expected coverage) or
+ *     D(p) = sum_n m_n(p) (normalize = 1, the coverage the masks really gave the cell; a cell no mask reached gets 0),
+ * coverage fp32 [Hm*Wm] = sum_n m_n(p).  Both sums run in fp64 over n = 0..N-1 in index order in one thread's registers, every
+ * term the exact product (double)P * (double)m; the quotient is taken in fp64 and rounded to fp32 once.  No atomics: the result's
+ * bits are a function of the inputs alone. */
+int bx_rise_accumulate(const float* P, const int* classes, const unsigned char* bits, const int* shifts, float* sal, float* coverage, int B,
+                       int N, int K, int gh, int gw, int Hm, int Wm, double p1, int normalize, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

@@ -170,6 +170,10 @@ SIGNATURES = {
     "bx_faith_perturb_spec": (i32, [vp, vp, vp, i32, vp] + [i32] * 10 + [vp]),
     "bx_faith_perturb_eeg": (i32, [vp, vp, i32, vp, i32, vp] + [i32] * 7 + [vp]),
     "bx_faith_curve": (i32, [vp] * 4 + [i32] * 4 + [vp]),
+    "bx_rise_masks": (i32, [vp, vp, vp] + [i32] * 7 + [vp]),
+    "bx_rise_perturb_spec": (i32, [vp, vp, vp, vp, i32, vp] + [i32] * 11 + [vp]),
+    "bx_rise_perturb_eeg": (i32, [vp, vp, vp, i32, vp, i32, vp] + [i32] * 8 + [vp]),
+    "bx_rise_accumulate": (i32, [vp] * 6 + [i32] * 7 + [C.c_double, i32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

@@ -12,6 +12,9 @@
 * ``deletion_insertion``      -- deletion / insertion curves of any of those maps (the causal metric of RISE, Petsiuk et al.,
                                  BMVC 2018; not in the reference): exact ranks (``attribution_ranks``, bx_rank_desc), perturbed
                                  batches in the model's layout (bx_faith_perturb_*), forward passes, curves and areas (bx_faith_curve).
+* ``rise``                    -- RISE saliency (the same paper; not in the reference): black-box maps of either input from randomly
+                                 masked forward passes; the masks are recomputed from their bit grids inside the perturb and
+                                 weighted-sum kernels (bx_rise_perturb_*, bx_rise_accumulate) and never stored; ``rise_masks`` builds them.
 """
 from __future__ import annotations
 
@@ -1172,3 +1175,280 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
     fractions = torch.tensor([min(N, i * per) / N for i in range(P)], dtype=torch.float64)
     d, i = res.get("deletion", (None, None)), res.get("insertion", (None, None))
     return FaithfulnessCurves(d[0], i[0], d[1], i[1], classes.long(), fractions, ranks)
+
+
+# ------------------------------------------------------------------------------------------------
+# RISE (Petsiuk et al., BMVC 2018): black-box saliency from randomly masked forward passes.  The definition is pinned in
+# include/brainxai.h; tests/rise_ref.py restates it in numpy.
+_RISE_MAX_G, _RISE_MAX_K, _RISE_MAX_MASKS = 32, 32, (1 << 24) - 1
+_RISE_NORMALIZE, _RISE_CELLS = ("expected", "coverage"), ("electrode_time", "time")
+
+RiseResult = collections.namedtuple("RiseResult", "saliency classes probs coverage bits shifts")
+RiseResult.__doc__ = """What ``rise(..., return_parts=True)`` returns: ``saliency`` fp32 [B,Hm,Wm] or [B,K,Hm,Wm], ``classes`` int64 [B] (None for
+class_idx='all'), ``probs`` fp32 [B,N,K] (the class probabilities of every masked input), ``coverage`` fp32 [Hm,Wm] = the sum of the
+masks, all on the device; ``bits`` uint8 [N,gh,gw] and ``shifts`` int32 [N,2] = (dy, dx) on the host: ``masks=(bits, shifts)`` repeats the call."""
+
+
+def _rise_geometry(who, grid, Hm, Wm):
+    """-> (gh, gw, ch, cw): the grid as a pair, checked against the mask domain, and the cell size ceil(Hm / gh) x ceil(Wm / gw)."""
+    if isinstance(grid, numbers.Integral) and not isinstance(grid, bool):
+        gh = gw = int(grid)
+        if Hm == 1:                                                   # a [1, T] domain has one row of cells
+            gh = 1
+    else:
+        try:
+            gh, gw = (int(v) for v in grid)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: grid must be an int or a pair (gh, gw), got {grid!r}") from None
+    if not (1 <= gh <= min(_RISE_MAX_G, Hm) and 1 <= gw <= min(_RISE_MAX_G, Wm)):
+        raise ValueError(f"{who}: grid {gh} x {gw} outside 1..min({_RISE_MAX_G}, {Hm}) x 1..min({_RISE_MAX_G}, {Wm})")
+    return gh, gw, -(-Hm // gh), -(-Wm // gw)
+
+
+def _rise_mask_set(who, num_masks, geom, p1, seed, masks):
+    """-> (bits uint8 [N,gh,gw], shifts int32 [N,2]) on the host: drawn from np.random.RandomState(seed), or ``masks`` checked."""
+    gh, gw, ch, cw = geom
+    if isinstance(p1, bool) or not isinstance(p1, numbers.Real) or not 0.0 < float(p1) <= 1.0:
+        raise ValueError(f"{who}: p1 = {p1!r} outside (0, 1]")
+    if masks is None:
+        N = int(num_masks)
+        if not 1 <= N <= _RISE_MAX_MASKS:
+            raise ValueError(f"{who}: num_masks = {N} outside 1..{_RISE_MAX_MASKS}")
+        rs = np.random.RandomState(seed)
+        bits = (rs.rand(N, gh, gw) < float(p1)).astype(np.uint8)
+        dy = rs.randint(0, ch, N)
+        dx = rs.randint(0, cw, N)
+        return bits, np.stack([dy, dx], axis=1).astype(np.int32)
+    try:
+        bits, shifts = masks
+        bits = np.asarray(bits.cpu() if isinstance(bits, torch.Tensor) else bits)
+        shifts = np.asarray(shifts.cpu() if isinstance(shifts, torch.Tensor) else shifts)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: masks must be a pair (bits [N,{gh},{gw}], shifts [N,2])") from None
+    if bits.ndim != 3 or bits.shape[1:] != (gh, gw) or not 1 <= bits.shape[0] <= _RISE_MAX_MASKS:
+        raise ValueError(f"{who}: bits of shape {bits.shape}; expected [N,{gh},{gw}] with 1 <= N <= {_RISE_MAX_MASKS}")
+    if shifts.shape != (bits.shape[0], 2) or shifts.dtype.kind not in "iu":
+        raise ValueError(f"{who}: shifts of shape {shifts.shape} ({shifts.dtype}); expected integers [N,2] = {(bits.shape[0], 2)}")
+    if bits.dtype.kind not in "biu" or not np.isin(bits, (0, 1)).all():
+        raise ValueError(f"{who}: bits must hold 0 / 1 only")
+    if (shifts < 0).any() or (shifts[:, 0] >= ch).any() or (shifts[:, 1] >= cw).any():
+        raise ValueError(f"{who}: shifts outside [0, cell): dy in 0..{ch - 1}, dx in 0..{cw - 1}")
+    return np.ascontiguousarray(bits.astype(np.uint8)), np.ascontiguousarray(shifts.astype(np.int32))
+
+
+def rise_masks(size, *, num_masks=4000, grid=8, p1=0.5, seed=0, masks=None, device=None, return_parts=False):
+    """The RISE masks themselves, fp32 [N,Hm,Wm] on the device (bx_rise_masks) -- for tests, plots and callers who want them;
+    ``rise`` never builds them.  size = (Hm, Wm); grid, p1, seed, masks as in ``rise``.  return_parts: (masks, bits, shifts)."""
+    who = "rise_masks"
+    try:
+        Hm, Wm = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: size must be a pair (Hm, Wm), got {size!r}") from None
+    if Hm < 1 or Wm < 1 or Hm * Wm > _FAITH_MAX_N:
+        raise ValueError(f"{who}: {Hm} x {Wm} cells per mask, supported 1..{_FAITH_MAX_N}")
+    geom = _rise_geometry(who, grid, Hm, Wm)
+    bits, shifts = _rise_mask_set(who, num_masks, geom, p1, seed, masks)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"brainxai.{who}: the masks are built on the GPU; there is no CPU path")
+    lib = L.load()
+    N = bits.shape[0]
+    with torch.cuda.device(dev):
+        bits_d, shifts_d = torch.from_numpy(bits).to(dev), torch.from_numpy(shifts).to(dev)
+        out = torch.empty(N, Hm, Wm, dtype=torch.float32, device=dev)
+        step = max(1, ((1 << 31) - 1) // (Hm * Wm))
+        for n0 in range(0, N, step):
+            n = min(step, N - n0)
+            L.check(lib.bx_rise_masks(_p(bits_d), _p(shifts_d), _p(out[n0:n0 + n]), N, geom[0], geom[1], Hm, Wm, n0, n, _stream()), "bx_rise_masks")
+    return (out, bits, shifts) if return_parts else out
+
+
+def _rise_perturb(x, bits_d, shifts_d, geom, base, kind, b0, nb, n0, n, dt, map_rows=None):
+    """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1: sample b seen through mask n0 + j.  x fp32 [B,C,H,W] -> internal layout
+    [nb*n,H,W,8] in dt (bx_rise_perturb_spec), or with map_rows fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_rise_perturb_eeg)."""
+    lib = L.load()
+    xs = x[b0:b0 + nb]
+    bs = base[b0:b0 + nb] if kind == 2 else base
+    N = bits_d.shape[0]
+    if map_rows is None:
+        _, Cc, H, W = x.shape
+        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
+        L.check(lib.bx_rise_perturb_spec(_p(xs), _p(bits_d), _p(shifts_d), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), N, geom[0], geom[1], n0, n,
+                                         ops.bx_dtype(dt), _stream()), "bx_rise_perturb_spec")
+    else:
+        _, _, Chans, T = x.shape
+        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
+        L.check(lib.bx_rise_perturb_eeg(_p(xs), _p(bits_d), _p(shifts_d), map_rows, _p(bs), kind, _p(out), nb, Chans, T, N, geom[0], geom[1], n0, n,
+                                        _stream()), "bx_rise_perturb_eeg")
+    return out
+
+
+def rise(model, eeg, spec, *, input="spec", num_masks=4000, grid=8, p1=0.5, class_idx=None, baseline=0.0, normalize="expected", seed=0,
+         masks=None, cells="electrode_time", max_batch=256, return_parts=False):
+    """RISE saliency (Petsiuk et al., BMVC 2018): sal[b,k,p] = sum_n P[b,n,k] m_n(p) / D(p), where m_n is the n-th random smooth mask,
+    P[b,n,k] the softmax probability of class k for the input base + m_n (x - base), and D the normaliser.  Forward-only, so it
+    explains either input of the multimodal model; the map has the input's own shape and fits ``deletion_insertion`` and
+    ``attribution_ranks`` as it is.
+
+    input:       'spec': masks over [H,W], one value for all channels of a pixel (C <= 4), map [B,H,W]; 'eeg': masks over [Chans,T],
+                 map [B,Chans,T], or with cells='time' over [1,T] (a column's value applies to every electrode), map [B,1,T].
+    model:       a MultimodalModel; a stand-alone Spectrogram_Model (eeg=None, input='spec'); a stand-alone EEGNet /
+                 EEGNetAttentionDeep (spec=None, input='eeg') -- the convention of grad_cam and deletion_insertion.
+    masks:       mask n is the crop [dy:dy+Hm, dx:dx+Wm] of the bilinear (align_corners=False) up-sampling of a gh x gw grid of 0 / 1
+                 to (gh+1) ch x (gw+1) cw, ch = ceil(Hm / gh), cw = ceil(Wm / gw).  grid: an int or a pair, 1..min(32, Hm) x
+                 1..min(32, Wm) (an int grid over a [1,T] domain means (1, grid)).  The draw is on the host from one
+                 np.random.RandomState(seed): bits = rand(N, gh, gw) < p1, dy = randint(0, ch, N), dx = randint(0, cw, N);
+                 masks=(bits [N,gh,gw], shifts [N,2]) replaces it.  One mask set serves the whole batch, as in the paper's code.
+                 (The paper's code resizes with skimage.transform.resize(order=1, mode='reflect'): the same coordinate map, and for a
+                 two-tap filter a reflected border equals the clamped one used here -- not checked here, skimage is not a dependency.)
+    baseline:    what a masked-out cell shows: a number; one value per channel (spec) / electrode (eeg); a tensor of the input's shape.
+    class_idx:   None = each sample's arg-max class on the unmasked input; an int; one class per sample (sequence / tensor [B]);
+                 'all' = every class, the map gains a class axis [B,K,Hm,Wm] (K <= 32).
+    normalize:   'expected': D = N p1, the paper's choice; 'coverage': D(p) = sum_n m_n(p), which removes the Monte-Carlo
+                 unevenness of how often each cell was shown (at N = 256 that unevenness is most of an 'expected' map).
+    max_batch:   rows (masked inputs) per forward pass.
+    N * B forward evaluations in eval mode without autograd.  The masks never exist in memory: the masked rows are written straight in
+    the model's layout from the bit grids (bx_rise_perturb_*), and the weighted sum recomputes every mask value in registers
+    (bx_rise_accumulate, fp64, fixed order: identical bits run to run and for every max_batch).  In a MultimodalModel the branch whose
+    input does not change runs once per sample and its output is repeated into the fusion head.  The training flag and every
+    requires_grad are restored on return.  Returns the map (device, fp32), or ``RiseResult`` with return_parts."""
+    return _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, normalize, seed, masks, cells, max_batch, return_parts)
+
+
+def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, normalize, seed, masks, cells, max_batch, return_parts, profile=None):
+    """``rise`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'perturb', 'forward',
+    'accumulate' -- device events around every phase of the pass (tools/rise_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "rise"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if normalize not in _RISE_NORMALIZE:
+        raise ValueError(f"{who}: unknown normalize {normalize!r}; use 'expected' or 'coverage'")
+    if cells not in _RISE_CELLS:
+        raise ValueError(f"{who}: unknown cells {cells!r}; use 'electrode_time' or 'time'")
+    if cells == "time" and input != "eeg":
+        raise ValueError(f"{who}: cells='time' masks time columns of the EEG input; input='spec' has no such map")
+    max_batch = int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    x = spec if input == "spec" else eeg
+    if x is None:
+        raise ValueError(f"{who}: input={input!r} but that tensor is None")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
+        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
+    B = int(x.shape[0])
+    if input == "spec":
+        Cc, H, W = (int(v) for v in x.shape[1:])
+        if not 1 <= Cc <= _FAITH_MAX_C:
+            raise ValueError(f"{who}: {Cc} channels, supported 1..{_FAITH_MAX_C}")
+        map_rows, Hm, Wm, per_len, what = None, H, W, Cc, "channel"
+    else:
+        Chans, T = int(x.shape[2]), int(x.shape[3])
+        map_rows = 1 if cells == "time" else Chans
+        Hm, Wm, per_len, what = map_rows, T, Chans, "electrode"
+    if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
+        raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
+    geom = _rise_geometry(who, grid, Hm, Wm)
+    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
+    if multimodal:
+        other = eeg if input == "spec" else spec
+        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
+            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
+        K = int(model.fc2.out_features)
+    elif input == "spec":
+        if not (hasattr(model, "block1") and hasattr(model, "fc")):
+            raise ValueError(f"{who}: input='spec' needs a MultimodalModel or a Spectrogram_Model")
+        K = int(model.fc.out_features)
+    else:
+        if not hasattr(model, "depthwiseConv"):
+            raise ValueError(f"{who}: input='eeg' needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
+        K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    all_classes = isinstance(class_idx, str)
+    if class_idx is None:
+        cls_h = None
+    elif all_classes:
+        if class_idx != "all":
+            raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int, one class per sample or 'all'")
+        cls_h = None
+    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
+        cls_h = [int(class_idx)] * B
+    else:
+        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
+        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
+            raise ValueError(f"{who}: class_idx must be None, an int, 'all' or {B} integers (one class per sample)")
+        cls_h = [int(c) for c in cls_t.tolist()]
+    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
+        raise ValueError(f"{who}: class outside [0, {K})")
+    try:
+        kind, base = _faith_baseline(baseline, x, per_len, what)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("deletion_insertion", who, 1)) from None
+    bits, shifts = _rise_mask_set(who, num_masks, geom, p1, seed, masks)
+    N = int(bits.shape[0])
+    if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
+        raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
+    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
+        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+
+    lib = L.load()
+    dev = x.device
+    spec_net = model.spectrogram_model if multimodal else model
+    dt = getattr(spec_net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
+    # a pass addresses its largest activation with 32-bit byte offsets: stage 1's H x W x 16 channels, EEGNet's F1 x Chans x T
+    row_bytes = H * W * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * Chans * T * 4
+    max_rows = max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+
+    @contextlib.contextmanager
+    def lap(name):
+        if profile is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        profile.append((name, e0, e1))
+
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
+        xs = x.detach().to(torch.float32).contiguous()
+        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+        bits_d, shifts_d = torch.from_numpy(bits).to(dev), torch.from_numpy(shifts).to(dev)
+        fixed = None
+        with lap("forward"):
+            if multimodal:                                          # the branch whose input does not change: once per sample
+                o = other.detach().to(torch.float32).contiguous()
+                fixed = (model.eeg_model(o) if input == "spec" else model.spectrogram_model(o)).float().contiguous()
+            if cls_h is None and not all_classes:                   # the explained class: the arg-max on the unmasked input
+                clean = model(eeg, spec) if multimodal else model(xs)
+                classes = clean.float().argmax(dim=1).to(torch.int32).contiguous()
+        if cls_h is not None:
+            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
+        elif all_classes:
+            classes = None
+        P = torch.empty(B, N, K, dtype=torch.float32, device=dev)
+        for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
+            with lap("perturb"):
+                rows = _rise_perturb(xs, bits_d, shifts_d, geom, base, kind, b0, nb, n0, n, dt, map_rows)
+            with lap("forward"):
+                if input == "spec":
+                    out = spec_net(rows.permute(0, 3, 1, 2))         # a logical-NCHW view of the internal layout: no further copy
+                else:
+                    out = (model.eeg_model if multimodal else model)(rows)
+                if multimodal:
+                    rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0)
+                    e, s = (rep, out) if input == "spec" else (out, rep)
+                    out = ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
+                logp = out.float().contiguous()
+                probs = torch.empty_like(logp)
+                L.check(lib.bx_softmax_rows(_p(logp), _p(probs), nb * n, K, _stream()), "bx_softmax_rows")
+                P[b0:b0 + nb, n0:n0 + n] = probs.reshape(nb, n, K)
+        with lap("accumulate"):
+            sal = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
+            coverage = torch.empty(Hm, Wm, dtype=torch.float32, device=dev)
+            L.check(lib.bx_rise_accumulate(_p(P), _p(classes), _p(bits_d), _p(shifts_d), _p(sal), _p(coverage), B, N, K, geom[0], geom[1], Hm, Wm,
+                                           float(p1), 1 if normalize == "coverage" else 0, _stream()), "bx_rise_accumulate")
+    if not return_parts:
+        return sal
+    return RiseResult(sal, None if classes is None else classes.long(), P, coverage, bits, shifts)
