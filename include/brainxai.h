@@ -143,6 +143,28 @@ int bx_conv3x3_wgrad_finish(bxWgradPending* pending, bxStream stream);
 int bx_conv3x3_carry(const void* x, const float* packed_f32, const void* packed_mfma, const float* bias,
                      const void* relu_mask_src, const void* addend, void* y, int B, int H, int W, int Ci, int Co,
                      int dtype, int flags, int algo, bxWgradPending* pending, bxStream stream);
+/* bx_conv3x3_carry with up to three pending sums (npending = 1..3): every valid pending[i] is summed by extra workgroups of THIS
+ * launch, in list order, each exactly as bx_conv3x3_carry would sum it alone; all are invalid on return.  A refused call
+ * (rc != BX_OK) leaves the descriptors valid. */
+int bx_conv3x3_carry_many(const void* x, const float* packed_f32, const void* packed_mfma, const float* bias,
+                          const void* relu_mask_src, const void* addend, void* y, int B, int H, int W, int Ci, int Co,
+                          int dtype, int flags, int algo, bxWgradPending* pending, int npending, bxStream stream);
+/* The weight gradients of n = 1..3 layers of one Block (same B, H, W, bf16 storage) in ONE launch.  Every layer must be a shape of
+ * the tile-owner kernel (Ci_p % 32 == 0, Co % 32 == 0: bx_conv3x3_wgrad_group_supported); list the heaviest layer first.
+ * The launch sums nothing: pending[i] (i < n) must be invalid on entry (a valid one is refused, wherever its partials live, so one
+ * inside `workspace` can never be overwritten) and describes layer i's partials on return -- hand the array
+ * to bx_conv3x3_carry_many (or finish each with bx_conv3x3_wgrad_finish).  dw / db are then bit for bit those of
+ * bx_conv3x3_wgrad_chained whose sum was carried.  The partials live in `workspace` (bx_conv3x3_wgrad_group_workspace bytes; 0 =
+ * refused), which must stay alive and unused until the sums have run.  Errors launch nothing and leave `pending` as it was. */
+typedef struct {
+  const void* x; const void* dz;   /* [B,H,W,Ci_p], [B,H,W,Co] */
+  float* dw; float* db;            /* [Co,Cin,3,3], [Co] (db may be NULL) */
+  int Cin, Ci_p, Co;
+} bxWgradGroupLayer;
+int bx_conv3x3_wgrad_group_supported(int n, const int* Ci_p, const int* Co, int W, int dtype);
+size_t bx_conv3x3_wgrad_group_workspace(const bxWgradGroupLayer* layers, int n, int B, int H, int W, int dtype);
+int bx_conv3x3_wgrad_group(const bxWgradGroupLayer* layers, int n, int B, int H, int W, int dtype, void* workspace,
+                           size_t workspace_bytes, bxWgradPending* pending, bxStream stream);
 /* Stage 1's backward, bf16 storage: the data AND weight gradient of a 16 -> 16 conv3x3 layer in one pass over dz (one kernel).
  *   dz [B,H,W,16] = dZ_L, xl [B,H,W,16] = X_L = relu(z_{L-1}) (the layer's input), packed_flip = bx_conv3x3_pack's data-gradient
  *   operand (transpose_flip) of W_L.

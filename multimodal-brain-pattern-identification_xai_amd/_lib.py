@@ -59,6 +59,10 @@ class WgradPending(C.Structure):
                 ("ztiles", i32), ("nfrag4", i32), ("valid", i32)]
 
 
+class WgradGroupLayer(C.Structure):
+    _fields_ = [("x", vp), ("dz", vp), ("dw", vp), ("db", vp), ("Cin", i32), ("Ci_p", i32), ("Co", i32)]
+
+
 class PackJob(C.Structure):
     _fields_ = [("w_oihw", vp), ("packed_mfma", vp), ("Cout", i32), ("Cin", i32), ("I_p", i32), ("O_p", i32),
                 ("transpose_flip", i32), ("block_begin", i32)]
@@ -89,6 +93,10 @@ SIGNATURES = {
     "bx_abs": (i32, [vp, vp, sz, vp]),
     "bx_conv3x3": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "bx_conv3x3_carry": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, P(WgradPending), vp]),
+    "bx_conv3x3_carry_many": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, P(WgradPending), i32, vp]),
+    "bx_conv3x3_wgrad_group_supported": (i32, [i32, P(i32), P(i32), i32, i32]),
+    "bx_conv3x3_wgrad_group_workspace": (sz, [P(WgradGroupLayer), i32, i32, i32, i32, i32]),
+    "bx_conv3x3_wgrad_group": (i32, [P(WgradGroupLayer), i32, i32, i32, i32, i32, vp, sz, P(WgradPending), vp]),
     "bx_conv3x3_wgrad_workspace": (sz, [i32, i32, i32, i32, i32, i32, i32]),
     "bx_conv3x3_wgrad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "bx_conv3x3_wgrad_chained": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, P(WgradPending), vp]),

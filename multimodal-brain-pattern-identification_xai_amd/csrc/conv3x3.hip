@@ -7,7 +7,7 @@
 
 // implemented in conv3x3_mfma.hip
 int bx_conv3x3_mfma_launch(const void* x, const void* packed_mfma, const float* bias, const void* relu_mask_src,
-                           const void* addend, void* y, int B, int H, int W, int Ci, int Co, int flags, hipStream_t s, bxWgradPending* carry);
+                           const void* addend, void* y, int B, int H, int W, int Ci, int Co, int flags, hipStream_t s, bxWgradPending* carry, int ncarry);
 int bx_conv3x3_mfma_supported(int Ci, int Co, int dtype);
 void bx_conv3x3_mfma_pack_launch(const float* w_oihw, void* packed, int Cout, int Cin, int I_p, int O_p, int tf, hipStream_t s);
 size_t bx_wgrad_mfma_workspace(int B, int H, int W, int Ci_p, int Co);
@@ -15,6 +15,10 @@ int bx_wgrad_mfma_supported(int Ci_p, int Co, int dtype);
 int bx_wgrad_mfma_launch(const void* x, const void* dz, float* dw, float* db, int B, int H, int W, int Cin, int Ci_p,
                          int Co, void* ws, size_t ws_bytes, bxWgradPending* pending, hipStream_t s);
 int bx_wgrad_mfma_finish(bxWgradPending* pending, hipStream_t s);
+int bx_wgrad_group_supported(int n, const int* Ci_p, const int* Co, int W, int dtype);
+size_t bx_wgrad_group_workspace(const bxWgradGroupLayer* layers, int n, int B, int H, int W);
+int bx_wgrad_group_launch(const bxWgradGroupLayer* layers, int n, int B, int H, int W, void* ws, size_t ws_bytes, bxWgradPending* pending,
+                          hipStream_t s);
 // implemented in conv3x3_split.hip: fp32 storage on the bf16 matrix cores (operands split hi + lo, three MFMAs per product)
 int bx_conv3x3_split_supported(int Ci, int Co);
 int bx_conv3x3_split_launch(const void* x, const void* packed_split, const float* bias, const void* relu_mask_src, const void* addend, void* y,
@@ -142,9 +146,18 @@ __global__ __launch_bounds__(256) void k_conv3x3_direct(const T* __restrict__ x,
   }
 }
 
+// paths that cannot carry a reduce finish the pending sums first, one launch each
+static int finish_pendings(bxWgradPending* carry, int ncarry, hipStream_t s) {
+  for (int i = 0; carry && i < ncarry; ++i)
+    if (carry[i].valid) {
+      const int rc = bx_wgrad_mfma_finish(&carry[i], s);
+      if (rc) return rc;
+    }
+  return BX_OK;
+}
 static int conv3x3_impl(const void* x, const float* packed_f32, const void* packed_mfma, const float* bias,
                         const void* relu_mask_src, const void* addend, void* y,
-                        int B, int H, int W, int Ci, int Co, int dtype, int flags, int algo, bxWgradPending* carry, bxStream stream) {
+                        int B, int H, int W, int Ci, int Co, int dtype, int flags, int algo, bxWgradPending* carry, int ncarry, bxStream stream) {
   BX_DTYPE_OK(dtype);
   BX_REQUIRE(x && y && B > 0 && H > 0 && W > 0, "bx_conv3x3: bad arguments");
   BX_REQUIRE(Ci % 8 == 0 && Co % 8 == 0, "bx_conv3x3: Ci (%d) and Co (%d) must be multiples of 8 (pad the tensors)", Ci, Co);
@@ -155,17 +168,15 @@ static int conv3x3_impl(const void* x, const float* packed_f32, const void* pack
     if (!packed_mfma || !conv_mfma_ok(Ci, Co, dtype))
       BX_FAIL(BX_EUNSUPPORTED, "bx_conv3x3: MFMA path needs packed_mfma in the layout of `dtype` and Ci%%8==0, Co%%16==0 (Ci=%d Co=%d dtype=%d)", Ci, Co, dtype);
     if (dtype == BX_F32) {                                       // fp32 storage: split-bf16 operands (conv3x3_split.hip); cannot carry a reduce
-      if (carry && carry->valid) {
-        const int rc = bx_wgrad_mfma_finish(carry, s);
-        if (rc) return rc;
-      }
+      const int rc = finish_pendings(carry, ncarry, s);
+      if (rc) return rc;
       return bx_conv3x3_split_launch(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, flags, s);
     }
-    return bx_conv3x3_mfma_launch(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, flags, s, carry);
+    return bx_conv3x3_mfma_launch(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, flags, s, carry, ncarry);
   }
   BX_REQUIRE(!(flags & BX_EPI_MASK_BITS), "bx_conv3x3: BX_EPI_MASK_BITS needs the MFMA path");
-  if (carry && carry->valid) {                                 // the direct kernels cannot carry a reduce: finish the chain first
-    const int rc = bx_wgrad_mfma_finish(carry, s);
+  {                                                            // the direct kernels cannot carry a reduce: finish the chain first
+    const int rc = finish_pendings(carry, ncarry, s);
     if (rc) return rc;
   }
   BX_REQUIRE(packed_f32, "bx_conv3x3: direct path needs packed_f32");
@@ -180,13 +191,20 @@ static int conv3x3_impl(const void* x, const float* packed_f32, const void* pack
 extern "C" int bx_conv3x3(const void* x, const float* packed_f32, const void* packed_mfma, const float* bias,
                           const void* relu_mask_src, const void* addend, void* y,
                           int B, int H, int W, int Ci, int Co, int dtype, int flags, int algo, bxStream stream) {
-  return conv3x3_impl(x, packed_f32, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, dtype, flags, algo, nullptr, stream);
+  return conv3x3_impl(x, packed_f32, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, dtype, flags, algo, nullptr, 0, stream);
 }
 extern "C" int bx_conv3x3_carry(const void* x, const float* packed_f32, const void* packed_mfma, const float* bias,
                                 const void* relu_mask_src, const void* addend, void* y,
                                 int B, int H, int W, int Ci, int Co, int dtype, int flags, int algo, bxWgradPending* pending, bxStream stream) {
   BX_REQUIRE(pending, "bx_conv3x3_carry: pending is NULL");
-  return conv3x3_impl(x, packed_f32, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, dtype, flags, algo, pending, stream);
+  return conv3x3_impl(x, packed_f32, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, dtype, flags, algo, pending, 1, stream);
+}
+extern "C" int bx_conv3x3_carry_many(const void* x, const float* packed_f32, const void* packed_mfma, const float* bias,
+                                     const void* relu_mask_src, const void* addend, void* y,
+                                     int B, int H, int W, int Ci, int Co, int dtype, int flags, int algo, bxWgradPending* pending, int npending,
+                                     bxStream stream) {
+  BX_REQUIRE(pending && npending >= 1 && npending <= 3, "bx_conv3x3_carry_many: needs 1..3 pendings (pending=%p npending=%d)", (void*)pending, npending);
+  return conv3x3_impl(x, packed_f32, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, dtype, flags, algo, pending, npending, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -315,6 +333,35 @@ extern "C" int bx_conv3x3_wgrad_chained(const void* x, const void* dz, float* dw
 extern "C" int bx_conv3x3_wgrad_finish(bxWgradPending* pending, bxStream stream) {
   BX_REQUIRE(pending, "bx_conv3x3_wgrad_finish: pending is NULL");
   return bx_wgrad_mfma_finish(pending, (hipStream_t)stream);
+}
+// ---- the weight gradients of up to three layers of one Block in one launch (k_wgrad_own_group, conv3x3_mfma.hip)
+extern "C" int bx_conv3x3_wgrad_group_supported(int n, const int* Ci_p, const int* Co, int W, int dtype) {
+  return bx_wgrad_group_supported(n, Ci_p, Co, W, dtype);
+}
+static int wgrad_group_args(const char* who, const bxWgradGroupLayer* layers, int n, int B, int H, int W, int dtype) {
+  BX_REQUIRE(layers && n >= 1 && n <= 3, "%s: needs 1..3 layers (layers=%p n=%d)", who, (const void*)layers, n);
+  BX_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+  BX_DTYPE_OK(dtype);
+  int ci[3], co[3];
+  for (int i = 0; i < n; ++i) { ci[i] = layers[i].Ci_p; co[i] = layers[i].Co; }
+  if (!bx_wgrad_group_supported(n, ci, co, W, dtype))
+    BX_FAIL(BX_EUNSUPPORTED, "%s: every layer must be a tile-owner shape (bf16 storage, Ci_p %% 32 == 0, Co %% 32 == 0); dtype=%d, layer 0 is %d -> %d",
+            who, dtype, ci[0], co[0]);
+  return BX_OK;
+}
+extern "C" size_t bx_conv3x3_wgrad_group_workspace(const bxWgradGroupLayer* layers, int n, int B, int H, int W, int dtype) {
+  if (wgrad_group_args("bx_conv3x3_wgrad_group_workspace", layers, n, B, H, W, dtype) != BX_OK) return 0;
+  return bx_wgrad_group_workspace(layers, n, B, H, W);
+}
+extern "C" int bx_conv3x3_wgrad_group(const bxWgradGroupLayer* layers, int n, int B, int H, int W, int dtype, void* workspace,
+                                      size_t workspace_bytes, bxWgradPending* pending, bxStream stream) {
+  const int rc = wgrad_group_args("bx_conv3x3_wgrad_group", layers, n, B, H, W, dtype);
+  if (rc != BX_OK) return rc;
+  BX_REQUIRE(pending, "bx_conv3x3_wgrad_group: pending is NULL");
+  for (int i = 0; i < n; ++i)
+    BX_REQUIRE(layers[i].x && layers[i].dz && layers[i].dw && layers[i].Cin > 0 && layers[i].Cin <= layers[i].Ci_p,
+               "bx_conv3x3_wgrad_group: layer %d has a NULL tensor or Cin (%d) outside 1..Ci_p (%d)", i, layers[i].Cin, layers[i].Ci_p);
+  return bx_wgrad_group_launch(layers, n, B, H, W, workspace, workspace_bytes, pending, (hipStream_t)stream);
 }
 static int wgrad_impl(const void* x, const void* dz, float* dw_oihw, float* dbias, int B, int H, int W, int Cin, int Ci_p, int Co, int dtype,
                       int algo, void* workspace, size_t workspace_bytes, bxWgradPending* pending, bxStream stream) {

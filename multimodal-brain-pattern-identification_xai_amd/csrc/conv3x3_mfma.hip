@@ -216,6 +216,11 @@ extern "C" int bx_conv3x3_pack_many_step(const bxPackJob* jobs_device, int njobs
 struct WgradRedJob { const float* partial; float* dw; float* db; int nsplit, Cin, Co, S, MA, NB, ztiles, nfrag4, nblocks; };
 __device__ __forceinline__ void wgrad_reduce3_body(const WgradRedJob& jb, int bid, float4* sm);
 static WgradRedJob wgrad_job_from(const bxWgradPending* pd, bool chained);
+// Up to three pending sums in one carrying launch (round 5: the three weight gradients of a Block leave one pending sum each): the
+// jobs' workgroup ranges are concatenated in list order; an unused entry has nblocks == 0.
+#define BX_WGRAD_RED_MAX 3
+struct WgradRedList { WgradRedJob job[BX_WGRAD_RED_MAX]; };
+__device__ __forceinline__ void wgrad_reduce_list(const WgradRedList& rl, int bid, float4* sm);
 
 template <int CK>
 __device__ __forceinline__ int lds_chunk(int c, int p) {
@@ -359,7 +364,7 @@ extern "C" int bx_debug_conv_stamps(unsigned long long* host_out) {
 template <int CK, int NC, int TW, int IMGS = 1, bool POOL = false, bool C8 = false, bool W22 = false>
 __global__ __launch_bounds__(256) void k_conv_mfma(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const float* __restrict__ bias,
     const bf16_t* __restrict__ mask_src, const bf16_t* __restrict__ addend, bf16_t* __restrict__ y,
-    int H, int W, int Ci, int Co, int relu, int tiles_x, int tiles_y, uint32_t x_bytes, BxConvPoolEpi pe, WgradRedJob red, int nred) {
+    int H, int W, int Ci, int Co, int relu, int tiles_x, int tiles_y, uint32_t x_bytes, BxConvPoolEpi pe, WgradRedList red, int nred) {
   constexpr int TH = 8, HWID = TW + 2, HH = TH + 2, CKB = CK * 2, NCH = CK / 8, KS = (9 * CK + 31) / 32;
   constexpr int MP = (W22 ? 2 : 1) * IMGS * TH * TW / 64;   // 16-pixel tiles per wave
   constexpr int NCW = W22 ? NC / 2 : NC;    // 16-channel tiles per wave
@@ -368,7 +373,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(const bf16_t* __restrict__ x,
   constexpr int TPR = TW / 16;              // 16-pixel tiles per tile row
   extern __shared__ __attribute__((aligned(16))) char lds[];
   if ((int)blockIdx.x < nred) {             // carried weight-gradient sum (nred = 0 in ordinary launches)
-    if (blockIdx.y == 0 && (int)blockIdx.x < red.nblocks) wgrad_reduce3_body(red, (int)blockIdx.x, reinterpret_cast<float4*>(lds));
+    if (blockIdx.y == 0) wgrad_reduce_list(red, (int)blockIdx.x, reinterpret_cast<float4*>(lds));
     return;
   }
   const int bid = (int)blockIdx.x - nred;
@@ -806,13 +811,13 @@ __global__ __launch_bounds__(256) void k_conv_mfma_c(const bf16_t* __restrict__ 
 template <int CK, int NC, int TW, bool POOL = false, bool C8 = false>
 __global__ __launch_bounds__(256, (CK == 16 && NC == 1 && TW == 32 && !POOL) ? 4 : 1) void k_conv_mfma_p(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, const float* __restrict__ bias,
     const bf16_t* __restrict__ mask_src, const bf16_t* __restrict__ addend, bf16_t* __restrict__ y,
-    int H, int W, int Co, int relu, int tiles_x, int tiles_y, int ntiles, uint32_t x_bytes, BxConvPoolEpi pe, WgradRedJob red, int nred) {
+    int H, int W, int Co, int relu, int tiles_x, int tiles_y, int ntiles, uint32_t x_bytes, BxConvPoolEpi pe, WgradRedList red, int nred) {
   constexpr int TH = 8, HWID = TW + 2, HH = TH + 2, CKB = CK * 2, NCH = CK / 8, KS = (9 * CK + 31) / 32;
   constexpr int MP = TH * TW / 64, TPR = TW / 16;
   constexpr int NU = HH * HWID * NCH, NR = (NU + 255) / 256;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   if ((int)blockIdx.x < nred) {             // carried weight-gradient sum (see k_conv_mfma)
-    if (blockIdx.y == 0 && (int)blockIdx.x < red.nblocks) wgrad_reduce3_body(red, (int)blockIdx.x, reinterpret_cast<float4*>(lds));
+    if (blockIdx.y == 0) wgrad_reduce_list(red, (int)blockIdx.x, reinterpret_cast<float4*>(lds));
     return;
   }
   const int first_tile = (int)blockIdx.x - nred, tile_stride = (int)gridDim.x - nred;
@@ -1337,15 +1342,20 @@ static int pool_tree_shape(BxConvPoolEpi* pe, int grid_x, int ygroups, int Co) {
              ygroups, pe->tree.ngroups);
   return BX_OK;
 }
+static int wgrad_red_total(const WgradRedList& rl) {
+  int n = 0;
+  for (int i = 0; i < BX_WGRAD_RED_MAX; ++i) n += rl.job[i].nblocks;
+  return n;
+}
 template <int CK, int NC, int TW>
 static int launch_conv(const void* x, const void* wp, const float* bias, const void* mask, const void* addend, void* y,
-                       int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe = nullptr, const WgradRedJob* red = nullptr) {
+                       int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe = nullptr, const WgradRedList* red = nullptr) {
   const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + 7) / 8;
   size_t lds = (size_t)10 * (TW + 2) * CK * 2;
   const BxConvPoolEpi none = {};
-  const WgradRedJob nored = {};
-  const int nred = red && !pe ? red->nblocks : 0;          // workgroups in front of grid.x that sum a pending weight gradient
-  const WgradRedJob& rj = nred ? *red : nored;
+  const WgradRedList nored = {};
+  const int nred = red && !pe ? wgrad_red_total(*red) : 0; // workgroups in front of grid.x that sum pending weight gradients
+  const WgradRedList& rj = nred ? *red : nored;
   if (nred && lds < 4096) lds = 4096;
   if (pe) {
     const size_t need = BX_STAT_TREE_LDS(2) + (size_t)4 * 2 * NC * 16 * sizeof(float);       // conv_pool_finish reuses the halo tile's LDS
@@ -1510,7 +1520,7 @@ static int try_conv_c(const void* x, const void* wp, const float* bias, const vo
 // own stage -> MFMA chain); prefer 8x16 pixel tiles and fewer output channels per workgroup until >= 512 are in flight.
 template <int CK, int NC>
 static int launch_conv_tw(const void* x, const void* wp, const float* bias, const void* mask, const void* addend, void* y,
-                          int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe = nullptr, const WgradRedJob* red = nullptr) {
+                          int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe = nullptr, const WgradRedList* red = nullptr) {
   // 8x32 tiles wherever the map is wide enough: a workgroup re-reads its whole weight slab from L2 per pixel tile, so
   // twice the pixels per tile halves the dominant L2 traffic of the late stages (measured: 16x32 maps 22.4 -> 17.3 us).  8x16 tiles
   // for the wide maps of one chunk size as well, training step (ms/step): chunk 32 / 16 / 8 / 64 1.556 / 1.560 / 1.547 / 1.575
@@ -1520,7 +1530,7 @@ static int launch_conv_tw(const void* x, const void* wp, const float* bias, cons
 }
 template <int CK>
 static int launch_conv_nc(const void* x, const void* wp, const float* bias, const void* mask, const void* addend, void* y,
-                          int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe = nullptr, const WgradRedJob* red = nullptr) {
+                          int B, int H, int W, int Ci, int Co, int relu, hipStream_t s, BxConvPoolEpi* pe = nullptr, const WgradRedList* red = nullptr) {
   // output channels per workgroup: 64 while that still launches >= 512 workgroups, else 32 (keeps two per CU in flight)
   const int tw = W <= 16 ? 16 : 32;
   const long long tiles = (long long)((W + tw - 1) / tw) * ((H + 7) / 8) * B;
@@ -1530,25 +1540,31 @@ static int launch_conv_nc(const void* x, const void* wp, const float* bias, cons
   return launch_conv_tw<CK, 1>(x, wp, bias, mask, addend, y, B, H, W, Ci, Co, relu, s, pe, red);
 }
 int bx_conv3x3_mfma_launch(const void* x, const void* packed_mfma, const float* bias, const void* relu_mask_src,
-                           const void* addend, void* y, int B, int H, int W, int Ci, int Co, int flags, hipStream_t s, bxWgradPending* carry) {
+                           const void* addend, void* y, int B, int H, int W, int Ci, int Co, int flags, hipStream_t s, bxWgradPending* carry, int ncarry) {
   const int relu = ((flags & BX_EPI_RELU) ? 1 : 0) | ((flags & BX_EPI_MASK_BITS) ? 2 : 0);
   BX_REQUIRE(!(flags & BX_EPI_MASK_BITS) || (relu_mask_src && Ci <= 32 && Co >= 16), "bx_conv3x3(mfma): BX_EPI_MASK_BITS applies to the early stages' data gradients (Ci <= 32)");
-  // a pending weight-gradient sum rides in this launch (pixel-split kernels only); the job is built like a chained reduce's
-  WgradRedJob job = {};
-  const WgradRedJob* red = nullptr;
-  if (carry && carry->valid) { job = wgrad_job_from(carry, true); red = &job; carry->valid = 0; }
+  // pending weight-gradient sums ride in this launch (pixel-split kernels only); the jobs are built like a chained reduce's
+  WgradRedList jobs = {};
+  const WgradRedList* red = nullptr;
+  BX_REQUIRE(ncarry >= 0 && ncarry <= BX_WGRAD_RED_MAX, "bx_conv3x3(mfma): a launch carries at most %d pending sums (%d given)", BX_WGRAD_RED_MAX, ncarry);
+  for (int i = 0, k = 0; carry && i < ncarry; ++i)
+    if (carry[i].valid) { jobs.job[k++] = wgrad_job_from(&carry[i], true); red = &jobs; }
   // the kernels address activations with 32-bit byte offsets through buffer resources
   BX_REQUIRE((size_t)B * H * W * (Ci > Co ? Ci : Co) * 2 < ((size_t)1 << 31), "bx_conv3x3(mfma): an activation tensor of 2 GiB or more is not supported (B=%d H=%d W=%d)", B, H, W);
   if (!red) {
     const int rc = try_conv_c(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr);
     if (rc >= 0) return rc;
   }
+  int rc;
   switch (mfma_ck(Ci)) {
-    case 8:  return launch_conv_nc<8>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red);
-    case 16: return launch_conv_nc<16>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red);
-    case 32: return launch_conv_nc<32>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red);
-    default: return launch_conv_nc<64>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red);
+    case 8:  rc = launch_conv_nc<8>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red); break;
+    case 16: rc = launch_conv_nc<16>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red); break;
+    case 32: rc = launch_conv_nc<32>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red); break;
+    default: rc = launch_conv_nc<64>(x, packed_mfma, bias, relu_mask_src, addend, y, B, H, W, Ci, Co, relu, s, nullptr, red); break;
   }
+  // the pending sums are taken only once the launch that carries them is queued: a refusal above leaves every descriptor valid
+  for (int i = 0; rc == BX_OK && carry && i < ncarry; ++i) carry[i].valid = 0;
+  return rc;
 }
 
 // conv3 of a Block: y = relu(conv + bias), pooled = pool2x2(y), batch statistics of pooled (+ finalize) -- one launch
@@ -1621,6 +1637,13 @@ __device__ __forceinline__ void wgrad_reduce3_body(const WgradRedJob& jb, int bi
       for (int j = 0; j < 4; ++j) db[b0 + j] = rr[j];
     }
   }
+}
+__device__ __forceinline__ void wgrad_reduce_list(const WgradRedList& rl, int bid, float4* sm) {
+  if (bid < rl.job[0].nblocks) { wgrad_reduce3_body(rl.job[0], bid, sm); return; }
+  bid -= rl.job[0].nblocks;
+  if (bid < rl.job[1].nblocks) { wgrad_reduce3_body(rl.job[1], bid, sm); return; }
+  bid -= rl.job[1].nblocks;
+  if (bid < rl.job[2].nblocks) wgrad_reduce3_body(rl.job[2], bid, sm);
 }
 // jb2: a second job in the same launch (workgroups from jb.nblocks on; nblocks == 0: none) -- the two weight gradients of
 // stage 1's fused conv2 backward (k_conv_mfma_bwd<true>)
@@ -1869,19 +1892,26 @@ extern "C" int bx_debug_wgrad_stamps(unsigned long long* host_out) {
 // fragments of a K-step are three shifted windows per tile row: a lane's 8 pixels of tap dx are pixels dx .. dx + 7 of the 10 it would
 // read for dx = 0 .. 2 together.  So each row is read ONCE as 12 pixels (three transposing reads) and the dx = 1 / 2 fragments are
 // built in registers (dword re-indexing and four v_alignbit): 9 + 2 reads per K-step instead of 18 + 2.
-template <int TW, int OCC>
-__global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dz, float* __restrict__ partial,
-    int H, int W, int Ci_p, int Co, int tiles_x, int tiles_y, int ntiles, int tiles_per_split, int nsplit, int ytiles, int ztiles,
-    WgradRedJob prev, int nred) {
+// One layer's launch as a record (round 5): k_wgrad_own builds it from its arguments, k_wgrad_own_group takes up to three by value
+// and every workgroup finds its own from blockIdx.x.  `first` = the job's first workgroup id in a group launch (a multiple of 8).
+struct WgradOwnJob {
+  const bf16_t* x; const bf16_t* dz; float* partial;
+  int H, W, Ci_p, Co, tiles_x, tiles_y, ntiles, tiles_per_split, nsplit, ytiles, ztiles, first;
+};
+#define BX_WGRAD_GROUP_MAX 3
+struct WgradOwnGroup { WgradOwnJob job[BX_WGRAD_GROUP_MAX]; };
+// L = the workgroup's index inside the job; L & 7 == blockIdx.x & 7 (what precedes the job in the grid is a multiple of 8)
+template <int TW>
+__device__ __forceinline__ void wgrad_own_body(const WgradOwnJob& jb, const int L, char* lds) {
   constexpr int TH = 8, HWID = TW + 2, HH = TH + 2, CIT = 32, COT = 32, XB = 64, ZB = 64;
   constexpr int KSTEPS = TH * TW / 32, ROWS_PER_STEP = 32 / TW;   // TW = 32: one tile row per K-step; TW = 16: two
   constexpr int XS_BYTES = HH * HWID * XB;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  if ((int)blockIdx.x < nred) {                                  // chained mode: sum the PREVIOUS layer's partials
-    if ((int)blockIdx.x < prev.nblocks) wgrad_reduce3_body(prev, (int)blockIdx.x, reinterpret_cast<float4*>(lds));
-    return;
-  }
-  const int L = (int)blockIdx.x - nred, YZ = ytiles * ztiles;     // nred is a multiple of 8: L & 7 == blockIdx.x & 7
+  const bf16_t* __restrict__ x = jb.x;
+  const bf16_t* __restrict__ dz = jb.dz;
+  float* __restrict__ partial = jb.partial;
+  const int H = jb.H, W = jb.W, Ci_p = jb.Ci_p, Co = jb.Co, tiles_x = jb.tiles_x, tiles_y = jb.tiles_y, ntiles = jb.ntiles;
+  const int tiles_per_split = jb.tiles_per_split, nsplit = jb.nsplit, ytiles = jb.ytiles, ztiles = jb.ztiles;
+  const int YZ = ytiles * ztiles;
   const int slot = L >> 3, yz = slot % YZ, split = (slot / YZ) * 8 + (L & 7);
   if (split >= nsplit) return;
   const int by = yz / ztiles, bz = yz - by * ztiles;
@@ -2041,6 +2071,31 @@ __global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict
   }
   BX_STAMP(6);
 }
+template <int TW, int OCC>
+__global__ __launch_bounds__(256, OCC) void k_wgrad_own(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dz, float* __restrict__ partial,
+    int H, int W, int Ci_p, int Co, int tiles_x, int tiles_y, int ntiles, int tiles_per_split, int nsplit, int ytiles, int ztiles,
+    WgradRedJob prev, int nred) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  if ((int)blockIdx.x < nred) {                                  // chained mode: sum the PREVIOUS layer's partials
+    if ((int)blockIdx.x < prev.nblocks) wgrad_reduce3_body(prev, (int)blockIdx.x, reinterpret_cast<float4*>(lds));
+    return;
+  }
+  const WgradOwnJob jb = {x, dz, partial, H, W, Ci_p, Co, tiles_x, tiles_y, ntiles, tiles_per_split, nsplit, ytiles, ztiles, 0};
+  wgrad_own_body<TW>(jb, (int)blockIdx.x - nred, lds);           // nred is a multiple of 8
+}
+// The weight gradients of up to three layers of one Block in ONE launch (round 5): the jobs' workgroup ranges are concatenated
+// (heaviest first), each a multiple of 8 long, so id & 7 still selects the XCD lane inside every job.  A workgroup does exactly what
+// a workgroup of the job's own k_wgrad_own launch does; no reduce role -- every job leaves a pending sum for a carrying launch.
+// Unused jobs have first == 0x7fffffff.
+template <int TW, int OCC>
+__global__ __launch_bounds__(256, OCC) void k_wgrad_own_group(WgradOwnGroup g) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int id = (int)blockIdx.x;
+  const WgradOwnJob* pj = &g.job[0];                             // one copy of the body: the job's fields are scalar loads from the table
+  if (id >= g.job[1].first) pj = &g.job[1];
+  if (id >= g.job[2].first) pj = &g.job[2];
+  wgrad_own_body<TW>(*pj, id - pj->first, lds);
+}
 
 struct WgradPlan { int ma, nb, tw, tiles_x, tiles_y, ntiles, ytiles, ztiles, nsplit, tps; size_t lds; };
 static WgradPlan wgrad_plan(int B, int H, int W, int Ci_p, int Co) {
@@ -2148,6 +2203,61 @@ int bx_wgrad_mfma_launch(const void* x, const void* dz, float* dw, float* db, in
   cur.ztiles = p.ztiles; cur.nfrag4 = p.ytiles * p.ztiles * 9 * p.ma * p.nb * 64; cur.valid = 1;
   if (pending) { *pending = cur; return BX_OK; }
   return bx_wgrad_mfma_finish(&cur, s);
+}
+
+// ---- group launch: the weight gradients of n = 1..3 layers that share B, H, W (one Block) in one k_wgrad_own_group launch
+// Every layer keeps its own wgrad_plan (splits, tiles per split, partial layout) and its own region of the workspace, so its partials
+// -- and, summed with the slice count of a carried sum, its dW / db -- are those of its own bx_conv3x3_wgrad_chained launch.
+static size_t wgrad_group_region(size_t bytes) { return (bytes + 255) / 256 * 256; }
+int bx_wgrad_group_supported(int n, const int* Ci_p, const int* Co, int W, int dtype) {
+  if (n < 1 || n > BX_WGRAD_GROUP_MAX || !Ci_p || !Co || W <= 0 || dtype != BX_BF16) return 0;
+  for (int i = 0; i < n; ++i)                                    // the tile-owner kernel's shapes: ma == 2 && nb == 2
+    if (Ci_p[i] < 32 || Co[i] < 32 || !bx_wgrad_mfma_supported(Ci_p[i], Co[i], dtype)) return 0;
+  return 1;
+}
+size_t bx_wgrad_group_workspace(const bxWgradGroupLayer* layers, int n, int B, int H, int W) {
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) total += wgrad_group_region(bx_wgrad_mfma_workspace(B, H, W, layers[i].Ci_p, layers[i].Co));
+  return total;
+}
+int bx_wgrad_group_launch(const bxWgradGroupLayer* layers, int n, int B, int H, int W, void* ws, size_t ws_bytes, bxWgradPending* pending,
+                          hipStream_t s) {
+  const size_t need = bx_wgrad_group_workspace(layers, n, B, H, W);
+  if (!ws || ws_bytes < need) BX_FAIL(BX_EWORKSPACE, "bx_conv3x3_wgrad_group: workspace %zu < %zu", ws_bytes, need);
+  for (int i = 0; i < n; ++i) {
+    BX_REQUIRE((size_t)B * H * W * (layers[i].Ci_p > layers[i].Co ? layers[i].Ci_p : layers[i].Co) * 2 < ((size_t)1 << 31),
+               "bx_conv3x3_wgrad_group: an activation tensor of 2 GiB or more is not supported");
+    // the launch sums nothing and writes every region of `ws`: a pending that is still valid -- its partials may lie in this very
+    // workspace -- has to be carried or finished first
+    BX_REQUIRE(!pending[i].valid, "bx_conv3x3_wgrad_group: pending[%d] is still valid (its partials may live in this call's workspace): carry or finish it first", i);
+  }
+  WgradOwnGroup g;
+  memset(&g, 0, sizeof(g));
+  bxWgradPending cur[BX_WGRAD_GROUP_MAX];
+  int nwg = 0, tw = 0;
+  size_t off = 0;
+  for (int i = 0; i < BX_WGRAD_GROUP_MAX; ++i) {
+    WgradOwnJob& jb = g.job[i];
+    if (i >= n) { jb.first = 0x7fffffff; continue; }
+    const bxWgradGroupLayer& ly = layers[i];
+    const WgradPlan p = wgrad_plan(B, H, W, ly.Ci_p, ly.Co);
+    float* part = (float*)((char*)ws + off);
+    off += wgrad_group_region(bx_wgrad_mfma_workspace(B, H, W, ly.Ci_p, ly.Co));
+    tw = p.tw;
+    jb.x = (const bf16_t*)ly.x; jb.dz = (const bf16_t*)ly.dz; jb.partial = part;
+    jb.H = H; jb.W = W; jb.Ci_p = ly.Ci_p; jb.Co = ly.Co; jb.tiles_x = p.tiles_x; jb.tiles_y = p.tiles_y; jb.ntiles = p.ntiles;
+    jb.tiles_per_split = p.tps; jb.nsplit = p.nsplit; jb.ytiles = p.ytiles; jb.ztiles = p.ztiles; jb.first = nwg;
+    nwg += (p.nsplit + 7) / 8 * 8 * p.ytiles * p.ztiles;          // a multiple of 8: the next job starts on XCD lane 0
+    bxWgradPending& c = cur[i];
+    c.partial = part; c.dw = ly.dw; c.db = ly.db; c.nsplit = p.nsplit; c.Cin = ly.Cin; c.Co = ly.Co; c.ma = p.ma; c.nb = p.nb;
+    c.ztiles = p.ztiles; c.nfrag4 = p.ytiles * p.ztiles * 9 * p.ma * p.nb * 64; c.valid = 1;
+  }
+  const size_t lds = (size_t)10 * (tw + 2) * 64 + (size_t)8 * tw * 64 + 256;       // as bx_wgrad_mfma_launch's
+  if (tw == 16) hipLaunchKernelGGL((k_wgrad_own_group<16, 2>), dim3(nwg), dim3(256), lds, s, g);
+  else hipLaunchKernelGGL((k_wgrad_own_group<32, 2>), dim3(nwg), dim3(256), lds, s, g);
+  BX_CHECK_LAUNCH("bx_conv3x3_wgrad_group");
+  for (int i = 0; i < n; ++i) pending[i] = cur[i];
+  return BX_OK;
 }
 
 // ================================================================================================

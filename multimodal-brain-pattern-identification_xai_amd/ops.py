@@ -456,7 +456,11 @@ def _conv(x, packed, bias, mask_src, addend, relu: bool, dtype, carry: bool = Fa
     st = _wg_chain_state(x.device) if carry and WGRAD_CARRY else None
     flags = (L.BX_EPI_RELU if relu else 0) | (L.BX_EPI_MASK_BITS if mask_bits else 0)
     with _Timed("fwd" if bias is not None else "dgrad", ("conv", B, H, W, Ci, op)):
-        if st is not None and st.pend.valid and st.stream == _stream():
+        if st is not None and any(pd.valid for pd in st.group_pend) and not st.pend.valid and st.stream == _stream():
+            L.check(L.load().bx_conv3x3_carry_many(_p(x), _p(pf), _p(pm), _p(bias), _p(mask_src), _p(addend), _p(y), B, H, W, Ci, op,
+                                                   bx_dtype(dtype), flags, algo, st.group_pend, 3, _stream()), "bx_conv3x3_carry_many")
+            st.group_keep = None
+        elif st is not None and st.pend.valid and st.stream == _stream():
             L.check(L.load().bx_conv3x3_carry(_p(x), _p(pf), _p(pm), _p(bias), _p(mask_src), _p(addend), _p(y), B, H, W, Ci, op,
                                               bx_dtype(dtype), flags, algo, C.byref(st.pend), _stream()), "bx_conv3x3_carry")
             st.keep = None
@@ -470,9 +474,14 @@ def _conv(x, packed, bias, mask_src, addend, relu: bool, dtype, carry: bool = Fa
 # (bx_conv3x3_wgrad_chained); BlockFn.backward finishes the chain before it returns (autograd may copy or accumulate a
 # returned gradient right away, so nothing may be pending then).  Per device: the pending descriptor, two partial buffers
 # used alternately (the pending partials must outlive the next launch) and the tensors to keep alive meanwhile.
+# A group launch (WGRAD_GROUP) leaves three pending sums at once: their partials live in a third buffer of their own (group_buf, three
+# regions) with three descriptors (group_pend); like the ring it is never freed, and wgrad_flush() finishes whatever is still pending.
 WGRAD_CHAIN = _os.environ.get("BX_WGRAD_CHAIN", "1") == "1"
 # the last pending sum of a Block's backward rides in conv1's data-gradient launch; 0 = a k_wgrad_reduce3 launch per Block
 WGRAD_CARRY = _os.environ.get("BX_WGRAD_CARRY", "1") == "1"
+# the three weight gradients of a stage 3-5 Block in one launch after the data gradients of conv3 and conv2 (bx_conv3x3_wgrad_group),
+# their sums carried by conv1's data gradient (bx_conv3x3_carry_many); 0 = one launch per layer, interleaved with the data gradients
+WGRAD_GROUP = _os.environ.get("BX_WGRAD_GROUP", "1") == "1"
 # batch-statistics finalizes inside the kernels that produce the partial sums (bxTailDesc.sync); 0 = separate finalize launches
 TAIL_IN_LAUNCH = _os.environ.get("BX_TAIL_IN_LAUNCH", "1") == "1"
 # conv3 of a Block pools and sums the batch statistics in its epilogue (bx_block_conv3_tail_fwd); 0 = conv3, then the pooling kernel
@@ -492,7 +501,9 @@ def _wg_chain_state(device):
     key = device.index if device.index is not None else torch.cuda.current_device()
     st = _WG_CHAIN.get(key)
     if st is None:
-        st = SimpleNamespace(pend=L.WgradPending(), ring=[None, None], slot=0, keep=None, stream=None, retired=[])
+        # group: the partial regions and pending descriptors of a group launch (_wgrad_group), beside the two-slot ring of the chain
+        st = SimpleNamespace(pend=L.WgradPending(), ring=[None, None], slot=0, keep=None, stream=None, retired=[],
+                             group_buf=None, group_pend=(L.WgradPending * 3)(), group_keep=None)
         _WG_CHAIN[key] = st
     return st
 
@@ -504,7 +515,10 @@ def wgrad_flush(device=None):
             continue
         if st.pend.valid:
             L.check(L.load().bx_conv3x3_wgrad_finish(C.byref(st.pend), st.stream), "bx_conv3x3_wgrad_finish")
-        st.keep = None
+        for pd in st.group_pend:
+            if pd.valid:
+                L.check(L.load().bx_conv3x3_wgrad_finish(C.byref(pd), st.stream), "bx_conv3x3_wgrad_finish")
+        st.keep = st.group_keep = None
 
 
 def _wgrad(x, dz, w: torch.Tensor, b: torch.Tensor, chain: bool = False):
@@ -542,6 +556,49 @@ def _wgrad(x, dz, w: torch.Tensor, b: torch.Tensor, chain: bool = False):
         L.check(lib.bx_conv3x3_wgrad(_p(x), _p(dz), _p(dw), _p(db), B, H, W, w.shape[1], Cip, Co, dt, algo, _p(ws), ws.numel(), _stream()),
                 "bx_conv3x3_wgrad")
     return dw, db
+
+
+def _wgrad_group_ok(acts, w3, dt):
+    """The grouped weight gradients apply: bf16 storage and three layers of the tile-owner kernel's shapes (stages 3-5)."""
+    if not (WGRAD_GROUP and WGRAD_CHAIN and WGRAD_CARRY) or dt != torch.bfloat16:
+        return False
+    if WGRAD_ALGO == L.BX_ALGO_DIRECT or CONV_ALGO == L.BX_ALGO_DIRECT:
+        return False
+    co = pad8(w3.shape[0])
+    ci = (C.c_int * 3)(acts[2].shape[3], acts[1].shape[3], acts[0].shape[3])
+    return bool(L.load().bx_conv3x3_wgrad_group_supported(3, ci, (C.c_int * 3)(co, co, co), acts[0].shape[2], bx_dtype(dt)))
+
+
+def _wgrad_group(xs, dzs, ws_, bs):
+    """One launch for the weight gradients of the layers (xs[i], dzs[i]) -> (ws_[i], bs[i]), heaviest first; the sums stay pending in
+    the chain state until a carrying convolution (_conv(carry=True)) or wgrad_flush() takes them."""
+    lib = L.load()
+    n = len(xs)
+    B, H, W, _ = xs[0].shape
+    st = _wg_chain_state(xs[0].device)
+    if st.stream != _stream() or st.pend.valid or any(pd.valid for pd in st.group_pend):
+        wgrad_flush(xs[0].device)                           # nothing may be pending across streams or under a group launch
+    grads = [(new_grad(w), new_grad(b)) for w, b in zip(ws_, bs)]
+    layers = (L.WgradGroupLayer * n)()
+    for i in range(n):
+        layers[i] = L.WgradGroupLayer(_p(xs[i]), _p(dzs[i]), _p(grads[i][0]), _p(grads[i][1]), ws_[i].shape[1], xs[i].shape[3], dzs[i].shape[3])
+    dt = bx_dtype(xs[0].dtype)
+    need = lib.bx_conv3x3_wgrad_group_workspace(layers, n, B, H, W, dt)
+    buf = st.group_buf
+    if buf is None or buf.numel() < need:
+        if buf is not None:
+            st.retired.append(buf)                          # never freed: see _wgrad
+        # the stages' needs are nearly equal (about 512 workgroups x 36 KB per layer whatever the shape): sized in 16 MiB steps, and
+        # never below what was there, the first block's buffer serves the later ones instead of being retired by a slightly larger need
+        step = 16 << 20
+        buf = torch.empty(max((int(need) + step - 1) // step * step, 0 if buf is None else buf.numel()), dtype=torch.uint8, device=xs[0].device)
+        st.group_buf = buf
+    st.stream = _stream()
+    # one profile entry per group launch, under the heaviest layer's name (bench.py divides the family totals by the fixed layer count)
+    with _Timed("wgrad", ("conv", B, H, W, xs[0].shape[3], dzs[0].shape[3])):
+        L.check(lib.bx_conv3x3_wgrad_group(layers, n, B, H, W, dt, _p(buf), buf.numel(), st.group_pend, st.stream), "bx_conv3x3_wgrad_group")
+    st.group_keep = (buf, grads, tuple(xs), tuple(dzs))    # what the launch and the pending sums read / write
+    return grads
 
 
 def _bwd_fused(dz, xl, packed, w, b, x0, w0, b0):
@@ -733,8 +790,25 @@ class BlockFn(torch.autograd.Function):
             if w1_form:
                 grads_w[0], grads_b[0] = g0
             layers = () if w1_form else (0,)
+        if need_w and need_dx and not ctx.fuse_bwd and not cfg.preact and _wgrad_group_ok(acts, w3, dt):
+            # stages 3-5: the data gradients first (the chain the step waits for), then the three weight gradients in ONE launch, whose
+            # sums ride in conv1's data gradient; dZ3 and dZ2 stay referenced (dzs) until that launch is queued
+            dzs = [dz3]
+            for k in (2, 1):
+                packed = cfg.prepacked.get(cfg.pack_base + k, True) if cfg.prepacked is not None else None
+                mb = ctx.masks is not None and CONV_ALGO != L.BX_ALGO_DIRECT
+                dzs.append(_conv(dzs[-1], packed or _pack(wts[k], flip=True, dtype=dt), None, ctx.masks[k - 1] if mb else acts[k], None, False, dt,
+                                 mask_bits=mb))
+            g = _wgrad_group((acts[2], acts[1], acts[0]), dzs, (w3, w2, w1), (b3, b2, b1))
+            for i, k in enumerate((2, 1, 0)):
+                grads_w[k], grads_b[k] = g[i]
+            dz = dzs[2]
+            del dzs
+            need_w_loop, layers = False, (0,)
+        else:
+            need_w_loop = need_w
         for k in layers:
-            if need_w:
+            if need_w_loop:
                 grads_w[k], grads_b[k] = _wgrad(acts[k], dz, wts[k], bss[k], chain=True)
             packed = cfg.prepacked.get(cfg.pack_base + k, True) if cfg.prepacked is not None else None
             if k > 0:
