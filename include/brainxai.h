@@ -650,6 +650,56 @@ int bx_rise_perturb_eeg(const float* x, const unsigned char* bits, const int* sh
  * bits are a function of the inputs alone. */
 int bx_rise_accumulate(const float* P, const int* classes, const unsigned char* bits, const int* shifts, float* sal, float* coverage, int B,
                        int N, int K, int gh, int gw, int Hm, int Wm, double p1, int normalize, bxStream stream);
+/* ---- Score-CAM (Wang et al., CVPR-W 2020; the reference ships no class-activation method): a class-activation map at a layer whose
+ * channel weights come from forward passes of the input seen through each up-sampled activation channel; no gradient.
+ * One activation is addressed by a base pointer, a dtype (BX_F32 / BX_BF16; bf16 is widened to fp32 first, which is exact) and four
+ * non-negative element strides: element (b, k, y, x) of A [B, C, h, w] lives at A[b sb + k sc + y sy + x sx], every offset below 2^31.
+ * The spectrogram branch's NHWC activation [B,h,w,C] is (h w C, 1, w C, C); the EEG branch's saved maps [B,C,T'] are (C T', T', 0, 1)
+ * with h = 1.  The mask domain is [Hm,Wm]: [H,W] of the spectrogram, [1,T] of the EEG input; Hm Wm < 2^20 and h w < 2^20.
+ * For one sample, with x the input, c the class and base the baseline:
+ *   1. U_k = bilinear up-sampling of plane k to Hm x Wm, align_corners=False, per axis in fp32 and without fused multiply-adds
+ *          s = max(scale (o + 0.5) - 0.5, 0), scale = (float)in / (float)out,  i0 = min((int)s, in - 1),  i1 = min(i0 + 1, in - 1),
+ *          l = s - i0;   top = (1 - lx) a00 + lx a01,  bot = (1 - lx) a10 + lx a11,  U = (1 - ly) top + ly bot
+ *      (horizontal blend first, then vertical: the convention of bx_resize_bilinear).
+ *   2. lo_k = min U_k, hi_k = max U_k over the UP-SAMPLED plane (with align_corners=False the interior extremes of A are not
+ *      attained); a zero extreme is +0.0.  Channel k is valid iff hi_k > lo_k; scale_k = 1 / (hi_k - lo_k) in fp32 if valid, else 0.
+ *   3. M_k(p) = min((U_k(p) - lo_k) scale_k, 1), in [0, 1];  row k is x_k = base + M_k (x - base), three roundings, one mask value for
+ *      all channels of a spectrogram pixel / all electrodes of an EEG time column.  An invalid channel's row is the baseline.
+ *   4. P[k, j] = softmax probability of class j for x_k (the model's own kernels and bx_softmax_rows).
+ *      BX_SCORECAM_PROB: w_k = P[k, c] (the authors' published code);  BX_SCORECAM_INCREASE: w_k = P[k, c] - P_base[c] in fp32, P_base
+ *      the probabilities of the all-baseline input (the paper's increase of confidence);  w_k = 0 for an invalid channel.
+ *   5. raw[s] = sum_k w_k A[k, s] at the activation's own resolution, in fp64 over k = 0..C-1 in index order, every term the exact
+ *      product, one rounding to fp32;  cam = max(raw, 0) if relu.  No normalisation (the conventions of bx_cam_reduce; the authors'
+ *      script sums up-sampled planes and min-max normalises the result).
+ * No mask is ever stored: every kernel recomputes U where it needs it.  Every entry point writes every element of its outputs and
+ * refuses its limits with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+#define BX_SCORECAM_PROB 0
+#define BX_SCORECAM_INCREASE 1
+/* lo, hi, scale fp32 [B,C] of step 2.  Two levels, no atomics: (plane, chunk of 4096 up-sampled values) -> one pair, then one fold per
+ * plane.  workspace: bx_scorecam_range_workspace bytes (0 for refused shapes), 4-byte aligned. */
+size_t bx_scorecam_range_workspace(int B, int C, int Hm, int Wm);
+int bx_scorecam_range(const void* A, int dtype, int sb, int sc, int sy, int sx, int B, int C, int h, int w, int Hm, int Wm, float* lo,
+                      float* hi, float* scale, void* workspace, size_t workspace_bytes, bxStream stream);
+/* Perturbed spectrogram rows.  x fp32 NCHW [B,Cin,H,W], 1 <= Cin <= 4 -> out [nb*n, H, W, Cp] (dtype; row bl*n + j is sample b0 + bl
+ * seen through channel k0 + j), channels Cin..Cp-1 zero, Cp = 8 -- bit for bit bx_nchw_to_nhwc of step 3's tensor, which is never
+ * built.  lo, scale fp32 [B,C] are ARGUMENTS (bx_scorecam_range's, or a reference's: the rows then do not depend on how the device
+ * rounds a division).  baseline fp32, by baseline_kind as in bx_rise_perturb_spec: 0 one value, 1 one value per channel [Cin], 2 a
+ * tensor of x's shape.  A, lo, scale, x and a kind-2 baseline are indexed by the sample b0 + bl.  One call's output stays below 2^32 bytes. */
+int bx_scorecam_perturb_spec(const float* x, const void* A, int dtype_a, int sb, int sc, int sy, int sx, int C, int h, int w, const float* lo,
+                             const float* scale, const float* baseline, int baseline_kind, void* out, int B, int Cin, int H, int W, int Cp,
+                             int b0, int nb, int k0, int n, int dtype, bxStream stream);
+/* Perturbed EEG rows.  x fp32 [B,1,Chans,T] -> out fp32 [nb*n,1,Chans,T], same row order and arithmetic; the planes have h = 1 (w
+ * values, strides sb, sc, sx) and column t's mask value applies to every electrode.  baseline_kind: 0 one value, 1 one value per
+ * electrode [Chans], 2 a tensor of x's shape. */
+int bx_scorecam_perturb_eeg(const float* x, const void* A, int dtype_a, int sb, int sc, int sx, int C, int w, const float* lo,
+                            const float* scale, const float* baseline, int baseline_kind, float* out, int B, int Chans, int T, int b0,
+                            int nb, int k0, int n, bxStream stream);
+/* Steps 4-5.  P fp32 [B,C,K] (K <= 32), P_base fp32 [B,K] (NULL for BX_SCORECAM_PROB), valid u8 [B,C] (non-zero = valid), classes
+ * i32 [B] (one map per sample, nm = 1) or NULL (a map for each class, nm = K).  raw and / or cam fp32 [B*nm, h*w] (either may be NULL,
+ * not both; map index = sample * nm + class), weights fp32 [B*nm, C] = w_k. */
+int bx_scorecam_combine(const float* P, const float* P_base, const int* classes, const unsigned char* valid, const void* A, int dtype_a, int sb,
+                        int sc, int sy, int sx, int B, int C, int h, int w, int K, int weight_mode, int relu, float* raw, float* cam,
+                        float* weights, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

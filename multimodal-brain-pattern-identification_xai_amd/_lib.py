@@ -19,6 +19,7 @@ BX_EPI_MASK_BITS = 2
 BX_TAIL_SYNC_WORDS = 8192
 BX_EEG_CAM_CONV1, BX_EEG_CAM_DEPTHWISE, BX_EEG_CAM_SEPARABLE = 0, 1, 2
 BX_CAM_GRADCAM, BX_CAM_GRADCAM_PP, BX_CAM_LAYERCAM = 0, 1, 2
+BX_SCORECAM_PROB, BX_SCORECAM_INCREASE = 0, 1
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -182,6 +183,11 @@ SIGNATURES = {
     "bx_rise_perturb_spec": (i32, [vp, vp, vp, vp, i32, vp] + [i32] * 11 + [vp]),
     "bx_rise_perturb_eeg": (i32, [vp, vp, vp, i32, vp, i32, vp] + [i32] * 8 + [vp]),
     "bx_rise_accumulate": (i32, [vp] * 6 + [i32] * 7 + [C.c_double, i32, vp]),
+    "bx_scorecam_range_workspace": (sz, [i32] * 4),
+    "bx_scorecam_range": (i32, [vp] + [i32] * 11 + [vp, vp, vp, vp, sz, vp]),
+    "bx_scorecam_perturb_spec": (i32, [vp, vp] + [i32] * 8 + [vp, vp, vp, i32, vp] + [i32] * 10 + [vp]),
+    "bx_scorecam_perturb_eeg": (i32, [vp, vp] + [i32] * 6 + [vp, vp, vp, i32, vp] + [i32] * 7 + [vp]),
+    "bx_scorecam_combine": (i32, [vp] * 5 + [i32] * 12 + [vp, vp, vp, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

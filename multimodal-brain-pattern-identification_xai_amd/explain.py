@@ -15,6 +15,11 @@
 * ``rise``                    -- RISE saliency (the same paper; not in the reference): black-box maps of either input from randomly
                                  masked forward passes; the masks are recomputed from their bit grids inside the perturb and
                                  weighted-sum kernels (bx_rise_perturb_*, bx_rise_accumulate) and never stored; ``rise_masks`` builds them.
+* ``score_cam``               -- Score-CAM (Wang et al., CVPR-W 2020; not in the reference): a class-activation map at every Grad-CAM
+                                 target but conv1 whose channel weights are class probabilities of the input seen through each
+                                 up-sampled activation channel; the masks are recomputed from the activation planes inside the range
+                                 and perturb kernels (bx_scorecam_range, bx_scorecam_perturb_*) and never stored; fp64 channel sum
+                                 (bx_scorecam_combine).
 """
 from __future__ import annotations
 
@@ -1452,3 +1457,304 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     if not return_parts:
         return sal
     return RiseResult(sal, None if classes is None else classes.long(), P, coverage, bits, shifts)
+
+
+# ------------------------------------------------------------------------------------------------
+# Score-CAM (Wang et al., CVPR-W 2020): a class-activation map whose channel weights come from forward passes of the input seen
+# through each up-sampled activation channel.  The definition is pinned in include/brainxai.h; tests/scorecam_ref.py restates it.
+_SCORECAM_WEIGHTS = {"prob": L.BX_SCORECAM_PROB, "increase": L.BX_SCORECAM_INCREASE}
+
+ScoreCamResult = collections.namedtuple("ScoreCamResult", "cam raw weights A out probs lo hi valid classes")
+ScoreCamResult.__doc__ = """What ``score_cam(..., return_parts=True)`` returns, all on the device: ``cam`` (what the plain call returns), ``raw`` fp32
+[B(,K),h,w] before ReLU and up-sampling, ``weights`` fp32 [B(,K),C] = w_k, ``A`` the target's activation (NHWC [B,h,w,C] in the model's
+storage dtype for a spectrogram target, fp32 [B,C,1,T'] for an EEG target), ``out`` the log-probabilities of the clean input [B,K],
+``probs`` fp32 [B,C,K] (the class probabilities of the input seen through every channel), ``lo`` / ``hi`` fp32 [B,C] (the extremes of
+every up-sampled channel), ``valid`` bool [B,C] (hi > lo) and ``classes`` int64 [B] (None for class_idx='all')."""
+
+
+def _scorecam_plane(A, eeg_target):
+    """-> (dtype code, sb, sc, sy, sx, C, h, w): how the library addresses channel k of sample b of A (NHWC [B,h,w,C], or [B,C,1,T'])."""
+    if eeg_target:
+        B, Cc, _, w = A.shape
+        return ops.bx_dtype(A.dtype), Cc * w, w, 0, 1, Cc, 1, w
+    B, h, w, Cc = A.shape
+    return ops.bx_dtype(A.dtype), h * w * Cc, 1, w * Cc, Cc, Cc, h, w
+
+
+def _scorecam_range(A, eeg_target, Hm, Wm):
+    """lo, hi, scale fp32 [B,C]: the extremes of every channel of A up-sampled to Hm x Wm, and 1 / (hi - lo) or 0 (bx_scorecam_range)."""
+    lib = L.load()
+    pl = _scorecam_plane(A, eeg_target)
+    B, Cc = A.shape[0], pl[5]
+    lo, hi, scale = (torch.empty(B, Cc, dtype=torch.float32, device=A.device) for _ in range(3))
+    nbytes = lib.bx_scorecam_range_workspace(B, Cc, Hm, Wm)
+    if nbytes == 0:
+        L.check(-1, "bx_scorecam_range_workspace")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=A.device)
+    L.check(lib.bx_scorecam_range(_p(A), *pl[:5], B, *pl[5:], Hm, Wm, _p(lo), _p(hi), _p(scale), _p(ws), nbytes, _stream()), "bx_scorecam_range")
+    return lo, hi, scale
+
+
+def _scorecam_perturb(x, A, eeg_target, lo, scale, base, kind, b0, nb, k0, n, dt):
+    """Rows (b, k), b in b0..b0+nb-1, k in k0..k0+n-1: sample b seen through channel k of A.  x fp32 [B,Cin,H,W] -> internal layout
+    [nb*n,H,W,8] in dt (bx_scorecam_perturb_spec), or for an EEG target fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_scorecam_perturb_eeg)."""
+    lib = L.load()
+    pl = _scorecam_plane(A, eeg_target)
+    B = x.shape[0]
+    if not eeg_target:
+        _, Cc, H, W = x.shape
+        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
+        L.check(lib.bx_scorecam_perturb_spec(_p(x), _p(A), *pl, _p(lo), _p(scale), _p(base), kind, _p(out), B, Cc, H, W, ops.pad8(Cc), b0, nb, k0, n,
+                                             ops.bx_dtype(dt), _stream()), "bx_scorecam_perturb_spec")
+    else:
+        _, _, Chans, T = x.shape
+        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
+        L.check(lib.bx_scorecam_perturb_eeg(_p(x), _p(A), pl[0], pl[1], pl[2], pl[4], pl[5], pl[7], _p(lo), _p(scale), _p(base), kind, _p(out), B, Chans, T,
+                                            b0, nb, k0, n, _stream()), "bx_scorecam_perturb_eeg")
+    return out
+
+
+def score_cam(model, eeg, spec, target_layer="spectrogram_model.block5", *, class_idx=None, weights="prob", baseline=0.0, upsample=True, relu=True,
+              max_batch=256, return_parts=False):
+    """Score-CAM (Wang et al., CVPR-W 2020): a class-activation map at ``target_layer`` whose channel weights come from forward passes
+    instead of gradients.  With A[k] channel k of the target's activation (a plane h x w), x the input the target's branch reads,
+    base the baseline and c the class:
+
+        U_k  = bilinear up-sampling (align_corners=False) of A[k] to the input's map domain;  lo_k, hi_k = its extremes
+        M_k  = min((U_k - lo_k) / (hi_k - lo_k), 1) in [0, 1]   (a channel with hi_k = lo_k is invalid: its weight is 0)
+        P[k] = softmax probabilities of the model for base + M_k (x - base)
+        w_k  = P[k, c] (weights='prob', the authors' published code)  or  P[k, c] - P_base[c] (weights='increase', the paper's
+               increase of confidence; P_base = the probabilities of the all-baseline input)
+        raw  = sum_k w_k A[k] at the activation's own resolution;  cam = ReLU(raw) if relu, then the optional up-sampling
+
+    These are the conventions of ``grad_cam``: the sum runs over A itself, the map is up-sampled afterwards (``resize_bilinear``) and
+    there is no final normalisation.  The authors' script instead sums the UP-SAMPLED planes and min-max normalises the result; for a
+    linear up-sampling the two sums agree, the normalisation is left to the caller.  pytorch-grad-cam's softmax over the channels of
+    w is not applied either.
+
+    target_layer: 'spectrogram_model.blockN' or 'spectrogram_model.blockN.convK' (the strings and the activation of ``grad_cam``): the
+                  masks cover the spectrogram [H,W], one value for all channels of a pixel (C <= 4), map [B,h,w] or, up-sampled,
+                  [B,H,W].  'eeg_model.depthwiseConv' / 'eeg_model.separableConv': the masks cover time columns of the EEG input, one
+                  value for every electrode, map [B,1,T] (separableConv: [B,1,T//4], resized to [B,1,T] by ``upsample``); the tuned
+                  EEGNet family only, as in ``grad_cam``.  'eeg_model.conv1' is refused: its activation is never formed.
+    model:        a MultimodalModel; a stand-alone Spectrogram_Model (eeg=None); a stand-alone EEGNet / EEGNetAttentionDeep
+                  (spec=None, 'depthwiseConv' / 'separableConv') -- the convention of grad_cam and rise.
+    class_idx:    None = each sample's arg-max class on the clean input; an int; one class per sample (sequence / tensor [B]);
+                  'all' = every class, the map gains a class axis [B,K,...] (K <= 32) at no further forward pass.
+    baseline:     what a masked-out cell shows: a number; one value per channel (spectrogram) / electrode (EEG); a tensor of the
+                  input's shape.
+    max_batch:    rows (masked inputs) per forward pass.
+    C * B forward evaluations (plus B for weights='increase') in eval mode without autograd, no backward pass.  The B x C masks never
+    exist in memory: the rows are written straight in the model's layout from the activation planes (bx_scorecam_perturb_*), and the
+    sum runs in fp64 in channel order (bx_scorecam_combine): identical bits run to run and for every max_batch.  In a MultimodalModel
+    the branch whose input does not change runs once per sample and its output is repeated into the fusion head.  The training flag
+    and every requires_grad are restored on return.  The map fits ``deletion_insertion`` and ``attribution_ranks`` as it is.
+    Returns the map (device, fp32), or ``ScoreCamResult`` with return_parts."""
+    return _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, upsample, relu, max_batch, return_parts)
+
+
+def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, upsample, relu, max_batch, return_parts, profile=None):
+    """``score_cam`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'range', 'perturb',
+    'forward', 'combine' -- device events around every phase of the pass (tools/scorecam_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "score_cam"
+    if weights not in _SCORECAM_WEIGHTS:
+        raise ValueError(f"{who}: unknown weights {weights!r}; use 'prob' or 'increase'")
+    max_batch = int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    if not isinstance(target_layer, str):
+        raise ValueError(f"{who}: target_layer must be a string, got {target_layer!r}")
+    me, ms = _EEG_TARGET.match(target_layer), _TARGET.match(target_layer)
+    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
+    if me:
+        if me.group(1) == "conv1":
+            raise ValueError(f"{who}: 'eeg_model.conv1' is no Score-CAM target: its [B,8,Chans,T] activation is never formed; use "
+                             "'eeg_model.depthwiseConv' or 'eeg_model.separableConv'")
+        eeg_target, x = True, eeg
+    elif ms:
+        eeg_target, x = False, spec
+    else:
+        raise ValueError(f"{who}: unsupported target {target_layer!r}; use 'spectrogram_model.blockN[.convK]', 'eeg_model.depthwiseConv' or "
+                         "'eeg_model.separableConv'")
+    if x is None:
+        raise ValueError(f"{who}: target {target_layer!r} reads the {'EEG' if eeg_target else 'spectrogram'} input, but that tensor is None")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (eeg_target and x.shape[1] != 1):
+        raise ValueError(f"{who}: the {'EEG' if eeg_target else 'spectrogram'} input must be a tensor " + ("[B,1,Chans,T]" if eeg_target else "[B,C,H,W]"))
+    B = int(x.shape[0])
+    if multimodal:
+        other = spec if eeg_target else eeg
+        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
+            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
+        K = int(model.fc2.out_features)
+        net = model.eeg_model if eeg_target else model.spectrogram_model
+    else:
+        net = model
+        if eeg_target:
+            if not hasattr(model, "depthwiseConv"):
+                raise ValueError(f"{who}: an EEG target needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
+            K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
+        else:
+            if not (hasattr(model, "block1") and hasattr(model, "fc")):
+                raise ValueError(f"{who}: a spectrogram target needs a MultimodalModel or a Spectrogram_Model")
+            K = int(model.fc.out_features)
+    if eeg_target:
+        from .models import EEGNet, EEGNetAttentionDeep
+        if not isinstance(net, (EEGNet, EEGNetAttentionDeep)):
+            raise ValueError(f"{who}: an EEG target needs an EEGNet / EEGNetAttentionDeep branch, got {type(net).__name__}")
+        Chans, T = int(x.shape[2]), int(x.shape[3])
+        g = net._geom
+        if not (g.F1 == 8 and g.D == 2 and g.F2 == 16 and g.K2 == 16 and g.K1 <= 64 and 1 <= Chans <= 64 and g.P1 <= T <= 15000):
+            raise ValueError(f"{who}: EEG targets support the tuned EEGNet family only: F1=8, D=2, F2=16, K2=16, kernLength <= 64, Chans <= 64, "
+                             f"T <= 15000 (got F1={g.F1}, D={g.D}, F2={g.F2}, kernLength={g.K1}, Chans={Chans}, T={T})")
+        Hm, Wm, per_len, what = 1, T, Chans, "electrode"
+    else:
+        Cc, H, W = (int(v) for v in x.shape[1:])
+        if not 1 <= Cc <= _FAITH_MAX_C:
+            raise ValueError(f"{who}: {Cc} channels, supported 1..{_FAITH_MAX_C}")
+        Hm, Wm, per_len, what = H, W, Cc, "channel"
+    if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
+        raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    all_classes = isinstance(class_idx, str)
+    if class_idx is None:
+        cls_h = None
+    elif all_classes:
+        if class_idx != "all":
+            raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int, one class per sample or 'all'")
+        cls_h = None
+    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
+        cls_h = [int(class_idx)] * B
+    else:
+        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
+        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
+            raise ValueError(f"{who}: class_idx must be None, an int, 'all' or {B} integers (one class per sample)")
+        cls_h = [int(c) for c in cls_t.tolist()]
+    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
+        raise ValueError(f"{who}: class outside [0, {K})")
+    try:
+        kind, base = _faith_baseline(baseline, x, per_len, what)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("deletion_insertion", who, 1)) from None
+    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
+        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+
+    lib = L.load()
+    dev = x.device
+    dt = torch.float32 if eeg_target else getattr(net, "compute_dtype", torch.float32)
+    # a pass addresses its largest activation with 32-bit byte offsets: stage 1's H x W x 16 channels, EEGNet's F1 x Chans x T
+    row_bytes = 8 * Chans * T * 4 if eeg_target else H * W * 16 * (2 if dt == torch.bfloat16 else 4)
+    max_rows = max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+    nm = K if all_classes else 1
+
+    @contextlib.contextmanager
+    def lap(name):
+        if profile is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        profile.append((name, e0, e1))
+
+    def head(rows_out, fixed_rows):
+        """log-probabilities of the whole model from the target branch's output and the other branch's (repeated) output"""
+        if not multimodal:
+            return rows_out
+        e, s = (rows_out, fixed_rows) if eeg_target else (fixed_rows, rows_out)
+        return ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
+
+    def probabilities(logp):
+        logp = logp.float().contiguous()
+        probs = torch.empty_like(logp)
+        L.check(lib.bx_softmax_rows(_p(logp), _p(probs), logp.shape[0], K, _stream()), "bx_softmax_rows")
+        return probs
+
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
+        xs = x.detach().to(torch.float32).contiguous()
+        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+        with lap("forward"):
+            # the clean pass: the activation, the explained class, and the branch whose input does not change (once per sample)
+            fixed = None
+            if multimodal:
+                o = other.detach().to(torch.float32).contiguous()
+                fixed = (model.spectrogram_model(o) if eeg_target else model.eeg_model(o)).float().contiguous()
+            if eeg_target:
+                feat, saved, desc, _, _ = ops.eeg_features_keep(net, xs)
+                off_d, off_s = C.c_size_t(0), C.c_size_t(0)
+                L.check(lib.bx_eeg_saved_layout(C.byref(desc), C.byref(off_d), C.byref(off_s)), "bx_eeg_saved_layout")
+                if me.group(1) == "depthwiseConv":
+                    A = saved[off_d.value:off_d.value + B * g.F1 * g.D * T * 4].view(torch.float32).reshape(B, g.F1 * g.D, 1, T).clone()
+                else:
+                    T1 = T // g.P1
+                    A = saved[off_s.value:off_s.value + B * g.F2 * T1 * 4].view(torch.float32).reshape(B, g.F2, 1, T1).clone()
+                clean = _eeg_head(net, feat)
+            else:
+                blk = getattr(net, f"block{ms.group(1)}")
+                conv_k = int(ms.group(2)) if ms.group(2) else 0
+                grabbed = {}
+                if conv_k:
+                    blk._preact, blk._capture = conv_k, {}
+                    hook = None
+                else:
+                    hook = blk.register_forward_hook(lambda _m, _i, o_: grabbed.__setitem__("A", o_))
+                try:
+                    clean = net(xs)
+                    A = blk._capture["act"] if conv_k else grabbed["A"].detach().permute(0, 2, 3, 1).contiguous()
+                finally:
+                    blk._preact, blk._capture = 0, None
+                    if hook is not None:
+                        hook.remove()
+            out = head(clean, fixed).float().contiguous()
+        pl = _scorecam_plane(A, eeg_target)
+        Cn, h, w = pl[5], pl[6], pl[7]
+        if cls_h is not None:
+            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
+        elif all_classes:
+            classes = None
+        else:
+            classes = out.argmax(dim=1).to(torch.int32).contiguous()
+        with lap("range"):
+            lo, hi, scale = _scorecam_range(A, eeg_target, Hm, Wm)
+            valid = hi > lo
+        P_base = None
+        if weights == "increase":
+            # the all-baseline input: the row of a channel whose scale is 0
+            zero = torch.zeros(B, Cn, dtype=torch.float32, device=dev)
+            for b0, nb, _, _ in _faith_chunks(B, 1, max_rows):
+                with lap("perturb"):
+                    rows = _scorecam_perturb(xs, A, eeg_target, zero, zero, base, kind, b0, nb, 0, 1, dt)
+                with lap("forward"):
+                    r = net(rows) if eeg_target else net(rows.permute(0, 3, 1, 2))
+                    pb = probabilities(head(r, None if fixed is None else fixed[b0:b0 + nb]))
+                    P_base = pb if P_base is None else torch.cat([P_base, pb])
+            P_base = P_base.contiguous()
+        P = torch.empty(B, Cn, K, dtype=torch.float32, device=dev)
+        for b0, nb, k0, n in _faith_chunks(B, Cn, max_rows):
+            with lap("perturb"):
+                rows = _scorecam_perturb(xs, A, eeg_target, lo, scale, base, kind, b0, nb, k0, n, dt)
+            with lap("forward"):
+                # (spectrogram rows: a logical-NCHW view of the internal layout, no further copy)
+                r = net(rows) if eeg_target else net(rows.permute(0, 3, 1, 2))
+                rep = None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)
+                P[b0:b0 + nb, k0:k0 + n] = probabilities(head(r, rep)).reshape(nb, n, K)
+        with lap("combine"):
+            raw = torch.empty(B * nm, h, w, dtype=torch.float32, device=dev)
+            cam = torch.empty_like(raw) if relu else None
+            wts = torch.empty(B * nm, Cn, dtype=torch.float32, device=dev)
+            L.check(lib.bx_scorecam_combine(_p(P), _p(P_base), _p(classes), _p(valid), _p(A), *pl[:5], B, Cn, h, w, K, _SCORECAM_WEIGHTS[weights],
+                                            1 if relu else 0, _p(raw), _p(cam), _p(wts), _stream()), "bx_scorecam_combine")
+            if cam is None:
+                cam = raw
+            if upsample and (h, w) != (Hm, Wm):
+                cam = resize_bilinear(cam, (Hm, Wm))
+    if eeg_target:
+        cam, raw = cam.reshape(B * nm, 1, -1), raw.reshape(B * nm, 1, -1)
+
+    def shape(t):
+        return t.reshape(B, nm, *t.shape[1:]) if all_classes else t
+    if not return_parts:
+        return shape(cam)
+    return ScoreCamResult(shape(cam), shape(raw), shape(wts), A, out, P, lo, hi, valid, None if classes is None else classes.long())
