@@ -700,6 +700,36 @@ int bx_scorecam_perturb_eeg(const float* x, const void* A, int dtype_a, int sb, 
 int bx_scorecam_combine(const float* P, const float* P_base, const int* classes, const unsigned char* valid, const void* A, int dtype_a, int sb,
                         int sc, int sy, int sx, int B, int C, int h, int w, int K, int weight_mode, int relu, float* raw, float* cam,
                         float* weights, bxStream stream);
+/* ---- Occlusion sensitivity (Zeiler & Fergus, ECCV 2014; Captum's Occlusion; the reference ships no black-box attribution): slide a
+ * window over the input, replace it by the baseline and record how much the class score drops.  Deterministic: no seed, no sampling.
+ * Domain [Hm,Wm]: [H,W] of a spectrogram [B,C,H,W] (a cell is a pixel with all its channels, 1 <= C <= 4) or [Chans,T] of an EEG
+ * input [B,1,Chans,T]; Hm * Wm < 2^20.  Window (wh, ww) and stride (sh, sw) with 1 <= sh <= wh <= Hm and 1 <= sw <= ww <= Wm
+ * (stride <= window is Captum's rule: every cell is covered).
+ * Window positions: ny = 1 + ceil((Hm - wh) / sh), nx = 1 + ceil((Wm - ww) / sw), N = ny * nx windows, window j = iy * nx + ix covers
+ * rows [iy sh, min(iy sh + wh, Hm)) and columns [ix sw, min(ix sw + ww, Wm)): the last window of an axis is clipped at the border (what
+ * Captum's padded mask does), and (ny - 1) sh + wh >= Hm, so it always reaches the border.
+ * Row j of sample b is x[b] with the cells of window j taken from the baseline and every other element x itself: a selection, not a
+ * blend -- every output element is bit for bit an element of x or of the baseline, -0.0 survives.  baseline fp32, by baseline_kind as in
+ * bx_faith_perturb_*: 0 one value, 1 one value per channel [C] (spectrogram) / electrode [Chans] (EEG), 2 a tensor of x's shape.
+ * With S[b,j,k] the score (softmax probability or log-probability) of class k for row j and S0[b,k] the score of the unperturbed input,
+ *     attr[b,k,p] = (1 / cnt(p)) * sum over the windows j covering p, in ascending j, of (S0[b,k] - S[b,j,k]),
+ * cnt(p) = cy(y) * cx(x) >= 1 the number of windows covering p: iy from max(0, ceil((y - wh + 1) / sh)) to min(ny - 1, floor(y / sh)),
+ * likewise for x.  Each difference, the sum and the quotient are fp64; the result is rounded to fp32 once.  No atomics: the result's
+ * bits are a function of the inputs alone.  Every entry point writes every element of its outputs and refuses its limits with
+ * BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+/* Perturbed spectrogram rows.  x fp32 NCHW [B,C,H,W] -> out [B*n, H, W, Cp] (dtype; sample-major: row b*n + j is sample b with window
+ * n0 + j occluded), channels C..Cp-1 zero, Cp = 8 -- bit for bit bx_nchw_to_nhwc of the selection, which is never built.
+ * 0 <= n0, 1 <= n, n0 + n <= N.  One call's output stays below 2^32 bytes. */
+int bx_occlusion_perturb_spec(const float* x, const float* baseline, int baseline_kind, void* out, int B, int C, int H, int W, int Cp, int wh,
+                              int ww, int sh, int sw, int n0, int n, int dtype, bxStream stream);
+/* Perturbed EEG rows.  x fp32 [B,1,Chans,T] -> out fp32 [B*n,1,Chans,T], same row order and selection over the domain [Chans,T]. */
+int bx_occlusion_perturb_eeg(const float* x, const float* baseline, int baseline_kind, float* out, int B, int Chans, int T, int wh, int ww,
+                             int sh, int sw, int n0, int n, bxStream stream);
+/* The map.  S fp32 [B,N,K], S0 fp32 [B,K], K <= 32; classes i32 [B] (one map per sample, of that class) or NULL (a map for each of the
+ * K classes).  attr fp32 [B,Hm*Wm] or [B,K,Hm*Wm] as defined above, counts i32 [Hm*Wm] = cnt(p).  Refused when ny * nx != N;
+ * B * N * K and B * K * Hm * Wm stay below 2^31. */
+int bx_occlusion_accumulate(const float* S, const float* S0, const int* classes, float* attr, int* counts, int B, int N, int K, int Hm, int Wm,
+                            int wh, int ww, int sh, int sw, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

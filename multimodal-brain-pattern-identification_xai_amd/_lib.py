@@ -183,6 +183,9 @@ SIGNATURES = {
     "bx_rise_perturb_spec": (i32, [vp, vp, vp, vp, i32, vp] + [i32] * 11 + [vp]),
     "bx_rise_perturb_eeg": (i32, [vp, vp, vp, i32, vp, i32, vp] + [i32] * 8 + [vp]),
     "bx_rise_accumulate": (i32, [vp] * 6 + [i32] * 7 + [C.c_double, i32, vp]),
+    "bx_occlusion_perturb_spec": (i32, [vp, vp, i32, vp] + [i32] * 12 + [vp]),
+    "bx_occlusion_perturb_eeg": (i32, [vp, vp, i32, vp] + [i32] * 9 + [vp]),
+    "bx_occlusion_accumulate": (i32, [vp] * 5 + [i32] * 9 + [vp]),
     "bx_scorecam_range_workspace": (sz, [i32] * 4),
     "bx_scorecam_range": (i32, [vp] + [i32] * 11 + [vp, vp, vp, vp, sz, vp]),
     "bx_scorecam_perturb_spec": (i32, [vp, vp] + [i32] * 8 + [vp, vp, vp, i32, vp] + [i32] * 10 + [vp]),

@@ -20,6 +20,11 @@
                                  up-sampled activation channel; the masks are recomputed from the activation planes inside the range
                                  and perturb kernels (bx_scorecam_range, bx_scorecam_perturb_*) and never stored; fp64 channel sum
                                  (bx_scorecam_combine).
+* ``occlusion``               -- occlusion sensitivity (Zeiler & Fergus, ECCV 2014; Captum's Occlusion; not in the reference): the
+                                 drop of the class score when a sliding window of either input shows the baseline -- electrode or
+                                 time-segment ablation on the EEG input, band or slab ablation on the spectrogram; deterministic; the
+                                 occluded rows are a selection written in the model's layout (bx_occlusion_perturb_*), the map an
+                                 fp64 mean over the covering windows in fixed order (bx_occlusion_accumulate).
 """
 from __future__ import annotations
 
@@ -1194,6 +1199,14 @@ class_idx='all'), ``probs`` fp32 [B,N,K] (the class probabilities of every maske
 masks, all on the device; ``bits`` uint8 [N,gh,gw] and ``shifts`` int32 [N,2] = (dy, dx) on the host: ``masks=(bits, shifts)`` repeats the call."""
 
 
+def _row_cap(x, input, dt, max_batch):
+    """Rows per forward pass: max_batch, capped so that a pass addresses its largest activation with 32-bit byte offsets -- stage 1's
+    H x W x 16 channels in dt for a spectrogram [B,C,H,W], EEGNet's F1 x Chans x T in fp32 for an EEG input [B,1,Chans,T]."""
+    cells = int(x.shape[2]) * int(x.shape[3])
+    row_bytes = cells * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * cells * 4
+    return max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+
+
 def _rise_geometry(who, grid, Hm, Wm):
     """-> (gh, gw, ch, cw): the grid as a pair, checked against the mask domain, and the cell size ceil(Hm / gh) x ceil(Wm / gw)."""
     if isinstance(grid, numbers.Integral) and not isinstance(grid, bool):
@@ -1401,9 +1414,7 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     dev = x.device
     spec_net = model.spectrogram_model if multimodal else model
     dt = getattr(spec_net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
-    # a pass addresses its largest activation with 32-bit byte offsets: stage 1's H x W x 16 channels, EEGNet's F1 x Chans x T
-    row_bytes = H * W * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * Chans * T * 4
-    max_rows = max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+    max_rows = _row_cap(x, input, dt, max_batch)
 
     @contextlib.contextmanager
     def lap(name):
@@ -1457,6 +1468,236 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     if not return_parts:
         return sal
     return RiseResult(sal, None if classes is None else classes.long(), P, coverage, bits, shifts)
+
+
+# ------------------------------------------------------------------------------------------------
+# Occlusion sensitivity (Zeiler & Fergus, ECCV 2014; Captum's Occlusion): the drop of the class score when a sliding window of the
+# input is replaced by the baseline.  The definition is pinned in include/brainxai.h; tests/occlusion_ref.py restates it.
+OcclusionResult = collections.namedtuple("OcclusionResult", "attribution drops classes scores clean counts grid")
+OcclusionResult.__doc__ = """What ``occlusion(..., return_parts=True)`` returns: ``attribution`` fp32 [B,Hm,Wm] or [B,K,Hm,Wm] (what the plain call
+returns), ``drops`` fp32 [B,ny,nx] or [B,K,ny,nx] = clean - scores per window, ``classes`` int64 [B] (None for class_idx='all'), ``scores``
+fp32 [B,N,K] (the score of every class for every occluded input, window j = iy * nx + ix), ``clean`` fp32 [B,K] (the scores of the
+unperturbed input), ``counts`` int32 [Hm,Wm] = the number of windows covering each cell, all on the device; ``grid`` = (ny, nx)."""
+
+
+def _occlusion_pair(who, name, value):
+    if isinstance(value, numbers.Integral) and not isinstance(value, bool):
+        return int(value), int(value)
+    try:
+        a, b = value
+        if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in (a, b)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: {name} must be an int or a pair of ints, got {value!r}") from None
+    return int(a), int(b)
+
+
+def _occlusion_geometry(who, window, stride, Hm, Wm):
+    """-> (wh, ww, sh, sw, ny, nx): window and stride as pairs, checked against the domain, and the window positions per axis."""
+    wh, ww = _occlusion_pair(who, "window", window)
+    sh, sw = (wh, ww) if stride is None else _occlusion_pair(who, "stride", stride)
+    if not (1 <= wh <= Hm and 1 <= ww <= Wm):
+        raise ValueError(f"{who}: window {wh} x {ww} outside 1..{Hm} x 1..{Wm}")
+    if not (1 <= sh <= wh and 1 <= sw <= ww):
+        raise ValueError(f"{who}: stride {sh} x {sw} outside 1..window = {wh} x {ww} (a stride above the window leaves cells uncovered)")
+    return wh, ww, sh, sw, 1 + -(-(Hm - wh) // sh), 1 + -(-(Wm - ww) // sw)
+
+
+def _occlusion_perturb(x, geom, base, kind, b0, nb, n0, n, dt, eeg_input=False):
+    """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1: sample b with window n0 + j taken from the baseline.  x fp32 [B,C,H,W] -> internal
+    layout [nb*n,H,W,8] in dt (bx_occlusion_perturb_spec), or with eeg_input fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T]
+    (bx_occlusion_perturb_eeg)."""
+    lib = L.load()
+    xs = x[b0:b0 + nb]
+    bs = base[b0:b0 + nb] if kind == 2 else base
+    wh, ww, sh, sw = geom[:4]
+    if not eeg_input:
+        _, Cc, H, W = x.shape
+        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
+        L.check(lib.bx_occlusion_perturb_spec(_p(xs), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), wh, ww, sh, sw, n0, n, ops.bx_dtype(dt),
+                                              _stream()), "bx_occlusion_perturb_spec")
+    else:
+        _, _, Chans, T = x.shape
+        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
+        L.check(lib.bx_occlusion_perturb_eeg(_p(xs), _p(bs), kind, _p(out), nb, Chans, T, wh, ww, sh, sw, n0, n, _stream()), "bx_occlusion_perturb_eeg")
+    return out
+
+
+def occlusion(model, eeg, spec, *, input="spec", window, stride=None, baseline=0.0, class_idx=None, score="prob", max_batch=256,
+              return_parts=False):
+    """Occlusion sensitivity (Zeiler & Fergus, ECCV 2014; Captum's ``Occlusion``): slide a window over the input, replace it by the
+    baseline and record how much the class score drops.  attr[b,k,p] = the mean, over the windows j that cover cell p, of
+    S0[b,k] - S[b,j,k], with S0 the score of the unperturbed input and S[b,j,.] that of the input with window j occluded.
+    Deterministic and forward-only, so it explains either input of the multimodal model; the map has the input's own shape and fits
+    ``deletion_insertion`` and ``attribution_ranks`` as it is.
+
+    input:       'spec': windows over [H,W], a cell is a pixel with all its channels (C <= 4), map [B,H,W]; 'eeg': windows over
+                 [Chans,T], map [B,Chans,T].  window=(1, T) on the EEG input is electrode ablation, (Chans, w) time-segment
+                 ablation; (h, W) / (H, w) on the spectrogram occlude a frequency band / a time slab.
+    model:       a MultimodalModel; a stand-alone Spectrogram_Model (eeg=None, input='spec'); a stand-alone EEGNet /
+                 EEGNetAttentionDeep (spec=None, input='eeg') -- the convention of grad_cam, deletion_insertion and rise.
+    window:      an int or a pair (wh, ww), 1 <= wh <= Hm, 1 <= ww <= Wm.
+    stride:      None = the window itself (tiles); an int or a pair (sh, sw) with 1 <= sh <= wh, 1 <= sw <= ww (Captum's rule: every
+                 cell is covered).  ny = 1 + ceil((Hm - wh) / sh) by nx = 1 + ceil((Wm - ww) / sw) windows, window j = iy * nx + ix at
+                 rows iy * sh .., columns ix * sw ..; the last window of an axis is clipped at the border, as Captum's padded mask is.
+    baseline:    what an occluded cell shows: a number; one value per channel (spec) / electrode (eeg); a tensor of the input's shape.
+    class_idx:   None = each sample's arg-max class on the unperturbed input; an int; one class per sample (sequence / tensor [B]);
+                 'all' = every class, the map gains a class axis [B,K,Hm,Wm] (K <= 32).
+    score:       'prob': the softmax probability; 'logprob': the log-probability.
+    max_batch:   rows (occluded inputs) per forward pass; no bit of the result depends on it.
+    (N + 1) * B forward evaluations in eval mode without autograd.  The occluded rows are written straight in the model's layout
+    (bx_occlusion_perturb_*: a selection, every element is bit for bit the input's or the baseline's); the map is an fp64 gather
+    in fixed order, rounded once (bx_occlusion_accumulate).  In a MultimodalModel the branch whose input does not change runs once per
+    sample and its output is repeated into the fusion head.  The training flag and every requires_grad are restored on return.
+    Returns the map (device, fp32), or ``OcclusionResult`` with return_parts (its ``drops`` for window=(1, T) on the EEG input are
+    the per-electrode importances)."""
+    return _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, score, max_batch, return_parts)
+
+
+def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, score, max_batch, return_parts, profile=None):
+    """``occlusion`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'perturb', 'forward',
+    'accumulate' -- device events around every phase of the pass (tools/occlusion_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "occlusion"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if score not in _FAITH_SCORES:
+        raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
+    max_batch = int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    x = spec if input == "spec" else eeg
+    if x is None:
+        raise ValueError(f"{who}: input={input!r} but that tensor is None")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
+        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
+    B = int(x.shape[0])
+    Hm, Wm = int(x.shape[2]), int(x.shape[3])
+    if input == "spec":
+        per_len, what = int(x.shape[1]), "channel"
+        if not 1 <= per_len <= _FAITH_MAX_C:
+            raise ValueError(f"{who}: {per_len} channels, supported 1..{_FAITH_MAX_C}")
+    else:
+        per_len, what = Hm, "electrode"
+    if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
+        raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
+    geom = _occlusion_geometry(who, window, stride, Hm, Wm)
+    ny, nx = geom[4:]
+    N = ny * nx
+    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
+    if multimodal:
+        other = eeg if input == "spec" else spec
+        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
+            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
+        K = int(model.fc2.out_features)
+    elif input == "spec":
+        if not (hasattr(model, "block1") and hasattr(model, "fc")):
+            raise ValueError(f"{who}: input='spec' needs a MultimodalModel or a Spectrogram_Model")
+        K = int(model.fc.out_features)
+    else:
+        if not hasattr(model, "depthwiseConv"):
+            raise ValueError(f"{who}: input='eeg' needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
+        K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    all_classes = isinstance(class_idx, str)
+    if class_idx is None:
+        cls_h = None
+    elif all_classes:
+        if class_idx != "all":
+            raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int, one class per sample or 'all'")
+        cls_h = None
+    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
+        cls_h = [int(class_idx)] * B
+    else:
+        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
+        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
+            raise ValueError(f"{who}: class_idx must be None, an int, 'all' or {B} integers (one class per sample)")
+        cls_h = [int(c) for c in cls_t.tolist()]
+    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
+        raise ValueError(f"{who}: class outside [0, {K})")
+    try:
+        kind, base = _faith_baseline(baseline, x, per_len, what)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("deletion_insertion", who, 1)) from None
+    if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
+        raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
+    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
+        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+
+    lib = L.load()
+    dev = x.device
+    spec_net = model.spectrogram_model if multimodal else model
+    dt = getattr(spec_net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
+    max_rows = _row_cap(x, input, dt, max_batch)
+    use_logprob = score == "logprob"
+
+    @contextlib.contextmanager
+    def lap(name):
+        if profile is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        profile.append((name, e0, e1))
+
+    def run(rows, rep):
+        """log-probabilities -> scores fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
+        if input == "spec":
+            out = spec_net(rows.permute(0, 3, 1, 2))                 # a logical-NCHW view of the internal layout: no further copy
+        else:
+            out = (model.eeg_model if multimodal else model)(rows)
+        if multimodal:
+            e, s = (rep, out) if input == "spec" else (out, rep)
+            out = ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
+        logp = out.float().contiguous()
+        if use_logprob:
+            return logp
+        probs = torch.empty_like(logp)
+        L.check(lib.bx_softmax_rows(_p(logp), _p(probs), logp.shape[0], K, _stream()), "bx_softmax_rows")
+        return probs
+
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
+        xs = x.detach().to(torch.float32).contiguous()
+        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+        fixed = None
+        with lap("forward"):
+            if multimodal:                                          # the branch whose input does not change: once per sample
+                o = other.detach().to(torch.float32).contiguous()
+                fixed = (model.eeg_model(o) if input == "spec" else model.spectrogram_model(o)).float().contiguous()
+            # the unperturbed input takes the path of the occluded rows, in chunks of the same size
+            clean = torch.empty(B, K, dtype=torch.float32, device=dev)
+            for b0 in range(0, B, max_rows):
+                nb = min(max_rows, B - b0)
+                rows = ops.to_nhwc(xs[b0:b0 + nb], dt) if input == "spec" else xs[b0:b0 + nb]
+                clean[b0:b0 + nb] = run(rows, None if fixed is None else fixed[b0:b0 + nb])
+        if cls_h is not None:
+            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
+        elif all_classes:
+            classes = None
+        else:                                                       # the explained class: the arg-max on the unperturbed input
+            classes = clean.argmax(dim=1).to(torch.int32).contiguous()
+        S = torch.empty(B, N, K, dtype=torch.float32, device=dev)
+        for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
+            with lap("perturb"):
+                rows = _occlusion_perturb(xs, geom, base, kind, b0, nb, n0, n, dt, input == "eeg")
+            with lap("forward"):
+                S[b0:b0 + nb, n0:n0 + n] = run(rows, None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)).reshape(nb, n, K)
+        with lap("accumulate"):
+            attr = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
+            counts = torch.empty(Hm, Wm, dtype=torch.int32, device=dev)
+            L.check(lib.bx_occlusion_accumulate(_p(S), _p(clean), _p(classes), _p(attr), _p(counts), B, N, K, Hm, Wm, *geom[:4], _stream()),
+                    "bx_occlusion_accumulate")
+        if not return_parts:
+            return attr
+        d = clean[:, None, :] - S                                   # [B,N,K]
+        if all_classes:
+            drops = d.permute(0, 2, 1).reshape(B, K, ny, nx).contiguous()
+        else:
+            drops = d.gather(2, classes.long().reshape(B, 1, 1).expand(B, N, 1)).reshape(B, ny, nx)
+    return OcclusionResult(attr, drops, None if classes is None else classes.long(), S, clean, counts, (ny, nx))
 
 
 # ------------------------------------------------------------------------------------------------
