@@ -1,11 +1,9 @@
 // Deletion / insertion curves (the causal metric of RISE, Petsiuk et al., BMVC 2018) for any attribution map: the exact descending
 // rank of every cell, the perturbed batches straight in the model's layouts, and the class curve with its area.  The forward
 // passes between them are the model's own kernels.  See include/brainxai.h for the contract of each entry point.
-#include "bx_common.h"
+#include "perturb_rows.h"
 
 #define FAITH_MAX_N ((1 << 20) - 1)
-#define FAITH_MAX_C 4
-#define FAITH_SPW 8                    // curve points of one sample a perturb workgroup writes for its 256 cells
 #define RANK_WAVES 16                  // one 1024-thread workgroup per row; a wave owns a contiguous chunk of the row
 
 // ---- rank: stable descending sort position of every cell ------------------------------------------------------------------------------
@@ -137,7 +135,7 @@ extern "C" int bx_rank_desc(const float* values, int* ranks, int B, int N, void*
 
 // ---- perturbed batches ----------------------------------------------------------------------------------------------------------------
 // Row (b, j) carries curve point i0 + j with cut k = min(N, (i0 + j) * per): a cell whose rank is below the cut is REPLACED by the
-// baseline (deletion) or is the only kind KEPT (insertion).
+// baseline (deletion) or is the only kind KEPT (insertion).  The kernels are perturb_rows.h's.
 static int faith_window_ok(const char* who, int B, long long N, int per, int i0, int n, int kind) {
   BX_REQUIRE(B > 0 && N > 0, "%s: bad shape B=%d N=%lld", who, B, N);
   if (N > FAITH_MAX_N) BX_FAIL(BX_EUNSUPPORTED, "%s: N = %lld cells per sample, supported 1..%d", who, N, FAITH_MAX_N);
@@ -149,99 +147,45 @@ static int faith_window_ok(const char* who, int B, long long N, int per, int i0,
   return BX_OK;
 }
 
-// x fp32 NCHW -> rows in the internal layout (NHWC, 8 channels, C..7 zero), the expression of k_nchw_to_nhwc applied to the
-// torch.where result, which is never built.  One thread per pixel; x, the baseline and the rank are read once per FAITH_SPW rows.
-template <typename T>
-__global__ __launch_bounds__(256) void k_faith_perturb_spec(const float* __restrict__ x, const int* __restrict__ ranks, const float* __restrict__ base,
-                                                            int kind, T* __restrict__ out, int HW, int C, int per, int i0, int n, int insertion) {
-  const int b = blockIdx.z, j0 = blockIdx.y * FAITH_SPW, p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= HW) return;
-  const int r = ranks[(size_t)b * HW + p];
-  float keep[FAITH_MAX_C], hide[FAITH_MAX_C];
-#pragma unroll
-  for (int c = 0; c < FAITH_MAX_C; ++c) {
-    const int cc = c < C ? c : 0;                                   // clamped, unconditional loads
-    const float xv = x[((size_t)b * C + cc) * HW + p];
-    const float bv = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)cc : ((size_t)b * C + cc) * HW + p];
-    keep[c] = c < C ? xv : 0.f;
-    hide[c] = c < C ? bv : 0.f;
-  }
-  for (int sj = 0; sj < FAITH_SPW && j0 + sj < n; ++sj) {
+// the rank of every cell is read once for the PERTURB_SPW rows of a group; a row compares it with its cut
+struct FaithMask {
+  struct Lds {};
+  const int* ranks;
+  int N, per, i0, insertion;
+  __device__ __forceinline__ void stage(Lds&, int, int, int) const {}
+  __device__ __forceinline__ int cell(int b, int idx, int, int) const { return ranks[(size_t)b * N + idx]; }
+  __device__ __forceinline__ bool row(const Lds&, int r, int, int j0, int sj) const {
     const long long cut = (long long)(i0 + j0 + sj) * per;
-    const bool below = (long long)r < (cut < HW ? cut : (long long)HW);
-    const bool from_x = insertion ? below : !below;
-    float v[8];
-#pragma unroll
-    for (int c = 0; c < FAITH_MAX_C; ++c) { v[c] = from_x ? keep[c] : hide[c]; v[4 + c] = 0.f; }
-    st8(out, (((size_t)b * n + j0 + sj) * HW + p) * 8, v);
+    const bool below = (long long)r < (cut < N ? cut : (long long)N);
+    return insertion ? below : !below;
   }
-}
+};
 extern "C" int bx_faith_perturb_spec(const float* x, const int* ranks, const float* baseline, int baseline_kind, void* out, int B, int C, int H,
                                      int W, int Cp, int per, int i0, int n, int insertion, int dtype, bxStream stream) {
   BX_DTYPE_OK(dtype);
   BX_REQUIRE(H > 0 && W > 0, "bx_faith_perturb_spec: bad shape H=%d W=%d", H, W);
-  const int rc = faith_window_ok("bx_faith_perturb_spec", B, (long long)H * W, per, i0, n, baseline_kind);
+  int rc = faith_window_ok("bx_faith_perturb_spec", B, (long long)H * W, per, i0, n, baseline_kind);
   if (rc) return rc;
-  if (C < 1 || C > FAITH_MAX_C) BX_FAIL(BX_EUNSUPPORTED, "bx_faith_perturb_spec: %d channels, supported 1..%d (Cp = 8)", C, FAITH_MAX_C);
-  BX_REQUIRE(Cp == 8, "bx_faith_perturb_spec: Cp = %d, the internal layout of 1..4 channels has 8", Cp);
-  BX_REQUIRE((unsigned long long)B * n * H * W * Cp * bx_esize(dtype) < (1ull << 32) && bx_ceil_div(n, FAITH_SPW) <= 65535 && B <= 65535,
-             "bx_faith_perturb_spec: output beyond 32-bit byte offsets (B*n*H*W = %lld pixels); use fewer rows per call", (long long)B * n * H * W);
+  if ((rc = perturb_layout_ok("bx_faith_perturb_spec", "channels", C, Cp)) != BX_OK) return rc;
+  if ((rc = perturb_rows_ok("bx_faith_perturb_spec", "B", B, n, H, W, Cp, dtype)) != BX_OK) return rc;
   BX_REQUIRE(x && ranks && baseline && out, "bx_faith_perturb_spec: null pointer");
-  const dim3 grid(bx_ceil_div((long long)H * W, 256), bx_ceil_div(n, FAITH_SPW), B);
-  BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_faith_perturb_spec<T>), grid, dim3(256), 0, (hipStream_t)stream, x, ranks, baseline, baseline_kind,
-                                                 (T*)out, H * W, C, per, i0, n, insertion ? 1 : 0));
+  const FaithMask mask = {ranks, H * W, per, i0, insertion ? 1 : 0};
+  BX_DISPATCH_DTYPE(dtype, T, perturb_launch_spec<T>(stream, x, baseline, baseline_kind, out, B, C, H, W, 0, n, mask));
   BX_CHECK_LAUNCH("bx_faith_perturb_spec");
   return BX_OK;
 }
 
-// fp32 [B,1,Chans,T] -> [B*n,1,Chans,T].  A thread owns V consecutive time steps of one electrode (V = 4 with 16-byte accesses when
-// T % 4 == 0, else 1); the cell of element (ch, t) is ch * T + t for an electrode-by-time map and t for a time-column map.
-template <int V>
-__global__ __launch_bounds__(256) void k_faith_perturb_eeg(const float* __restrict__ x, const int* __restrict__ ranks, const float* __restrict__ base,
-                                                           int kind, float* __restrict__ out, int Chans, int T, int map_rows, int per, int i0, int n,
-                                                           int insertion) {
-  const int b = blockIdx.z, j0 = blockIdx.y * FAITH_SPW, CT = Chans * T, N = map_rows * T;
-  const int e = (blockIdx.x * 256 + threadIdx.x) * V;
-  if (e >= CT) return;
-  const int ch = e / T, t = e - ch * T, cell = map_rows == 1 ? t : e;
-  float keep[V], hide[V];
-  int r[V];
-#pragma unroll
-  for (int q = 0; q < V; ++q) {
-    keep[q] = x[(size_t)b * CT + e + q];
-    hide[q] = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)ch : (size_t)b * CT + e + q];
-    r[q] = ranks[(size_t)b * N + cell + q];
-  }
-  for (int sj = 0; sj < FAITH_SPW && j0 + sj < n; ++sj) {
-    const long long cut0 = (long long)(i0 + j0 + sj) * per, cut = cut0 < N ? cut0 : (long long)N;
-    float v[V];
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      const bool below = (long long)r[q] < cut;
-      v[q] = (insertion ? below : !below) ? keep[q] : hide[q];
-    }
-    float* dst = out + ((size_t)b * n + j0 + sj) * CT + e;
-    if (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[V > 1 ? 1 : 0], v[V > 2 ? 2 : 0], v[V > 3 ? 3 : 0]);
-    else dst[0] = v[0];
-  }
-}
+// the cell of element (ch, t) is ch * T + t for an electrode-by-time map and t for a time-column map
 extern "C" int bx_faith_perturb_eeg(const float* x, const int* ranks, int map_rows, const float* baseline, int baseline_kind, float* out, int B,
                                     int Chans, int T, int per, int i0, int n, int insertion, bxStream stream) {
   BX_REQUIRE(Chans > 0 && T > 0 && (map_rows == Chans || map_rows == 1), "bx_faith_perturb_eeg: bad shape Chans=%d T=%d map_rows=%d (Chans or 1)", Chans, T, map_rows);
   BX_REQUIRE((long long)Chans * T < (1ll << 31), "bx_faith_perturb_eeg: Chans * T beyond 32-bit offsets");
-  const int rc = faith_window_ok("bx_faith_perturb_eeg", B, (long long)map_rows * T, per, i0, n, baseline_kind);
+  int rc = faith_window_ok("bx_faith_perturb_eeg", B, (long long)map_rows * T, per, i0, n, baseline_kind);
   if (rc) return rc;
-  BX_REQUIRE((unsigned long long)B * n * Chans * T * 4 < (1ull << 32) && bx_ceil_div(n, FAITH_SPW) <= 65535 && B <= 65535,
-             "bx_faith_perturb_eeg: output beyond 32-bit byte offsets (B*n*Chans*T = %lld values); use fewer rows per call", (long long)B * n * Chans * T);
+  if ((rc = perturb_rows_ok("bx_faith_perturb_eeg", "B", B, n, Chans, T, 0, BX_F32)) != BX_OK) return rc;
   BX_REQUIRE(x && ranks && baseline && out, "bx_faith_perturb_eeg: null pointer");
-  const bool vec = T % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-  const dim3 grid(bx_ceil_div((long long)Chans * T, vec ? 1024 : 256), bx_ceil_div(n, FAITH_SPW), B);
-  if (vec)
-    hipLaunchKernelGGL((k_faith_perturb_eeg<4>), grid, dim3(256), 0, (hipStream_t)stream, x, ranks, baseline, baseline_kind, out, Chans, T, map_rows, per,
-                       i0, n, insertion ? 1 : 0);
-  else
-    hipLaunchKernelGGL((k_faith_perturb_eeg<1>), grid, dim3(256), 0, (hipStream_t)stream, x, ranks, baseline, baseline_kind, out, Chans, T, map_rows, per,
-                       i0, n, insertion ? 1 : 0);
+  const FaithMask mask = {ranks, map_rows * T, per, i0, insertion ? 1 : 0};
+  perturb_launch_eeg(stream, x, baseline, baseline_kind, out, B, Chans, T, map_rows, 0, n, mask);
   BX_CHECK_LAUNCH("bx_faith_perturb_eeg");
   return BX_OK;
 }

@@ -1,12 +1,10 @@
 // LIME for images (lime 0.2.0.1, LimeImageExplainer.explain_instance; reference XAI_Multimodality.py:1658-1670), everything after the
 // segmentation: the fudged colour table, the perturbed batch straight in the model's channels-last layout, the weighted ridge
 // surrogate in fp64 and the per-pixel weight map.  See include/brainxai.h for the contract of each entry point.
-#include "bx_common.h"
+#include "perturb_rows.h"
 
 #define LIME_MAX_S 1024
-#define LIME_MAX_C 4
 #define LIME_MAX_K 32
-#define LIME_SPW 8                     // samples of one image a perturb workgroup writes for its 256 pixels
 
 static int lime_shape_ok(const char* who, int B, int H, int W, int S) {
   BX_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
@@ -15,7 +13,7 @@ static int lime_shape_ok(const char* who, int B, int H, int W, int S) {
   return BX_OK;
 }
 static int lime_channels_ok(const char* who, int C) {
-  if (C < 1 || C > LIME_MAX_C) BX_FAIL(BX_EUNSUPPORTED, "%s: %d channels, supported 1..%d (Cp = 8)", who, C, LIME_MAX_C);
+  if (C < 1 || C > PERTURB_MAX_C) BX_FAIL(BX_EUNSUPPORTED, "%s: %d channels, supported 1..%d (Cp = 8)", who, C, PERTURB_MAX_C);
   return BX_OK;
 }
 
@@ -26,25 +24,25 @@ static int lime_channels_ok(const char* who, int C) {
 #define LIME_SEG_WG 16
 __global__ __launch_bounds__(1024) void k_lime_segment_mean(const unsigned char* __restrict__ img, const int* __restrict__ seg,
                                                             unsigned char* __restrict__ colours, int HW, int C, int S, int nseg) {
-  __shared__ unsigned long long acc[LIME_SEG_WG * (LIME_MAX_C + 1)];
+  __shared__ unsigned long long acc[LIME_SEG_WG * (PERTURB_MAX_C + 1)];
   const int b = blockIdx.y, s0 = blockIdx.x * nseg, tid = threadIdx.x;
   const int mine = S - s0 < nseg ? S - s0 : nseg;
-  if (tid < LIME_SEG_WG * (LIME_MAX_C + 1)) acc[tid] = 0ull;
+  if (tid < LIME_SEG_WG * (PERTURB_MAX_C + 1)) acc[tid] = 0ull;
   __syncthreads();
   const int* sg = seg + (size_t)b * HW;
   const unsigned char* im = img + (size_t)b * HW * C;
   for (int p = tid; p < HW; p += 1024) {
     const int s = sg[p] - s0;
     if ((unsigned)s < (unsigned)mine) {
-      atomicAdd(&acc[s * (LIME_MAX_C + 1) + LIME_MAX_C], 1ull);
-      for (int c = 0; c < C; ++c) atomicAdd(&acc[s * (LIME_MAX_C + 1) + c], (unsigned long long)im[(size_t)p * C + c]);
+      atomicAdd(&acc[s * (PERTURB_MAX_C + 1) + PERTURB_MAX_C], 1ull);
+      for (int c = 0; c < C; ++c) atomicAdd(&acc[s * (PERTURB_MAX_C + 1) + c], (unsigned long long)im[(size_t)p * C + c]);
     }
   }
   __syncthreads();
   if (tid < mine * C) {
     const int s = tid / C, c = tid % C;
-    const unsigned long long n = acc[s * (LIME_MAX_C + 1) + LIME_MAX_C];
-    colours[((size_t)b * S + s0 + s) * C + c] = n ? (unsigned char)((double)acc[s * (LIME_MAX_C + 1) + c] / (double)n) : (unsigned char)0;
+    const unsigned long long n = acc[s * (PERTURB_MAX_C + 1) + PERTURB_MAX_C];
+    colours[((size_t)b * S + s0 + s) * C + c] = n ? (unsigned char)((double)acc[s * (PERTURB_MAX_C + 1) + c] / (double)n) : (unsigned char)0;
   }
 }
 extern "C" int bx_lime_segment_mean(const unsigned char* img, const int* segments, unsigned char* colours, int B, int H, int W, int C,
@@ -63,15 +61,16 @@ extern "C" int bx_lime_segment_mean(const unsigned char* img, const int* segment
 // ---- perturbed batch ---------------------------------------------------------------------------------------------------------------
 // x[(b*n + j), p, :] = scale * (Z[b, n0+j, seg[p]] ? img[b, p, :] : colours[b, seg[p], :]), channels C..7 zero: the expression of
 // k_u8_to_nhwc applied to the perturbed uint8 image, which is never materialised.  One thread per pixel; a workgroup writes its 256
-// pixels for LIME_SPW samples, whose mask rows sit in LDS as bits, so the image and the label map are read once per LIME_SPW
-// samples (from L2) and the output is written once.
+// pixels for PERTURB_SPW samples, whose mask rows sit in LDS as bits, so the image and the label map are read once per PERTURB_SPW
+// samples (from L2) and the output is written once.  The skeleton is perturb_rows.h's, but this kernel reads a uint8 NHWC image, takes
+// its colours from LDS and has no baseline kinds, so it shares that header's host checks, grid and store and keeps its own body.
 template <typename T>
 __global__ __launch_bounds__(256) void k_lime_perturb(const unsigned char* __restrict__ img, const int* __restrict__ seg,
                                                       const unsigned char* __restrict__ colours, const unsigned char* __restrict__ Z,
                                                       T* __restrict__ x, int HW, int C, int S, int N, int n0, int n, float scale) {
-  __shared__ uint32_t bits[LIME_SPW][LIME_MAX_S / 32];
-  __shared__ unsigned char col[LIME_MAX_S * LIME_MAX_C];
-  const int b = blockIdx.z, j0 = blockIdx.y * LIME_SPW, tid = threadIdx.x;
+  __shared__ uint32_t bits[PERTURB_SPW][LIME_MAX_S / 32];
+  __shared__ unsigned char col[LIME_MAX_S * PERTURB_MAX_C];
+  const int b = blockIdx.z, j0 = blockIdx.y * PERTURB_SPW, tid = threadIdx.x;
   {
     const int sj = tid >> 5, w = tid & 31, j = j0 + sj;
     uint32_t m = 0u;
@@ -92,18 +91,18 @@ __global__ __launch_bounds__(256) void k_lime_perturb(const unsigned char* __res
   if (p >= HW) return;
   int s = seg[(size_t)b * HW + p];
   s = (unsigned)s < (unsigned)S ? s : 0;
-  float keep[LIME_MAX_C], hide[LIME_MAX_C];
+  float keep[PERTURB_MAX_C], hide[PERTURB_MAX_C];
 #pragma unroll
-  for (int c = 0; c < LIME_MAX_C; ++c) {
+  for (int c = 0; c < PERTURB_MAX_C; ++c) {
     keep[c] = c < C ? (float)img[((size_t)b * HW + p) * C + c] * scale : 0.f;
     hide[c] = c < C ? (float)col[s * C + c] * scale : 0.f;
   }
-  for (int sj = 0; sj < LIME_SPW && j0 + sj < n; ++sj) {
+  for (int sj = 0; sj < PERTURB_SPW && j0 + sj < n; ++sj) {
     const bool on = (bits[sj][s >> 5] >> (s & 31)) & 1u;
-    float v[8];
+    float v[PERTURB_MAX_C];
 #pragma unroll
-    for (int c = 0; c < LIME_MAX_C; ++c) { v[c] = on ? keep[c] : hide[c]; v[4 + c] = 0.f; }
-    st8(x, (((size_t)b * n + j0 + sj) * HW + p) * 8, v);
+    for (int c = 0; c < PERTURB_MAX_C; ++c) v[c] = on ? keep[c] : hide[c];
+    perturb_store8(x, (size_t)b * n + j0 + sj, HW, p, v);
   }
 }
 extern "C" int bx_lime_perturb(const unsigned char* img, const int* segments, const unsigned char* colours, const unsigned char* Z,
@@ -111,14 +110,12 @@ extern "C" int bx_lime_perturb(const unsigned char* img, const int* segments, co
   BX_DTYPE_OK(dtype);
   int rc = lime_shape_ok("bx_lime_perturb", B, H, W, S);
   if (rc) return rc;
-  if ((rc = lime_channels_ok("bx_lime_perturb", C))) return rc;
-  BX_REQUIRE(Cp == 8, "bx_lime_perturb: Cp = %d, the internal layout of 1..4 channels has 8", Cp);
+  if ((rc = perturb_layout_ok("bx_lime_perturb", "channels", C, Cp)) != BX_OK) return rc;
   BX_REQUIRE(N >= 2, "bx_lime_perturb: num_samples N = %d < 2", N);
   BX_REQUIRE(n0 >= 0 && n > 0 && (long long)n0 + n <= N, "bx_lime_perturb: rows n0 = %d, n = %d outside 0..N = %d", n0, n, N);
-  BX_REQUIRE((unsigned long long)B * n * H * W * Cp * bx_esize(dtype) < (1ull << 32) && bx_ceil_div(n, LIME_SPW) <= 65535 && B <= 65535,
-             "bx_lime_perturb: output beyond 32-bit byte offsets (B*n*H*W = %lld pixels); use fewer rows per call", (long long)B * n * H * W);
+  if ((rc = perturb_rows_ok("bx_lime_perturb", "B", B, n, H, W, Cp, dtype)) != BX_OK) return rc;
   BX_REQUIRE(img && segments && colours && Z && x, "bx_lime_perturb: null pointer");
-  const dim3 grid(bx_ceil_div((long long)H * W, 256), bx_ceil_div(n, LIME_SPW), B);
+  const dim3 grid = perturb_grid((long long)H * W, 256, n, B);
   const float scale = (float)(1.0 / 255.0);
   BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_lime_perturb<T>), grid, dim3(256), 0, (hipStream_t)stream, img, segments, colours, Z,
                                                  (T*)x, H * W, C, S, N, n0, n, scale));

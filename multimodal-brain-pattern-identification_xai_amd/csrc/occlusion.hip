@@ -3,12 +3,10 @@
 // function of its index and six integers, so no mask is ever stored.  The forward passes between perturb and accumulate are the
 // model's own kernels.  See include/brainxai.h for the definition and the contract of each entry point.
 // A row is a selection, not a blend: there is no multiply to contract, so the file needs no flags of its own.
-#include "bx_common.h"
+#include "perturb_rows.h"
 
-#define OCC_MAX_C 4
 #define OCC_MAX_K 32
 #define OCC_MAX_HW ((1 << 20) - 1)     // cells of a map, the limit of bx_rank_desc: the map drops straight into deletion_insertion
-#define OCC_SPW 8                      // windows a perturb workgroup writes for its 256 cells
 
 struct OccGeom {
   int wh, ww, sh, sw, ny, nx;          // window, stride, window positions per axis: n = 1 + ceil((size - w) / s)
@@ -39,34 +37,20 @@ static int occ_rows_ok(const char* who, const OccGeom& g, int B, int kind, int n
 }
 
 // ---- perturbed batches ------------------------------------------------------------------------------------------------------------------
-// x fp32 NCHW -> rows in the internal layout (NHWC, 8 channels, C..7 zero), the expression of k_nchw_to_nhwc applied to the torch.where
-// result, which is never built.  One thread per pixel; x and the baseline are read once per OCC_SPW rows, a row costs two wave-uniform
-// window corners, two compares and one 16-byte (bf16) or two 16-byte (fp32) stores.
-template <typename T>
-__global__ __launch_bounds__(256) void k_occ_perturb_spec(const float* __restrict__ x, const float* __restrict__ base, int kind, T* __restrict__ out,
-                                                          OccGeom g, int HW, int Wm, int C, int n0, int n) {
-  const int b = blockIdx.z, j0 = blockIdx.y * OCC_SPW, p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= HW) return;
-  float keep[OCC_MAX_C], hide[OCC_MAX_C];
-#pragma unroll
-  for (int c = 0; c < OCC_MAX_C; ++c) {
-    const int cc = c < C ? c : 0;                                   // clamped, unconditional loads
-    const float xv = x[((size_t)b * C + cc) * HW + p];
-    const float bv = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)cc : ((size_t)b * C + cc) * HW + p];
-    keep[c] = c < C ? xv : 0.f;
-    hide[c] = c < C ? bv : 0.f;
-  }
-  const int y = p / Wm, xx = p - y * Wm;
-  for (int sj = 0; sj < OCC_SPW && j0 + sj < n; ++sj) {
+// A cell keeps its (y, x); a row costs two wave-uniform window corners and two compares (the kernels are perturb_rows.h's).
+struct OccMask {
+  struct Lds {};
+  struct Cell { int y, x; };
+  OccGeom g;
+  int n0;
+  __device__ __forceinline__ void stage(Lds&, int, int, int) const {}
+  __device__ __forceinline__ Cell cell(int, int, int y, int x) const { return {y, x}; }
+  __device__ __forceinline__ bool row(const Lds&, const Cell& c, int, int j0, int sj) const {
     int y0, x0;
     occ_window(g, n0 + j0 + sj, y0, x0);
-    const bool in = occ_inside(y, y0, g.wh) && occ_inside(xx, x0, g.ww);
-    float v[8];
-#pragma unroll
-    for (int c = 0; c < OCC_MAX_C; ++c) { v[c] = in ? hide[c] : keep[c]; v[4 + c] = 0.f; }
-    st8(out, (((size_t)b * n + j0 + sj) * HW + p) * 8, v);
+    return !(occ_inside(c.y, y0, g.wh) && occ_inside(c.x, x0, g.ww));
   }
-}
+};
 extern "C" int bx_occlusion_perturb_spec(const float* x, const float* baseline, int baseline_kind, void* out, int B, int C, int H, int W, int Cp, int wh,
                                          int ww, int sh, int sw, int n0, int n, int dtype, bxStream stream) {
   BX_DTYPE_OK(dtype);
@@ -74,60 +58,26 @@ extern "C" int bx_occlusion_perturb_spec(const float* x, const float* baseline, 
   int rc = occ_geom_ok("bx_occlusion_perturb_spec", H, W, wh, ww, sh, sw, &g);
   if (rc) return rc;
   if ((rc = occ_rows_ok("bx_occlusion_perturb_spec", g, B, baseline_kind, n0, n)) != BX_OK) return rc;
-  if (C < 1 || C > OCC_MAX_C) BX_FAIL(BX_EUNSUPPORTED, "bx_occlusion_perturb_spec: %d channels, supported 1..%d (Cp = 8)", C, OCC_MAX_C);
-  BX_REQUIRE(Cp == 8, "bx_occlusion_perturb_spec: Cp = %d, the internal layout of 1..4 channels has 8", Cp);
-  BX_REQUIRE((unsigned long long)B * n * H * W * Cp * bx_esize(dtype) < (1ull << 32) && bx_ceil_div(n, OCC_SPW) <= 65535 && B <= 65535,
-             "bx_occlusion_perturb_spec: output beyond 32-bit byte offsets (B*n*H*W = %lld pixels); use fewer rows per call", (long long)B * n * H * W);
+  if ((rc = perturb_layout_ok("bx_occlusion_perturb_spec", "channels", C, Cp)) != BX_OK) return rc;
+  if ((rc = perturb_rows_ok("bx_occlusion_perturb_spec", "B", B, n, H, W, Cp, dtype)) != BX_OK) return rc;
   BX_REQUIRE(x && baseline && out, "bx_occlusion_perturb_spec: null pointer");
-  const dim3 grid(bx_ceil_div((long long)H * W, 256), bx_ceil_div(n, OCC_SPW), B);
-  BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_occ_perturb_spec<T>), grid, dim3(256), 0, (hipStream_t)stream, x, baseline, baseline_kind, (T*)out, g,
-                                                 H * W, W, C, n0, n));
+  const OccMask mask = {g, n0};
+  BX_DISPATCH_DTYPE(dtype, T, perturb_launch_spec<T>(stream, x, baseline, baseline_kind, out, B, C, H, W, 0, n, mask));
   BX_CHECK_LAUNCH("bx_occlusion_perturb_spec");
   return BX_OK;
 }
 
-// fp32 [B,1,Chans,T] -> [B*n,1,Chans,T].  A thread owns V consecutive time steps of one electrode (V = 4 with 16-byte accesses when
-// T % 4 == 0, else 1); the cell of element (ch, t) is (ch, t).
-template <int V>
-__global__ __launch_bounds__(256) void k_occ_perturb_eeg(const float* __restrict__ x, const float* __restrict__ base, int kind, float* __restrict__ out,
-                                                         OccGeom g, int Chans, int T, int n0, int n) {
-  const int b = blockIdx.z, j0 = blockIdx.y * OCC_SPW, CT = Chans * T;
-  const int e = (blockIdx.x * 256 + threadIdx.x) * V;
-  if (e >= CT) return;
-  const int ch = e / T, t = e - ch * T;
-  float keep[V], hide[V];
-#pragma unroll
-  for (int q = 0; q < V; ++q) {
-    keep[q] = x[(size_t)b * CT + e + q];
-    hide[q] = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)ch : (size_t)b * CT + e + q];
-  }
-  for (int sj = 0; sj < OCC_SPW && j0 + sj < n; ++sj) {
-    int y0, x0;
-    occ_window(g, n0 + j0 + sj, y0, x0);
-    const bool in_row = occ_inside(ch, y0, g.wh);
-    float v[V];
-#pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = (in_row && occ_inside(t + q, x0, g.ww)) ? hide[q] : keep[q];
-    float* dst = out + ((size_t)b * n + j0 + sj) * CT + e;
-    if (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[V > 1 ? 1 : 0], v[V > 2 ? 2 : 0], v[V > 3 ? 3 : 0]);
-    else dst[0] = v[0];
-  }
-}
+// the cell of element (ch, t) is (ch, t)
 extern "C" int bx_occlusion_perturb_eeg(const float* x, const float* baseline, int baseline_kind, float* out, int B, int Chans, int T, int wh, int ww,
                                         int sh, int sw, int n0, int n, bxStream stream) {
   OccGeom g;
   int rc = occ_geom_ok("bx_occlusion_perturb_eeg", Chans, T, wh, ww, sh, sw, &g);
   if (rc) return rc;
   if ((rc = occ_rows_ok("bx_occlusion_perturb_eeg", g, B, baseline_kind, n0, n)) != BX_OK) return rc;
-  BX_REQUIRE((unsigned long long)B * n * Chans * T * 4 < (1ull << 32) && bx_ceil_div(n, OCC_SPW) <= 65535 && B <= 65535,
-             "bx_occlusion_perturb_eeg: output beyond 32-bit byte offsets (B*n*Chans*T = %lld values); use fewer rows per call", (long long)B * n * Chans * T);
+  if ((rc = perturb_rows_ok("bx_occlusion_perturb_eeg", "B", B, n, Chans, T, 0, BX_F32)) != BX_OK) return rc;
   BX_REQUIRE(x && baseline && out, "bx_occlusion_perturb_eeg: null pointer");
-  const bool vec = T % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-  const dim3 grid(bx_ceil_div((long long)Chans * T, vec ? 1024 : 256), bx_ceil_div(n, OCC_SPW), B);
-  if (vec)
-    hipLaunchKernelGGL((k_occ_perturb_eeg<4>), grid, dim3(256), 0, (hipStream_t)stream, x, baseline, baseline_kind, out, g, Chans, T, n0, n);
-  else
-    hipLaunchKernelGGL((k_occ_perturb_eeg<1>), grid, dim3(256), 0, (hipStream_t)stream, x, baseline, baseline_kind, out, g, Chans, T, n0, n);
+  const OccMask mask = {g, n0};
+  perturb_launch_eeg(stream, x, baseline, baseline_kind, out, B, Chans, T, Chans, 0, n, mask);
   BX_CHECK_LAUNCH("bx_occlusion_perturb_eeg");
   return BX_OK;
 }

@@ -5,13 +5,11 @@
 // See include/brainxai.h for the definition and the contract of each entry point.
 // Compiled with -ffp-contract=off (build.py): every product and sum below rounds on its own, which is what lets a numpy float32
 // restatement of the mask and of base + m * (x - base) match bit for bit.
-#include "bx_common.h"
+#include "perturb_rows.h"
 
 #define RISE_MAX_G 32                  // grid cells per axis: one row of bits is one 32-bit word
-#define RISE_MAX_C 4
 #define RISE_MAX_K 32
 #define RISE_MAX_HW ((1 << 20) - 1)    // cells of a map, the limit of bx_rank_desc: the map drops straight into deletion_insertion
-#define RISE_SPW 8                     // masks a perturb workgroup writes for its 256 cells
 #define RISE_CHUNK 32                  // masks staged per step of the weighted sum
 #define RISE_TQ 8                      // (sample, class) pairs a thread of the weighted sum accumulates
 
@@ -74,13 +72,13 @@ static int rise_shape_ok(const char* who, int N, int gh, int gw, int Hm, int Wm,
 // ---- the masks themselves ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rise_masks(const unsigned char* __restrict__ bits, const int* __restrict__ shifts, float* __restrict__ out,
                                                     RiseGeom g, int N, int HW, int Wm, int n0, int n) {
-  __shared__ uint32_t rows[RISE_SPW * RISE_MAX_G];
-  const int j0 = blockIdx.y * RISE_SPW, p = blockIdx.x * 256 + threadIdx.x;
-  rise_stage(rows, bits, n0 + j0, RISE_SPW, N, g.gh, g.gw);
+  __shared__ uint32_t rows[PERTURB_SPW * RISE_MAX_G];
+  const int j0 = blockIdx.y * PERTURB_SPW, p = blockIdx.x * 256 + threadIdx.x;
+  rise_stage(rows, bits, n0 + j0, PERTURB_SPW, N, g.gh, g.gw);
   __syncthreads();
   if (p >= HW) return;
   const int y = p / Wm, x = p - y * Wm;
-  for (int sj = 0; sj < RISE_SPW && j0 + sj < n; ++sj) {
+  for (int sj = 0; sj < PERTURB_SPW && j0 + sj < n; ++sj) {
     int dy, dx, y0, y1, x0, x1; float ly, lx;
     rise_shift(shifts, n0 + j0 + sj, g, dy, dx);
     rise_axis(y + dy, g.sy, g.gh, y0, y1, ly);
@@ -92,49 +90,38 @@ extern "C" int bx_rise_masks(const unsigned char* bits, const int* shifts, float
                              bxStream stream) {
   const int rc = rise_shape_ok("bx_rise_masks", N, gh, gw, Hm, Wm, n0, n);
   if (rc) return rc;
-  BX_REQUIRE((long long)n * Hm * Wm < (1ll << 31) && bx_ceil_div(n, RISE_SPW) <= 65535,
+  BX_REQUIRE((long long)n * Hm * Wm < (1ll << 31) && bx_ceil_div(n, PERTURB_SPW) <= 65535,
              "bx_rise_masks: n * Hm * Wm = %lld values beyond 32-bit offsets; use a smaller window", (long long)n * Hm * Wm);
   BX_REQUIRE(bits && shifts && out, "bx_rise_masks: null pointer");
-  const dim3 grid(bx_ceil_div((long long)Hm * Wm, 256), bx_ceil_div(n, RISE_SPW));
+  const dim3 grid(bx_ceil_div((long long)Hm * Wm, 256), bx_ceil_div(n, PERTURB_SPW));
   hipLaunchKernelGGL(k_rise_masks, grid, dim3(256), 0, (hipStream_t)stream, bits, shifts, out, rise_geom(gh, gw, Hm, Wm), N, Hm * Wm, Wm, n0, n);
   BX_CHECK_LAUNCH("bx_rise_masks");
   return BX_OK;
 }
 
 // ---- perturbed batches ------------------------------------------------------------------------------------------------------------------
-// x fp32 NCHW -> rows in the internal layout (NHWC, 8 channels, C..7 zero): base + m * (x - base) per channel, the mask value m shared
-// by the channels of a pixel.  One thread per pixel; x and the baseline are read once per RISE_SPW rows.
-template <typename T>
-__global__ __launch_bounds__(256) void k_rise_perturb_spec(const float* __restrict__ x, const unsigned char* __restrict__ bits, const int* __restrict__ shifts,
-                                                           const float* __restrict__ base, int kind, T* __restrict__ out, RiseGeom g, int N, int HW,
-                                                           int Wm, int C, int n0, int n) {
-  __shared__ uint32_t rows[RISE_SPW * RISE_MAX_G];
-  const int b = blockIdx.z, j0 = blockIdx.y * RISE_SPW, p = blockIdx.x * 256 + threadIdx.x;
-  rise_stage(rows, bits, n0 + j0, RISE_SPW, N, g.gh, g.gw);
-  __syncthreads();
-  if (p >= HW) return;
-  float from[RISE_MAX_C], diff[RISE_MAX_C];
-#pragma unroll
-  for (int c = 0; c < RISE_MAX_C; ++c) {
-    const int cc = c < C ? c : 0;                                   // clamped, unconditional loads
-    const float xv = x[((size_t)b * C + cc) * HW + p];
-    const float bv = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)cc : ((size_t)b * C + cc) * HW + p];
-    from[c] = c < C ? bv : 0.f;
-    diff[c] = c < C ? xv - bv : 0.f;
+// base + m * (x - base), the mask value m shared by the channels of a pixel (the kernels are perturb_rows.h's).  A group's bit rows are
+// staged in LDS; a cell keeps its (y, x) and a row shifts it, finds its source cells and blends.
+struct RiseMask {
+  struct Lds { uint32_t rows[PERTURB_SPW * RISE_MAX_G]; };
+  struct Cell { int y, x; };
+  const unsigned char* bits;
+  const int* shifts;
+  RiseGeom g;
+  int N, n0;
+  __device__ __forceinline__ void stage(Lds& lds, int, int j0, int) const {
+    rise_stage(lds.rows, bits, n0 + j0, PERTURB_SPW, N, g.gh, g.gw);
+    __syncthreads();
   }
-  const int y = p / Wm, xx = p - y * Wm;
-  for (int sj = 0; sj < RISE_SPW && j0 + sj < n; ++sj) {
+  __device__ __forceinline__ Cell cell(int, int, int y, int x) const { return {y, x}; }
+  __device__ __forceinline__ float row(const Lds& lds, const Cell& c, int, int j0, int sj) const {
     int dy, dx, y0, y1, x0, x1; float ly, lx;
     rise_shift(shifts, n0 + j0 + sj, g, dy, dx);
-    rise_axis(y + dy, g.sy, g.gh, y0, y1, ly);
-    rise_axis(xx + dx, g.sx, g.gw, x0, x1, lx);
-    const float m = rise_value(rows + sj * g.gh, y0, y1, ly, x0, x1, lx);
-    float v[8];
-#pragma unroll
-    for (int c = 0; c < RISE_MAX_C; ++c) { v[c] = c < C ? from[c] + m * diff[c] : 0.f; v[4 + c] = 0.f; }
-    st8(out, (((size_t)b * n + j0 + sj) * HW + p) * 8, v);
+    rise_axis(c.y + dy, g.sy, g.gh, y0, y1, ly);
+    rise_axis(c.x + dx, g.sx, g.gw, x0, x1, lx);
+    return rise_value(lds.rows + sj * g.gh, y0, y1, ly, x0, x1, lx);
   }
-}
+};
 static int rise_baseline_ok(const char* who, int B, int kind) {
   BX_REQUIRE(B > 0, "%s: bad shape B=%d", who, B);
   BX_REQUIRE(kind >= 0 && kind <= 2, "%s: baseline_kind %d (0 scalar, 1 per channel, 2 full tensor)", who, kind);
@@ -146,54 +133,16 @@ extern "C" int bx_rise_perturb_spec(const float* x, const unsigned char* bits, c
   int rc = rise_shape_ok("bx_rise_perturb_spec", N, gh, gw, H, W, n0, n);
   if (rc) return rc;
   if ((rc = rise_baseline_ok("bx_rise_perturb_spec", B, baseline_kind)) != BX_OK) return rc;
-  if (C < 1 || C > RISE_MAX_C) BX_FAIL(BX_EUNSUPPORTED, "bx_rise_perturb_spec: %d channels, supported 1..%d (Cp = 8)", C, RISE_MAX_C);
-  BX_REQUIRE(Cp == 8, "bx_rise_perturb_spec: Cp = %d, the internal layout of 1..4 channels has 8", Cp);
-  BX_REQUIRE((unsigned long long)B * n * H * W * Cp * bx_esize(dtype) < (1ull << 32) && bx_ceil_div(n, RISE_SPW) <= 65535 && B <= 65535,
-             "bx_rise_perturb_spec: output beyond 32-bit byte offsets (B*n*H*W = %lld pixels); use fewer rows per call", (long long)B * n * H * W);
+  if ((rc = perturb_layout_ok("bx_rise_perturb_spec", "channels", C, Cp)) != BX_OK) return rc;
+  if ((rc = perturb_rows_ok("bx_rise_perturb_spec", "B", B, n, H, W, Cp, dtype)) != BX_OK) return rc;
   BX_REQUIRE(x && bits && shifts && baseline && out, "bx_rise_perturb_spec: null pointer");
-  const dim3 grid(bx_ceil_div((long long)H * W, 256), bx_ceil_div(n, RISE_SPW), B);
-  BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_rise_perturb_spec<T>), grid, dim3(256), 0, (hipStream_t)stream, x, bits, shifts, baseline, baseline_kind,
-                                                 (T*)out, rise_geom(gh, gw, H, W), N, H * W, W, C, n0, n));
+  const RiseMask mask = {bits, shifts, rise_geom(gh, gw, H, W), N, n0};
+  BX_DISPATCH_DTYPE(dtype, T, perturb_launch_spec<T>(stream, x, baseline, baseline_kind, out, B, C, H, W, 0, n, mask));
   BX_CHECK_LAUNCH("bx_rise_perturb_spec");
   return BX_OK;
 }
 
-// fp32 [B,1,Chans,T] -> [B*n,1,Chans,T].  A thread owns V consecutive time steps of one electrode (V = 4 with 16-byte accesses when
-// T % 4 == 0, else 1); the mask row of element (ch, t) is ch for an electrode-by-time mask and 0 for a time-column mask.
-template <int V>
-__global__ __launch_bounds__(256) void k_rise_perturb_eeg(const float* __restrict__ x, const unsigned char* __restrict__ bits, const int* __restrict__ shifts,
-                                                          const float* __restrict__ base, int kind, float* __restrict__ out, RiseGeom g, int N,
-                                                          int Chans, int T, int map_rows, int n0, int n) {
-  __shared__ uint32_t rows[RISE_SPW * RISE_MAX_G];
-  const int b = blockIdx.z, j0 = blockIdx.y * RISE_SPW, CT = Chans * T;
-  const int e = (blockIdx.x * 256 + threadIdx.x) * V;
-  rise_stage(rows, bits, n0 + j0, RISE_SPW, N, g.gh, g.gw);
-  __syncthreads();
-  if (e >= CT) return;
-  const int ch = e / T, t = e - ch * T, y = map_rows == 1 ? 0 : ch;
-  float from[V], diff[V];
-#pragma unroll
-  for (int q = 0; q < V; ++q) {
-    const float xv = x[(size_t)b * CT + e + q];
-    from[q] = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)ch : (size_t)b * CT + e + q];
-    diff[q] = xv - from[q];
-  }
-  for (int sj = 0; sj < RISE_SPW && j0 + sj < n; ++sj) {
-    int dy, dx, y0, y1; float ly;
-    rise_shift(shifts, n0 + j0 + sj, g, dy, dx);
-    rise_axis(y + dy, g.sy, g.gh, y0, y1, ly);
-    float v[V];
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      int x0, x1; float lx;
-      rise_axis(t + q + dx, g.sx, g.gw, x0, x1, lx);
-      v[q] = from[q] + rise_value(rows + sj * g.gh, y0, y1, ly, x0, x1, lx) * diff[q];
-    }
-    float* dst = out + ((size_t)b * n + j0 + sj) * CT + e;
-    if (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[V > 1 ? 1 : 0], v[V > 2 ? 2 : 0], v[V > 3 ? 3 : 0]);
-    else dst[0] = v[0];
-  }
-}
+// the mask row of element (ch, t) is ch for an electrode-by-time mask and 0 for a time-column mask
 extern "C" int bx_rise_perturb_eeg(const float* x, const unsigned char* bits, const int* shifts, int map_rows, const float* baseline, int baseline_kind,
                                    float* out, int B, int Chans, int T, int N, int gh, int gw, int n0, int n, bxStream stream) {
   BX_REQUIRE(Chans > 0 && T > 0 && (map_rows == Chans || map_rows == 1), "bx_rise_perturb_eeg: bad shape Chans=%d T=%d map_rows=%d (Chans or 1)", Chans, T, map_rows);
@@ -201,18 +150,10 @@ extern "C" int bx_rise_perturb_eeg(const float* x, const unsigned char* bits, co
   int rc = rise_shape_ok("bx_rise_perturb_eeg", N, gh, gw, map_rows, T, n0, n);
   if (rc) return rc;
   if ((rc = rise_baseline_ok("bx_rise_perturb_eeg", B, baseline_kind)) != BX_OK) return rc;
-  BX_REQUIRE((unsigned long long)B * n * Chans * T * 4 < (1ull << 32) && bx_ceil_div(n, RISE_SPW) <= 65535 && B <= 65535,
-             "bx_rise_perturb_eeg: output beyond 32-bit byte offsets (B*n*Chans*T = %lld values); use fewer rows per call", (long long)B * n * Chans * T);
+  if ((rc = perturb_rows_ok("bx_rise_perturb_eeg", "B", B, n, Chans, T, 0, BX_F32)) != BX_OK) return rc;
   BX_REQUIRE(x && bits && shifts && baseline && out, "bx_rise_perturb_eeg: null pointer");
-  const bool vec = T % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-  const dim3 grid(bx_ceil_div((long long)Chans * T, vec ? 1024 : 256), bx_ceil_div(n, RISE_SPW), B);
-  const RiseGeom g = rise_geom(gh, gw, map_rows, T);
-  if (vec)
-    hipLaunchKernelGGL((k_rise_perturb_eeg<4>), grid, dim3(256), 0, (hipStream_t)stream, x, bits, shifts, baseline, baseline_kind, out, g, N, Chans, T,
-                       map_rows, n0, n);
-  else
-    hipLaunchKernelGGL((k_rise_perturb_eeg<1>), grid, dim3(256), 0, (hipStream_t)stream, x, bits, shifts, baseline, baseline_kind, out, g, N, Chans, T,
-                       map_rows, n0, n);
+  const RiseMask mask = {bits, shifts, rise_geom(gh, gw, map_rows, T), N, n0};
+  perturb_launch_eeg(stream, x, baseline, baseline_kind, out, B, Chans, T, map_rows, 0, n, mask);
   BX_CHECK_LAUNCH("bx_rise_perturb_eeg");
   return BX_OK;
 }

@@ -5,14 +5,12 @@
 // See include/brainxai.h for the definition and the contract of each entry point.
 // Compiled with -ffp-contract=off (build.py): every product and sum of the up-sampling, of the mask and of base + m * (x - base)
 // rounds on its own, which is what lets a numpy float32 restatement (tests/scorecam_ref.py) match them bit for bit.
-#include "bx_common.h"
+#include "perturb_rows.h"
 #include <math.h>
 
 #define SC_MAX_K 32
-#define SC_MAX_CIN 4
 #define SC_MAX_HW ((1 << 20) - 1)      // cells of a map, the limit of bx_rank_desc: the map drops straight into deletion_insertion
-#define SC_SPW 8                       // rows (channels of A) a perturb workgroup writes for its 256 pixels
-#define SC_PLANE 1024                  // values of one plane staged by a perturb workgroup (SC_SPW planes: 32 KB)
+#define SC_PLANE 1024                  // values of one plane staged by a perturb workgroup (PERTURB_SPW planes: 32 KB)
 #define SC_PLANE_LD (SC_PLANE + 4)     // LDS stride of a staged plane: 8 planes x 4 positions written by 32 lanes land on 32 banks
 #define SC_RANGE_PLANE 4096            // values of the plane staged by a range workgroup
 #define SC_RANGE_PER 16                // up-sampled values per thread of the range pass: 4096 per workgroup
@@ -130,64 +128,56 @@ extern "C" int bx_scorecam_range(const void* A, int dtype, int sb, int sc, int s
 }
 
 // ---- perturbed batches ------------------------------------------------------------------------------------------------------------------
-// x fp32 NCHW -> rows in the internal layout (NHWC, 8 channels, Cin..7 zero): base + m * (x - base) per channel, the mask value m of
-// channel k of A shared by the input channels of a pixel.  One thread per pixel: x, the baseline and the pixel's two source
-// coordinates are taken once for SC_SPW rows.  The SC_SPW planes of a workgroup are staged in LDS when each holds at most SC_PLANE
-// values (the late stages: 2 x 4 ... 16 x 32); larger planes are as large as the image or half of it, every value is used by one to
-// four pixels, and they are read through the cache.  With channel stride 1 (NHWC) the SC_SPW channels of a position are adjacent
-// in memory and the fill walks them fastest; otherwise it walks the positions of a plane fastest.
-template <typename T, typename TA, bool STAGED>
-__global__ __launch_bounds__(256) void k_sc_perturb_spec(const float* __restrict__ x, const TA* __restrict__ A, ScPlane pl, const float* __restrict__ lo,
-                                                         const float* __restrict__ scale, const float* __restrict__ base, int kind, T* __restrict__ out,
-                                                         int HW, int Wm, int Cin, int b0, int k0, int n) {
-  __shared__ float src[STAGED ? SC_SPW * SC_PLANE_LD : 1];
-  const int bl = blockIdx.z, b = b0 + bl, j0 = blockIdx.y * SC_SPW, p = blockIdx.x * 256 + threadIdx.x;
-  const int abase = b * pl.sb, hw = pl.h * pl.w;
-  if (STAGED) {
-    for (int i = threadIdx.x; i < SC_SPW * hw; i += 256) {
+// base + m * (x - base), the mask value m of channel k of A shared by the input channels of a pixel (the kernels are perturb_rows.h's).
+// A pixel's two source coordinates are taken once for the PERTURB_SPW rows of a group.  The group's planes are staged in LDS when each
+// holds at most SC_PLANE values (the late stages: 2 x 4 ... 16 x 32); larger planes are as large as the image or half of it, every value
+// is used by one to four pixels, and they are read through the cache.  With channel stride 1 (NHWC) the PERTURB_SPW channels of a
+// position are adjacent in memory and the fill walks them fastest; otherwise it walks the positions of a plane fastest.
+template <typename TA, bool STAGED>
+struct ScMask {
+  struct Lds { float src[STAGED ? PERTURB_SPW * SC_PLANE_LD : 1]; };
+  struct Cell { int o00, o01, o10, o11; float ly, lx; };
+  const TA* A;
+  ScPlane pl;
+  const float* lo;
+  const float* scale;
+  int k0;
+  __device__ __forceinline__ void stage(Lds& lds, int b, int j0, int n) const {
+    if (!STAGED) return;
+    const int abase = b * pl.sb, hw = pl.h * pl.w;
+    for (int i = threadIdx.x; i < PERTURB_SPW * hw; i += 256) {
       int j, s;
-      if (pl.sc == 1) { s = i / SC_SPW; j = i - s * SC_SPW; }
+      if (pl.sc == 1) { s = i / PERTURB_SPW; j = i - s * PERTURB_SPW; }
       else { j = i / hw; s = i - j * hw; }
       const int kk = k0 + (j0 + j < n ? j0 + j : n - 1);              // rows past the window repeat its last channel and are not written
       const int y = s / pl.w, xx = s - y * pl.w;
-      src[j * SC_PLANE_LD + s] = ldf(A, (size_t)(abase + kk * pl.sc + y * pl.sy + xx * pl.sx));
+      lds.src[j * SC_PLANE_LD + s] = ldf(A, (size_t)(abase + kk * pl.sc + y * pl.sy + xx * pl.sx));
     }
     __syncthreads();
   }
-  if (p >= HW) return;
-  float from[SC_MAX_CIN], diff[SC_MAX_CIN];
-#pragma unroll
-  for (int c = 0; c < SC_MAX_CIN; ++c) {
-    const int cc = c < Cin ? c : 0;                                   // clamped, unconditional loads
-    const float xv = x[((size_t)b * Cin + cc) * HW + p];
-    const float bv = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)cc : ((size_t)b * Cin + cc) * HW + p];
-    from[c] = c < Cin ? bv : 0.f;
-    diff[c] = c < Cin ? xv - bv : 0.f;
+  __device__ __forceinline__ Cell cell(int, int, int oy, int ox) const {
+    Cell c;
+    int y0, y1, x0, x1;
+    bilinear_src(oy, pl.ry, pl.h, y0, y1, c.ly);
+    bilinear_src(ox, pl.rx, pl.w, x0, x1, c.lx);
+    c.o00 = STAGED ? y0 * pl.w + x0 : y0 * pl.sy + x0 * pl.sx; c.o01 = STAGED ? y0 * pl.w + x1 : y0 * pl.sy + x1 * pl.sx;
+    c.o10 = STAGED ? y1 * pl.w + x0 : y1 * pl.sy + x0 * pl.sx; c.o11 = STAGED ? y1 * pl.w + x1 : y1 * pl.sy + x1 * pl.sx;
+    return c;
   }
-  const int oy = p / Wm, ox = p - oy * Wm;
-  int y0, y1, x0, x1; float ly, lx;
-  bilinear_src(oy, pl.ry, pl.h, y0, y1, ly);
-  bilinear_src(ox, pl.rx, pl.w, x0, x1, lx);
-  const int o00 = STAGED ? y0 * pl.w + x0 : y0 * pl.sy + x0 * pl.sx, o01 = STAGED ? y0 * pl.w + x1 : y0 * pl.sy + x1 * pl.sx;
-  const int o10 = STAGED ? y1 * pl.w + x0 : y1 * pl.sy + x0 * pl.sx, o11 = STAGED ? y1 * pl.w + x1 : y1 * pl.sy + x1 * pl.sx;
-  for (int sj = 0; sj < SC_SPW && j0 + sj < n; ++sj) {
+  __device__ __forceinline__ float row(const Lds& lds, const Cell& c, int b, int j0, int sj) const {
     const int kk = k0 + j0 + sj;
     const float l = lo[(size_t)b * pl.C + kk], sc = scale[(size_t)b * pl.C + kk];      // wave-uniform
     float a00, a01, a10, a11;
     if (STAGED) {
-      const float* s = src + sj * SC_PLANE_LD;
-      a00 = s[o00]; a01 = s[o01]; a10 = s[o10]; a11 = s[o11];
+      const float* s = lds.src + sj * SC_PLANE_LD;
+      a00 = s[c.o00]; a01 = s[c.o01]; a10 = s[c.o10]; a11 = s[c.o11];
     } else {
-      const size_t kb = (size_t)(abase + kk * pl.sc);
-      a00 = ldf(A, kb + o00); a01 = ldf(A, kb + o01); a10 = ldf(A, kb + o10); a11 = ldf(A, kb + o11);
+      const size_t kb = (size_t)(b * pl.sb + kk * pl.sc);
+      a00 = ldf(A, kb + c.o00); a01 = ldf(A, kb + c.o01); a10 = ldf(A, kb + c.o10); a11 = ldf(A, kb + c.o11);
     }
-    const float m = fminf((sc_blend(a00, a01, a10, a11, ly, lx) - l) * sc, 1.f);
-    float v[8];
-#pragma unroll
-    for (int c = 0; c < SC_MAX_CIN; ++c) { v[c] = c < Cin ? from[c] + m * diff[c] : 0.f; v[4 + c] = 0.f; }
-    st8(out, (((size_t)bl * n + j0 + sj) * HW + p) * 8, v);
+    return fminf((sc_blend(a00, a01, a10, a11, c.ly, c.lx) - l) * sc, 1.f);
   }
-}
+};
 static int sc_window_ok(const char* who, int B, int C, int b0, int nb, int k0, int n, int kind) {
   BX_REQUIRE(b0 >= 0 && nb >= 1 && (long long)b0 + nb <= B, "%s: samples b0 = %d, nb = %d outside 0..B = %d", who, b0, nb, B);
   BX_REQUIRE(k0 >= 0 && n >= 1 && (long long)k0 + n <= C, "%s: channels k0 = %d, n = %d outside 0..C = %d", who, k0, n, C);
@@ -202,65 +192,48 @@ extern "C" int bx_scorecam_perturb_spec(const float* x, const void* A, int dtype
   int rc = sc_plane_ok("bx_scorecam_perturb_spec", A, dtype_a, sb, sc, sy, sx, B, C, h, w, H, W, &pl);
   if (rc) return rc;
   if ((rc = sc_window_ok("bx_scorecam_perturb_spec", B, C, b0, nb, k0, n, baseline_kind)) != BX_OK) return rc;
-  if (Cin < 1 || Cin > SC_MAX_CIN) BX_FAIL(BX_EUNSUPPORTED, "bx_scorecam_perturb_spec: %d input channels, supported 1..%d (Cp = 8)", Cin, SC_MAX_CIN);
-  BX_REQUIRE(Cp == 8, "bx_scorecam_perturb_spec: Cp = %d, the internal layout of 1..4 channels has 8", Cp);
+  if ((rc = perturb_layout_ok("bx_scorecam_perturb_spec", "input channels", Cin, Cp)) != BX_OK) return rc;
   BX_REQUIRE((long long)B * Cin * H * W < (1ll << 31), "bx_scorecam_perturb_spec: input beyond 32-bit offsets");
-  BX_REQUIRE((unsigned long long)nb * n * H * W * Cp * bx_esize(dtype) < (1ull << 32) && bx_ceil_div(n, SC_SPW) <= 65535 && nb <= 65535,
-             "bx_scorecam_perturb_spec: output beyond 32-bit byte offsets (nb*n*H*W = %lld pixels); use fewer rows per call", (long long)nb * n * H * W);
+  if ((rc = perturb_rows_ok("bx_scorecam_perturb_spec", "nb", nb, n, H, W, Cp, dtype)) != BX_OK) return rc;
   BX_REQUIRE(x && A && lo && scale && baseline && out, "bx_scorecam_perturb_spec: null pointer");
-  const dim3 grid(bx_ceil_div((long long)H * W, 256), bx_ceil_div(n, SC_SPW), nb);
   const bool staged = h * w <= SC_PLANE;
   BX_DISPATCH_DTYPE(dtype, T, BX_DISPATCH_DTYPE(dtype_a, TA, {
-    if (staged)
-      hipLaunchKernelGGL((k_sc_perturb_spec<T, TA, true>), grid, dim3(256), 0, (hipStream_t)stream, x, (const TA*)A, pl, lo, scale, baseline, baseline_kind,
-                         (T*)out, H * W, W, Cin, b0, k0, n);
-    else
-      hipLaunchKernelGGL((k_sc_perturb_spec<T, TA, false>), grid, dim3(256), 0, (hipStream_t)stream, x, (const TA*)A, pl, lo, scale, baseline, baseline_kind,
-                         (T*)out, H * W, W, Cin, b0, k0, n);
+    if (staged) perturb_launch_spec<T>(stream, x, baseline, baseline_kind, out, nb, Cin, H, W, b0, n, ScMask<TA, true>{(const TA*)A, pl, lo, scale, k0});
+    else perturb_launch_spec<T>(stream, x, baseline, baseline_kind, out, nb, Cin, H, W, b0, n, ScMask<TA, false>{(const TA*)A, pl, lo, scale, k0});
   }));
   BX_CHECK_LAUNCH("bx_scorecam_perturb_spec");
   return BX_OK;
 }
 
-// fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T].  A thread owns V consecutive time steps of one electrode (V = 4 with 16-byte accesses when
-// T % 4 == 0, else 1); the plane is one row of w values (h = 1) and the mask value of column t serves every electrode.  A row of
-// T or T/4 values is read where it is needed: consecutive lanes read consecutive values, and the Chans threads of a column share them
-// through the cache.  The vertical blend of the definition is kept although both of its rows are the plane's only row.
-template <int V, typename TA>
-__global__ __launch_bounds__(256) void k_sc_perturb_eeg(const float* __restrict__ x, const TA* __restrict__ A, ScPlane pl, const float* __restrict__ lo,
-                                                        const float* __restrict__ scale, const float* __restrict__ base, int kind, float* __restrict__ out,
-                                                        int Chans, int T, int b0, int k0, int n) {
-  const int bl = blockIdx.z, b = b0 + bl, j0 = blockIdx.y * SC_SPW, CT = Chans * T;
-  const int e = (blockIdx.x * 256 + threadIdx.x) * V;
-  if (e >= CT) return;
-  const int ch = e / T, t = e - ch * T;
-  float from[V], diff[V], lx[V], ly;
-  int o0[V], o1[V], y0, y1;
-  bilinear_src(0, pl.ry, 1, y0, y1, ly);
-#pragma unroll
-  for (int q = 0; q < V; ++q) {
-    const float xv = x[(size_t)b * CT + e + q];
-    from[q] = base[kind == 0 ? (size_t)0 : kind == 1 ? (size_t)ch : (size_t)b * CT + e + q];
-    diff[q] = xv - from[q];
-    int x0, x1;
-    bilinear_src(t + q, pl.rx, pl.w, x0, x1, lx[q]);
-    o0[q] = x0 * pl.sx; o1[q] = x1 * pl.sx;
+// EEG: the plane is one row of w values (h = 1) and the mask value of column t serves every electrode.  A row of T or T/4 values is
+// read where it is needed: consecutive lanes read consecutive values, and the Chans threads of a column share them through the cache.
+// The vertical blend of the definition is kept although both of its rows are the plane's only row.
+template <typename TA>
+struct ScMaskEeg {
+  struct Lds {};
+  struct Cell { int o0, o1; float ly, lx; };
+  const TA* A;
+  ScPlane pl;
+  const float* lo;
+  const float* scale;
+  int k0;
+  __device__ __forceinline__ void stage(Lds&, int, int, int) const {}
+  __device__ __forceinline__ Cell cell(int, int, int, int t) const {
+    Cell c;
+    int y0, y1, x0, x1;
+    bilinear_src(0, pl.ry, 1, y0, y1, c.ly);
+    bilinear_src(t, pl.rx, pl.w, x0, x1, c.lx);
+    c.o0 = x0 * pl.sx; c.o1 = x1 * pl.sx;
+    return c;
   }
-  for (int sj = 0; sj < SC_SPW && j0 + sj < n; ++sj) {
+  __device__ __forceinline__ float row(const Lds&, const Cell& c, int b, int j0, int sj) const {
     const int kk = k0 + j0 + sj;
     const float l = lo[(size_t)b * pl.C + kk], sc = scale[(size_t)b * pl.C + kk];      // wave-uniform
     const size_t kb = (size_t)(b * pl.sb + kk * pl.sc);
-    float v[V];
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      const float a0 = ldf(A, kb + o0[q]), a1 = ldf(A, kb + o1[q]);
-      v[q] = from[q] + fminf((sc_blend(a0, a1, a0, a1, ly, lx[q]) - l) * sc, 1.f) * diff[q];
-    }
-    float* dst = out + ((size_t)bl * n + j0 + sj) * CT + e;
-    if (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[V > 1 ? 1 : 0], v[V > 2 ? 2 : 0], v[V > 3 ? 3 : 0]);
-    else dst[0] = v[0];
+    const float a0 = ldf(A, kb + c.o0), a1 = ldf(A, kb + c.o1);
+    return fminf((sc_blend(a0, a1, a0, a1, c.ly, c.lx) - l) * sc, 1.f);
   }
-}
+};
 extern "C" int bx_scorecam_perturb_eeg(const float* x, const void* A, int dtype_a, int sb, int sc, int sx, int C, int w, const float* lo,
                                        const float* scale, const float* baseline, int baseline_kind, float* out, int B, int Chans, int T, int b0,
                                        int nb, int k0, int n, bxStream stream) {
@@ -269,19 +242,10 @@ extern "C" int bx_scorecam_perturb_eeg(const float* x, const void* A, int dtype_
   int rc = sc_plane_ok("bx_scorecam_perturb_eeg", A, dtype_a, sb, sc, 0, sx, B, C, 1, w, 1, T, &pl);
   if (rc) return rc;
   if ((rc = sc_window_ok("bx_scorecam_perturb_eeg", B, C, b0, nb, k0, n, baseline_kind)) != BX_OK) return rc;
-  BX_REQUIRE((unsigned long long)nb * n * Chans * T * 4 < (1ull << 32) && bx_ceil_div(n, SC_SPW) <= 65535 && nb <= 65535,
-             "bx_scorecam_perturb_eeg: output beyond 32-bit byte offsets (nb*n*Chans*T = %lld values); use fewer rows per call", (long long)nb * n * Chans * T);
+  if ((rc = perturb_rows_ok("bx_scorecam_perturb_eeg", "nb", nb, n, Chans, T, 0, BX_F32)) != BX_OK) return rc;
   BX_REQUIRE(x && A && lo && scale && baseline && out, "bx_scorecam_perturb_eeg: null pointer");
-  const bool vec = T % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-  const dim3 grid(bx_ceil_div((long long)Chans * T, vec ? 1024 : 256), bx_ceil_div(n, SC_SPW), nb);
-  BX_DISPATCH_DTYPE(dtype_a, TA, {
-    if (vec)
-      hipLaunchKernelGGL((k_sc_perturb_eeg<4, TA>), grid, dim3(256), 0, (hipStream_t)stream, x, (const TA*)A, pl, lo, scale, baseline, baseline_kind, out,
-                         Chans, T, b0, k0, n);
-    else
-      hipLaunchKernelGGL((k_sc_perturb_eeg<1, TA>), grid, dim3(256), 0, (hipStream_t)stream, x, (const TA*)A, pl, lo, scale, baseline, baseline_kind, out,
-                         Chans, T, b0, k0, n);
-  });
+  BX_DISPATCH_DTYPE(dtype_a, TA, perturb_launch_eeg(stream, x, baseline, baseline_kind, out, nb, Chans, T, 1, b0, n,
+                                                    ScMaskEeg<TA>{(const TA*)A, pl, lo, scale, k0}));
   BX_CHECK_LAUNCH("bx_scorecam_perturb_eeg");
   return BX_OK;
 }

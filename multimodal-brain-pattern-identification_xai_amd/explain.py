@@ -1000,22 +1000,128 @@ def _faith_perturb(x, ranks, base, kind, b0, nb, i0, n, per, insertion, dt, map_
     return out
 
 
-def _faith_baseline(baseline, x, per_len, what):
+def _baseline_for(who, baseline, x, per_len, what):
     """-> (kind, fp32 host or device tensor): 0 one value, 1 one per channel / electrode, 2 a tensor of the input's shape."""
     if isinstance(baseline, numbers.Real) and not isinstance(baseline, bool):
         return 0, torch.tensor([float(baseline)], dtype=torch.float32)
     try:
         t = baseline.detach() if isinstance(baseline, torch.Tensor) else torch.as_tensor(np.asarray(baseline, dtype=np.float32))
     except (TypeError, ValueError) as exc:
-        raise ValueError(f"deletion_insertion: baseline is neither a number, a sequence nor a tensor ({exc})") from None
+        raise ValueError(f"{who}: baseline is neither a number, a sequence nor a tensor ({exc})") from None
     if t.dim() == 0:
         return 0, t.reshape(1)
     if t.dim() == 1 and t.shape[0] == per_len:
         return 1, t
     if tuple(t.shape) == tuple(x.shape) or (x.shape[1] == 1 and tuple(t.shape) == (x.shape[0],) + tuple(x.shape[2:])):
         return 2, t
-    raise ValueError(f"deletion_insertion: baseline of shape {tuple(t.shape)} is none of: a number, one value per {what} [{per_len}], "
+    raise ValueError(f"{who}: baseline of shape {tuple(t.shape)} is none of: a number, one value per {what} [{per_len}], "
                      f"a tensor of the input's shape {tuple(x.shape)}")
+
+
+def _faith_baseline(baseline, x, per_len, what):
+    return _baseline_for("deletion_insertion", baseline, x, per_len, what)
+
+
+# ---- what the perturb-and-predict drivers (deletion_insertion, rise, occlusion, score_cam) share: straight-line pieces, each driver
+# keeps its own order of checks and its own loop ----
+@contextlib.contextmanager
+def _lap(profile, name):
+    """Device events around a phase, appended to ``profile`` as (name, start, end); nothing when profile is None."""
+    if profile is None:
+        yield
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    yield
+    e1.record()
+    profile.append((name, e0, e1))
+
+
+def _input_tensor(who, input, eeg, spec):
+    """The tensor the rows are made of, [B,C,H,W] for input='spec' and [B,1,Chans,T] for 'eeg'."""
+    x = spec if input == "spec" else eeg
+    if x is None:
+        raise ValueError(f"{who}: input={input!r} but that tensor is None")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
+        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
+    return x
+
+
+def _target_model(who, model, x, other, input_is_spec):
+    """-> (multimodal, K, net): whether ``model`` has both branches (``other`` is then the input of the branch that does not read x),
+    its class count, and the branch that reads x.  score_cam words the two stand-alone refusals by target, the others by input."""
+    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
+    if multimodal:
+        if not isinstance(other, torch.Tensor) or other.shape[0] != x.shape[0]:
+            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
+        return True, int(model.fc2.out_features), model.spectrogram_model if input_is_spec else model.eeg_model
+    what = f"input={'spec' if input_is_spec else 'eeg'!r}"
+    if who == "score_cam":
+        what = "a spectrogram target" if input_is_spec else "an EEG target"
+    if input_is_spec:
+        if not (hasattr(model, "block1") and hasattr(model, "fc")):
+            raise ValueError(f"{who}: {what} needs a MultimodalModel or a Spectrogram_Model")
+        return False, int(model.fc.out_features), model
+    if not hasattr(model, "depthwiseConv"):
+        raise ValueError(f"{who}: {what} needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
+    return False, int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features), model
+
+
+def _explained_classes(who, class_idx, B, K, allow_all):
+    """-> (cls_h, all_classes): one class per sample as a host list (None: the arg-max of the clean input, or every class)."""
+    use, must = ("None, an int, one class per sample or 'all'", "None, an int, 'all' or") if allow_all else ("None, an int or one class per sample", "None, an int or")
+    if class_idx is None:
+        return None, False
+    if isinstance(class_idx, str):
+        if not (allow_all and class_idx == "all"):
+            raise ValueError(f"{who}: class_idx {class_idx!r}; use {use}")
+        return None, True
+    if isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
+        cls_h = [int(class_idx)] * B
+    else:
+        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
+        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
+            raise ValueError(f"{who}: class_idx must be {must} {B} integers (one class per sample)")
+        cls_h = [int(c) for c in cls_t.tolist()]
+    if any(not 0 <= c < K for c in cls_h):
+        raise ValueError(f"{who}: class outside [0, {K})")
+    return cls_h, False
+
+
+def _row_cap(x, input, dt, max_batch):
+    """Rows per forward pass: max_batch, capped so that a pass addresses its largest activation with 32-bit byte offsets -- stage 1's
+    H x W x 16 channels in dt for a spectrogram [B,C,H,W], EEGNet's F1 x Chans x T in fp32 for an EEG input [B,1,Chans,T]."""
+    cells = int(x.shape[2]) * int(x.shape[3])
+    row_bytes = cells * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * cells * 4
+    return max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+
+
+def _fixed_branch(model, other, input_is_spec):
+    """The output of the branch whose input does not change, fp32 [B, features]: once per sample."""
+    o = other.detach().to(torch.float32).contiguous()
+    return (model.eeg_model(o) if input_is_spec else model.spectrogram_model(o)).float().contiguous()
+
+
+def _fuse(model, multimodal, input_is_spec, out, rep):
+    """Log-probabilities of the whole model from the perturbed branch's output and the other branch's output ``rep``, row for row."""
+    if not multimodal:
+        return out
+    e, s = (rep, out) if input_is_spec else (out, rep)
+    return ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
+
+
+def _rows_forward(model, net, multimodal, input_is_spec, rows, rep):
+    """fp32 log-probabilities [rows, K] of a batch in the model's layout (spectrogram rows are the internal NHWC layout: the branch gets
+    a logical-NCHW view, no further copy)."""
+    out = net(rows.permute(0, 3, 1, 2) if input_is_spec else rows)
+    return _fuse(model, multimodal, input_is_spec, out, rep).float().contiguous()
+
+
+def _softmax_rows(logp):
+    """fp32 probabilities of fp32 log-probabilities [rows, K] (bx_softmax_rows)."""
+    probs = torch.empty_like(logp)
+    L.check(L.load().bx_softmax_rows(_p(logp), _p(probs), logp.shape[0], logp.shape[1], _stream()), "bx_softmax_rows")
+    return probs
 
 
 def deletion_insertion(model, eeg, spec, attribution, *, input="spec", mode="both", steps=32, baseline=0.0, class_idx=None, score="prob",
@@ -1060,11 +1166,7 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
     steps, max_batch = int(steps), int(max_batch)
     if max_batch < 1:
         raise ValueError(f"{who}: max_batch = {max_batch} < 1")
-    x = spec if input == "spec" else eeg
-    if x is None:
-        raise ValueError(f"{who}: input={input!r} but that tensor is None")
-    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
-        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
+    x = _input_tensor(who, input, eeg, spec)
     if not isinstance(attribution, torch.Tensor):
         raise ValueError(f"{who}: attribution must be a tensor")
     B = int(x.shape[0])
@@ -1089,85 +1191,39 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
         raise ValueError(f"{who}: {N} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     if not 1 <= steps <= N:
         raise ValueError(f"{who}: steps = {steps} outside 1..N = {N}")
-    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
-    if multimodal:
-        other = eeg if input == "spec" else spec
-        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
-            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
-        K = int(model.fc2.out_features)
-    elif input == "spec":
-        if not (hasattr(model, "block1") and hasattr(model, "fc")):
-            raise ValueError(f"{who}: input='spec' needs a MultimodalModel or a Spectrogram_Model")
-        K = int(model.fc.out_features)
-    else:
-        if not hasattr(model, "depthwiseConv"):
-            raise ValueError(f"{who}: input='eeg' needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
-        K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
-    if class_idx is None:
-        cls_h = None
-    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
-        cls_h = [int(class_idx)] * B
-    elif isinstance(class_idx, str):
-        raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int or one class per sample")
-    else:
-        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
-        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
-            raise ValueError(f"{who}: class_idx must be None, an int or {B} integers (one class per sample)")
-        cls_h = [int(c) for c in cls_t.tolist()]
-    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
-        raise ValueError(f"{who}: class outside [0, {K})")
-    kind, base = _faith_baseline(baseline, x, per_len, what)
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
+    cls_h, _ = _explained_classes(who, class_idx, B, K, allow_all=False)
+    kind, base = _baseline_for(who, baseline, x, per_len, what)
     if not (x.is_cuda and attribution.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
         raise RuntimeError(f"brainxai.{who}: the model, its inputs and the attribution must live on the GPU; there is no CPU path")
 
     lib = L.load()
     dev = x.device
     P, per = steps + 1, -(-N // steps)
-    spec_net = model.spectrogram_model if multimodal else model
-    dt = getattr(spec_net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
-    # a pass addresses its largest activation with 32-bit byte offsets: stage 1's H x W x 16 channels, EEGNet's F1 x Chans x T
-    row_bytes = H * W * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * Chans * T * 4
-    max_rows = max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
-
-    @contextlib.contextmanager
-    def lap(name):
-        if profile is None:
-            yield
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        yield
-        e1.record()
-        profile.append((name, e0, e1))
+    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
+    max_rows = _row_cap(x, input, dt, max_batch)
 
     with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
         xs = x.detach().to(torch.float32).contiguous()
         base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
-        with lap("rank"):
+        with _lap(profile, "rank"):
             ranks = attribution_ranks(attribution)
         fixed = None
-        if multimodal:                                              # the branch whose input does not change: once per sample
-            with lap("forward"):
-                o = other.detach().to(torch.float32).contiguous()
-                fixed = (model.eeg_model(o) if input == "spec" else model.spectrogram_model(o)).float().contiguous()
+        if multimodal:
+            with _lap(profile, "forward"):
+                fixed = _fixed_branch(model, other, input == "spec")
         logps = {}
         for m in ("deletion", "insertion"):
             if mode not in ("both", m):
                 continue
             logp = torch.empty(B, P, K, dtype=torch.float32, device=dev)
             for b0, nb, i0, n in _faith_chunks(B, P, max_rows):
-                with lap("perturb"):
+                with _lap(profile, "perturb"):
                     rows = _faith_perturb(xs, ranks, base, kind, b0, nb, i0, n, per, m == "insertion", dt, map_rows)
-                with lap("forward"):
-                    if input == "spec":
-                        out = spec_net(rows.permute(0, 3, 1, 2))     # a logical-NCHW view of the internal layout: no further copy
-                    else:
-                        out = (model.eeg_model if multimodal else model)(rows)
-                    if multimodal:
-                        rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0)
-                        e, s = (rep, out) if input == "spec" else (out, rep)
-                        out = ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
-                    logp[b0:b0 + nb, i0:i0 + n] = out.float().reshape(nb, n, K)
+                with _lap(profile, "forward"):
+                    rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0) if multimodal else None
+                    logp[b0:b0 + nb, i0:i0 + n] = _rows_forward(model, net, multimodal, input == "spec", rows, rep).reshape(nb, n, K)
             logps[m] = logp
         unperturbed = logps["deletion"][:, 0] if "deletion" in logps else logps["insertion"][:, P - 1]
         if cls_h is None:
@@ -1175,7 +1231,7 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
         else:
             classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
         res = {}
-        with lap("curve"):
+        with _lap(profile, "curve"):
             for m, logp in logps.items():
                 curve = torch.empty(B, P, dtype=torch.float32, device=dev)
                 auc = torch.empty(B, dtype=torch.float64, device=dev)
@@ -1197,14 +1253,6 @@ RiseResult = collections.namedtuple("RiseResult", "saliency classes probs covera
 RiseResult.__doc__ = """What ``rise(..., return_parts=True)`` returns: ``saliency`` fp32 [B,Hm,Wm] or [B,K,Hm,Wm], ``classes`` int64 [B] (None for
 class_idx='all'), ``probs`` fp32 [B,N,K] (the class probabilities of every masked input), ``coverage`` fp32 [Hm,Wm] = the sum of the
 masks, all on the device; ``bits`` uint8 [N,gh,gw] and ``shifts`` int32 [N,2] = (dy, dx) on the host: ``masks=(bits, shifts)`` repeats the call."""
-
-
-def _row_cap(x, input, dt, max_batch):
-    """Rows per forward pass: max_batch, capped so that a pass addresses its largest activation with 32-bit byte offsets -- stage 1's
-    H x W x 16 channels in dt for a spectrogram [B,C,H,W], EEGNet's F1 x Chans x T in fp32 for an EEG input [B,1,Chans,T]."""
-    cells = int(x.shape[2]) * int(x.shape[3])
-    row_bytes = cells * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * cells * 4
-    return max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
 
 
 def _rise_geometry(who, grid, Hm, Wm):
@@ -1349,11 +1397,7 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     max_batch = int(max_batch)
     if max_batch < 1:
         raise ValueError(f"{who}: max_batch = {max_batch} < 1")
-    x = spec if input == "spec" else eeg
-    if x is None:
-        raise ValueError(f"{who}: input={input!r} but that tensor is None")
-    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
-        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
+    x = _input_tensor(who, input, eeg, spec)
     B = int(x.shape[0])
     if input == "spec":
         Cc, H, W = (int(v) for v in x.shape[1:])
@@ -1367,42 +1411,12 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     geom = _rise_geometry(who, grid, Hm, Wm)
-    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
-    if multimodal:
-        other = eeg if input == "spec" else spec
-        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
-            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
-        K = int(model.fc2.out_features)
-    elif input == "spec":
-        if not (hasattr(model, "block1") and hasattr(model, "fc")):
-            raise ValueError(f"{who}: input='spec' needs a MultimodalModel or a Spectrogram_Model")
-        K = int(model.fc.out_features)
-    else:
-        if not hasattr(model, "depthwiseConv"):
-            raise ValueError(f"{who}: input='eeg' needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
-        K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
     if K > _RISE_MAX_K:
         raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    all_classes = isinstance(class_idx, str)
-    if class_idx is None:
-        cls_h = None
-    elif all_classes:
-        if class_idx != "all":
-            raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int, one class per sample or 'all'")
-        cls_h = None
-    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
-        cls_h = [int(class_idx)] * B
-    else:
-        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
-        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
-            raise ValueError(f"{who}: class_idx must be None, an int, 'all' or {B} integers (one class per sample)")
-        cls_h = [int(c) for c in cls_t.tolist()]
-    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
-        raise ValueError(f"{who}: class outside [0, {K})")
-    try:
-        kind, base = _faith_baseline(baseline, x, per_len, what)
-    except ValueError as exc:
-        raise ValueError(str(exc).replace("deletion_insertion", who, 1)) from None
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    kind, base = _baseline_for(who, baseline, x, per_len, what)
     bits, shifts = _rise_mask_set(who, num_masks, geom, p1, seed, masks)
     N = int(bits.shape[0])
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
@@ -1412,30 +1426,17 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
 
     lib = L.load()
     dev = x.device
-    spec_net = model.spectrogram_model if multimodal else model
-    dt = getattr(spec_net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
+    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
     max_rows = _row_cap(x, input, dt, max_batch)
-
-    @contextlib.contextmanager
-    def lap(name):
-        if profile is None:
-            yield
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        yield
-        e1.record()
-        profile.append((name, e0, e1))
 
     with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
         xs = x.detach().to(torch.float32).contiguous()
         base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
         bits_d, shifts_d = torch.from_numpy(bits).to(dev), torch.from_numpy(shifts).to(dev)
         fixed = None
-        with lap("forward"):
-            if multimodal:                                          # the branch whose input does not change: once per sample
-                o = other.detach().to(torch.float32).contiguous()
-                fixed = (model.eeg_model(o) if input == "spec" else model.spectrogram_model(o)).float().contiguous()
+        with _lap(profile, "forward"):
+            if multimodal:
+                fixed = _fixed_branch(model, other, input == "spec")
             if cls_h is None and not all_classes:                   # the explained class: the arg-max on the unmasked input
                 clean = model(eeg, spec) if multimodal else model(xs)
                 classes = clean.float().argmax(dim=1).to(torch.int32).contiguous()
@@ -1445,22 +1446,12 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
             classes = None
         P = torch.empty(B, N, K, dtype=torch.float32, device=dev)
         for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
-            with lap("perturb"):
+            with _lap(profile, "perturb"):
                 rows = _rise_perturb(xs, bits_d, shifts_d, geom, base, kind, b0, nb, n0, n, dt, map_rows)
-            with lap("forward"):
-                if input == "spec":
-                    out = spec_net(rows.permute(0, 3, 1, 2))         # a logical-NCHW view of the internal layout: no further copy
-                else:
-                    out = (model.eeg_model if multimodal else model)(rows)
-                if multimodal:
-                    rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0)
-                    e, s = (rep, out) if input == "spec" else (out, rep)
-                    out = ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
-                logp = out.float().contiguous()
-                probs = torch.empty_like(logp)
-                L.check(lib.bx_softmax_rows(_p(logp), _p(probs), nb * n, K, _stream()), "bx_softmax_rows")
-                P[b0:b0 + nb, n0:n0 + n] = probs.reshape(nb, n, K)
-        with lap("accumulate"):
+            with _lap(profile, "forward"):
+                rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0) if multimodal else None
+                P[b0:b0 + nb, n0:n0 + n] = _softmax_rows(_rows_forward(model, net, multimodal, input == "spec", rows, rep)).reshape(nb, n, K)
+        with _lap(profile, "accumulate"):
             sal = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
             coverage = torch.empty(Hm, Wm, dtype=torch.float32, device=dev)
             L.check(lib.bx_rise_accumulate(_p(P), _p(classes), _p(bits_d), _p(shifts_d), _p(sal), _p(coverage), B, N, K, geom[0], geom[1], Hm, Wm,
@@ -1566,11 +1557,7 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
     max_batch = int(max_batch)
     if max_batch < 1:
         raise ValueError(f"{who}: max_batch = {max_batch} < 1")
-    x = spec if input == "spec" else eeg
-    if x is None:
-        raise ValueError(f"{who}: input={input!r} but that tensor is None")
-    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
-        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
+    x = _input_tensor(who, input, eeg, spec)
     B = int(x.shape[0])
     Hm, Wm = int(x.shape[2]), int(x.shape[3])
     if input == "spec":
@@ -1584,42 +1571,12 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
     geom = _occlusion_geometry(who, window, stride, Hm, Wm)
     ny, nx = geom[4:]
     N = ny * nx
-    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
-    if multimodal:
-        other = eeg if input == "spec" else spec
-        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
-            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
-        K = int(model.fc2.out_features)
-    elif input == "spec":
-        if not (hasattr(model, "block1") and hasattr(model, "fc")):
-            raise ValueError(f"{who}: input='spec' needs a MultimodalModel or a Spectrogram_Model")
-        K = int(model.fc.out_features)
-    else:
-        if not hasattr(model, "depthwiseConv"):
-            raise ValueError(f"{who}: input='eeg' needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
-        K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
     if K > _RISE_MAX_K:
         raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    all_classes = isinstance(class_idx, str)
-    if class_idx is None:
-        cls_h = None
-    elif all_classes:
-        if class_idx != "all":
-            raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int, one class per sample or 'all'")
-        cls_h = None
-    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
-        cls_h = [int(class_idx)] * B
-    else:
-        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
-        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
-            raise ValueError(f"{who}: class_idx must be None, an int, 'all' or {B} integers (one class per sample)")
-        cls_h = [int(c) for c in cls_t.tolist()]
-    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
-        raise ValueError(f"{who}: class outside [0, {K})")
-    try:
-        kind, base = _faith_baseline(baseline, x, per_len, what)
-    except ValueError as exc:
-        raise ValueError(str(exc).replace("deletion_insertion", who, 1)) from None
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    kind, base = _baseline_for(who, baseline, x, per_len, what)
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
     if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
@@ -1627,46 +1584,22 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
 
     lib = L.load()
     dev = x.device
-    spec_net = model.spectrogram_model if multimodal else model
-    dt = getattr(spec_net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
+    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
     max_rows = _row_cap(x, input, dt, max_batch)
     use_logprob = score == "logprob"
 
-    @contextlib.contextmanager
-    def lap(name):
-        if profile is None:
-            yield
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        yield
-        e1.record()
-        profile.append((name, e0, e1))
-
     def run(rows, rep):
-        """log-probabilities -> scores fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
-        if input == "spec":
-            out = spec_net(rows.permute(0, 3, 1, 2))                 # a logical-NCHW view of the internal layout: no further copy
-        else:
-            out = (model.eeg_model if multimodal else model)(rows)
-        if multimodal:
-            e, s = (rep, out) if input == "spec" else (out, rep)
-            out = ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
-        logp = out.float().contiguous()
-        if use_logprob:
-            return logp
-        probs = torch.empty_like(logp)
-        L.check(lib.bx_softmax_rows(_p(logp), _p(probs), logp.shape[0], K, _stream()), "bx_softmax_rows")
-        return probs
+        """scores fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
+        logp = _rows_forward(model, net, multimodal, input == "spec", rows, rep)
+        return logp if use_logprob else _softmax_rows(logp)
 
     with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
         xs = x.detach().to(torch.float32).contiguous()
         base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
         fixed = None
-        with lap("forward"):
-            if multimodal:                                          # the branch whose input does not change: once per sample
-                o = other.detach().to(torch.float32).contiguous()
-                fixed = (model.eeg_model(o) if input == "spec" else model.spectrogram_model(o)).float().contiguous()
+        with _lap(profile, "forward"):
+            if multimodal:
+                fixed = _fixed_branch(model, other, input == "spec")
             # the unperturbed input takes the path of the occluded rows, in chunks of the same size
             clean = torch.empty(B, K, dtype=torch.float32, device=dev)
             for b0 in range(0, B, max_rows):
@@ -1681,11 +1614,11 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
             classes = clean.argmax(dim=1).to(torch.int32).contiguous()
         S = torch.empty(B, N, K, dtype=torch.float32, device=dev)
         for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
-            with lap("perturb"):
+            with _lap(profile, "perturb"):
                 rows = _occlusion_perturb(xs, geom, base, kind, b0, nb, n0, n, dt, input == "eeg")
-            with lap("forward"):
+            with _lap(profile, "forward"):
                 S[b0:b0 + nb, n0:n0 + n] = run(rows, None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)).reshape(nb, n, K)
-        with lap("accumulate"):
+        with _lap(profile, "accumulate"):
             attr = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
             counts = torch.empty(Hm, Wm, dtype=torch.int32, device=dev)
             L.check(lib.bx_occlusion_accumulate(_p(S), _p(clean), _p(classes), _p(attr), _p(counts), B, N, K, Hm, Wm, *geom[:4], _stream()),
@@ -1807,7 +1740,6 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
     if not isinstance(target_layer, str):
         raise ValueError(f"{who}: target_layer must be a string, got {target_layer!r}")
     me, ms = _EEG_TARGET.match(target_layer), _TARGET.match(target_layer)
-    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
     if me:
         if me.group(1) == "conv1":
             raise ValueError(f"{who}: 'eeg_model.conv1' is no Score-CAM target: its [B,8,Chans,T] activation is never formed; use "
@@ -1823,22 +1755,8 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
     if not isinstance(x, torch.Tensor) or x.dim() != 4 or (eeg_target and x.shape[1] != 1):
         raise ValueError(f"{who}: the {'EEG' if eeg_target else 'spectrogram'} input must be a tensor " + ("[B,1,Chans,T]" if eeg_target else "[B,C,H,W]"))
     B = int(x.shape[0])
-    if multimodal:
-        other = spec if eeg_target else eeg
-        if not isinstance(other, torch.Tensor) or other.shape[0] != B:
-            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
-        K = int(model.fc2.out_features)
-        net = model.eeg_model if eeg_target else model.spectrogram_model
-    else:
-        net = model
-        if eeg_target:
-            if not hasattr(model, "depthwiseConv"):
-                raise ValueError(f"{who}: an EEG target needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
-            K = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features)
-        else:
-            if not (hasattr(model, "block1") and hasattr(model, "fc")):
-                raise ValueError(f"{who}: a spectrogram target needs a MultimodalModel or a Spectrogram_Model")
-            K = int(model.fc.out_features)
+    other = spec if eeg_target else eeg
+    multimodal, K, net = _target_model(who, model, x, other, not eeg_target)
     if eeg_target:
         from .models import EEGNet, EEGNetAttentionDeep
         if not isinstance(net, (EEGNet, EEGNetAttentionDeep)):
@@ -1858,70 +1776,27 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     if K > _RISE_MAX_K:
         raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    all_classes = isinstance(class_idx, str)
-    if class_idx is None:
-        cls_h = None
-    elif all_classes:
-        if class_idx != "all":
-            raise ValueError(f"{who}: class_idx {class_idx!r}; use None, an int, one class per sample or 'all'")
-        cls_h = None
-    elif isinstance(class_idx, numbers.Integral) and not isinstance(class_idx, bool):
-        cls_h = [int(class_idx)] * B
-    else:
-        cls_t = class_idx.detach().cpu() if isinstance(class_idx, torch.Tensor) else torch.as_tensor(np.asarray(class_idx))
-        if cls_t.dim() != 1 or cls_t.shape[0] != B or cls_t.dtype.is_floating_point or cls_t.dtype == torch.bool:
-            raise ValueError(f"{who}: class_idx must be None, an int, 'all' or {B} integers (one class per sample)")
-        cls_h = [int(c) for c in cls_t.tolist()]
-    if cls_h is not None and any(not 0 <= c < K for c in cls_h):
-        raise ValueError(f"{who}: class outside [0, {K})")
-    try:
-        kind, base = _faith_baseline(baseline, x, per_len, what)
-    except ValueError as exc:
-        raise ValueError(str(exc).replace("deletion_insertion", who, 1)) from None
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    kind, base = _baseline_for(who, baseline, x, per_len, what)
     if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
         raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
 
     lib = L.load()
     dev = x.device
     dt = torch.float32 if eeg_target else getattr(net, "compute_dtype", torch.float32)
-    # a pass addresses its largest activation with 32-bit byte offsets: stage 1's H x W x 16 channels, EEGNet's F1 x Chans x T
-    row_bytes = 8 * Chans * T * 4 if eeg_target else H * W * 16 * (2 if dt == torch.bfloat16 else 4)
-    max_rows = max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+    max_rows = _row_cap(x, "eeg" if eeg_target else "spec", dt, max_batch)
     nm = K if all_classes else 1
 
-    @contextlib.contextmanager
-    def lap(name):
-        if profile is None:
-            yield
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        yield
-        e1.record()
-        profile.append((name, e0, e1))
-
-    def head(rows_out, fixed_rows):
-        """log-probabilities of the whole model from the target branch's output and the other branch's (repeated) output"""
-        if not multimodal:
-            return rows_out
-        e, s = (rows_out, fixed_rows) if eeg_target else (fixed_rows, rows_out)
-        return ops.FusionHeadFn.apply(e, s, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
-
-    def probabilities(logp):
-        logp = logp.float().contiguous()
-        probs = torch.empty_like(logp)
-        L.check(lib.bx_softmax_rows(_p(logp), _p(probs), logp.shape[0], K, _stream()), "bx_softmax_rows")
-        return probs
+    def probabilities(rows, rep):
+        """class probabilities fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
+        return _softmax_rows(_rows_forward(model, net, multimodal, not eeg_target, rows, rep))
 
     with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
         xs = x.detach().to(torch.float32).contiguous()
         base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
-        with lap("forward"):
+        with _lap(profile, "forward"):
             # the clean pass: the activation, the explained class, and the branch whose input does not change (once per sample)
-            fixed = None
-            if multimodal:
-                o = other.detach().to(torch.float32).contiguous()
-                fixed = (model.spectrogram_model(o) if eeg_target else model.eeg_model(o)).float().contiguous()
+            fixed = _fixed_branch(model, other, not eeg_target) if multimodal else None
             if eeg_target:
                 feat, saved, desc, _, _ = ops.eeg_features_keep(net, xs)
                 off_d, off_s = C.c_size_t(0), C.c_size_t(0)
@@ -1948,7 +1823,7 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
                     blk._preact, blk._capture = 0, None
                     if hook is not None:
                         hook.remove()
-            out = head(clean, fixed).float().contiguous()
+            out = _fuse(model, multimodal, not eeg_target, clean, fixed).float().contiguous()
         pl = _scorecam_plane(A, eeg_target)
         Cn, h, w = pl[5], pl[6], pl[7]
         if cls_h is not None:
@@ -1957,7 +1832,7 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
             classes = None
         else:
             classes = out.argmax(dim=1).to(torch.int32).contiguous()
-        with lap("range"):
+        with _lap(profile, "range"):
             lo, hi, scale = _scorecam_range(A, eeg_target, Hm, Wm)
             valid = hi > lo
         P_base = None
@@ -1965,23 +1840,20 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
             # the all-baseline input: the row of a channel whose scale is 0
             zero = torch.zeros(B, Cn, dtype=torch.float32, device=dev)
             for b0, nb, _, _ in _faith_chunks(B, 1, max_rows):
-                with lap("perturb"):
+                with _lap(profile, "perturb"):
                     rows = _scorecam_perturb(xs, A, eeg_target, zero, zero, base, kind, b0, nb, 0, 1, dt)
-                with lap("forward"):
-                    r = net(rows) if eeg_target else net(rows.permute(0, 3, 1, 2))
-                    pb = probabilities(head(r, None if fixed is None else fixed[b0:b0 + nb]))
+                with _lap(profile, "forward"):
+                    pb = probabilities(rows, None if fixed is None else fixed[b0:b0 + nb])
                     P_base = pb if P_base is None else torch.cat([P_base, pb])
             P_base = P_base.contiguous()
         P = torch.empty(B, Cn, K, dtype=torch.float32, device=dev)
         for b0, nb, k0, n in _faith_chunks(B, Cn, max_rows):
-            with lap("perturb"):
+            with _lap(profile, "perturb"):
                 rows = _scorecam_perturb(xs, A, eeg_target, lo, scale, base, kind, b0, nb, k0, n, dt)
-            with lap("forward"):
-                # (spectrogram rows: a logical-NCHW view of the internal layout, no further copy)
-                r = net(rows) if eeg_target else net(rows.permute(0, 3, 1, 2))
+            with _lap(profile, "forward"):
                 rep = None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)
-                P[b0:b0 + nb, k0:k0 + n] = probabilities(head(r, rep)).reshape(nb, n, K)
-        with lap("combine"):
+                P[b0:b0 + nb, k0:k0 + n] = probabilities(rows, rep).reshape(nb, n, K)
+        with _lap(profile, "combine"):
             raw = torch.empty(B * nm, h, w, dtype=torch.float32, device=dev)
             cam = torch.empty_like(raw) if relu else None
             wts = torch.empty(B * nm, Cn, dtype=torch.float32, device=dev)
