@@ -730,6 +730,51 @@ int bx_occlusion_perturb_eeg(const float* x, const float* baseline, int baseline
  * B * N * K and B * K * Hm * Wm stay below 2^31. */
 int bx_occlusion_accumulate(const float* S, const float* S0, const int* classes, float* attr, int* counts, int B, int N, int K, int Hm, int Wm,
                             int wh, int ww, int sh, int sw, bxStream stream);
+/* ---- Kernel SHAP (Lundberg & Lee, NeurIPS 2017; the reference explains its EEG branch with shap.GradientExplainer and reduces the
+ * values to per-electrode importances): Shapley values of M players from forward passes alone, so either input of the multimodal
+ * model can be explained; the values of a sample add up to score(input) - score(baseline).
+ * Players and coalitions.  The players are the M labels 0..M-1 (2 <= M <= 256, all present) of an int32 label map seg over the
+ * input's map domain: [H,W] of a spectrogram [B,C,H,W] (a cell is a pixel with all its channels, 1 <= C <= 4), [Chans,T] or [1,T] (a
+ * time column, every electrode) of an EEG input [B,1,Chans,T]; Hm * Wm < 2^20.  One label map serves the whole batch.  A coalition
+ * z in {0,1}^M shows the input on the cells whose label is in z and the baseline elsewhere: a selection, not a blend -- every element
+ * of a row is bit for bit an element of x or of the baseline, -0.0 survives.  baseline fp32, by baseline_kind as in
+ * bx_faith_perturb_*: 0 one value, 1 one value per channel [C] (spectrogram) / electrode [Chans] (EEG), 2 a tensor of x's shape.
+ * v_b,k(z) is the score (softmax probability or log-probability) of class k for sample b under coalition z; v(1) is the score of the
+ * unperturbed input (clean), v(0) that of the baseline (empty).
+ * Values.  phi[b,k,.] minimises sum_n w_n (v(z_n) - phi0 - sum_i phi_i z_ni)^2 subject to phi0 = v(0) and sum_i phi_i = v(1) - v(0).
+ * The constraint is eliminated on the last player: Xt[n,i] = z_ni - z_n,M-1 for i < M-1 (-1, 0 or 1),
+ * yt_n = v(z_n) - v(0) - z_n,M-1 D with D = v(1) - v(0); (Xt' W Xt) phi' = Xt' W yt is solved by Cholesky in fp64; phi_M-1 = D - sum phi'.
+ * Coalition set (built by the caller; the same for every sample).  Exact, when 2^M - 2 <= num_samples: every proper non-empty
+ * coalition in increasing order of the integer whose bit i is player i, w = (M-1) / (C(M,s) s (M-s)), s = |z| -- the exact Shapley
+ * values.  Sampled, otherwise: N = num_samples rounded down to even, rng = numpy.random.default_rng(seed),
+ * sizes = rng.choice(arange(1, M), size=N/2, p ~ (M-1) / (s (M-s))), row 2j = the players rng.permutation(M)[:sizes[j]], row 2j+1 its
+ * complement (paired sampling, Covert & Lee 2021), all weights 1.  Given: any Z [N,M] without an all-zero or all-one row (the
+ * constraint already holds those two) and weights [N] > 0.
+ * Every entry point refuses its limits with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+/* Perturbed spectrogram rows.  x fp32 NCHW [B,C,H,W], segments i32 [H*W], Z u8 [N,M] (non-zero = the player is shown) -> out
+ * [B*n, H, W, Cp] (dtype; sample-major: row b*n + j is sample b under coalition n0 + j), channels C..Cp-1 zero, Cp = 8 -- bit for bit
+ * bx_nchw_to_nhwc of the selection, which is never built.  0 <= n0, 1 <= n, n0 + n <= N.  A label outside 0..M-1 counts as player 0.
+ * Every element of out is written; one call's output stays below 2^32 bytes. */
+int bx_shap_perturb_spec(const float* x, const float* baseline, int baseline_kind, void* out, int B, int C, int H, int W, int Cp,
+                         const int* segments, const unsigned char* Z, int M, int N, int n0, int n, int dtype, bxStream stream);
+/* Perturbed EEG rows.  x fp32 [B,1,Chans,T] -> out fp32 [B*n,1,Chans,T], same row order; segments i32 [map_rows*T] with
+ * map_rows = Chans (element (ch,t) belongs to cell (ch,t)) or 1 (to cell (0,t)). */
+int bx_shap_perturb_eeg(const float* x, const float* baseline, int baseline_kind, float* out, int B, int Chans, int T, int map_rows,
+                        const int* segments, const unsigned char* Z, int M, int N, int n0, int n, bxStream stream);
+/* The fit.  S fp32 [B,N,K] (the scores of the N coalitions), clean and empty fp32 [B,K], K <= 32; classes i32 [B] (R = 1: the values
+ * of that class) or NULL (R = K: of every class); Z u8 [N,M], weights fp64 [N].  phi fp64 [B,R,M] as defined above; info i32 [1].
+ * The Gram matrix is computed once per call, for B * R right-hand sides; every sum is taken by one thread in index order (the last
+ * player's with Neumaier's compensation): no atomics, the result's bits are a function of the inputs alone.  A Cholesky pivot that is
+ * not above (M-1) 2^-52 times its diagonal entry of the Gram matrix -- non-positive up to the rounding of the eliminations, which is
+ * what an exactly singular matrix leaves -- writes its index + 1 to info and leaves phi untouched: the coalitions do not determine
+ * the values.  Otherwise info = 0.  2 <= M <= 256, N >= M - 1, B * N * K < 2^31.  The workspace (8-byte aligned) holds the matrix and
+ * the right-hand sides; bx_shap_fit_workspace returns its size in bytes (all_classes: classes is NULL), 0 for refused arguments. */
+size_t bx_shap_fit_workspace(int B, int N, int K, int M, int all_classes);
+int bx_shap_fit(const float* S, const float* clean, const float* empty, const int* classes, const unsigned char* Z, const double* weights,
+                int B, int N, int K, int M, void* workspace, size_t workspace_bytes, double* phi, int* info, bxStream stream);
+/* The map.  map[b,r,p] = (float) phi[b,r,segments[p]] (0 for a label outside 0..M-1); phi fp64 [B,R,M], map fp32 [B,R,Hm*Wm], R <= 32,
+ * B * R * Hm * Wm < 2^31. */
+int bx_shap_value_map(const double* phi, const int* segments, float* map, int B, int R, int Hm, int Wm, int M, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

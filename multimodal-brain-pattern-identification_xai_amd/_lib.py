@@ -186,6 +186,11 @@ SIGNATURES = {
     "bx_occlusion_perturb_spec": (i32, [vp, vp, i32, vp] + [i32] * 12 + [vp]),
     "bx_occlusion_perturb_eeg": (i32, [vp, vp, i32, vp] + [i32] * 9 + [vp]),
     "bx_occlusion_accumulate": (i32, [vp] * 5 + [i32] * 9 + [vp]),
+    "bx_shap_perturb_spec": (i32, [vp, vp, i32, vp] + [i32] * 5 + [vp, vp] + [i32] * 5 + [vp]),
+    "bx_shap_perturb_eeg": (i32, [vp, vp, i32, vp] + [i32] * 4 + [vp, vp] + [i32] * 4 + [vp]),
+    "bx_shap_fit_workspace": (sz, [i32] * 5),
+    "bx_shap_fit": (i32, [vp] * 6 + [i32] * 4 + [vp, sz, vp, vp, vp]),
+    "bx_shap_value_map": (i32, [vp] * 3 + [i32] * 5 + [vp]),
     "bx_scorecam_range_workspace": (sz, [i32] * 4),
     "bx_scorecam_range": (i32, [vp] + [i32] * 11 + [vp, vp, vp, vp, sz, vp]),
     "bx_scorecam_perturb_spec": (i32, [vp, vp] + [i32] * 8 + [vp, vp, vp, i32, vp] + [i32] * 10 + [vp]),

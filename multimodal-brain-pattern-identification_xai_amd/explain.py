@@ -25,12 +25,19 @@
                                  time-segment ablation on the EEG input, band or slab ablation on the spectrogram; deterministic; the
                                  occluded rows are a selection written in the model's layout (bx_occlusion_perturb_*), the map an
                                  fp64 mean over the covering windows in fixed order (bx_occlusion_accumulate).
+* ``kernel_shap``             -- Kernel SHAP (Lundberg & Lee, NeurIPS 2017; the reference's SHAP is a GradientExplainer on the EEG branch,
+                                 reduced to per-electrode importances): Shapley values of the segments of either input -- electrodes,
+                                 time slabs, a time-by-frequency grid -- from forward passes of coalitions; exact for few players,
+                                 paired sampling otherwise; the values add up to score(input) - score(baseline).  The rows are a
+                                 selection written in the model's layout (bx_shap_perturb_*), the constrained fit is fp64 in fixed
+                                 order (bx_shap_fit), the map the values gathered through the label map (bx_shap_value_map).
 """
 from __future__ import annotations
 
 import collections
 import contextlib
 import ctypes as C
+import math
 import numbers
 import re
 
@@ -1631,6 +1638,279 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
         else:
             drops = d.gather(2, classes.long().reshape(B, 1, 1).expand(B, N, 1)).reshape(B, ny, nx)
     return OcclusionResult(attr, drops, None if classes is None else classes.long(), S, clean, counts, (ny, nx))
+
+
+# ------------------------------------------------------------------------------------------------
+# Kernel SHAP (Lundberg & Lee, NeurIPS 2017; paired sampling: Covert & Lee, AISTATS 2021): Shapley values of the segments of either
+# input from forward passes alone.  The definition is pinned in include/brainxai.h; tests/kernel_shap_ref.py restates it.
+_SHAP_MAX_M = 256
+
+KernelShapResult = collections.namedtuple("KernelShapResult", "attribution values classes scores clean empty coalitions weights segments exact")
+KernelShapResult.__doc__ = """What ``kernel_shap(..., return_parts=True)`` returns: ``attribution`` fp32 [B,Hm,Wm] or [B,K,Hm,Wm] (what the plain call
+returns), ``values`` fp64 [B,M] or [B,K,M] = the Shapley value of every player (with segments='electrodes' the per-electrode
+importances), ``classes`` int64 [B] (None for class_idx='all'), ``scores`` fp32 [B,N,K] (the score of every class under every coalition),
+``clean`` / ``empty`` fp32 [B,K] (the scores of the unperturbed input and of the baseline), all on the device; ``coalitions`` uint8 [N,M],
+``weights`` fp64 [N] and ``segments`` int32 [Hm,Wm] on the host (``coalitions=(coalitions, weights)`` repeats the call); ``exact``: whether
+the set is every proper non-empty coalition, so that the values are the exact Shapley values."""
+
+
+def _shap_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _shap_segments(who, segments, input, Hd, Wd):
+    """-> (seg int32 [Hm,Wm] on the host, M): the label map over the map domain, [H,W] for a spectrogram and [Chans,T] or [1,T] for the
+    EEG input (Hd x Wd is the input's own H x W / Chans x T)."""
+    if isinstance(segments, str):
+        if segments != "electrodes" or input != "eeg":
+            raise ValueError(f"{who}: segments {segments!r}; use a label map, (rows, cols)" + (", 'electrodes' or ('time', n)" if input == "eeg" else
+                                                                                              " (the words name segmentations of the EEG input)"))
+        seg = np.repeat(np.arange(Hd, dtype=np.int32)[:, None], Wd, axis=1)
+    elif isinstance(segments, (tuple, list)) and len(segments) == 2 and isinstance(segments[0], str) and segments[0] == "time":
+        if input != "eeg" or not _shap_int(segments[1]) or not 1 <= segments[1] <= Wd:
+            raise ValueError(f"{who}: segments {segments!r}; ('time', n) cuts the EEG input's {Wd} time steps into 1 <= n <= T slabs")
+        seg = grid_segments(1, Wd, 1, int(segments[1]))
+    elif isinstance(segments, (tuple, list)) and len(segments) == 2 and all(_shap_int(v) for v in segments):
+        rows, cols = int(segments[0]), int(segments[1])
+        if not (1 <= rows <= Hd and 1 <= cols <= Wd):
+            raise ValueError(f"{who}: segments (rows, cols) = {(rows, cols)} outside 1..{Hd} x 1..{Wd}")
+        seg = grid_segments(Hd, Wd, rows, cols)
+    else:
+        try:
+            seg = segments.detach().cpu().numpy() if isinstance(segments, torch.Tensor) else np.asarray(segments)
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"{who}: segments is neither a label map, (rows, cols) nor a named segmentation ({exc})") from None
+        if seg.dtype.kind not in "iu":
+            raise ValueError(f"{who}: the label map must hold integers, got {seg.dtype}")
+        shapes = [(Hd, Wd)] + ([(1, Wd)] if input == "eeg" else [])
+        if tuple(seg.shape) not in shapes:
+            raise ValueError(f"{who}: label map of shape {tuple(seg.shape)}; expected " + " or ".join(str(list(s)) for s in shapes))
+    M = int(seg.max()) + 1
+    if int(seg.min()) < 0 or not np.array_equal(np.unique(seg), np.arange(M)):
+        raise ValueError(f"{who}: the labels must be 0..M-1 with every label present; got {np.unique(seg).size} labels in {int(seg.min())}..{M - 1}")
+    if not 2 <= M <= _SHAP_MAX_M:
+        raise ValueError(f"{who}: {M} players, supported 2..{_SHAP_MAX_M}")
+    return np.ascontiguousarray(seg.astype(np.int32)), M
+
+
+def _shap_coalitions(who, M, num_samples, seed, coalitions):
+    """-> (Z uint8 [N,M], weights fp64 [N], exact): the coalition set of include/brainxai.h, built on the host."""
+    if coalitions is not None:
+        try:
+            Z, w = coalitions
+            Z = np.asarray(Z.detach().cpu() if isinstance(Z, torch.Tensor) else Z)
+            w = None if w is None else np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: coalitions must be a pair (Z [N,M], weights [N] or None)") from None
+        if Z.ndim != 2 or Z.shape[1] != M or Z.dtype.kind not in "biuf" or not np.isin(Z, (0, 1)).all():
+            raise ValueError(f"{who}: coalitions must be 0 / 1 in shape [N, M = {M}], got {tuple(Z.shape)}")
+        Z = np.ascontiguousarray(Z.astype(np.uint8))
+        size = Z.sum(1)
+        if ((size == 0) | (size == M)).any():
+            raise ValueError(f"{who}: a coalition row is all-zero or all-one; the constraint already holds the baseline and the input")
+        if w is None:
+            w = np.ones(Z.shape[0], dtype=np.float64)
+        if w.shape != (Z.shape[0],):
+            raise ValueError(f"{who}: {w.size} weights for {Z.shape[0]} coalitions")
+        if not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError(f"{who}: the weights must be positive and finite")
+        exact = False
+    else:
+        if not _shap_int(num_samples):
+            raise ValueError(f"{who}: num_samples must be an int or None, got {num_samples!r}")
+        if (1 << M) - 2 <= num_samples:
+            c = np.arange(1, (1 << M) - 1, dtype=np.int64)
+            Z = ((c[:, None] >> np.arange(M, dtype=np.int64)[None, :]) & 1).astype(np.uint8)
+            per_size = np.array([0.0] + [(M - 1) / (math.comb(M, s) * s * (M - s)) for s in range(1, M)])
+            w, exact = per_size[Z.sum(1)], True
+        else:
+            N = int(num_samples) // 2 * 2
+            if N < max(2, M - 1):
+                raise ValueError(f"{who}: num_samples = {num_samples} gives N = {N} coalitions, which cannot determine {M} players (N >= M - 1)")
+            rng = np.random.default_rng(seed)
+            s = np.arange(1, M)
+            p = (M - 1) / (s * (M - s))
+            sizes = rng.choice(s, size=N // 2, p=p / p.sum())
+            Z = np.zeros((N, M), dtype=np.uint8)
+            for j, k in enumerate(sizes):
+                Z[2 * j, rng.permutation(M)[:k]] = 1
+                Z[2 * j + 1] = 1 - Z[2 * j]
+            w, exact = np.ones(N, dtype=np.float64), False
+    if Z.shape[0] < M - 1:
+        raise ValueError(f"{who}: N = {Z.shape[0]} coalitions cannot determine {M} players (N >= M - 1)")
+    return Z, np.ascontiguousarray(w), exact
+
+
+def _shap_perturb(x, seg_d, Z_d, M, base, kind, b0, nb, n0, n, dt, map_rows=None):
+    """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1: sample b under coalition n0 + j of Z_d.  x fp32 [B,C,H,W] -> internal layout
+    [nb*n,H,W,8] in dt (bx_shap_perturb_spec), or with map_rows fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_shap_perturb_eeg)."""
+    lib = L.load()
+    xs = x[b0:b0 + nb]
+    bs = base[b0:b0 + nb] if kind == 2 else base
+    N = Z_d.shape[0]
+    if map_rows is None:
+        _, Cc, H, W = x.shape
+        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
+        L.check(lib.bx_shap_perturb_spec(_p(xs), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), _p(seg_d), _p(Z_d), M, N, n0, n, ops.bx_dtype(dt),
+                                         _stream()), "bx_shap_perturb_spec")
+    else:
+        _, _, Chans, T = x.shape
+        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
+        L.check(lib.bx_shap_perturb_eeg(_p(xs), _p(bs), kind, _p(out), nb, Chans, T, map_rows, _p(seg_d), _p(Z_d), M, N, n0, n, _stream()),
+                "bx_shap_perturb_eeg")
+    return out
+
+
+def _shap_fit(S, clean, empty, classes, Z_d, w_d):
+    """phi fp64 [B,R,M] (R = 1 with classes, else K) of scores S fp32 [B,N,K] (bx_shap_fit); ValueError when the coalitions leave the
+    values undetermined."""
+    lib = L.load()
+    B, N, K = S.shape
+    M = Z_d.shape[1]
+    nbytes = lib.bx_shap_fit_workspace(B, N, K, M, 1 if classes is None else 0)
+    if nbytes == 0:
+        L.check(-1, "bx_shap_fit_workspace")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=S.device)
+    phi = torch.zeros(B, K if classes is None else 1, M, dtype=torch.float64, device=S.device)
+    info = torch.zeros(1, dtype=torch.int32, device=S.device)
+    L.check(lib.bx_shap_fit(_p(S), _p(clean), _p(empty), _p(classes), _p(Z_d), _p(w_d), B, N, K, M, _p(ws), nbytes, _p(phi), _p(info), _stream()),
+            "bx_shap_fit")
+    bad = int(info.item())
+    if bad:
+        raise ValueError(f"kernel_shap: the {N} coalitions leave the values of the {M} players undetermined (the fit's pivot {bad - 1} vanishes): "
+                         "more samples are needed")
+    return phi
+
+
+def kernel_shap(model, eeg, spec, *, input="spec", segments, num_samples=None, baseline=0.0, class_idx=None, score="prob", seed=0, coalitions=None,
+                max_batch=256, return_parts=False):
+    """Kernel SHAP (Lundberg & Lee, NeurIPS 2017): the Shapley values of the M segments of one input, estimated from forward passes of
+    coalitions -- the input on the segments of the coalition, the baseline elsewhere.  phi[b,k,.] minimises
+    sum_n w_n (v(z_n) - v(0) - sum_i phi_i z_ni)^2 subject to sum_i phi_i = v(1) - v(0), with v(z) the class score under coalition z, so
+    the values of a sample add up exactly to score(input) - score(baseline), which LIME, occlusion and RISE do not give.  Forward-only,
+    so it explains either input of the multimodal model (the reference's SHAP, a GradientExplainer on the EEG branch reduced to
+    per-electrode importances, is ``segments='electrodes'`` here); the map has the input's own shape and fits ``deletion_insertion`` and
+    ``attribution_ranks`` as it is.
+
+    input:       'spec': segments over [H,W], a cell is a pixel with all its channels (C <= 4), map [B,H,W]; 'eeg': segments over
+                 [Chans,T], map [B,Chans,T], or over [1,T] (a label applies to every electrode), map [B,1,T].
+    model:       a MultimodalModel; a stand-alone Spectrogram_Model (eeg=None, input='spec'); a stand-alone EEGNet /
+                 EEGNetAttentionDeep (spec=None, input='eeg') -- the convention of grad_cam, deletion_insertion, rise and occlusion.
+    segments:    an int label map over the domain with the labels 0..M-1 all present (2 <= M <= 256; one map for the whole batch);
+                 (rows, cols) = ``grid_segments(Hm, Wm, rows, cols)``; for the EEG input also 'electrodes' (label = electrode) and
+                 ('time', n) (n slabs over [1,T]).
+    num_samples: the budget of coalitions, None = 2 M + 2048.  When 2^M - 2 <= num_samples every proper non-empty coalition is used, in
+                 increasing order of the integer whose bit i is player i, with the Shapley kernel w = (M-1) / (C(M,s) s (M-s)): the
+                 exact Shapley values.  Otherwise N = num_samples rounded down to even; one np.random.default_rng(seed) draws
+                 sizes = rng.choice(arange(1, M), N/2, p ~ (M-1) / (s (M-s))), row 2j = the players rng.permutation(M)[:sizes[j]], row
+                 2j+1 its complement (paired sampling, Covert & Lee 2021), all weights 1.  One set serves the whole batch.
+    coalitions:  (Z [N,M] of 0 / 1, weights [N] or None) replaces the set; an all-zero or all-one row is refused.
+    baseline:    what a cell outside the coalition shows: a number; one value per channel (spec) / electrode (eeg); a tensor of the
+                 input's shape.
+    class_idx:   None = each sample's arg-max class on the unperturbed input; an int; one class per sample (sequence / tensor [B]);
+                 'all' = every class, the map gains a class axis [B,K,Hm,Wm] (K <= 32).
+    score:       'prob': the softmax probability; 'logprob': the log-probability.
+    max_batch:   rows (coalitions) per forward pass; no bit of the result depends on it.
+    (N + 2) * B forward evaluations in eval mode without autograd.  The rows are written straight in the model's layout
+    (bx_shap_perturb_*: a selection, every element is bit for bit the input's or the baseline's); the fit is fp64 with every sum in a
+    fixed order (bx_shap_fit: one Gram matrix and one Cholesky factorisation per call, shared by all samples and classes); the map is
+    the values gathered through the label map (bx_shap_value_map).  In a MultimodalModel the branch whose input does not change runs
+    once per sample and its output is repeated into the fusion head.  ValueError when the coalitions leave the values undetermined.
+    The training flag and every requires_grad are restored on return.  Returns the map (device, fp32), or ``KernelShapResult`` with
+    return_parts."""
+    return _kernel_shap(model, eeg, spec, input, segments, num_samples, baseline, class_idx, score, seed, coalitions, max_batch, return_parts)
+
+
+def _kernel_shap(model, eeg, spec, input, segments, num_samples, baseline, class_idx, score, seed, coalitions, max_batch, return_parts, profile=None):
+    """``kernel_shap`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'perturb', 'forward',
+    'fit' -- device events around every phase of the pass (tools/kernel_shap_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "kernel_shap"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if score not in _FAITH_SCORES:
+        raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
+    max_batch = int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    x = _input_tensor(who, input, eeg, spec)
+    B = int(x.shape[0])
+    Hd, Wd = int(x.shape[2]), int(x.shape[3])
+    if input == "spec":
+        per_len, what = int(x.shape[1]), "channel"
+        if not 1 <= per_len <= _FAITH_MAX_C:
+            raise ValueError(f"{who}: {per_len} channels, supported 1..{_FAITH_MAX_C}")
+    else:
+        per_len, what = Hd, "electrode"
+    if B < 1 or not 1 <= Hd * Wd <= _FAITH_MAX_N:
+        raise ValueError(f"{who}: {Hd * Wd} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
+    seg, M = _shap_segments(who, segments, input, Hd, Wd)
+    Hm, Wm = seg.shape
+    map_rows = None if input == "spec" else Hm
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    kind, base = _baseline_for(who, baseline, x, per_len, what)
+    Z, weights, exact = _shap_coalitions(who, M, 2 * M + 2048 if num_samples is None else num_samples, seed, coalitions)
+    N = int(Z.shape[0])
+    if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31 or N * M >= 1 << 31:
+        raise ValueError(f"{who}: B * N * K = {B * N * K}, B * K * Hm * Wm = {B * K * Hm * Wm} or N * M = {N * M} beyond 32-bit offsets; "
+                         "use fewer samples per call")
+    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
+        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+
+    lib = L.load()
+    dev = x.device
+    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
+    max_rows = _row_cap(x, input, dt, max_batch)
+    use_logprob = score == "logprob"
+
+    def run(rows, rep):
+        """scores fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
+        logp = _rows_forward(model, net, multimodal, input == "spec", rows, rep)
+        return logp if use_logprob else _softmax_rows(logp)
+
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
+        xs = x.detach().to(torch.float32).contiguous()
+        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+        seg_d, Z_d, w_d = torch.from_numpy(seg).to(dev), torch.from_numpy(Z).to(dev), torch.from_numpy(weights).to(dev)
+        none_d = torch.zeros(1, M, dtype=torch.uint8, device=dev)      # the empty coalition: the baseline itself
+        fixed = None
+        clean, empty = (torch.empty(B, K, dtype=torch.float32, device=dev) for _ in range(2))
+        if multimodal:
+            with _lap(profile, "forward"):
+                fixed = _fixed_branch(model, other, input == "spec")
+        # v(1) and v(0): the unperturbed input and the baseline take the path of the coalition rows, in chunks of the same size
+        for b0 in range(0, B, max_rows):
+            nb = min(max_rows, B - b0)
+            rep = None if fixed is None else fixed[b0:b0 + nb]
+            with _lap(profile, "perturb"):
+                rows0 = _shap_perturb(xs, seg_d, none_d, M, base, kind, b0, nb, 0, 1, dt, map_rows)
+            with _lap(profile, "forward"):
+                clean[b0:b0 + nb] = run(ops.to_nhwc(xs[b0:b0 + nb], dt) if input == "spec" else xs[b0:b0 + nb], rep)
+                empty[b0:b0 + nb] = run(rows0, rep)
+        if cls_h is not None:
+            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
+        elif all_classes:
+            classes = None
+        else:                                                       # the explained class: the arg-max on the unperturbed input
+            classes = clean.argmax(dim=1).to(torch.int32).contiguous()
+        S = torch.empty(B, N, K, dtype=torch.float32, device=dev)
+        for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
+            with _lap(profile, "perturb"):
+                rows = _shap_perturb(xs, seg_d, Z_d, M, base, kind, b0, nb, n0, n, dt, map_rows)
+            with _lap(profile, "forward"):
+                S[b0:b0 + nb, n0:n0 + n] = run(rows, None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)).reshape(nb, n, K)
+        with _lap(profile, "fit"):
+            phi = _shap_fit(S, clean, empty, classes, Z_d, w_d)
+            R = phi.shape[1]
+            attr = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
+            L.check(lib.bx_shap_value_map(_p(phi), _p(seg_d), _p(attr), B, R, Hm, Wm, M, _stream()), "bx_shap_value_map")
+    if not return_parts:
+        return attr
+    return KernelShapResult(attr, phi if all_classes else phi[:, 0], None if classes is None else classes.long(), S, clean, empty, Z, weights, seg, exact)
 
 
 # ------------------------------------------------------------------------------------------------
