@@ -775,6 +775,38 @@ int bx_shap_fit(const float* S, const float* clean, const float* empty, const in
 /* The map.  map[b,r,p] = (float) phi[b,r,segments[p]] (0 for a label outside 0..M-1); phi fp64 [B,R,M], map fp32 [B,R,Hm*Wm], R <= 32,
  * B * R * Hm * Wm < 2^31. */
 int bx_shap_value_map(const double* phi, const int* segments, float* map, int B, int R, int Hm, int Wm, int M, bxStream stream);
+/* ---- Expected gradients (SHAP's GradientExplainer, the one attribution the reference computes from SHAP; Erion et al. 2021), batched.
+ * For the explained input x [B,per], a background set bg [Nb,per] of the same trailing shape, n draws per sample and F_c the model's
+ * output log-probability of class c:
+ *     phi[b,c,e] = (1/n) * sum_{k=0..n-1} d[b,k,e] * dF_c/dx( r[b,k] )[e]
+ *     d[b,k] = x[b] - bg[idx[b,k]]                      (one fp32 rounding)
+ *     r[b,k] = bg[idx[b,k]] + fl(alpha[b,k] * d[b,k])   (product and sum rounded separately, no fma)
+ * Draws (made by the caller on the host): one numpy.random.default_rng(seed); for b = 0..B-1 in order idx[b] = rng.integers(0, Nb, n),
+ * then alpha[b] = rng.random(n).astype(float32).  idx i32 [B,n], alpha fp32 [B,n], on the device; an index outside 0..Nb-1 counts as
+ * the nearest end.  per = C*H*W of a spectrogram in its logical layout [C,H,W], or Chans*T of an EEG input [1,Chans,T]: the layout the
+ * model takes as an autograd leaf.  Rows are numbered globally j = b * n + k, sample-major; a call handles rows [row0, row0 + rows),
+ * which may start and end inside a sample.  The sum over k is fp64 in ascending k (d * g of two floats is exact in fp64), carried
+ * between calls in acc, so the result does not depend on how the rows were split into calls; it is divided by n in fp64 and rounded to
+ * fp32 once.  No atomics.  B * n, B * per, Nb * per, rows * per and B * Kc * per stay below 2^31; every entry point refuses its limits
+ * with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+/* The interpolants: out fp32 [rows, per], row r = r[b,k] of global row row0 + r.  Every element of every row is written exactly once. */
+int bx_expgrad_rows(const float* x, const float* bg, const int* idx, const float* alpha, float* out, int B, int Nb, int n, int per, int row0,
+                    int rows, bxStream stream);
+/* The running sum of one class slot: acc[b,slot,e] += sum of d[b,k,e] * g[j - row0, e] over the rows j = b * n + k of the call that belong
+ * to sample b, in ascending k.  acc fp64 [B,Kc,per] (Kc <= 32; the other slots are not touched), g fp32 [rows, per] the input gradient of
+ * the call's rows, read exactly once; d is recomputed from x and the gathered background row and never stored. */
+int bx_expgrad_accumulate(const float* x, const float* bg, const int* idx, const float* g, double* acc, int B, int Nb, int n, int per, int Kc,
+                          int slot, int row0, int rows, bxStream stream);
+/* Mean and map.  acc fp64 [BK,C,HW] -> values fp32 [BK,C,HW] = fl32(acc / n) and map fp32 [BK,HW] = fl32 of the fp64 sum of acc / n over
+ * the C channels in ascending order (a sum keeps the attributions additive).  A spectrogram passes its C and HW = H*W; an EEG input
+ * passes C = 1, HW = Chans*T and map = NULL (its map is values itself).  BK = B * Kc <= 65535. */
+int bx_expgrad_finish(const double* acc, float* values, float* map, int BK, int C, int HW, int n, bxStream stream);
+/* Gradient seeds of sample-major rows: seed fp32 [rows,K], row r = onehot(classes[(row0 + r) / n]) with classes i32 [B] on the device (a
+ * class outside 0..K-1 counts as the nearest end), or onehot(class_all) for every row when classes is NULL. */
+int bx_expgrad_seed(const int* classes, int class_all, float* seed, int B, int n, int K, int row0, int rows, bxStream stream);
+/* The reference's per-electrode reduction: out[r] = fl32( (sum_t |v[r,t]|) / L ) for v fp32 [R,L].  The sum is fp64 in an order that does
+ * not depend on the launch: 64 partial sums over t = l, l + 64, ... (ascending), added by a fixed pairwise tree.  R * L < 2^31. */
+int bx_mean_abs_rows(const float* v, float* out, int R, int L, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

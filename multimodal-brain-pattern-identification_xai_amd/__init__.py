@@ -9,7 +9,8 @@ from .models import (Attention, Block, EEGNet, EEGNetAttentionDeep, KLDivLoss, M
 from .explain import (GradCamSweep, expected_gradients, generate_saliency_maps, grad_cam, integrated_gradients, saliency,   # noqa: F401
                       predict_fn, shard_bounds, sharded_sweep, LimeExplanation, grid_segments, lime_image,
                       FaithfulnessCurves, attribution_ranks, deletion_insertion, RiseResult, rise, rise_masks, ScoreCamResult, score_cam,
-                      OcclusionResult, occlusion, KernelShapResult, kernel_shap)
+                      OcclusionResult, occlusion, KernelShapResult, kernel_shap,
+                      GradientShapResult, gradient_shap, channel_importance, GradientExplainer)
 from .data import (EEGStacker, stack_eeg, EEGMontageStacker, stack_eeg_montage,          # noqa: F401
                    SpectrogramPreprocessor, preprocess_spectrograms, SpectrogramRegionStacker, stack_spectrogram_regions, StagingRing)                                        # noqa: F401
 from .train import (FlatAdamW, DataParallel, GraphedTrainStep, AsyncCheckpointer, train_and_validate_combined, train_and_validate_eeg_distributed,   # noqa: F401

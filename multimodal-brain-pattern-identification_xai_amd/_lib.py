@@ -196,6 +196,11 @@ SIGNATURES = {
     "bx_scorecam_perturb_spec": (i32, [vp, vp] + [i32] * 8 + [vp, vp, vp, i32, vp] + [i32] * 10 + [vp]),
     "bx_scorecam_perturb_eeg": (i32, [vp, vp] + [i32] * 6 + [vp, vp, vp, i32, vp] + [i32] * 7 + [vp]),
     "bx_scorecam_combine": (i32, [vp] * 5 + [i32] * 12 + [vp, vp, vp, vp]),
+    "bx_expgrad_rows": (i32, [vp] * 5 + [i32] * 6 + [vp]),
+    "bx_expgrad_accumulate": (i32, [vp] * 5 + [i32] * 8 + [vp]),
+    "bx_expgrad_finish": (i32, [vp, vp, vp] + [i32] * 4 + [vp]),
+    "bx_expgrad_seed": (i32, [vp, i32, vp] + [i32] * 5 + [vp]),
+    "bx_mean_abs_rows": (i32, [vp, vp, i32, i32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

@@ -31,6 +31,13 @@
                                  paired sampling otherwise; the values add up to score(input) - score(baseline).  The rows are a
                                  selection written in the model's layout (bx_shap_perturb_*), the constrained fit is fp64 in fixed
                                  order (bx_shap_fit), the map the values gathered through the label map (bx_shap_value_map).
+* ``gradient_shap``           -- expected gradients (SHAP's GradientExplainer, reference XAI_Multimodality.py:2283-2290) of either input
+                                 of the multimodal model or of a stand-alone branch, batched over samples, draws and classes: the
+                                 interpolants of a pass in one launch (bx_expgrad_rows), one forward pass for all classes, an fp64 running
+                                 sum in fixed draw order after every backward pass (bx_expgrad_accumulate), the mean and the
+                                 channel-summed map (bx_expgrad_finish).  ``channel_importance`` is the reference's mean |.| per
+                                 electrode (bx_mean_abs_rows), ``GradientExplainer`` SHAP's calling form.  ``expected_gradients`` is
+                                 the same estimator as a host loop over one stand-alone model.
 """
 from __future__ import annotations
 
@@ -2151,3 +2158,208 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
     if not return_parts:
         return shape(cam)
     return ScoreCamResult(shape(cam), shape(raw), shape(wts), A, out, P, lo, hi, valid, None if classes is None else classes.long())
+
+
+# ------------------------------------------------------------------------------------------------
+# Expected gradients, batched (SHAP's GradientExplainer; the one attribution the reference computes from SHAP).  The definition is
+# pinned in include/brainxai.h; tests/gradient_shap_ref.py restates it.
+GradientShapResult = collections.namedtuple("GradientShapResult", "attribution values classes out idx alpha nsamples")
+GradientShapResult.__doc__ = """What ``gradient_shap(..., return_parts=True)`` returns: ``attribution`` fp32 [B,H,W] / [B,Chans,T], with a class axis for
+class_idx='all' (what the plain call returns), ``values`` fp32 [B(,K),*x.shape[1:]] (the estimator element by element), ``classes`` int64
+[B] (None for class_idx='all'), ``out`` fp32 [B,K] (the log-probabilities of the clean input), all on the device; ``idx`` int32 [B,n] and
+``alpha`` fp32 [B,n] on the host: ``draws=(idx, alpha)`` repeats the call; ``nsamples`` = n."""
+
+
+def _gradshap_draws(who, B, Nb, n, seed, draws):
+    """-> (idx int32 [B,n], alpha fp32 [B,n]) on the host.  From one np.random.default_rng(seed), sample by sample: the background indices
+    of a sample, then its interpolation points -- the draws of ``expected_gradients``; or ``draws`` checked."""
+    if draws is None:
+        rng = np.random.default_rng(seed)
+        idx, alpha = np.empty((B, n), dtype=np.int32), np.empty((B, n), dtype=np.float32)
+        for b in range(B):
+            idx[b] = rng.integers(0, Nb, size=n)
+            alpha[b] = rng.random(n).astype(np.float32)
+        return idx, alpha
+    if not isinstance(draws, (tuple, list)) or len(draws) != 2:
+        raise ValueError(f"{who}: draws must be (idx [B,n] integer, alpha [B,n] float)")
+    idx, alpha = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in draws)
+    if idx.dtype.kind not in "iu" or alpha.dtype.kind != "f":
+        raise ValueError(f"{who}: draws must be (idx [B,n] integer, alpha [B,n] float), got dtypes {idx.dtype}, {alpha.dtype}")
+    if idx.shape != (B, n) or alpha.shape != (B, n):
+        raise ValueError(f"{who}: draws of shapes {idx.shape}, {alpha.shape}; expected [B,n] = {(B, n)} twice")
+    if idx.min() < 0 or idx.max() >= Nb:
+        raise ValueError(f"{who}: draws index outside [0, Nb = {Nb})")
+    if not np.isfinite(alpha).all():
+        raise ValueError(f"{who}: draws alpha is not finite")
+    return np.ascontiguousarray(idx.astype(np.int32)), np.ascontiguousarray(alpha.astype(np.float32))
+
+
+def gradient_shap(model, eeg, spec, background, *, input="eeg", nsamples=200, class_idx=None, seed=0, draws=None, max_batch=256, return_parts=False):
+    """Expected gradients (SHAP's GradientExplainer; the reference's ``shap.GradientExplainer(eeg_model, background).shap_values(x)``), for
+    either input of the multimodal model or a stand-alone branch, batched over samples, draws and classes:
+        phi[b,c] = (1/n) sum_k d[b,k] * dF_c/dx(r[b,k]),   d[b,k] = x[b] - bg[idx[b,k]],   r[b,k] = bg[idx[b,k]] + alpha[b,k] * d[b,k]
+    with F_c the model's output log-probability of class c.  The map has the input's own shape and fits ``deletion_insertion`` and
+    ``attribution_ranks`` as it is.
+
+    input:       'eeg': x = eeg [B,1,Chans,T], map [B,Chans,T]; 'spec': x = spec [B,C,H,W], map [B,H,W] = the values summed over the
+                 channels (a sum keeps the attributions additive).
+    model:       a MultimodalModel (the other input stays the sample's own); a stand-alone Spectrogram_Model (eeg=None, input='spec');
+                 a stand-alone EEGNet / EEGNetAttentionDeep (spec=None, input='eeg').
+    background:  [Nb, *x.shape[1:]], the set the baselines are drawn from.
+    nsamples:    n, the draws per sample.  One np.random.default_rng(seed) gives, sample by sample, idx = rng.integers(0, Nb, n) and then
+                 alpha = rng.random(n).astype(float32): the draws of ``expected_gradients`` for the same seed.
+    draws:       (idx [B,n] integer, alpha [B,n] float) replaces them.
+    class_idx:   None = each sample's arg-max class on the clean input; an int; one class per sample (sequence / tensor [B]); 'all' =
+                 every class, the map gains a class axis [B,K,...] (K <= 32): one forward pass then serves K backward passes.
+    max_batch:   rows (interpolants) per pass, capped so that a pass addresses its largest activation with 32-bit offsets.  The sum over
+                 the draws is carried in fp64 between passes, so, given the same gradients, no bit of the result depends on it.
+    The rows of a pass are written by one launch (bx_expgrad_rows), the one-hot gradient seeds by one (bx_expgrad_seed); every backward
+    pass is followed by one bx_expgrad_accumulate (fp64, ascending draw order, no atomics), and bx_expgrad_finish divides by n and sums
+    the channels.  In a MultimodalModel the branch whose input does not change runs once per sample and its output is gathered into the
+    fusion head.  The training flag and every requires_grad are restored on return.  Returns the map (device, fp32), or
+    ``GradientShapResult`` with return_parts."""
+    return _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, seed, draws, max_batch, return_parts)
+
+
+def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, seed, draws, max_batch, return_parts, profile=None):
+    """``gradient_shap`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'rows', 'forward',
+    'backward', 'accumulate', 'finish' -- device events around every phase of the pass (tools/gradient_shap_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "gradient_shap"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if isinstance(nsamples, bool) or not isinstance(nsamples, numbers.Integral):
+        raise ValueError(f"{who}: nsamples must be an int, got {nsamples!r}")
+    n, max_batch = int(nsamples), int(max_batch)
+    if n < 1:
+        raise ValueError(f"{who}: nsamples = {n} < 1")
+    if max_batch < 1:
+        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    x = _input_tensor(who, input, eeg, spec)
+    B = int(x.shape[0])
+    if B < 1 or x.numel() == 0:
+        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
+    if not isinstance(background, torch.Tensor) or background.dim() != 4 or tuple(background.shape[1:]) != tuple(x.shape[1:]):
+        got = tuple(background.shape) if isinstance(background, torch.Tensor) else type(background).__name__
+        raise ValueError(f"{who}: background of shape {got}; expected [Nb, {', '.join(str(int(v)) for v in x.shape[1:])}] like the {input} input")
+    Nb = int(background.shape[0])
+    if Nb < 1:
+        raise ValueError(f"{who}: empty background (Nb = 0)")
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    Kc = K if all_classes else 1
+    per = x.numel() // B
+    if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or Nb * per >= 1 << 31:
+        raise ValueError(f"{who}: B * n = {B * n}, B * Kc * per = {B * Kc * per} or Nb * per = {Nb * per} beyond 32-bit offsets; use fewer samples per call")
+    idx, alpha = _gradshap_draws(who, B, Nb, n, seed, draws)
+    if not (x.is_cuda and background.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
+        raise RuntimeError(f"brainxai.{who}: the model, its inputs and the background must live on the GPU; there is no CPU path")
+
+    lib = L.load()
+    dev = x.device
+    is_spec = input == "spec"
+    dt = getattr(net, "compute_dtype", torch.float32) if is_spec else torch.float32
+    max_rows = min(_row_cap(x, input, dt, max_batch), ((1 << 31) - 1) // per)
+    total = B * n
+    Cc, HW = (int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])) if is_spec else (1, per)
+
+    with torch.cuda.device(dev), _eval_frozen(model):
+        xs = x.detach().to(torch.float32).contiguous()
+        bgs = background.detach().to(dev, torch.float32).contiguous()
+        idx_d, alpha_d = torch.from_numpy(idx).to(dev), torch.from_numpy(alpha).to(dev)
+        fixed = None
+        with torch.no_grad(), _lap(profile, "forward"):
+            if multimodal:
+                fixed = _fixed_branch(model, other, is_spec)
+            out = _fuse(model, multimodal, is_spec, net(xs), fixed).float().contiguous()
+        if cls_h is not None:
+            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
+        elif all_classes:
+            classes = None
+        else:                                                       # the explained class: the arg-max on the clean input
+            classes = out.argmax(dim=1).to(torch.int32).contiguous()
+        acc = torch.zeros(B, Kc, per, dtype=torch.float64, device=dev)
+        for row0 in range(0, total, max_rows):
+            rows = min(max_rows, total - row0)
+            with _lap(profile, "rows"):
+                r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=dev)
+                L.check(lib.bx_expgrad_rows(_p(xs), _p(bgs), _p(idx_d), _p(alpha_d), _p(r), B, Nb, n, per, row0, rows, _stream()), "bx_expgrad_rows")
+            with _lap(profile, "forward"):
+                r.requires_grad_(True)
+                rep = None
+                if multimodal:                                      # the other branch's output of the sample each row belongs to
+                    rep = fixed.index_select(0, torch.div(torch.arange(row0, row0 + rows, device=dev), n, rounding_mode="floor"))
+                y = _fuse(model, multimodal, is_spec, net(r), rep).float()
+            seed_rows = torch.empty(rows, K, dtype=torch.float32, device=dev)
+            for slot in range(Kc):
+                with _lap(profile, "backward"):
+                    L.check(lib.bx_expgrad_seed(_p(classes), slot if all_classes else -1, _p(seed_rows), B, n, K, row0, rows, _stream()), "bx_expgrad_seed")
+                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows, retain_graph=slot + 1 < Kc)
+                    g = g.to(torch.float32).contiguous()
+                with _lap(profile, "accumulate"):
+                    L.check(lib.bx_expgrad_accumulate(_p(xs), _p(bgs), _p(idx_d), _p(g), _p(acc), B, Nb, n, per, Kc, slot, row0, rows, _stream()),
+                            "bx_expgrad_accumulate")
+            del y, r
+        with _lap(profile, "finish"):
+            values = torch.empty(B, Kc, *xs.shape[1:], dtype=torch.float32, device=dev)
+            amap = torch.empty(B, Kc, int(x.shape[2]), int(x.shape[3]), dtype=torch.float32, device=dev) if is_spec else None
+            L.check(lib.bx_expgrad_finish(_p(acc), _p(values), _p(amap), B * Kc, Cc, HW, n, _stream()), "bx_expgrad_finish")
+            if amap is None:
+                amap = values[:, :, 0]
+    if not all_classes:
+        amap, values = amap[:, 0], values[:, 0]
+    if not return_parts:
+        return amap
+    return GradientShapResult(amap, values, None if classes is None else classes.long(), out, idx, alpha, n)
+
+
+def channel_importance(values, top=None):
+    """The reference's reduction of its SHAP values (XAI_Multimodality.py: mean |.| over time per electrode, then the top-n electrodes):
+    mean |values| over the last axis of [..., L] -> fp32 [...], one launch (bx_mean_abs_rows: fp64 sum in a fixed order, one rounding).
+    With ``top=n`` returns (importance, indices): int64 [..., n], the n largest along the new last axis in descending order, ties by
+    the lower index.  On ``GradientShapResult.values`` [B,K,1,Chans,T] that is the reference's electrode ranking."""
+    who = "channel_importance"
+    if not isinstance(values, torch.Tensor) or values.dim() < 1 or values.numel() == 0:
+        raise ValueError(f"{who}: values must be a non-empty tensor [..., L]")
+    lead = tuple(int(v) for v in values.shape[:-1])
+    Ln = int(values.shape[-1])
+    R = values.numel() // Ln
+    if top is not None:
+        if isinstance(top, bool) or not isinstance(top, numbers.Integral):
+            raise ValueError(f"{who}: top must be None or an int, got {top!r}")
+        if not lead:
+            raise ValueError(f"{who}: top needs values with at least two axes [..., channels, L]")
+        if not 1 <= int(top) <= lead[-1]:
+            raise ValueError(f"{who}: top = {int(top)} outside 1..{lead[-1]}")
+    if R * Ln >= 1 << 31:
+        raise ValueError(f"{who}: {R * Ln} values beyond 32-bit offsets")
+    if not values.is_cuda:
+        raise RuntimeError(f"brainxai.{who}: the values must live on the GPU; there is no CPU path")
+    v = values.detach().to(torch.float32).contiguous()
+    imp = torch.empty(lead, dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        L.check(L.load().bx_mean_abs_rows(_p(v), _p(imp), R, Ln, _stream()), "bx_mean_abs_rows")
+    if top is None:
+        return imp
+    order = torch.sort(imp, dim=-1, descending=True, stable=True).indices
+    return imp, order[..., :int(top)].contiguous()
+
+
+class GradientExplainer:
+    """SHAP's calling form over ``gradient_shap``: ``GradientExplainer(model, background).shap_values(x)`` returns a list of K numpy
+    arrays shaped like x, one per class -- the reference's two lines (XAI_Multimodality.py:2283-2290) run unchanged apart from the
+    import.  ``input`` names the input x is ('eeg' or 'spec'); a MultimodalModel also takes the other input as ``other``."""
+
+    def __init__(self, model, background, input="eeg"):
+        if input not in _FAITH_INPUTS:
+            raise ValueError(f"GradientExplainer: unknown input {input!r}; use 'spec' or 'eeg'")
+        self.model, self.background, self.input = model, background, input
+
+    def shap_values(self, x, other=None, nsamples=200, seed=0):
+        eeg, spec = (x, other) if self.input == "eeg" else (other, x)
+        res = gradient_shap(self.model, eeg, spec, self.background, input=self.input, nsamples=nsamples, class_idx="all", seed=seed, return_parts=True)
+        vals = res.values.cpu().numpy()
+        return [vals[:, c] for c in range(vals.shape[1])]
