@@ -995,21 +995,33 @@ def _faith_chunks(B, P, max_rows):
             yield b0, min(nb, B - b0), i0, min(n, P - i0)
 
 
+def _empty_rows(x, rows, dt, eeg_rows):
+    """-> (out, dims): ``rows`` empty rows in the model's layout, [rows,H,W,pad8(C)] in dt with dims = (C, H, W, pad8(C)) for a
+    spectrogram x [B,C,H,W], fp32 [rows,1,Chans,T] with dims = (Chans, T) for eeg_rows."""
+    if eeg_rows:
+        _, _, Chans, T = x.shape
+        return torch.empty(rows, 1, Chans, T, dtype=torch.float32, device=x.device), (Chans, T)
+    _, Cc, H, W = x.shape
+    return torch.empty(rows, H, W, ops.pad8(Cc), dtype=dt, device=x.device), (Cc, H, W, ops.pad8(Cc))
+
+
+def _row_buffers(x, base, kind, b0, nb, n, dt, eeg_rows):
+    """What a row writer starts from -> (xs, bs, out, dims): samples b0..b0+nb-1 of x and of a kind-2 baseline (any other baseline as
+    it is), and the nb*n empty rows of ``_empty_rows``."""
+    return (x[b0:b0 + nb], base[b0:b0 + nb] if kind == 2 else base, *_empty_rows(x, nb * n, dt, eeg_rows))
+
+
 def _faith_perturb(x, ranks, base, kind, b0, nb, i0, n, per, insertion, dt, map_rows=None):
     """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1, of the perturbed batch at curve points i0 + j.  x: fp32 [B,C,H,W] -> internal
     layout [nb*n,H,W,8] in dt (bx_faith_perturb_spec), or with map_rows fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_faith_perturb_eeg)."""
     lib = L.load()
-    xs, rs = x[b0:b0 + nb], ranks[b0:b0 + nb]
-    bs = base[b0:b0 + nb] if kind == 2 else base
+    xs, bs, out, dims = _row_buffers(x, base, kind, b0, nb, n, dt, map_rows is not None)
+    rs = ranks[b0:b0 + nb]
     if map_rows is None:
-        _, Cc, H, W = x.shape
-        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
-        L.check(lib.bx_faith_perturb_spec(_p(xs), _p(rs), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), per, i0, n, 1 if insertion else 0,
-                                          ops.bx_dtype(dt), _stream()), "bx_faith_perturb_spec")
+        L.check(lib.bx_faith_perturb_spec(_p(xs), _p(rs), _p(bs), kind, _p(out), nb, *dims, per, i0, n, 1 if insertion else 0, ops.bx_dtype(dt),
+                                          _stream()), "bx_faith_perturb_spec")
     else:
-        _, _, Chans, T = x.shape
-        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
-        L.check(lib.bx_faith_perturb_eeg(_p(xs), _p(rs), map_rows, _p(bs), kind, _p(out), nb, Chans, T, per, i0, n, 1 if insertion else 0, _stream()),
+        L.check(lib.bx_faith_perturb_eeg(_p(xs), _p(rs), map_rows, _p(bs), kind, _p(out), nb, *dims, per, i0, n, 1 if insertion else 0, _stream()),
                 "bx_faith_perturb_eeg")
     return out
 
@@ -1036,8 +1048,8 @@ def _faith_baseline(baseline, x, per_len, what):
     return _baseline_for("deletion_insertion", baseline, x, per_len, what)
 
 
-# ---- what the perturb-and-predict drivers (deletion_insertion, rise, occlusion, score_cam) share: straight-line pieces, each driver
-# keeps its own order of checks and its own loop ----
+# ---- what the perturb-and-predict drivers (deletion_insertion, rise, occlusion, kernel_shap, score_cam) share: each driver keeps its
+# own order of checks, built from the pieces below, and its own clean pass; the rows all go through one _RowPass ----
 @contextlib.contextmanager
 def _lap(profile, name):
     """Device events around a phase, appended to ``profile`` as (name, start, end); nothing when profile is None."""
@@ -1049,6 +1061,29 @@ def _lap(profile, name):
     yield
     e1.record()
     profile.append((name, e0, e1))
+
+
+def _max_batch(who, v):
+    v = int(v)
+    if v < 1:
+        raise ValueError(f"{who}: max_batch = {v} < 1")
+    return v
+
+
+def _per_cell(who, x, input_is_spec):
+    """-> (per_len, what): the length and the name of a one-value-per-channel / per-electrode baseline; a spectrogram has 1..4 channels."""
+    if not input_is_spec:
+        return int(x.shape[2]), "electrode"
+    Cc = int(x.shape[1])
+    if not 1 <= Cc <= _FAITH_MAX_C:
+        raise ValueError(f"{who}: {Cc} channels, supported 1..{_FAITH_MAX_C}")
+    return Cc, "channel"
+
+
+def _need_gpu(who, what, model, *tensors):
+    """The closing refusal: every tensor that is given (None: a stand-alone model's other input) and the model live on the GPU."""
+    if not (all(t.is_cuda for t in tensors if t is not None) and next(model.parameters()).is_cuda):
+        raise RuntimeError(f"brainxai.{who}: {what} must live on the GPU; there is no CPU path")
 
 
 def _input_tensor(who, input, eeg, spec):
@@ -1138,6 +1173,79 @@ def _softmax_rows(logp):
     return probs
 
 
+def _class_tensor(cls_h, all_classes, clean_scores, dev):
+    """The explained classes as int32 [B] on the device, None for every class: the host list of ``_explained_classes``, or the arg-max
+    of the clean input's fp32 scores [B, K]."""
+    if cls_h is not None:
+        return torch.tensor(cls_h, dtype=torch.int32, device=dev)
+    if all_classes:
+        return None
+    return clean_scores.argmax(dim=1).to(torch.int32).contiguous()
+
+
+class _RowPass:
+    """What the five drivers do alike once their arguments are checked: rows of perturbed samples, written in the model's layout, run
+    through the branch that reads them, the other branch's per-sample output is repeated into the fusion head, and the scores of every
+    class land in fp32 [B, N, K].  A driver brings its row writer and its clean pass; the chunking by max_batch, the layout, the repeat,
+    the fusion and the 'perturb' / 'forward' laps of ``profile`` are here.  Inside ``open()``, ``xs`` is the explained input (fp32,
+    contiguous) and ``base`` the baseline on the device in its kind's shape; ``fixed`` is None until ``fix_other`` and for a
+    stand-alone model."""
+
+    def __init__(self, model, net, multimodal, K, x, other, input_is_spec, kind, base, max_batch, profile):
+        self.model, self.net, self.multimodal, self.K, self.other, self.input_is_spec = model, net, multimodal, K, other, input_is_spec
+        self.xs, self.kind, self.base, self.profile, self.fixed = x, kind, base, profile, None
+        self.dev, self.B = x.device, int(x.shape[0])
+        self.dt = getattr(net, "compute_dtype", torch.float32) if input_is_spec else torch.float32
+        self.max_rows = _row_cap(x, "spec" if input_is_spec else "eeg", self.dt, max_batch)
+
+    @contextlib.contextmanager
+    def open(self):
+        """The pass's device, eval mode with frozen parameters, no autograd."""
+        with torch.cuda.device(self.dev), _eval_frozen(self.model), torch.no_grad():
+            self.xs = self.xs.detach().to(torch.float32).contiguous()
+            self.base = self.base.to(self.dev, torch.float32).reshape(self.xs.shape if self.kind == 2 else (-1,)).contiguous()
+            yield self
+
+    def lap(self, name):
+        return _lap(self.profile, name)
+
+    def fix_other(self):
+        """Run the branch whose input does not change, once per sample (nothing for a stand-alone model); the lap is the driver's."""
+        if self.multimodal:
+            self.fixed = _fixed_branch(self.model, self.other, self.input_is_spec)
+
+    def groups(self):
+        """(b0, nb): the samples in groups of at most max_rows, the groups of ``sweep``."""
+        for b0 in range(0, self.B, self.max_rows):
+            yield b0, min(self.max_rows, self.B - b0)
+
+    def clean_rows(self, b0, nb):
+        """Samples b0..b0+nb-1 unperturbed, in the layout of the rows."""
+        return ops.to_nhwc(self.xs[b0:b0 + nb], self.dt) if self.input_is_spec else self.xs[b0:b0 + nb]
+
+    def scores(self, rows, b0, nb, n=1, logprob=False):
+        """fp32 [nb*n, K] log-probabilities (logprob) or probabilities of rows in the model's layout, n consecutive ones per sample of
+        b0..b0+nb-1; one row per sample takes the other branch's output as it is, without the launch of a repeat."""
+        rep = None
+        if self.fixed is not None:
+            rep = self.fixed[b0:b0 + nb]
+            if n > 1:
+                rep = rep.repeat_interleave(n, dim=0)
+        logp = _rows_forward(self.model, self.net, self.multimodal, self.input_is_spec, rows, rep)
+        return logp if logprob else _softmax_rows(logp)
+
+    def sweep(self, N, write, logprob=False):
+        """fp32 [B, N, K]: the scores of the N perturbed rows of every sample; ``write(b0, nb, n0, n)`` returns rows (b, j), b in
+        b0..b0+nb-1, j in n0..n0+n-1, sample-major, in the model's layout."""
+        out = torch.empty(self.B, N, self.K, dtype=torch.float32, device=self.dev)
+        for b0, nb, n0, n in _faith_chunks(self.B, N, self.max_rows):
+            with self.lap("perturb"):
+                rows = write(b0, nb, n0, n)
+            with self.lap("forward"):
+                out[b0:b0 + nb, n0:n0 + n] = self.scores(rows, b0, nb, n, logprob).reshape(nb, n, self.K)
+        return out
+
+
 def deletion_insertion(model, eeg, spec, attribution, *, input="spec", mode="both", steps=32, baseline=0.0, class_idx=None, score="prob",
                        max_batch=256):
     """Deletion and insertion curves of an attribution map (the causal metric of RISE, Petsiuk et al., BMVC 2018).
@@ -1177,20 +1285,18 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
         raise ValueError(f"{who}: unknown mode {mode!r}; use one of " + ", ".join(f"'{m}'" for m in _FAITH_MODES))
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
-    steps, max_batch = int(steps), int(max_batch)
-    if max_batch < 1:
-        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    steps = int(steps)
+    max_batch = _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
     if not isinstance(attribution, torch.Tensor):
         raise ValueError(f"{who}: attribution must be a tensor")
     B = int(x.shape[0])
+    per_len, what = _per_cell(who, x, input == "spec")
     if input == "spec":
-        Cc, H, W = (int(v) for v in x.shape[1:])
-        if not 1 <= Cc <= _FAITH_MAX_C:
-            raise ValueError(f"{who}: {Cc} channels, supported 1..{_FAITH_MAX_C}")
+        H, W = int(x.shape[2]), int(x.shape[3])
         if tuple(attribution.shape) != (B, H, W):
             raise ValueError(f"{who}: wrong map shape {tuple(attribution.shape)} for input='spec'; expected [B,H,W] = {(B, H, W)}")
-        map_rows, N, per_len, what = None, H * W, Cc, "channel"
+        map_rows, N = None, H * W
     else:
         Chans, T = int(x.shape[2]), int(x.shape[3])
         if tuple(attribution.shape) == (B, Chans, T):
@@ -1200,7 +1306,7 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
         else:
             raise ValueError(f"{who}: wrong map shape {tuple(attribution.shape)} for input='eeg'; expected [B,Chans,T] = {(B, Chans, T)} or "
                              f"[B,1,T] = {(B, 1, T)}")
-        N, per_len, what = map_rows * T, Chans, "electrode"
+        N = map_rows * T
     if B < 1 or not 1 <= N <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {N} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     if not 1 <= steps <= N:
@@ -1209,43 +1315,29 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
     multimodal, K, net = _target_model(who, model, x, other, input == "spec")
     cls_h, _ = _explained_classes(who, class_idx, B, K, allow_all=False)
     kind, base = _baseline_for(who, baseline, x, per_len, what)
-    if not (x.is_cuda and attribution.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
-        raise RuntimeError(f"brainxai.{who}: the model, its inputs and the attribution must live on the GPU; there is no CPU path")
+    _need_gpu(who, "the model, its inputs and the attribution", model, x, attribution, other if multimodal else None)
 
     lib = L.load()
     dev = x.device
     P, per = steps + 1, -(-N // steps)
-    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
-    max_rows = _row_cap(x, input, dt, max_batch)
+    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
 
-    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
-        xs = x.detach().to(torch.float32).contiguous()
-        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
-        with _lap(profile, "rank"):
+    with rp.open():
+        with rp.lap("rank"):
             ranks = attribution_ranks(attribution)
-        fixed = None
         if multimodal:
-            with _lap(profile, "forward"):
-                fixed = _fixed_branch(model, other, input == "spec")
+            with rp.lap("forward"):
+                rp.fix_other()
         logps = {}
         for m in ("deletion", "insertion"):
-            if mode not in ("both", m):
-                continue
-            logp = torch.empty(B, P, K, dtype=torch.float32, device=dev)
-            for b0, nb, i0, n in _faith_chunks(B, P, max_rows):
-                with _lap(profile, "perturb"):
-                    rows = _faith_perturb(xs, ranks, base, kind, b0, nb, i0, n, per, m == "insertion", dt, map_rows)
-                with _lap(profile, "forward"):
-                    rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0) if multimodal else None
-                    logp[b0:b0 + nb, i0:i0 + n] = _rows_forward(model, net, multimodal, input == "spec", rows, rep).reshape(nb, n, K)
-            logps[m] = logp
+            if mode in ("both", m):
+                logps[m] = rp.sweep(P, lambda *chunk: _faith_perturb(rp.xs, ranks, rp.base, kind, *chunk, per, m == "insertion", rp.dt, map_rows),
+                                    logprob=True)
+        # there is no clean pass: the unperturbed input is a curve's first or last point
         unperturbed = logps["deletion"][:, 0] if "deletion" in logps else logps["insertion"][:, P - 1]
-        if cls_h is None:
-            classes = unperturbed.argmax(dim=1).to(torch.int32).contiguous()
-        else:
-            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
+        classes = _class_tensor(cls_h, False, unperturbed, dev)
         res = {}
-        with _lap(profile, "curve"):
+        with rp.lap("curve"):
             for m, logp in logps.items():
                 curve = torch.empty(B, P, dtype=torch.float32, device=dev)
                 auc = torch.empty(B, dtype=torch.float64, device=dev)
@@ -1347,18 +1439,13 @@ def _rise_perturb(x, bits_d, shifts_d, geom, base, kind, b0, nb, n0, n, dt, map_
     """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1: sample b seen through mask n0 + j.  x fp32 [B,C,H,W] -> internal layout
     [nb*n,H,W,8] in dt (bx_rise_perturb_spec), or with map_rows fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_rise_perturb_eeg)."""
     lib = L.load()
-    xs = x[b0:b0 + nb]
-    bs = base[b0:b0 + nb] if kind == 2 else base
+    xs, bs, out, dims = _row_buffers(x, base, kind, b0, nb, n, dt, map_rows is not None)
     N = bits_d.shape[0]
     if map_rows is None:
-        _, Cc, H, W = x.shape
-        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
-        L.check(lib.bx_rise_perturb_spec(_p(xs), _p(bits_d), _p(shifts_d), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), N, geom[0], geom[1], n0, n,
+        L.check(lib.bx_rise_perturb_spec(_p(xs), _p(bits_d), _p(shifts_d), _p(bs), kind, _p(out), nb, *dims, N, geom[0], geom[1], n0, n,
                                          ops.bx_dtype(dt), _stream()), "bx_rise_perturb_spec")
     else:
-        _, _, Chans, T = x.shape
-        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
-        L.check(lib.bx_rise_perturb_eeg(_p(xs), _p(bits_d), _p(shifts_d), map_rows, _p(bs), kind, _p(out), nb, Chans, T, N, geom[0], geom[1], n0, n,
+        L.check(lib.bx_rise_perturb_eeg(_p(xs), _p(bits_d), _p(shifts_d), map_rows, _p(bs), kind, _p(out), nb, *dims, N, geom[0], geom[1], n0, n,
                                         _stream()), "bx_rise_perturb_eeg")
     return out
 
@@ -1408,20 +1495,15 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
         raise ValueError(f"{who}: unknown cells {cells!r}; use 'electrode_time' or 'time'")
     if cells == "time" and input != "eeg":
         raise ValueError(f"{who}: cells='time' masks time columns of the EEG input; input='spec' has no such map")
-    max_batch = int(max_batch)
-    if max_batch < 1:
-        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    max_batch = _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
     B = int(x.shape[0])
+    per_len, what = _per_cell(who, x, input == "spec")
     if input == "spec":
-        Cc, H, W = (int(v) for v in x.shape[1:])
-        if not 1 <= Cc <= _FAITH_MAX_C:
-            raise ValueError(f"{who}: {Cc} channels, supported 1..{_FAITH_MAX_C}")
-        map_rows, Hm, Wm, per_len, what = None, H, W, Cc, "channel"
+        map_rows, Hm, Wm = None, int(x.shape[2]), int(x.shape[3])
     else:
-        Chans, T = int(x.shape[2]), int(x.shape[3])
-        map_rows = 1 if cells == "time" else Chans
-        Hm, Wm, per_len, what = map_rows, T, Chans, "electrode"
+        map_rows = 1 if cells == "time" else int(x.shape[2])
+        Hm, Wm = map_rows, int(x.shape[3])
     if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     geom = _rise_geometry(who, grid, Hm, Wm)
@@ -1435,37 +1517,22 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     N = int(bits.shape[0])
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
-    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
-        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
 
     lib = L.load()
     dev = x.device
-    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
-    max_rows = _row_cap(x, input, dt, max_batch)
+    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
 
-    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
-        xs = x.detach().to(torch.float32).contiguous()
-        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+    with rp.open():
         bits_d, shifts_d = torch.from_numpy(bits).to(dev), torch.from_numpy(shifts).to(dev)
-        fixed = None
-        with _lap(profile, "forward"):
-            if multimodal:
-                fixed = _fixed_branch(model, other, input == "spec")
-            if cls_h is None and not all_classes:                   # the explained class: the arg-max on the unmasked input
-                clean = model(eeg, spec) if multimodal else model(xs)
-                classes = clean.float().argmax(dim=1).to(torch.int32).contiguous()
-        if cls_h is not None:
-            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
-        elif all_classes:
-            classes = None
-        P = torch.empty(B, N, K, dtype=torch.float32, device=dev)
-        for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
-            with _lap(profile, "perturb"):
-                rows = _rise_perturb(xs, bits_d, shifts_d, geom, base, kind, b0, nb, n0, n, dt, map_rows)
-            with _lap(profile, "forward"):
-                rep = fixed[b0:b0 + nb].repeat_interleave(n, dim=0) if multimodal else None
-                P[b0:b0 + nb, n0:n0 + n] = _softmax_rows(_rows_forward(model, net, multimodal, input == "spec", rows, rep)).reshape(nb, n, K)
-        with _lap(profile, "accumulate"):
+        clean = None
+        with rp.lap("forward"):
+            rp.fix_other()
+            if cls_h is None and not all_classes:                   # the explained class: the arg-max on the unmasked input, one pass
+                clean = (model(eeg, spec) if multimodal else model(rp.xs)).float()
+        classes = _class_tensor(cls_h, all_classes, clean, dev)
+        P = rp.sweep(N, lambda *chunk: _rise_perturb(rp.xs, bits_d, shifts_d, geom, rp.base, kind, *chunk, rp.dt, map_rows))
+        with rp.lap("accumulate"):
             sal = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
             coverage = torch.empty(Hm, Wm, dtype=torch.float32, device=dev)
             L.check(lib.bx_rise_accumulate(_p(P), _p(classes), _p(bits_d), _p(shifts_d), _p(sal), _p(coverage), B, N, K, geom[0], geom[1], Hm, Wm,
@@ -1513,18 +1580,12 @@ def _occlusion_perturb(x, geom, base, kind, b0, nb, n0, n, dt, eeg_input=False):
     layout [nb*n,H,W,8] in dt (bx_occlusion_perturb_spec), or with eeg_input fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T]
     (bx_occlusion_perturb_eeg)."""
     lib = L.load()
-    xs = x[b0:b0 + nb]
-    bs = base[b0:b0 + nb] if kind == 2 else base
-    wh, ww, sh, sw = geom[:4]
+    xs, bs, out, dims = _row_buffers(x, base, kind, b0, nb, n, dt, eeg_input)
     if not eeg_input:
-        _, Cc, H, W = x.shape
-        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
-        L.check(lib.bx_occlusion_perturb_spec(_p(xs), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), wh, ww, sh, sw, n0, n, ops.bx_dtype(dt),
-                                              _stream()), "bx_occlusion_perturb_spec")
+        L.check(lib.bx_occlusion_perturb_spec(_p(xs), _p(bs), kind, _p(out), nb, *dims, *geom[:4], n0, n, ops.bx_dtype(dt), _stream()),
+                "bx_occlusion_perturb_spec")
     else:
-        _, _, Chans, T = x.shape
-        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
-        L.check(lib.bx_occlusion_perturb_eeg(_p(xs), _p(bs), kind, _p(out), nb, Chans, T, wh, ww, sh, sw, n0, n, _stream()), "bx_occlusion_perturb_eeg")
+        L.check(lib.bx_occlusion_perturb_eeg(_p(xs), _p(bs), kind, _p(out), nb, *dims, *geom[:4], n0, n, _stream()), "bx_occlusion_perturb_eeg")
     return out
 
 
@@ -1568,18 +1629,11 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
         raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
-    max_batch = int(max_batch)
-    if max_batch < 1:
-        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    max_batch = _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
     B = int(x.shape[0])
     Hm, Wm = int(x.shape[2]), int(x.shape[3])
-    if input == "spec":
-        per_len, what = int(x.shape[1]), "channel"
-        if not 1 <= per_len <= _FAITH_MAX_C:
-            raise ValueError(f"{who}: {per_len} channels, supported 1..{_FAITH_MAX_C}")
-    else:
-        per_len, what = Hm, "electrode"
+    per_len, what = _per_cell(who, x, input == "spec")
     if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     geom = _occlusion_geometry(who, window, stride, Hm, Wm)
@@ -1593,46 +1647,23 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
-    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
-        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
 
     lib = L.load()
     dev = x.device
-    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
-    max_rows = _row_cap(x, input, dt, max_batch)
     use_logprob = score == "logprob"
+    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
 
-    def run(rows, rep):
-        """scores fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
-        logp = _rows_forward(model, net, multimodal, input == "spec", rows, rep)
-        return logp if use_logprob else _softmax_rows(logp)
-
-    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
-        xs = x.detach().to(torch.float32).contiguous()
-        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
-        fixed = None
-        with _lap(profile, "forward"):
-            if multimodal:
-                fixed = _fixed_branch(model, other, input == "spec")
+    with rp.open():
+        with rp.lap("forward"):
+            rp.fix_other()
             # the unperturbed input takes the path of the occluded rows, in chunks of the same size
             clean = torch.empty(B, K, dtype=torch.float32, device=dev)
-            for b0 in range(0, B, max_rows):
-                nb = min(max_rows, B - b0)
-                rows = ops.to_nhwc(xs[b0:b0 + nb], dt) if input == "spec" else xs[b0:b0 + nb]
-                clean[b0:b0 + nb] = run(rows, None if fixed is None else fixed[b0:b0 + nb])
-        if cls_h is not None:
-            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
-        elif all_classes:
-            classes = None
-        else:                                                       # the explained class: the arg-max on the unperturbed input
-            classes = clean.argmax(dim=1).to(torch.int32).contiguous()
-        S = torch.empty(B, N, K, dtype=torch.float32, device=dev)
-        for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
-            with _lap(profile, "perturb"):
-                rows = _occlusion_perturb(xs, geom, base, kind, b0, nb, n0, n, dt, input == "eeg")
-            with _lap(profile, "forward"):
-                S[b0:b0 + nb, n0:n0 + n] = run(rows, None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)).reshape(nb, n, K)
-        with _lap(profile, "accumulate"):
+            for b0, nb in rp.groups():
+                clean[b0:b0 + nb] = rp.scores(rp.clean_rows(b0, nb), b0, nb, logprob=use_logprob)
+        classes = _class_tensor(cls_h, all_classes, clean, dev)
+        S = rp.sweep(N, lambda *chunk: _occlusion_perturb(rp.xs, geom, rp.base, kind, *chunk, rp.dt, input == "eeg"), logprob=use_logprob)
+        with rp.lap("accumulate"):
             attr = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
             counts = torch.empty(Hm, Wm, dtype=torch.int32, device=dev)
             L.check(lib.bx_occlusion_accumulate(_p(S), _p(clean), _p(classes), _p(attr), _p(counts), B, N, K, Hm, Wm, *geom[:4], _stream()),
@@ -1752,18 +1783,13 @@ def _shap_perturb(x, seg_d, Z_d, M, base, kind, b0, nb, n0, n, dt, map_rows=None
     """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1: sample b under coalition n0 + j of Z_d.  x fp32 [B,C,H,W] -> internal layout
     [nb*n,H,W,8] in dt (bx_shap_perturb_spec), or with map_rows fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_shap_perturb_eeg)."""
     lib = L.load()
-    xs = x[b0:b0 + nb]
-    bs = base[b0:b0 + nb] if kind == 2 else base
+    xs, bs, out, dims = _row_buffers(x, base, kind, b0, nb, n, dt, map_rows is not None)
     N = Z_d.shape[0]
     if map_rows is None:
-        _, Cc, H, W = x.shape
-        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
-        L.check(lib.bx_shap_perturb_spec(_p(xs), _p(bs), kind, _p(out), nb, Cc, H, W, ops.pad8(Cc), _p(seg_d), _p(Z_d), M, N, n0, n, ops.bx_dtype(dt),
-                                         _stream()), "bx_shap_perturb_spec")
+        L.check(lib.bx_shap_perturb_spec(_p(xs), _p(bs), kind, _p(out), nb, *dims, _p(seg_d), _p(Z_d), M, N, n0, n, ops.bx_dtype(dt), _stream()),
+                "bx_shap_perturb_spec")
     else:
-        _, _, Chans, T = x.shape
-        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
-        L.check(lib.bx_shap_perturb_eeg(_p(xs), _p(bs), kind, _p(out), nb, Chans, T, map_rows, _p(seg_d), _p(Z_d), M, N, n0, n, _stream()),
+        L.check(lib.bx_shap_perturb_eeg(_p(xs), _p(bs), kind, _p(out), nb, *dims, map_rows, _p(seg_d), _p(Z_d), M, N, n0, n, _stream()),
                 "bx_shap_perturb_eeg")
     return out
 
@@ -1837,18 +1863,11 @@ def _kernel_shap(model, eeg, spec, input, segments, num_samples, baseline, class
         raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
-    max_batch = int(max_batch)
-    if max_batch < 1:
-        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    max_batch = _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
     B = int(x.shape[0])
     Hd, Wd = int(x.shape[2]), int(x.shape[3])
-    if input == "spec":
-        per_len, what = int(x.shape[1]), "channel"
-        if not 1 <= per_len <= _FAITH_MAX_C:
-            raise ValueError(f"{who}: {per_len} channels, supported 1..{_FAITH_MAX_C}")
-    else:
-        per_len, what = Hd, "electrode"
+    per_len, what = _per_cell(who, x, input == "spec")
     if B < 1 or not 1 <= Hd * Wd <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hd * Wd} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     seg, M = _shap_segments(who, segments, input, Hd, Wd)
@@ -1865,52 +1884,30 @@ def _kernel_shap(model, eeg, spec, input, segments, num_samples, baseline, class
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31 or N * M >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K}, B * K * Hm * Wm = {B * K * Hm * Wm} or N * M = {N * M} beyond 32-bit offsets; "
                          "use fewer samples per call")
-    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
-        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
 
     lib = L.load()
     dev = x.device
-    dt = getattr(net, "compute_dtype", torch.float32) if input == "spec" else torch.float32
-    max_rows = _row_cap(x, input, dt, max_batch)
     use_logprob = score == "logprob"
+    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
 
-    def run(rows, rep):
-        """scores fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
-        logp = _rows_forward(model, net, multimodal, input == "spec", rows, rep)
-        return logp if use_logprob else _softmax_rows(logp)
-
-    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
-        xs = x.detach().to(torch.float32).contiguous()
-        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+    with rp.open():
         seg_d, Z_d, w_d = torch.from_numpy(seg).to(dev), torch.from_numpy(Z).to(dev), torch.from_numpy(weights).to(dev)
         none_d = torch.zeros(1, M, dtype=torch.uint8, device=dev)      # the empty coalition: the baseline itself
-        fixed = None
         clean, empty = (torch.empty(B, K, dtype=torch.float32, device=dev) for _ in range(2))
         if multimodal:
-            with _lap(profile, "forward"):
-                fixed = _fixed_branch(model, other, input == "spec")
+            with rp.lap("forward"):
+                rp.fix_other()
         # v(1) and v(0): the unperturbed input and the baseline take the path of the coalition rows, in chunks of the same size
-        for b0 in range(0, B, max_rows):
-            nb = min(max_rows, B - b0)
-            rep = None if fixed is None else fixed[b0:b0 + nb]
-            with _lap(profile, "perturb"):
-                rows0 = _shap_perturb(xs, seg_d, none_d, M, base, kind, b0, nb, 0, 1, dt, map_rows)
-            with _lap(profile, "forward"):
-                clean[b0:b0 + nb] = run(ops.to_nhwc(xs[b0:b0 + nb], dt) if input == "spec" else xs[b0:b0 + nb], rep)
-                empty[b0:b0 + nb] = run(rows0, rep)
-        if cls_h is not None:
-            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
-        elif all_classes:
-            classes = None
-        else:                                                       # the explained class: the arg-max on the unperturbed input
-            classes = clean.argmax(dim=1).to(torch.int32).contiguous()
-        S = torch.empty(B, N, K, dtype=torch.float32, device=dev)
-        for b0, nb, n0, n in _faith_chunks(B, N, max_rows):
-            with _lap(profile, "perturb"):
-                rows = _shap_perturb(xs, seg_d, Z_d, M, base, kind, b0, nb, n0, n, dt, map_rows)
-            with _lap(profile, "forward"):
-                S[b0:b0 + nb, n0:n0 + n] = run(rows, None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)).reshape(nb, n, K)
-        with _lap(profile, "fit"):
+        for b0, nb in rp.groups():
+            with rp.lap("perturb"):
+                rows0 = _shap_perturb(rp.xs, seg_d, none_d, M, rp.base, kind, b0, nb, 0, 1, rp.dt, map_rows)
+            with rp.lap("forward"):
+                clean[b0:b0 + nb] = rp.scores(rp.clean_rows(b0, nb), b0, nb, logprob=use_logprob)
+                empty[b0:b0 + nb] = rp.scores(rows0, b0, nb, logprob=use_logprob)
+        classes = _class_tensor(cls_h, all_classes, clean, dev)
+        S = rp.sweep(N, lambda *chunk: _shap_perturb(rp.xs, seg_d, Z_d, M, rp.base, kind, *chunk, rp.dt, map_rows), logprob=use_logprob)
+        with rp.lap("fit"):
             phi = _shap_fit(S, clean, empty, classes, Z_d, w_d)
             R = phi.shape[1]
             attr = torch.empty((B, K, Hm, Wm) if all_classes else (B, Hm, Wm), dtype=torch.float32, device=dev)
@@ -1962,15 +1959,12 @@ def _scorecam_perturb(x, A, eeg_target, lo, scale, base, kind, b0, nb, k0, n, dt
     lib = L.load()
     pl = _scorecam_plane(A, eeg_target)
     B = x.shape[0]
+    out, dims = _empty_rows(x, nb * n, dt, eeg_target)               # no slices: the library takes the whole x and base, and b0
     if not eeg_target:
-        _, Cc, H, W = x.shape
-        out = torch.empty(nb * n, H, W, ops.pad8(Cc), dtype=dt, device=x.device)
-        L.check(lib.bx_scorecam_perturb_spec(_p(x), _p(A), *pl, _p(lo), _p(scale), _p(base), kind, _p(out), B, Cc, H, W, ops.pad8(Cc), b0, nb, k0, n,
-                                             ops.bx_dtype(dt), _stream()), "bx_scorecam_perturb_spec")
+        L.check(lib.bx_scorecam_perturb_spec(_p(x), _p(A), *pl, _p(lo), _p(scale), _p(base), kind, _p(out), B, *dims, b0, nb, k0, n, ops.bx_dtype(dt),
+                                             _stream()), "bx_scorecam_perturb_spec")
     else:
-        _, _, Chans, T = x.shape
-        out = torch.empty(nb * n, 1, Chans, T, dtype=torch.float32, device=x.device)
-        L.check(lib.bx_scorecam_perturb_eeg(_p(x), _p(A), pl[0], pl[1], pl[2], pl[4], pl[5], pl[7], _p(lo), _p(scale), _p(base), kind, _p(out), B, Chans, T,
+        L.check(lib.bx_scorecam_perturb_eeg(_p(x), _p(A), pl[0], pl[1], pl[2], pl[4], pl[5], pl[7], _p(lo), _p(scale), _p(base), kind, _p(out), B, *dims,
                                             b0, nb, k0, n, _stream()), "bx_scorecam_perturb_eeg")
     return out
 
@@ -2021,9 +2015,7 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
     who = "score_cam"
     if weights not in _SCORECAM_WEIGHTS:
         raise ValueError(f"{who}: unknown weights {weights!r}; use 'prob' or 'increase'")
-    max_batch = int(max_batch)
-    if max_batch < 1:
-        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    max_batch = _max_batch(who, max_batch)
     if not isinstance(target_layer, str):
         raise ValueError(f"{who}: target_layer must be a string, got {target_layer!r}")
     me, ms = _EEG_TARGET.match(target_layer), _TARGET.match(target_layer)
@@ -2053,37 +2045,28 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
         if not (g.F1 == 8 and g.D == 2 and g.F2 == 16 and g.K2 == 16 and g.K1 <= 64 and 1 <= Chans <= 64 and g.P1 <= T <= 15000):
             raise ValueError(f"{who}: EEG targets support the tuned EEGNet family only: F1=8, D=2, F2=16, K2=16, kernLength <= 64, Chans <= 64, "
                              f"T <= 15000 (got F1={g.F1}, D={g.D}, F2={g.F2}, kernLength={g.K1}, Chans={Chans}, T={T})")
-        Hm, Wm, per_len, what = 1, T, Chans, "electrode"
+        Hm, Wm = 1, T
     else:
-        Cc, H, W = (int(v) for v in x.shape[1:])
-        if not 1 <= Cc <= _FAITH_MAX_C:
-            raise ValueError(f"{who}: {Cc} channels, supported 1..{_FAITH_MAX_C}")
-        Hm, Wm, per_len, what = H, W, Cc, "channel"
+        Hm, Wm = int(x.shape[2]), int(x.shape[3])
+    per_len, what = _per_cell(who, x, not eeg_target)
     if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     if K > _RISE_MAX_K:
         raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
     cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
     kind, base = _baseline_for(who, baseline, x, per_len, what)
-    if not (x.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
-        raise RuntimeError(f"brainxai.{who}: the model and its inputs must live on the GPU; there is no CPU path")
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
 
     lib = L.load()
     dev = x.device
-    dt = torch.float32 if eeg_target else getattr(net, "compute_dtype", torch.float32)
-    max_rows = _row_cap(x, "eeg" if eeg_target else "spec", dt, max_batch)
     nm = K if all_classes else 1
+    rp = _RowPass(model, net, multimodal, K, x, other, not eeg_target, kind, base, max_batch, profile)
 
-    def probabilities(rows, rep):
-        """class probabilities fp32 [rows, K] of a batch in the model's layout; rep: the other branch's output, row for row"""
-        return _softmax_rows(_rows_forward(model, net, multimodal, not eeg_target, rows, rep))
-
-    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
-        xs = x.detach().to(torch.float32).contiguous()
-        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
-        with _lap(profile, "forward"):
+    with rp.open():
+        xs = rp.xs
+        with rp.lap("forward"):
             # the clean pass: the activation, the explained class, and the branch whose input does not change (once per sample)
-            fixed = _fixed_branch(model, other, not eeg_target) if multimodal else None
+            rp.fix_other()
             if eeg_target:
                 feat, saved, desc, _, _ = ops.eeg_features_keep(net, xs)
                 off_d, off_s = C.c_size_t(0), C.c_size_t(0)
@@ -2110,37 +2093,27 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
                     blk._preact, blk._capture = 0, None
                     if hook is not None:
                         hook.remove()
-            out = _fuse(model, multimodal, not eeg_target, clean, fixed).float().contiguous()
+            out = _fuse(model, multimodal, not eeg_target, clean, rp.fixed).float().contiguous()
         pl = _scorecam_plane(A, eeg_target)
         Cn, h, w = pl[5], pl[6], pl[7]
-        if cls_h is not None:
-            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
-        elif all_classes:
-            classes = None
-        else:
-            classes = out.argmax(dim=1).to(torch.int32).contiguous()
-        with _lap(profile, "range"):
+        classes = _class_tensor(cls_h, all_classes, out, dev)
+        with rp.lap("range"):
             lo, hi, scale = _scorecam_range(A, eeg_target, Hm, Wm)
             valid = hi > lo
         P_base = None
         if weights == "increase":
-            # the all-baseline input: the row of a channel whose scale is 0
+            # the all-baseline input: the row of a channel whose scale is 0.  Not a sweep(1, ...): the store into its [B,1,K] would be
+            # a launch that the concatenation of one sample group (the usual case) does not have
             zero = torch.zeros(B, Cn, dtype=torch.float32, device=dev)
-            for b0, nb, _, _ in _faith_chunks(B, 1, max_rows):
-                with _lap(profile, "perturb"):
-                    rows = _scorecam_perturb(xs, A, eeg_target, zero, zero, base, kind, b0, nb, 0, 1, dt)
-                with _lap(profile, "forward"):
-                    pb = probabilities(rows, None if fixed is None else fixed[b0:b0 + nb])
+            for b0, nb in rp.groups():
+                with rp.lap("perturb"):
+                    rows = _scorecam_perturb(xs, A, eeg_target, zero, zero, rp.base, kind, b0, nb, 0, 1, rp.dt)
+                with rp.lap("forward"):
+                    pb = rp.scores(rows, b0, nb)
                     P_base = pb if P_base is None else torch.cat([P_base, pb])
             P_base = P_base.contiguous()
-        P = torch.empty(B, Cn, K, dtype=torch.float32, device=dev)
-        for b0, nb, k0, n in _faith_chunks(B, Cn, max_rows):
-            with _lap(profile, "perturb"):
-                rows = _scorecam_perturb(xs, A, eeg_target, lo, scale, base, kind, b0, nb, k0, n, dt)
-            with _lap(profile, "forward"):
-                rep = None if fixed is None else fixed[b0:b0 + nb].repeat_interleave(n, dim=0)
-                P[b0:b0 + nb, k0:k0 + n] = probabilities(rows, rep).reshape(nb, n, K)
-        with _lap(profile, "combine"):
+        P = rp.sweep(Cn, lambda *chunk: _scorecam_perturb(xs, A, eeg_target, lo, scale, rp.base, kind, *chunk, rp.dt))
+        with rp.lap("combine"):
             raw = torch.empty(B * nm, h, w, dtype=torch.float32, device=dev)
             cam = torch.empty_like(raw) if relu else None
             wts = torch.empty(B * nm, Cn, dtype=torch.float32, device=dev)
@@ -2275,12 +2248,7 @@ def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, see
             if multimodal:
                 fixed = _fixed_branch(model, other, is_spec)
             out = _fuse(model, multimodal, is_spec, net(xs), fixed).float().contiguous()
-        if cls_h is not None:
-            classes = torch.tensor(cls_h, dtype=torch.int32, device=dev)
-        elif all_classes:
-            classes = None
-        else:                                                       # the explained class: the arg-max on the clean input
-            classes = out.argmax(dim=1).to(torch.int32).contiguous()
+        classes = _class_tensor(cls_h, all_classes, out, dev)
         acc = torch.zeros(B, Kc, per, dtype=torch.float64, device=dev)
         for row0 in range(0, total, max_rows):
             rows = min(max_rows, total - row0)

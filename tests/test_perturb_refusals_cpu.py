@@ -1,6 +1,6 @@
-"""CPU: the exact refusal texts of the four perturb-and-predict drivers (deletion_insertion, rise, occlusion, score_cam) for the argument
-errors their shared checks cover, and which of two errors is reported when two are present.  Tiny models and inputs; nothing reaches
-the library."""
+"""CPU: the exact refusal texts of the five perturb-and-predict drivers (deletion_insertion, rise, occlusion, kernel_shap, score_cam)
+for the argument errors their shared checks cover, and which of two errors is reported when two are present.  Tiny models and inputs;
+nothing reaches the library."""
 from types import SimpleNamespace
 
 import pytest
@@ -38,12 +38,15 @@ def _call(fn, kind, kw):
         kw.setdefault("window", 4)
     if fn == "rise":
         kw.setdefault("grid", 2)                                      # fits the 4 electrode rows of the EEG domain too
+    if fn == "kernel_shap":
+        kw.setdefault("segments", (2, 2))
     return getattr(brainxai, fn)(model, eeg, spec, **kw)
 
 
 GPU = {"deletion_insertion": "brainxai.deletion_insertion: the model, its inputs and the attribution must live on the GPU; there is no CPU path",
        "rise": "brainxai.rise: the model and its inputs must live on the GPU; there is no CPU path",
        "occlusion": "brainxai.occlusion: the model and its inputs must live on the GPU; there is no CPU path",
+       "kernel_shap": "brainxai.kernel_shap: the model and its inputs must live on the GPU; there is no CPU path",
        "score_cam": "brainxai.score_cam: the model and its inputs must live on the GPU; there is no CPU path"}
 SHAPE_MSG = ("baseline of shape {} is none of: a number, one value per {} [{}], a tensor of the input's shape {}")
 
@@ -54,7 +57,7 @@ def _add(name, fn, kind, kw, exc, msg):
     CASES.append(pytest.param(fn, kind, kw, exc, msg, id=f"{fn}-{name}"))
 
 
-for who in ("deletion_insertion", "rise", "occlusion"):
+for who in ("deletion_insertion", "rise", "occlusion", "kernel_shap"):
     all_ok = who != "deletion_insertion"
     use = "use None, an int, one class per sample or 'all'" if all_ok else "use None, an int or one class per sample"
     must = f"must be None, an int, 'all' or {B} integers (one class per sample)" if all_ok else f"must be None, an int or {B} integers (one class per sample)"
@@ -108,9 +111,9 @@ for who in ("deletion_insertion", "rise", "occlusion"):
                            ("cpu_eegnet", "eegnet", dict(input="eeg", class_idx=torch.tensor([5, 0]), baseline=True))]:
         _add(name, who, kind, kw, RuntimeError, GPU[who])
 
-# more than 32 classes: deletion_insertion has no such limit, the three others refuse before they look at class_idx
+# more than 32 classes: deletion_insertion has no such limit, the others refuse before they look at class_idx
 _add("classes_33", "deletion_insertion", "spectrogram33", dict(), RuntimeError, GPU["deletion_insertion"])
-for who in ("rise", "occlusion"):
+for who in ("rise", "occlusion", "kernel_shap"):
     _add("classes_33", who, "spectrogram33", dict(), ValueError, f"{who}: 33 classes, supported 1..32")
     _add("classes_33_eeg", who, "eegnet33", dict(input="eeg"), ValueError, f"{who}: 33 classes, supported 1..32")
     _add("classes_33_and_class_word", who, "spectrogram33", dict(class_idx="every"), ValueError, f"{who}: 33 classes, supported 1..32")
