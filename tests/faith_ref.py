@@ -7,6 +7,8 @@ A map has N cells per sample.  Spectrogram input [B,C,H,W]: map [B,H,W], a cell 
 import numpy as np
 import torch
 
+from tests.perturb_ref import baseline_tensor  # noqa: F401  (part of this module's interface)
+
 
 def keys(a):
     """fp32 sort keys [B,N]: NaN counts as -inf, -0.0 as +0.0."""
@@ -51,17 +53,6 @@ def cell_mask(rank, k, shape):
         return below.reshape(B, 1, shape[2], shape[3])
     assert below.shape[1] == shape[3], (below.shape, shape)        # time columns of [B,1,Chans,T]
     return below.reshape(B, 1, 1, shape[3])
-
-
-def baseline_tensor(baseline, x):
-    """The three baseline forms as a tensor broadcastable to x: a number; one value per channel (x [B,C,H,W]) or per electrode
-    (x [B,1,Chans,T]); a tensor of x's shape."""
-    if np.ndim(baseline) == 0:
-        return torch.full((1, 1, 1, 1), float(baseline), dtype=x.dtype)
-    t = torch.as_tensor(np.asarray(baseline)).to(x.dtype)
-    if t.dim() == 1:
-        return t.reshape(1, 1, -1, 1) if x.shape[1] == 1 else t.reshape(1, -1, 1, 1)    # [B,1,Chans,T]: per electrode; else per channel
-    return t.reshape(x.shape)
 
 
 def perturbed(x, rank, baseline, k, insertion):

@@ -20,6 +20,8 @@ import math
 import numpy as np
 import torch
 
+from tests.perturb_ref import baseline_tensor, score_fn, sweep  # noqa: F401  (baseline_tensor is part of this module's interface)
+
 
 def coalition_set(M, num_samples, seed=0):
     """-> (Z uint8 [N,M], w fp64 [N], exact)."""
@@ -47,17 +49,6 @@ def grid_segments(H, W, rows, cols):
 def masks(seg, Z):
     """bool [N,Hm,Wm]: True where coalition n shows the input."""
     return np.asarray(Z).astype(bool)[:, np.asarray(seg)]
-
-
-def baseline_tensor(baseline, x):
-    """The three baseline forms as a tensor broadcastable to x: a number; one value per channel (x [B,C,H,W]) or per electrode
-    (x [B,1,Chans,T]); a tensor of x's shape."""
-    if np.ndim(baseline) == 0:
-        return torch.full((1, 1, 1, 1), float(baseline), dtype=x.dtype)
-    t = torch.as_tensor(np.asarray(baseline)).to(x.dtype)
-    if t.dim() == 1:
-        return t.reshape(1, 1, -1, 1) if x.shape[1] == 1 else t.reshape(1, -1, 1, 1)
-    return t.reshape(x.shape)
 
 
 def perturbed(x, m, baseline):
@@ -137,16 +128,10 @@ def scores(f, x, m, baseline=0.0, score="prob", chunk=32):
     """f: input rows [R,...] -> log-probabilities (or logits) [R,K] (torch).  Returns (S [B,N,K], clean [B,K], empty [B,K]) fp64 numpy:
     the softmax probability (score='logprob': its logarithm) of sample b under coalition n, of the unperturbed sample and of the
     baseline.  f sees coalition-major batches [n*B, ...]: the samples of coalition n0, then those of n0 + 1, ..."""
-    B, N = x.shape[0], m.shape[0]
-    fn = (lambda z: torch.log_softmax(z.double(), dim=1)) if score == "logprob" else (lambda z: torch.softmax(z.double(), dim=1))
-    rows = []
+    S, clean = sweep(f, x, m, baseline, perturbed, score, True, chunk)
     with torch.no_grad():
-        clean = fn(f(x)).numpy()
-        empty = fn(f(perturbed(x, np.zeros_like(m[0]), baseline))).numpy()
-        for n0 in range(0, N, chunk):
-            out = fn(f(torch.cat([perturbed(x, m[n], baseline) for n in range(n0, min(N, n0 + chunk))])))
-            rows.append(out.reshape(-1, B, out.shape[1]))
-    return torch.cat(rows).permute(1, 0, 2).contiguous().numpy(), clean, empty
+        empty = score_fn(score)(f(perturbed(x, np.zeros_like(m[0]), baseline))).numpy()
+    return S, clean, empty
 
 
 def all_coalition_values(M, game):

@@ -7,6 +7,8 @@ j = iy * nx + ix covers rows [iy sh, min(iy sh + wh, Hm)) and columns [ix sw, mi
 import numpy as np
 import torch
 
+from tests.perturb_ref import baseline_tensor, sweep  # noqa: F401  (baseline_tensor is part of this module's interface)
+
 
 def pair(v):
     return (int(v), int(v)) if np.ndim(v) == 0 else (int(v[0]), int(v[1]))
@@ -38,17 +40,6 @@ def masks(Hm, Wm, window, stride=None):
     return m
 
 
-def baseline_tensor(baseline, x):
-    """The three baseline forms as a tensor broadcastable to x: a number; one value per channel (x [B,C,H,W]) or per electrode
-    (x [B,1,Chans,T]); a tensor of x's shape."""
-    if np.ndim(baseline) == 0:
-        return torch.full((1, 1, 1, 1), float(baseline), dtype=x.dtype)
-    t = torch.as_tensor(np.asarray(baseline)).to(x.dtype)
-    if t.dim() == 1:
-        return t.reshape(1, 1, -1, 1) if x.shape[1] == 1 else t.reshape(1, -1, 1, 1)
-    return t.reshape(x.shape)
-
-
 def perturbed(x, m, baseline):
     """x [B,C,H,W] or [B,1,Chans,T] with the cells of one window m (bool [Hm,Wm]) taken from the baseline: a selection (torch.where)."""
     base = baseline_tensor(baseline, x).expand_as(x)
@@ -71,13 +62,4 @@ def scores(f, x, m, baseline=0.0, score="prob", chunk=32):
     """f: input rows [R,...] -> log-probabilities (or logits) [R,K] (torch).  Returns (S [B,N,K], S0 [B,K]) fp64 numpy: the softmax
     probability (score='logprob': its logarithm) of sample b with window n occluded, and of the unperturbed sample.  f sees
     window-major batches [n*B, ...]: the samples of window n0, then those of window n0 + 1, ..."""
-    B, N = x.shape[0], m.shape[0]
-    fn = (lambda z: torch.log_softmax(z.double(), dim=1)) if score == "logprob" else (lambda z: torch.softmax(z.double(), dim=1))
-    rows = []
-    with torch.no_grad():
-        S0 = fn(f(x)).numpy()
-        for n0 in range(0, N, chunk):
-            xs = torch.cat([perturbed(x, m[n], baseline) for n in range(n0, min(N, n0 + chunk))])
-            out = fn(f(xs))
-            rows.append(out.reshape(-1, B, out.shape[1]))
-    return torch.cat(rows).permute(1, 0, 2).contiguous().numpy(), S0
+    return sweep(f, x, m, baseline, perturbed, score, True, chunk)

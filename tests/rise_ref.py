@@ -8,6 +8,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from tests.perturb_ref import baseline_tensor, sweep  # noqa: F401  (baseline_tensor is part of this module's interface)
+
 f32 = np.float32
 
 
@@ -62,17 +64,6 @@ def masks_interpolate(bits, shifts, Hm, Wm):
     return np.stack([up[n, int(dy):int(dy) + Hm, int(dx):int(dx) + Wm].numpy() for n, (dy, dx) in enumerate(np.asarray(shifts))])
 
 
-def baseline_tensor(baseline, x):
-    """The three baseline forms as a tensor broadcastable to x: a number; one value per channel (x [B,C,H,W]) or per electrode
-    (x [B,1,Chans,T]); a tensor of x's shape."""
-    if np.ndim(baseline) == 0:
-        return torch.full((1, 1, 1, 1), float(baseline), dtype=x.dtype)
-    t = torch.as_tensor(np.asarray(baseline)).to(x.dtype)
-    if t.dim() == 1:
-        return t.reshape(1, 1, -1, 1) if x.shape[1] == 1 else t.reshape(1, -1, 1, 1)
-    return t.reshape(x.shape)
-
-
 def perturbed(x, m, baseline):
     """base + m * (x - base) in x's dtype, three roundings.  x [B,C,H,W] or [B,1,Chans,T]; m one mask [Hm,Wm] (Hm = 1: a time-column
     mask, applied to every electrode)."""
@@ -97,12 +88,5 @@ def saliency(P, m, p1, normalize="expected"):
 
 def scores(f, x, m, baseline=0.0, chunk=64):
     """f: perturbed input [R,...] -> log-probabilities [R,K] (torch).  Returns P [B,N,K] fp64 numpy: softmax probabilities of sample b
-    seen through mask n."""
-    B, N = x.shape[0], m.shape[0]
-    rows = []
-    with torch.no_grad():
-        for n0 in range(0, N, chunk):
-            xs = torch.cat([perturbed(x, m[n], baseline) for n in range(n0, min(N, n0 + chunk))])      # mask-major [n*B, ...]
-            out = torch.softmax(f(xs).double(), dim=1)
-            rows.append(out.reshape(-1, B, out.shape[1]))
-    return torch.cat(rows).permute(1, 0, 2).contiguous().numpy()
+    seen through mask n.  f sees mask-major batches [n*B, ...]."""
+    return sweep(f, x, m, baseline, perturbed, "prob", False, chunk)

@@ -7,7 +7,7 @@ across electrodes).  Every product and every sum of ``upsample``, ``mask`` and t
 import numpy as np
 import torch
 
-from tests import rise_ref
+from tests import perturb_ref, rise_ref
 
 f32 = np.float32
 
@@ -84,13 +84,8 @@ def combine(w, A):
 def scores(f, x, M, baseline=0.0, chunk=64):
     """f: perturbed input [R,...] of ONE sample -> log-probabilities [R,K] (torch; called as f(b, rows)).  Returns P [B,C,K] fp64:
     the softmax probabilities of sample b seen through channel k."""
-    B, C = M.shape[:2]
-    out = []
-    with torch.no_grad():
-        for b in range(B):
-            per = []
-            for k0 in range(0, C, chunk):
-                xs = rows(x, M, baseline, b, 1, k0, min(chunk, C - k0))
-                per.append(torch.softmax(f(b, xs).double(), dim=1))
-            out.append(torch.cat(per))
-    return torch.stack(out).numpy()
+    per = []
+    for b in range(M.shape[0]):
+        bb = baseline[b:b + 1] if isinstance(baseline, torch.Tensor) and baseline.dim() == 4 else baseline
+        per.append(perturb_ref.sweep(lambda xs: f(b, xs), x[b:b + 1], M[b], bb, rise_ref.perturbed, "prob", False, chunk))
+    return np.concatenate(per)

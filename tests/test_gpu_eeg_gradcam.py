@@ -6,11 +6,11 @@ import torch.nn.functional as F
 
 import brainxai
 from oracle import ref_torch as O
+from tests.eeg_gradcam_setup import TARGETS, bn_nontrivial, inputs
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 TOL = 1e-3                     # north_star: 1e-3 relative fp32
-TARGETS = ("conv1", "depthwiseConv", "separableConv")
 
 
 def _rel(a, b, scale=None):
@@ -19,25 +19,12 @@ def _rel(a, b, scale=None):
     return float((a.detach().cpu().double() - b).abs().max()) / (scale + 1e-30)
 
 
-def _bn_nontrivial(eeg_net, seed):
-    """BatchNorm running statistics and affine parameters far from identity, so that every s_k / h_k enters the maps."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for name in ("batchnorm1", "batchnorm2", "batchnorm3"):
-            bn = getattr(eeg_net, name)
-            n = bn.num_features
-            bn.running_mean.copy_(torch.rand(n, generator=g) * 1.0 - 0.5)
-            bn.running_var.copy_(torch.rand(n, generator=g) * 2.8 + 0.2)
-            bn.weight.copy_(torch.rand(n, generator=g) * 1.7 + 0.3)
-            bn.bias.copy_(torch.rand(n, generator=g) * 1.0 - 0.5)
-
-
 def _mm_pair(chans, samples, seed=5, kern=64):
     ref = O.build_multimodal(chans, samples, 4, dropout=0.0)
     if kern != 64:
         ref.eeg_model = O.EEGNet(6, Chans=chans, Samples=samples, dropoutRate=0.0, kernLength=kern)
     O.fill_params(ref, seed=seed)
-    _bn_nontrivial(ref.eeg_model, seed + 1)
+    bn_nontrivial(ref.eeg_model, seed + 1)
     mine = brainxai.build_multimodal(chans, samples, 4, dropout=0.0)
     if kern != 64:
         mine.eeg_model = brainxai.EEGNet(6, Chans=chans, Samples=samples, dropoutRate=0.0, kernLength=kern)
@@ -54,10 +41,6 @@ class _Two(torch.nn.Module):
 
     def forward(self, eeg, _spec):
         return self.eeg_model(eeg)
-
-
-def _inputs(B, chans, samples, seed=11):
-    return O.seeded((B, 1, chans, samples), seed, "randn"), O.seeded((B, 4, 32, 64), seed + 1, "rand")
 
 
 def _check(ref, mine, eeg, spec, target, class_idx):
@@ -85,7 +68,7 @@ def bench_pair():
 @pytest.mark.parametrize("target", TARGETS)
 def test_eeg_gradcam_matches_oracle(bench_pair, target, class_idx):
     ref, mine = bench_pair
-    eeg, spec = _inputs(2, 19, 2000)
+    eeg, spec = inputs(2, 19, 2000)
     _check(ref, mine, eeg, spec, target, class_idx)
 
 
@@ -93,7 +76,7 @@ def test_eeg_gradcam_matches_oracle(bench_pair, target, class_idx):
 def test_eeg_gradcam_pool_tails_and_native_geometry(chans, samples, B):
     # 2100 and 300: T//4 is not a multiple of 8, so the second pooling drops a tail (T2*P2 < T1)
     ref, mine = _mm_pair(chans, samples, seed=7)
-    eeg, spec = _inputs(B, chans, samples, seed=13)
+    eeg, spec = inputs(B, chans, samples, seed=13)
     for target in TARGETS:
         _check(ref, mine, eeg, spec, target, "all")
 
@@ -101,14 +84,14 @@ def test_eeg_gradcam_pool_tails_and_native_geometry(chans, samples, B):
 def test_eeg_gradcam_kernlength_32():
     # a 32-tap conv1 takes the layer-by-layer evaluation path (its arena also holds the conv1 output)
     ref, mine = _mm_pair(19, 2000, seed=9, kern=32)
-    eeg, spec = _inputs(2, 19, 2000, seed=17)
+    eeg, spec = inputs(2, 19, 2000, seed=17)
     for target in TARGETS:
         _check(ref, mine, eeg, spec, target, "all")
 
 
 def test_eeg_gradcam_bench_batch(bench_pair):
     ref, mine = bench_pair
-    eeg, spec = _inputs(64, 19, 2000, seed=19)
+    eeg, spec = inputs(64, 19, 2000, seed=19)
     for target in TARGETS:
         _check(ref, mine, eeg, spec, target, None)
 
@@ -117,7 +100,7 @@ def test_eeg_gradcam_bench_batch(bench_pair):
 def test_eeg_gradcam_standalone_nets(cls):
     chans, samples = 19, 2048
     ref_net = O.fill_params(getattr(O, cls)(6, Chans=chans, Samples=samples, dropoutRate=0.0), seed=21)
-    _bn_nontrivial(ref_net, 22)
+    bn_nontrivial(ref_net, 22)
     mine = getattr(brainxai, cls)(6, Chans=chans, Samples=samples, dropoutRate=0.0)
     mine.load_state_dict(ref_net.state_dict())
     mine.to(DEV)
@@ -135,7 +118,7 @@ def test_eeg_gradcam_standalone_nets(cls):
 
 def test_eeg_gradcam_upsample(bench_pair):
     _, mine = bench_pair
-    eeg, spec = (t.to(DEV) for t in _inputs(2, 19, 2000, seed=29))
+    eeg, spec = (t.to(DEV) for t in inputs(2, 19, 2000, seed=29))
     small = brainxai.grad_cam(mine, eeg, spec, "eeg_model.separableConv", "all", upsample=False)
     up = brainxai.grad_cam(mine, eeg, spec, "eeg_model.separableConv", "all", upsample=True)
     assert tuple(small.shape) == (2, 6, 1, 500) and tuple(up.shape) == (2, 6, 1, 2000)
@@ -153,7 +136,7 @@ def test_eeg_gradcam_bf16_storage():
     mine16.load_state_dict(ref.state_dict())
     brainxai.set_compute_dtype(mine16, torch.bfloat16)
     mine16.to(DEV)
-    eeg, spec = (t.to(DEV) for t in _inputs(2, 19, 2000, seed=37))
+    eeg, spec = (t.to(DEV) for t in inputs(2, 19, 2000, seed=37))
     for target in TARGETS:
         _, r32, *_ = brainxai.grad_cam(mine32, eeg, spec, "eeg_model." + target, "all", upsample=False, return_parts=True, relu=False)
         _, r16, *_ = brainxai.grad_cam(mine16, eeg, spec, "eeg_model." + target, "all", upsample=False, return_parts=True, relu=False)
@@ -162,7 +145,7 @@ def test_eeg_gradcam_bf16_storage():
 
 def test_eeg_gradcam_restores_state_and_leaves_spectrogram_path(bench_pair):
     _, mine = bench_pair
-    eeg, spec = (t.to(DEV) for t in _inputs(2, 19, 2000, seed=41))
+    eeg, spec = (t.to(DEV) for t in inputs(2, 19, 2000, seed=41))
     mine.train()
     mine.fc1.weight.requires_grad_(False)
     flags = [p.requires_grad for p in mine.parameters()]

@@ -24,24 +24,12 @@ from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
 from tests import gradient_shap_ref as R
+from tests import perturb_gpu as PG
 from tests.golden_util import matched_oracle
-from tests.test_gpu_faithfulness import _scaled_multimodal
+from tests.perturb_gpu import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 TOL = 1e-3
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(DEV)
 
 
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
@@ -70,10 +58,10 @@ def test_rows_bit_for_bit(name):
     want = R.rows(x, bg, IDX, ALPHA)
     assert np.signbit(want).any() and not np.isnan(want).any()
     lib = L.load()
-    xd, bd, idx_d, alpha_d = _dev(x), _dev(bg), _dev(IDX), _dev(ALPHA)
+    xd, bd, idx_d, alpha_d = PG.dev(x), PG.dev(bg), PG.dev(IDX), PG.dev(ALPHA)
     for row0, rows in WINDOWS:
         out = torch.full((rows, *shape), float("nan"), dtype=torch.float32, device=DEV)
-        L.check(lib.bx_expgrad_rows(_p(xd), _p(bd), _p(idx_d), _p(alpha_d), _p(out), KB, KNB, KN, per, row0, rows, _stream()), "bx_expgrad_rows")
+        L.check(lib.bx_expgrad_rows(PG.p(xd), PG.p(bd), PG.p(idx_d), PG.p(alpha_d), PG.p(out), KB, KNB, KN, per, row0, rows, PG.stream()), "bx_expgrad_rows")
         got = out.cpu().numpy()
         assert not np.isnan(got).any(), f"{name} rows {row0}..{row0 + rows}: elements left unwritten"
         assert np.array_equal(got.view(np.int32), want[row0:row0 + rows].view(np.int32)), f"{name} rows {row0}..{row0 + rows}"
@@ -93,7 +81,7 @@ def test_accumulate_and_finish_against_numpy(name, Kc):
     slot = Kc // 2
     g = O.seeded((rows_all, *shape), 7, "randn")
     lib = L.load()
-    xd, bd, idx_d, gd = _dev(x), _dev(bg), _dev(IDX), _dev(g)
+    xd, bd, idx_d, gd = PG.dev(x), PG.dev(bg), PG.dev(IDX), PG.dev(g)
     SENTINEL = 7.25
 
     def run(splits):
@@ -101,7 +89,7 @@ def test_accumulate_and_finish_against_numpy(name, Kc):
         acc[:, slot] = 0.0
         for row0, rows in splits:
             gs = gd[row0:row0 + rows].contiguous()
-            L.check(lib.bx_expgrad_accumulate(_p(xd), _p(bd), _p(idx_d), _p(gs), _p(acc), KB, KNB, KN, per, Kc, slot, row0, rows, _stream()),
+            L.check(lib.bx_expgrad_accumulate(PG.p(xd), PG.p(bd), PG.p(idx_d), PG.p(gs), PG.p(acc), KB, KNB, KN, per, Kc, slot, row0, rows, PG.stream()),
                     "bx_expgrad_accumulate")
         return acc
     one, two = run([(0, rows_all)]), run([(0, 7), (7, rows_all - 7)])                    # row 7 is inside sample 1
@@ -116,7 +104,7 @@ def test_accumulate_and_finish_against_numpy(name, Kc):
     acc[:, others] = 0.0
     values = torch.full((KB, Kc, *shape), float("nan"), dtype=torch.float32, device=DEV)
     amap = torch.full((KB, Kc, shape[1], shape[2]), float("nan"), dtype=torch.float32, device=DEV) if spec else None
-    L.check(lib.bx_expgrad_finish(_p(acc), _p(values), _p(amap), KB * Kc, Cc, HW, KN, _stream()), "bx_expgrad_finish")
+    L.check(lib.bx_expgrad_finish(PG.p(acc), PG.p(values), PG.p(amap), KB * Kc, Cc, HW, KN, PG.stream()), "bx_expgrad_finish")
     values = values.cpu().numpy()
     assert not np.isnan(values).any()
     want = (want_acc[:, 0] / KN).reshape(KB, *shape)
@@ -136,7 +124,7 @@ def test_accumulate_and_finish_against_numpy(name, Kc):
 def test_mean_abs_rows_against_numpy(Ln):
     v = O.seeded((3, 7, Ln), 40 + Ln, "randn")                            # 21 rows: the last workgroup is not full
     v.view(-1)[::5] = -0.0
-    got = brainxai.channel_importance(_dev(v))
+    got = brainxai.channel_importance(PG.dev(v))
     assert got.shape == (3, 7) and got.dtype == torch.float32
     want = R.channel_importance(v.numpy())
     bound = np.abs(want) * 2.0 ** -23 + Ln * 2.0 ** -52 * np.abs(v.numpy().astype(np.float64)).mean()
@@ -149,7 +137,7 @@ def test_channel_importance_top_with_exact_ties():
     v = O.seeded((2, 8, 333), 9, "randn")
     v[:, 4], v[:, 6] = -v[:, 1], v[:, 1].abs()                            # the same |.| in the same order: exact ties of channels 1, 4, 6
     v[:, 0], v[:, 7] = 0.0, -0.0                                          # and a tie at zero
-    imp, order = brainxai.channel_importance(_dev(v), top=8)
+    imp, order = brainxai.channel_importance(PG.dev(v), top=8)
     imp_h, order_h = imp.cpu().numpy(), order.cpu().numpy()
     assert order.dtype == torch.int64 and order_h.shape == (2, 8)
     assert np.array_equal(imp_h[:, 1], imp_h[:, 4]) and np.array_equal(imp_h[:, 1], imp_h[:, 6]) and not imp_h[:, [0, 7]].any()
@@ -158,7 +146,7 @@ def test_channel_importance_top_with_exact_ties():
     for b in range(2):
         pos = {int(c): i for i, c in enumerate(order_h[b])}
         assert pos[1] + 1 == pos[4] and pos[4] + 1 == pos[6], "ties by the lower index"
-    imp3, top3 = brainxai.channel_importance(_dev(v), top=3)
+    imp3, top3 = brainxai.channel_importance(PG.dev(v), top=3)
     assert torch.equal(imp3, imp) and np.array_equal(top3.cpu().numpy(), want[:, :3])
     assert np.array_equal(R.channel_importance(v.numpy(), top=8)[1], want)
 
@@ -203,7 +191,7 @@ def _eeg_case(kind):
         mine = brainxai.EEGNetAttentionDeep(6, Chans=19, Samples=2000, dropoutRate=0.0)
         x, bg, other, n, seed, max_batch = _mm_inputs()[0], O.seeded((3, 1, 19, 2000), 14, "randn"), None, 6, 3, 256
     else:
-        ref, mine = _scaled_multimodal()
+        ref, mine = PG.scaled_multimodal()
         (x, other), bg, n, seed, max_batch = _mm_inputs(), O.seeded((3, 1, 19, 2000), 14, "randn"), 6, 3, 256
     if kind != "multimodal":
         mine.load_state_dict(ref.state_dict())
@@ -282,12 +270,12 @@ def _composed(model, eeg, spec, bg, idx_d, alpha_d, max_batch):
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_spec_input_against_the_same_pass_from_pieces(dt):
     """The gradients are then the same launches on the same bits: what remains is the bound of the accumulate kernel."""
-    _, mine = _scaled_multimodal(dt)
+    _, mine = PG.scaled_multimodal(dt)
     eeg, spec, bg, idx, alpha = _spec_case()
     eeg, spec, bg = eeg.to(DEV), spec.to(DEV), bg.to(DEV)
     max_batch = 5                                                         # three passes; the first two end inside a sample
     res = brainxai.gradient_shap(mine, eeg, spec, bg, input="spec", nsamples=6, class_idx="all", draws=(idx, alpha), max_batch=max_batch, return_parts=True)
-    r_all, want, absacc = _composed(mine, eeg, spec, bg, _dev(idx), _dev(alpha), max_batch)
+    r_all, want, absacc = _composed(mine, eeg, spec, bg, PG.dev(idx), PG.dev(alpha), max_batch)
     assert np.array_equal(r_all.cpu().numpy().view(np.int32), R.rows(spec, bg, idx, alpha).view(np.int32)), "the composed rows are not the restatement's"
     assert res.values.shape == (2, 6, 4, 32, 64) and res.attribution.shape == (2, 6, 32, 64)
     want, absacc = want.cpu().numpy(), absacc.cpu().numpy()
@@ -300,7 +288,7 @@ def test_spec_input_against_the_same_pass_from_pieces(dt):
 
 
 def test_spec_input_against_the_fp64_oracle():
-    ref, mine = _scaled_multimodal()
+    ref, mine = PG.scaled_multimodal()
     eeg, spec, bg, idx, alpha = _spec_case()
     B, n = idx.shape
     f64 = copy.deepcopy(ref).double().eval()
@@ -335,7 +323,7 @@ def test_spec_input_against_the_fp64_oracle():
 # ---- interface --------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _iface():
-    _, mine = _scaled_multimodal()
+    _, mine = PG.scaled_multimodal()
     eeg, spec, bg, idx, alpha = _spec_case()
     return mine, eeg.to(DEV), spec.to(DEV), O.seeded((3, 1, 19, 2000), 14, "randn").to(DEV), bg.to(DEV)
 

@@ -665,14 +665,14 @@ def test_eeg_target_gradcam_at_n_classes(N):
     """Grad-CAM at the EEG branch's convolutions with N classes (bx_eeg_gradcam gets N gradient maps under "all"), at the
     tolerance of tests/test_gpu_eeg_gradcam.py, against the oracle's hook Grad-CAM in fp64: this two-class model puts
     p = 1 - 1.6e-6 on its arg-max class, where the fp32 oracle's log-softmax backward keeps only 2 digits of 1 - p."""
-    from tests.test_gpu_eeg_gradcam import TARGETS, _bn_nontrivial, _inputs
+    from tests.eeg_gradcam_setup import TARGETS, bn_nontrivial, inputs
     ref = O.fill_params(O.build_multimodal(19, 2000, 4, num_classes=N, dropout=0.0), seed=80 + N)
-    _bn_nontrivial(ref.eeg_model, 81 + N)
+    bn_nontrivial(ref.eeg_model, 81 + N)
     mine = brainxai.build_multimodal(19, 2000, 4, num_classes=N, dropout=0.0)
     mine.load_state_dict(ref.state_dict())
     mine.to(DEV)
     ref64 = copy.deepcopy(ref).double()
-    eeg, spec = _inputs(2, 19, 2000, seed=83)
+    eeg, spec = inputs(2, 19, 2000, seed=83)
     for target in TARGETS:
         for class_idx in (None, N - 1, "all"):
             cam_r, raw_r, w_r, A_r, _ = O.grad_cam(ref64, eeg.double(), spec.double(), "eeg_model." + target, class_idx, upsample=False,

@@ -1,16 +1,13 @@
 """GPU: brainxai.kernel_shap and the bx_shap_* entry points against the restatement of the definition (tests/kernel_shap_ref.py):
 perturbed rows bit for bit, the fit against numpy fp64 and brute-force Shapley values, and the values end to end against the oracle's
-classes run in fp64 on the CPU with the same coalitions, in the setting of tests/test_gpu_faithfulness.py (its models and inputs are
-imported).
+classes run in fp64 on the CPU with the same coalitions, on the models and inputs of tests/perturb_gpu.py.
 
 Bounds.  bx_shap_fit alone: (M + N) 2^-52 kappa(Xt' W Xt) max|phi_ref| per case -- the textbook bound of a Cholesky solve with the
 length of the Gram sums added; kappa is computed by the test.  End to end, fp32 storage: |scores - ref| <= 1e-5, the project's
-probability bound (TOL of test_gpu_faithfulness.py), and |values - ref| <= amp 1e-5 with amp the largest absolute row sum of the fit's
-solution operator (the columns of clean and empty included; computed in numpy): the fit is linear in the scores.  Every compared case is
-first checked ON THE REFERENCE SIDE to discriminate: the reference values with the score rows shuffled across the coalitions differ
-from the true ones by more than 100 x the bound for every sample.  Additivity: |sum_m values - (clean - empty)| <= 2^-50 sum_m |values|,
-the sum taken exactly (math.fsum).  bf16 storage: amp x 2e-2 x the log-probability scale, the derived bf16 bound of
-test_bf16_storage_maps (tests/test_gpu_rise.py) applied to the scores.
+probability bound (TOL of tests/perturb_gpu.py), and |values - ref| <= amp 1e-5 with amp the largest absolute row sum of the fit's
+solution operator (the columns of clean and empty included; computed in numpy): the fit is linear in the scores.  Every compared case
+passes the guard of tests/perturb_gpu.py first.  Additivity: |sum_m values - (clean - empty)| <= 2^-50 sum_m |values|, the sum taken
+exactly (math.fsum).  bf16 storage: amp x BF16_LOGP x the log-probability scale (tests/perturb_gpu.py), the bound applied to the scores.
 Observed worst figures are printed by each test (run with -s) and recorded in DESIGN.md section 6."""
 import copy
 import functools
@@ -26,41 +23,11 @@ from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
 from tests import kernel_shap_ref as R
-from tests import test_gpu_faithfulness as FT
+from tests import perturb_gpu as PG
+from tests.perturb_gpu import DEV, TOL
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-TOL = 1e-5
 EPS = 2.0 ** -52
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(DEV)
-
-
-def _bits(t):
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
-
-
-def _row_windows(N):
-    """(n0, n): all rows; a range that starts past 0, crosses the kernel's groups of 8 and ends on the last coalition; the last alone."""
-    return sorted({(0, N), (N // 3, N - N // 3), (N - 1, 1)})
-
-
-def _want_rows(x, m, base, n0, n):
-    rows = []
-    for b in range(x.shape[0]):
-        bb = base[b:b + 1] if isinstance(base, torch.Tensor) and base.dim() == 4 else base
-        rows += [R.perturbed(x[b:b + 1], m[n0 + j], bb) for j in range(n)]
-    return torch.cat(rows)
 
 
 def _random_map(Hm, Wm, M, seed):
@@ -90,26 +57,16 @@ def test_perturbed_spectrogram_rows_bit_for_bit(shape, kind, dt):
     assert np.array_equal(np.unique(seg), np.arange(M))
     if shape == "2x16x24 grid 2x3":
         assert N == 62 and np.array_equal(X._shap_segments("kernel_shap", (2, 3), "spec", H, W)[0], seg)
-    x = O.seeded((B, C, H, W), 3, "randn")
-    x[:, :, ::7, ::5] = -0.0
+    x, base, bkind, base_d = PG.row_inputs((B, C, H, W), kind)
     m = R.masks(seg, Z)
     assert m[:, seg == M - 1].any() and (~m[:, seg == M - 1]).any(), "the last player is shown in some rows and hidden in others"
-    base = FT._baseline(kind, x, 4)
-    bkind, base_d = FT._base_dev(base)
-    x_d, seg_d, Z_d = x.to(DEV), _dev(seg), _dev(Z)
-    for n0, n in _row_windows(N):
-        out = torch.full((B * n, H, W, 8), float("nan"), dtype=dt, device=DEV)
-        L.check(L.load().bx_shap_perturb_spec(_p(x_d), _p(base_d), bkind, _p(out), B, C, H, W, 8, _p(seg_d), _p(Z_d), M, N, n0, n, ops.bx_dtype(dt), _stream()),
+    x_d, seg_d, Z_d = x.to(DEV), PG.dev(seg), PG.dev(Z)
+
+    def launch(out, n0, n):
+        L.check(L.load().bx_shap_perturb_spec(PG.p(x_d), PG.p(base_d), bkind, PG.p(out), B, C, H, W, 8, PG.p(seg_d), PG.p(Z_d), M, N, n0, n, ops.bx_dtype(dt), PG.stream()),
                 "bx_shap_perturb_spec")
-        want = ops.to_nhwc(_want_rows(x, m, base, n0, n).to(DEV), dt)
-        torch.cuda.synchronize()
-        assert not torch.isnan(out.float()).any(), "unwritten elements"
-        assert out.shape == want.shape and torch.equal(_bits(out), _bits(want)), f"{shape} {kind} rows {(n0, n)}"
-        helper = X._shap_perturb(x_d, seg_d, Z_d, M, base_d, bkind, 0, B, n0, n, dt)
-        assert torch.equal(_bits(helper), _bits(want))
-        one = X._shap_perturb(x_d, seg_d, Z_d, M, base_d, bkind, 1, 1, n0, n, dt)                   # a sample group that does not start at 0
-        assert torch.equal(_bits(one), _bits(want[n:]))
-    assert float(out[:, :, :, C:].float().abs().max()) == 0.0
+    PG.check_spec_rows(launch, lambda b, j, bb: R.perturbed(x[b:b + 1], m[j], bb), x, base, PG.row_windows(N),
+                       lambda b0, nb, n0, n: X._shap_perturb(x_d, seg_d, Z_d, M, base_d, bkind, b0, nb, n0, n, dt), dt, f"{shape} {kind}")
 
 
 # ---- 2. perturbed EEG rows, bit for bit -----------------------------------------------------------------------------------------------------
@@ -131,22 +88,15 @@ def test_perturbed_eeg_rows_bit_for_bit(shape, kind):
     named = {"19x2000 electrodes": "electrodes", "37x3000 time 8": ("time", 8)}.get(shape)
     if named is not None:
         assert np.array_equal(X._shap_segments("kernel_shap", named, "eeg", chans, T)[0], seg)
-    x = O.seeded((B, 1, chans, T), 6, "randn")
-    x[:, :, ::3, ::11] = -0.0
+    x, base, bkind, base_d = PG.row_inputs((B, 1, chans, T), kind)
     m = R.masks(seg, Z)
-    base = FT._baseline(kind, x, 8)
-    bkind, base_d = FT._base_dev(base)
-    x_d, seg_d, Z_d = x.to(DEV), _dev(seg), _dev(Z)
-    for n0, n in _row_windows(N):
-        out = torch.full((B * n, 1, chans, T), float("nan"), dtype=torch.float32, device=DEV)
-        L.check(L.load().bx_shap_perturb_eeg(_p(x_d), _p(base_d), bkind, _p(out), B, chans, T, map_rows, _p(seg_d), _p(Z_d), M, N, n0, n, _stream()),
+    x_d, seg_d, Z_d = x.to(DEV), PG.dev(seg), PG.dev(Z)
+
+    def launch(out, n0, n):
+        L.check(L.load().bx_shap_perturb_eeg(PG.p(x_d), PG.p(base_d), bkind, PG.p(out), B, chans, T, map_rows, PG.p(seg_d), PG.p(Z_d), M, N, n0, n, PG.stream()),
                 "bx_shap_perturb_eeg")
-        want = _want_rows(x, m, base, n0, n).to(DEV)
-        torch.cuda.synchronize()
-        assert not torch.isnan(out).any(), "unwritten elements"
-        assert out.shape == want.shape and torch.equal(_bits(out), _bits(want)), f"{shape} {kind} rows {(n0, n)}"
-        helper = X._shap_perturb(x_d, seg_d, Z_d, M, base_d, bkind, 1, 1, n0, n, torch.float32, map_rows)
-        assert torch.equal(_bits(helper), _bits(want[n:]))
+    PG.check_eeg_rows(launch, lambda b, j, bb: R.perturbed(x[b:b + 1], m[j], bb), x, base, PG.row_windows(N),
+                      lambda b0, nb, n0, n: X._shap_perturb(x_d, seg_d, Z_d, M, base_d, bkind, b0, nb, n0, n, torch.float32, map_rows), f"{shape} {kind}")
 
 
 # ---- 3. the fit alone -----------------------------------------------------------------------------------------------------------------------
@@ -160,7 +110,8 @@ def _fit(S_d, clean_d, empty_d, cls_d, Z_d, w_d, fill=7.0):
     ws = torch.full((nbytes // 8,), float("nan"), dtype=torch.float64, device=DEV)
     phi = torch.full((B, K if cls_d is None else 1, M), fill, dtype=torch.float64, device=DEV)
     info = torch.full((1,), -1, dtype=torch.int32, device=DEV)
-    L.check(lib.bx_shap_fit(_p(S_d), _p(clean_d), _p(empty_d), _p(cls_d), _p(Z_d), _p(w_d), B, N, K, M, _p(ws), nbytes, _p(phi), _p(info), _stream()), "bx_shap_fit")
+    L.check(lib.bx_shap_fit(PG.p(S_d), PG.p(clean_d), PG.p(empty_d), PG.p(cls_d), PG.p(Z_d), PG.p(w_d), B, N, K, M, PG.p(ws), nbytes, PG.p(phi), PG.p(info),
+                            PG.stream()), "bx_shap_fit")
     torch.cuda.synchronize()
     return phi.cpu().numpy(), int(info.item())
 
@@ -183,11 +134,11 @@ def test_fit_against_numpy_fp64(case, B):
     want = R.values(Z, w, S, clean, empty)                          # [B,K,M], the normal equations
     kappa = R.gram_cond(Z, w)
     bound = (M + N) * EPS * kappa * np.abs(want).max()
-    S_d, clean_d, empty_d, Z_d, w_d = (_dev(a) for a in (S, clean, empty, Z, w))
+    S_d, clean_d, empty_d, Z_d, w_d = (PG.dev(a) for a in (S, clean, empty, Z, w))
     got, info = _fit(S_d, clean_d, empty_d, None, Z_d, w_d)
     assert info == 0 and got.shape == (B, K, M) and np.isfinite(got).all()
     err = float(np.abs(got - want).max())
-    got_c, info_c = _fit(S_d, clean_d, empty_d, _dev(classes), Z_d, w_d)
+    got_c, info_c = _fit(S_d, clean_d, empty_d, PG.dev(classes), Z_d, w_d)
     sel = np.arange(B)
     assert info_c == 0 and got_c.shape == (B, 1, M) and np.array_equal(got_c[:, 0].view(np.int64), got[sel, classes].view(np.int64))
     lstsq = float(np.abs(R.values(Z, w, S, clean, empty, "lstsq") - want).max())
@@ -217,14 +168,14 @@ def test_fit_refuses_a_rank_deficient_set():
     N = Z.shape[0]
     assert N >= M - 1 and np.linalg.matrix_rank(R.reduced(Z, np.ones(N))[2]) == M - 2
     g = np.random.default_rng(0)
-    S, clean, empty = (_dev(g.random(s).astype(np.float32)) for s in ((2, N, K), (2, K), (2, K)))
-    phi, info = _fit(S, clean, empty, None, _dev(Z), _dev(np.ones(N)))
+    S, clean, empty = (PG.dev(g.random(s).astype(np.float32)) for s in ((2, N, K), (2, K), (2, K)))
+    phi, info = _fit(S, clean, empty, None, PG.dev(Z), PG.dev(np.ones(N)))
     print(f"bx_shap_fit rank-deficient set: info {info}")
     assert info == 6 and (phi == 7.0).all(), "the pivot of the second twin (index 5) vanishes; phi stays untouched"
     with pytest.raises(ValueError, match="undetermined.*more samples"):
-        X._shap_fit(S, clean, empty, None, _dev(Z), _dev(np.ones(N)))
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+        X._shap_fit(S, clean, empty, None, PG.dev(Z), PG.dev(np.ones(N)))
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     with pytest.raises(ValueError, match="undetermined.*more samples"):
         brainxai.kernel_shap(mine, eeg, spec, segments=(2, 4), coalitions=(Z, None))
 
@@ -235,8 +186,8 @@ def test_value_map_is_the_gather():
         seg = _random_map(Hm, Wm, M, M)
         phi = g.standard_normal((B, Rr, M))
         out = torch.full((B, Rr, Hm, Wm), float("nan"), dtype=torch.float32, device=DEV)
-        phi_d, seg_d = _dev(phi), _dev(seg)
-        L.check(L.load().bx_shap_value_map(_p(phi_d), _p(seg_d), _p(out), B, Rr, Hm, Wm, M, _stream()), "bx_shap_value_map")
+        phi_d, seg_d = PG.dev(phi), PG.dev(seg)
+        L.check(L.load().bx_shap_value_map(PG.p(phi_d), PG.p(seg_d), PG.p(out), B, Rr, Hm, Wm, M, PG.stream()), "bx_shap_value_map")
         assert np.array_equal(out.cpu().numpy(), phi.astype(np.float32)[:, :, seg])
 
 
@@ -257,8 +208,8 @@ def _reference(which):
     deviation, they move by 2e-2 (520 - 630 x)."""
     with torch.no_grad():
         if which in ("mm spec", "mm eeg"):
-            ref_model, _ = FT._scaled_multimodal()
-            eeg, spec = FT._mm_inputs()
+            ref_model, _ = PG.scaled_multimodal()
+            eeg, spec = PG.mm_inputs()
             r64 = copy.deepcopy(ref_model).double()
             if which == "mm spec":
                 seg, (Z, w, _) = R.grid_segments(64, 128, 2, 3), R.coalition_set(6, 2 * 6 + 2048)
@@ -271,12 +222,12 @@ def _reference(which):
             full = r64(eeg.double(), spec.double())
             assert float((f(x.double()) - full).abs().max()) <= 1e-12
         elif which == "spectrogram":
-            ref_model, _ = FT._scaled_multimodal()
+            ref_model, _ = PG.scaled_multimodal()
             n64 = copy.deepcopy(ref_model.spectrogram_model).double()
             seg, (Z, w, _) = R.grid_segments(64, 128, 3, 4), R.coalition_set(12, 40)
-            x, f = FT._mm_inputs()[1], lambda xs: n64(xs)
+            x, f = PG.mm_inputs()[1], lambda xs: n64(xs)
         else:
-            ref_model, _ = FT._eegnet_pair()
+            ref_model, _ = PG.eegnet_pair()
             n64 = copy.deepcopy(ref_model).double()
             seg, (Z, w, _) = R.grid_segments(1, 2000, 1, 6), R.coalition_set(6, 2 * 6 + 2048)
             x, f = O.seeded((3, 1, 19, 2000), 91, "randn"), lambda xe: n64(xe)
@@ -289,10 +240,8 @@ def _guarded(Z, w, S, clean, empty, cls, what, unit=TOL):
     B, N = S.shape[0], S.shape[1]
     phi, amp = R.values(Z, w, S, clean, empty), R.amplification(Z, w)
     shuffled = R.values(Z, w, S[:, np.random.RandomState(1).permutation(N)], clean, empty)
-    moved = np.array([np.abs(phi[b, cls[b]] - shuffled[b, cls[b]]).max() for b in range(B)])
-    print(f"{what}: reference classes {cls} amp {amp:.3g} kappa {R.gram_cond(Z, w):.3g} max|values| {[round(float(np.abs(phi[b, cls[b]]).max()), 4) for b in range(B)]} "
-          f"|values - shuffled| / bound {(moved / (amp * unit)).round(0)}")
-    assert moved.min() > 100 * amp * unit, f"{what}: shuffling the scores moves the reference values by {moved.min():.1e} only"
+    shown = f"amp {amp:.3g} kappa {R.gram_cond(Z, w):.3g} max|values| {[round(float(np.abs(phi[b, cls[b]]).max()), 4) for b in range(B)]}"
+    PG.guard_moved(phi, shuffled, cls, amp * unit, what, shown, "values")
     return phi, amp
 
 
@@ -321,8 +270,8 @@ def _check(res, seg, Z, w, S, clean, empty, cls, what, all_classes=False):
 @pytest.mark.parametrize("class_idx", [None, 5, "all"], ids=["argmax", "class 5", "all classes"])
 def test_spectrogram_input_exact_against_fp64_oracle(class_idx):
     seg, Z, w, S, clean, empty = _reference("mm spec")
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     res = brainxai.kernel_shap(mine, eeg, spec, segments=(2, 3), class_idx=class_idx, return_parts=True)
     assert res.exact and Z.shape == (62, 6)
     cls = clean.argmax(1) if class_idx in (None, "all") else np.full(3, class_idx)
@@ -340,12 +289,12 @@ def test_spectrogram_input_exact_against_fp64_oracle(class_idx):
 
 def test_eeg_input_electrodes_against_fp64_oracle():
     seg, Z, w, S, clean, empty = _reference("mm eeg")
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     mine.train()
-    before = mine.training, [p.requires_grad for p in mine.parameters()]
+    before = PG.model_state(mine)
     res = brainxai.kernel_shap(mine, eeg, spec, input="eeg", segments="electrodes", num_samples=64, baseline=EEG_BASE, return_parts=True)
-    assert (mine.training, [p.requires_grad for p in mine.parameters()]) == before and all(p.grad is None for p in mine.parameters())
+    assert PG.model_state(mine) == before and all(p.grad is None for p in mine.parameters())
     cls = clean.argmax(1)
     assert not res.exact and np.array_equal(res.classes.cpu().numpy(), cls) and tuple(res.attribution.shape) == (3, 19, 2000) and tuple(res.values.shape) == (3, 19)
     _check(res, seg, Z, w, S, clean, empty, cls, "multimodal EEG input, electrodes, N = 64")
@@ -358,8 +307,8 @@ def test_eeg_input_electrodes_against_fp64_oracle():
 
 def test_stand_alone_spectrogram_model_against_fp64_oracle():
     seg, Z, w, S, clean, empty = _reference("spectrogram")
-    _, mine = FT._scaled_multimodal()
-    spec = FT._mm_inputs()[1].to(DEV)
+    _, mine = PG.scaled_multimodal()
+    spec = PG.mm_inputs()[1].to(DEV)
     res = brainxai.kernel_shap(mine.spectrogram_model, None, spec, segments=(3, 4), num_samples=40, return_parts=True)
     cls = clean.argmax(1)
     assert not res.exact and np.array_equal(res.classes.cpu().numpy(), cls)
@@ -368,7 +317,7 @@ def test_stand_alone_spectrogram_model_against_fp64_oracle():
 
 def test_stand_alone_eegnet_against_fp64_oracle():
     seg, Z, w, S, clean, empty = _reference("eegnet")
-    _, mine = FT._eegnet_pair()
+    _, mine = PG.eegnet_pair()
     xe = O.seeded((3, 1, 19, 2000), 91, "randn").to(DEV)
     res = brainxai.kernel_shap(mine, xe, None, input="eeg", segments=("time", 6), class_idx="all", score="prob", return_parts=True)
     assert res.exact and res.classes is None and tuple(res.attribution.shape) == (3, 6, 1, 2000) and tuple(res.values.shape) == (3, 6, 6)
@@ -382,18 +331,17 @@ def test_stand_alone_eegnet_against_fp64_oracle():
 # ---- 5. bf16 storage ----------------------------------------------------------------------------------------------------------------------
 def test_bf16_storage_values():
     """bf16 storage.  The rows are bit-identical to the host-built ones (test_perturbed_spectrogram_rows_bit_for_bit); the values stay
-    within the project's derived bf16 bound of the fp64 oracle's: log-probabilities within 2e-2 of their scale
-    (test_bench_config_bf16_train_step), |dp| = p |dlogp| <= |dlogp| for every score -- coalitions, clean and empty -- carried through
-    the fit's solution operator, whose largest absolute row sum is amp."""
+    within the project's derived bf16 bound of the fp64 oracle's (BF16_LOGP of tests/perturb_gpu.py) for every score -- coalitions,
+    clean and empty -- carried through the fit's solution operator, whose largest absolute row sum is amp."""
     seg, Z, w, S, clean, empty = _reference("mm spec")
-    ref_model, mine = FT._scaled_multimodal(torch.bfloat16)
-    eeg, spec = FT._mm_inputs()
-    with torch.no_grad():
-        scale = float(copy.deepcopy(ref_model).double()(eeg.double(), spec.double()).abs().max())
+    ref_model, mine = PG.scaled_multimodal(torch.bfloat16)
+    eeg, spec = PG.mm_inputs()
+    scale = PG.logp_scale(ref_model, eeg, spec)
     res = brainxai.kernel_shap(mine, eeg.to(DEV), spec.to(DEV), segments=(2, 3), return_parts=True)
     cls = clean.argmax(1)
     assert np.array_equal(res.classes.cpu().numpy(), cls)
     phi, amp = _guarded(Z, w, S, clean, empty, cls, "multimodal spec input (bf16 case)")
     worst = float(np.abs(res.values.cpu().numpy() - phi[np.arange(3), cls]).max())
-    print(f"kernel_shap multimodal spec input 2x3 grid, bf16 storage: |values - reference| {worst:.2e} (bound {amp * 2e-2 * scale:.2e}, log-probability scale {scale:.2f})")
-    assert worst <= amp * 2e-2 * scale
+    print(f"kernel_shap multimodal spec input 2x3 grid, bf16 storage: |values - reference| {worst:.2e} (bound {amp * PG.BF16_LOGP * scale:.2e}, "
+          f"log-probability scale {scale:.2f})")
+    assert worst <= amp * PG.BF16_LOGP * scale

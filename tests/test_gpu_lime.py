@@ -19,22 +19,11 @@ from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
 from tests import lime_ref as R
+from tests import perturb_gpu as PG
+from tests.perturb_gpu import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 TOL = 1e-9
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _pair(make_ref, make_mine, seed):
@@ -65,8 +54,8 @@ def _u8(shape, seed):
 def _segment_mean(img, seg, S):
     B, H, W, C = img.shape
     col = torch.empty(B, S, C, dtype=torch.uint8, device=DEV)
-    img_d, seg_d = _dev(img), _dev(seg)                              # held until the launch is queued: a temporary's block is reused at once
-    L.check(L.load().bx_lime_segment_mean(_p(img_d), _p(seg_d), _p(col), B, H, W, C, S, _stream()), "bx_lime_segment_mean")
+    img_d, seg_d = PG.dev(img), PG.dev(seg)                              # held until the launch is queued: a temporary's block is reused at once
+    L.check(L.load().bx_lime_segment_mean(PG.p(img_d), PG.p(seg_d), PG.p(col), B, H, W, C, S, PG.stream()), "bx_lime_segment_mean")
     torch.cuda.synchronize()
     return col
 
@@ -75,9 +64,9 @@ def _perturb(img_u8, seg, col, Z, n0, n, dt):
     B, H, W, C = img_u8.shape
     S, N = Z.shape[2], Z.shape[1]
     x = torch.full((B * n, H, W, 8), float("nan"), dtype=dt, device=DEV)
-    img_d, seg_d, Z_d = _dev(img_u8), _dev(seg), _dev(Z)
-    L.check(L.load().bx_lime_perturb(_p(img_d), _p(seg_d), _p(col), _p(Z_d), _p(x), B, H, W, C, 8, S, N, n0, n, ops.bx_dtype(dt),
-                                     _stream()), "bx_lime_perturb")
+    img_d, seg_d, Z_d = PG.dev(img_u8), PG.dev(seg), PG.dev(Z)
+    L.check(L.load().bx_lime_perturb(PG.p(img_d), PG.p(seg_d), PG.p(col), PG.p(Z_d), PG.p(x), B, H, W, C, 8, S, N, n0, n, ops.bx_dtype(dt),
+                                     PG.stream()), "bx_lime_perturb")
     torch.cuda.synchronize()
     return x
 
@@ -85,8 +74,8 @@ def _perturb(img_u8, seg, col, Z, n0, n, dt):
 def _u8_to_nhwc(imgs_u8, dt):
     n, H, W, C = imgs_u8.shape
     x = torch.empty(n, H, W, 8, dtype=dt, device=DEV)
-    src = _dev(imgs_u8)
-    L.check(L.load().bx_u8_to_nhwc(_p(src), _p(x), n, H, W, C, 8, 1.0 / 255.0, ops.bx_dtype(dt), _stream()), "bx_u8_to_nhwc")
+    src = PG.dev(imgs_u8)
+    L.check(L.load().bx_u8_to_nhwc(PG.p(src), PG.p(x), n, H, W, C, 8, 1.0 / 255.0, ops.bx_dtype(dt), PG.stream()), "bx_u8_to_nhwc")
     torch.cuda.synchronize()
     return x
 
@@ -113,7 +102,7 @@ def test_perturbed_batch_bit_for_bit(geom, B, n0, n, hide, dt):
     rs = np.random.RandomState(9)
     Z = np.stack([R.draw_masks(N, S, rs) for _ in range(B)]).astype(np.uint8)
     col_h = X._lime_colours_host(imgs, segs, S, hide)
-    col = _segment_mean(imgs, segs, S) if col_h is None else _dev(col_h)
+    col = _segment_mean(imgs, segs, S) if col_h is None else PG.dev(col_h)
     got = _perturb(imgs, segs, col, Z, n0, n, dt)
     want = []
     for b in range(B):
@@ -136,7 +125,7 @@ def test_perturbed_batch_float_image(dt):
     print(f"float image: smallest distance of a segment mean from an integer {gap:.2e}")
     assert gap >= 1e-6                                               # truncation of the means cannot depend on summation order
     Z = R.draw_masks(N, S, np.random.RandomState(2)).astype(np.uint8)[None]
-    col = _dev(X._lime_colours_host(img[None], seg[None], S, None))
+    col = PG.dev(X._lime_colours_host(img[None], seg[None], S, None))
     got = _perturb(img[None].astype(np.uint8), seg[None], col, Z, 0, N, dt)
     want = np.stack(R.perturbed_images(img, seg, R.fudged_image(img, seg), Z[0])).astype(np.uint8)
     assert torch.equal(got, _u8_to_nhwc(want, dt))
@@ -163,7 +152,7 @@ def test_segment_means_equal_numpy(case):
 
 # ---- 3. the fit alone ----------------------------------------------------------------------------------------------------------------
 def _fit(Z, P, labels, used, alpha, kw=0.25):
-    args = (_dev(Z), _dev(P), _dev(labels), None if used is None else _dev(used))
+    args = (PG.dev(Z), PG.dev(P), PG.dev(labels), None if used is None else PG.dev(used))
     out = X._lime_fit(*args, alpha, kw)
     torch.cuda.synchronize()
     return [t.cpu().numpy() for t in out]
@@ -220,8 +209,8 @@ def test_fit_on_a_used_subset():
     seg = brainxai.grid_segments(40, 60, 5, 10)
     segs = np.stack([seg, seg[::-1].copy()])
     out = torch.empty(2, 1, 40, 60, dtype=torch.float32, device=DEV)
-    coef_d, used_d, segs_d = _dev(got[0]), _dev(used), _dev(segs)
-    L.check(L.load().bx_lime_weight_map(_p(coef_d), _p(used_d), _p(segs_d), _p(out), 2, 1, 40, 60, 50, 10, _stream()), "bx_lime_weight_map")
+    coef_d, used_d, segs_d = PG.dev(got[0]), PG.dev(used), PG.dev(segs)
+    L.check(L.load().bx_lime_weight_map(PG.p(coef_d), PG.p(used_d), PG.p(segs_d), PG.p(out), 2, 1, 40, 60, 50, 10, PG.stream()), "bx_lime_weight_map")
     torch.cuda.synchronize()
     for b in range(2):
         full = np.zeros(50)

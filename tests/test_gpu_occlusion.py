@@ -1,14 +1,13 @@
 """GPU: brainxai.occlusion and the bx_occlusion_* entry points against the restatement of the definition (tests/occlusion_ref.py):
 perturbed rows bit for bit, the map against numpy fp64, and the maps end to end against the oracle's classes run in fp64 on the CPU,
-in the setting of tests/test_gpu_faithfulness.py (its models and inputs are imported).
+on the models and inputs of tests/perturb_gpu.py.
 
 Bounds.  bx_occlusion_accumulate, per cell: |want| 2^-23 + M 2^-52 (sum_j |S0 - S_j|) / cnt + 2^-149, M the number of covering windows
 -- one fp32 rounding of the result plus the fp64 rounding of M signed terms, their sum and the quotient.  End to end, fp32 storage:
-|scores - ref| <= 1e-5, the project's probability bound (TOL of test_gpu_faithfulness.py), and |attr - ref| <= 2e-5: the bound applies
-to the clean and to the occluded score of each difference and carries through the mean, whose weights sum to 1.  Every compared case is
-first checked ON THE REFERENCE SIDE to discriminate: the reference map with its score rows shuffled across the windows differs from
-the true one by more than 100 x the bound for every sample.  bf16 storage: 2 x 2e-2 x the log-probability scale, the derived bf16 bound
-of test_bf16_storage_maps (tests/test_gpu_rise.py) applied to both scores of a difference.
+|scores - ref| <= 1e-5, the project's probability bound (TOL of tests/perturb_gpu.py), and |attr - ref| <= 2e-5: the bound applies
+to the clean and to the occluded score of each difference and carries through the mean, whose weights sum to 1.  Every compared case
+passes the guard of tests/perturb_gpu.py first.  bf16 storage: 2 x BF16_LOGP x the log-probability scale (tests/perturb_gpu.py), the
+bound applied to both scores of a difference.
 Observed worst figures are printed by each test (run with -s) and recorded in DESIGN.md section 6."""
 import copy
 import functools
@@ -23,40 +22,10 @@ from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
 from tests import occlusion_ref as R
-from tests import test_gpu_faithfulness as FT
+from tests import perturb_gpu as PG
+from tests.perturb_gpu import DEV, TOL
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-TOL = 1e-5
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(a):
-    return (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(DEV)
-
-
-def _bits(t):
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
-
-
-def _row_windows(N):
-    """(n0, n): all rows; a range that starts past 0, crosses the kernel's groups of 8 and ends on the last window; the last alone."""
-    return sorted({(0, N), (N // 3, N - N // 3), (N - 1, 1)})
-
-
-def _want_rows(x, m, base, n0, n):
-    rows = []
-    for b in range(x.shape[0]):
-        bb = base[b:b + 1] if isinstance(base, torch.Tensor) and base.dim() == 4 else base
-        rows += [R.perturbed(x[b:b + 1], m[n0 + j], bb) for j in range(n)]
-    return torch.cat(rows)
 
 
 # ---- 1. perturbed spectrogram rows, bit for bit ---------------------------------------------------------------------------------------------
@@ -75,26 +44,17 @@ def test_perturbed_spectrogram_rows_bit_for_bit(shape, kind, dt):
     assert X._occlusion_geometry("occlusion", window, stride, H, W) == geom
     wh, ww, sh, sw, ny, nx = geom
     N = ny * nx
-    x = O.seeded((B, C, H, W), 3, "randn")
-    x[:, :, ::7, ::5] = -0.0
+    x, base, bkind, base_d = PG.row_inputs((B, C, H, W), kind)
     m = R.masks(H, W, window, stride)
-    base = FT._baseline(kind, x, 4)
-    bkind, base_d = FT._base_dev(base)
     x_d = x.to(DEV)
-    for n0, n in _row_windows(N):
-        out = torch.full((B * n, H, W, 8), float("nan"), dtype=dt, device=DEV)
-        L.check(L.load().bx_occlusion_perturb_spec(_p(x_d), _p(base_d), bkind, _p(out), B, C, H, W, 8, wh, ww, sh, sw, n0, n, ops.bx_dtype(dt), _stream()),
+
+    def launch(out, n0, n):
+        L.check(L.load().bx_occlusion_perturb_spec(PG.p(x_d), PG.p(base_d), bkind, PG.p(out), B, C, H, W, 8, wh, ww, sh, sw, n0, n, ops.bx_dtype(dt), PG.stream()),
                 "bx_occlusion_perturb_spec")
-        want = ops.to_nhwc(_want_rows(x, m, base, n0, n).to(DEV), dt)
-        torch.cuda.synchronize()
-        assert not torch.isnan(out.float()).any(), "unwritten elements"
-        assert out.shape == want.shape and torch.equal(_bits(out), _bits(want)), f"{shape} {kind} rows {(n0, n)}"
-        helper = X._occlusion_perturb(x_d, geom, base_d, bkind, 0, B, n0, n, dt)
-        assert torch.equal(_bits(helper), _bits(want))
-        one = X._occlusion_perturb(x_d, geom, base_d, bkind, 1, 1, n0, n, dt)                    # a sample group that does not start at 0
-        assert torch.equal(_bits(one), _bits(want[n:]))
-    assert float(out[:, :, :, C:].float().abs().max()) == 0.0
+    PG.check_spec_rows(launch, lambda b, j, bb: R.perturbed(x[b:b + 1], m[j], bb), x, base, PG.row_windows(N),
+                       lambda b0, nb, n0, n: X._occlusion_perturb(x_d, geom, base_d, bkind, b0, nb, n0, n, dt), dt, f"{shape} {kind}")
     if N == 1 and kind == "scalar":                                  # one window: the row is the baseline
+        out = X._occlusion_perturb(x_d, geom, base_d, bkind, 0, B, 0, 1, dt)
         assert float((out[:, :, :, :C].float() - 0.25).abs().max()) == 0.0
 
 
@@ -111,29 +71,22 @@ def test_perturbed_eeg_rows_bit_for_bit(shape, kind):
     geom = R.geometry(chans, T, window, stride)
     wh, ww, sh, sw, ny, nx = geom
     N = ny * nx
-    x = O.seeded((B, 1, chans, T), 6, "randn")
-    x[:, :, ::3, ::11] = -0.0
+    x, base, bkind, base_d = PG.row_inputs((B, 1, chans, T), kind)
     m = R.masks(chans, T, window, stride)
-    base = FT._baseline(kind, x, 8)
-    bkind, base_d = FT._base_dev(base)
     x_d = x.to(DEV)
-    for n0, n in _row_windows(N):
-        out = torch.full((B * n, 1, chans, T), float("nan"), dtype=torch.float32, device=DEV)
-        L.check(L.load().bx_occlusion_perturb_eeg(_p(x_d), _p(base_d), bkind, _p(out), B, chans, T, wh, ww, sh, sw, n0, n, _stream()),
+
+    def launch(out, n0, n):
+        L.check(L.load().bx_occlusion_perturb_eeg(PG.p(x_d), PG.p(base_d), bkind, PG.p(out), B, chans, T, wh, ww, sh, sw, n0, n, PG.stream()),
                 "bx_occlusion_perturb_eeg")
-        want = _want_rows(x, m, base, n0, n).to(DEV)
-        torch.cuda.synchronize()
-        assert not torch.isnan(out).any(), "unwritten elements"
-        assert out.shape == want.shape and torch.equal(_bits(out), _bits(want)), f"{shape} {kind} rows {(n0, n)}"
-        helper = X._occlusion_perturb(x_d, geom, base_d, bkind, 1, 1, n0, n, torch.float32, True)
-        assert torch.equal(_bits(helper), _bits(want[n:]))
+    PG.check_eeg_rows(launch, lambda b, j, bb: R.perturbed(x[b:b + 1], m[j], bb), x, base, PG.row_windows(N),
+                      lambda b0, nb, n0, n: X._occlusion_perturb(x_d, geom, base_d, bkind, b0, nb, n0, n, torch.float32, True), f"{shape} {kind}")
 
 
 # ---- 3. the map -----------------------------------------------------------------------------------------------------------------------------
 def _accumulate(S_d, S0_d, cls_d, B, N, K, Hm, Wm, geom):
     attr = torch.full((B, K if cls_d is None else 1, Hm, Wm), float("nan"), dtype=torch.float32, device=DEV)
     cnt = torch.full((Hm, Wm), -1, dtype=torch.int32, device=DEV)
-    L.check(L.load().bx_occlusion_accumulate(_p(S_d), _p(S0_d), _p(cls_d), _p(attr), _p(cnt), B, N, K, Hm, Wm, *geom[:4], _stream()), "bx_occlusion_accumulate")
+    L.check(L.load().bx_occlusion_accumulate(PG.p(S_d), PG.p(S0_d), PG.p(cls_d), PG.p(attr), PG.p(cnt), B, N, K, Hm, Wm, *geom[:4], PG.stream()), "bx_occlusion_accumulate")
     torch.cuda.synchronize()
     return attr.cpu().numpy(), cnt.cpu().numpy()
 
@@ -158,12 +111,12 @@ def test_accumulate_against_numpy_fp64(case):
     M = R.counts(m)
     absdrop = np.abs(S0.astype(np.float64)[:, None, :] - S.astype(np.float64))
     bound = np.abs(want) * 2.0 ** -23 + M * 2.0 ** -52 * np.einsum("bnk,nhw->bkhw", absdrop, m.astype(np.float64)) / M + 2.0 ** -149
-    S_d, S0_d = _dev(S), _dev(S0)
+    S_d, S0_d = PG.dev(S), PG.dev(S0)
     got, cnt = _accumulate(S_d, S0_d, None, B, N, K, Hm, Wm, geom)
     assert not np.isnan(got).any() and cnt.min() >= 1, "unwritten elements"
     assert cnt.dtype == np.int32 and np.array_equal(cnt, M)
     excess = float((np.abs(got - want) / bound).max())
-    got_c, cnt_c = _accumulate(S_d, S0_d, _dev(classes), B, N, K, Hm, Wm, geom)
+    got_c, cnt_c = _accumulate(S_d, S0_d, PG.dev(classes), B, N, K, Hm, Wm, geom)
     sel = np.arange(B)
     excess_c = float((np.abs(got_c[:, 0] - want[sel, classes]) / bound[sel, classes]).max())
     print(f"bx_occlusion_accumulate {case}: {N} windows, counts {M.min()}..{M.max()}, worst error / bound: all classes {excess:.2f}, per-sample classes {excess_c:.2f}")
@@ -171,7 +124,7 @@ def test_accumulate_against_numpy_fp64(case):
     assert np.array_equal(cnt, cnt_c) and np.array_equal(got[sel, classes].view(np.int32), got_c[:, 0].view(np.int32))
     again, cnt_again = _accumulate(S_d, S0_d, None, B, N, K, Hm, Wm, geom)
     assert np.array_equal(got.view(np.int32), again.view(np.int32)) and np.array_equal(cnt, cnt_again)
-    flat, _ = _accumulate(_dev(np.full((B, N, K), 0.375, dtype=np.float32)), _dev(np.full((B, K), 0.375, dtype=np.float32)), None, B, N, K, Hm, Wm, geom)
+    flat, _ = _accumulate(PG.dev(np.full((B, N, K), 0.375, dtype=np.float32)), PG.dev(np.full((B, K), 0.375, dtype=np.float32)), None, B, N, K, Hm, Wm, geom)
     assert (flat.view(np.int32) == 0).all(), "constant scores give an exactly-zero map"
 
 
@@ -183,7 +136,7 @@ def test_accumulate_finds_a_planted_cell():
     for spot in [(0, 0), (15, 23), (8, 11)]:
         covering = m[:, spot[0], spot[1]]
         S = np.where(covering, 0.25, 0.75).astype(np.float32).reshape(1, N, 1)
-        got, _ = _accumulate(_dev(S), _dev(np.full((1, 1), 0.75, dtype=np.float32)), None, 1, N, 1, Hm, Wm, geom)
+        got, _ = _accumulate(PG.dev(S), PG.dev(np.full((1, 1), 0.75, dtype=np.float32)), None, 1, N, 1, Hm, Wm, geom)
         assert got[0, 0][spot] == 0.5 == got.max() and m[covering].any(0)[got[0, 0] == 0.5].all()
         assert np.array_equal(got[0, 0].astype(np.float64), R.attribution(S, np.full((1, 1), 0.75), m)[0, 0].astype(np.float32).astype(np.float64))
 
@@ -195,22 +148,19 @@ EEG_GEOMS = {"electrodes": ((1, 2000), None), "19x250 stride 19x125": ((19, 250)
 
 def _guarded(S, S0, m, cls, what, tol=2 * TOL):
     """The fp64 reference map of the explained classes, with the guard on the reference side alone."""
-    B, N = S.shape[0], S.shape[1]
+    N = S.shape[1]
     amap = R.attribution(S, S0, m)
     perm = np.random.RandomState(1).permutation(N)
     if N > 1:
-        shuffled = R.attribution(S[:, perm], S0, m)
-        moved = np.array([np.abs(amap[b, cls[b]] - shuffled[b, cls[b]]).max() for b in range(B)])
-        print(f"{what}: reference classes {cls} span {[round(float(np.ptp(amap[b, cls[b]])), 4) for b in range(B)]} |map - shuffled| / bound {(moved / tol).round(0)}")
-        assert moved.min() > 100 * tol, f"{what}: shuffling the scores moves the reference map by {moved.min():.1e} only"
+        PG.guard_moved(amap, R.attribution(S[:, perm], S0, m), cls, tol, what)
     return amap
 
 
 @functools.lru_cache(maxsize=None)
 def _mm_reference(which, name):
     """(masks, S, S0, classes) of the fp64 oracle for the scaled multimodal model, zero baseline; computed once, shared, never changed."""
-    ref_model, _ = FT._scaled_multimodal()
-    eeg, spec = FT._mm_inputs()
+    ref_model, _ = PG.scaled_multimodal()
+    eeg, spec = PG.mm_inputs()
     r64 = copy.deepcopy(ref_model).double()
     if which == "spec":
         window, stride = SPEC_GEOMS[name]
@@ -241,8 +191,8 @@ def _check(res, m, S, S0, cls, what, tol=TOL, all_classes=False):
 @pytest.mark.parametrize("name", sorted(SPEC_GEOMS))
 def test_spectrogram_input_against_fp64_oracle(name):
     m, S, S0, cls = _mm_reference("spec", name)
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     window, stride = SPEC_GEOMS[name]
     res = brainxai.occlusion(mine, eeg, spec, window=window, stride=stride, return_parts=True)
     assert np.array_equal(res.classes.cpu().numpy(), cls)
@@ -252,16 +202,16 @@ def test_spectrogram_input_against_fp64_oracle(name):
 def test_spectrogram_input_all_classes_against_fp64_oracle():
     name = "16x32 stride 8x16"
     m, S, S0, cls = _mm_reference("spec", name)
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     res = brainxai.occlusion(mine, eeg, spec, window=SPEC_GEOMS[name][0], stride=SPEC_GEOMS[name][1], class_idx="all", return_parts=True, max_batch=100)
     assert res.classes is None and tuple(res.attribution.shape) == (3, 6, 64, 128)
     _check(res, m, S, S0, cls, f"multimodal spec input {name}, fp32, all classes", all_classes=True)
 
 
 def test_spectrogram_input_tensor_baseline_and_classes_against_fp64_oracle():
-    ref_model, mine = FT._scaled_multimodal()
-    eeg, spec = FT._mm_inputs()
+    ref_model, mine = PG.scaled_multimodal()
+    eeg, spec = PG.mm_inputs()
     r64 = copy.deepcopy(ref_model).double()
     f = lambda xs: r64(eeg.double().repeat(xs.shape[0] // 3, 1, 1, 1), xs)                         # noqa: E731
     base, cls = (0.5 * spec).contiguous(), np.array([3, 5, 5])       # the other classes have p < 0.1 here: their maps move too little to discriminate
@@ -277,8 +227,8 @@ def test_spectrogram_input_tensor_baseline_and_classes_against_fp64_oracle():
 @pytest.mark.parametrize("name", sorted(EEG_GEOMS))
 def test_eeg_input_of_the_multimodal_model_against_fp64_oracle(name):
     m, S, S0, cls = _mm_reference("eeg", name)
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     window, stride = EEG_GEOMS[name]
     res = brainxai.occlusion(mine, eeg, spec, input="eeg", window=window, stride=stride, return_parts=True)
     assert np.array_equal(res.classes.cpu().numpy(), cls) and tuple(res.attribution.shape) == (3, 19, 2000)
@@ -287,7 +237,7 @@ def test_eeg_input_of_the_multimodal_model_against_fp64_oracle(name):
 
 @pytest.mark.parametrize("name", sorted(EEG_GEOMS))
 def test_stand_alone_eegnet_against_fp64_oracle(name):
-    ref_model, mine = FT._eegnet_pair()
+    ref_model, mine = PG.eegnet_pair()
     xe = O.seeded((3, 1, 19, 2000), 91, "randn")
     n64 = copy.deepcopy(ref_model).double()
     window, stride = EEG_GEOMS[name]
@@ -302,38 +252,32 @@ def test_stand_alone_eegnet_against_fp64_oracle(name):
 # ---- 5. bf16 storage ----------------------------------------------------------------------------------------------------------------------
 def test_bf16_storage_maps():
     """bf16 storage.  The occluded rows are bit-identical to the host-built ones (test_perturbed_spectrogram_rows_bit_for_bit); the map
-    stays within the project's derived bf16 bound of the fp64 oracle's: log-probabilities within 2e-2 of their scale
-    (test_bench_config_bf16_train_step), |dp| = p |dlogp| <= |dlogp|, for the clean and the occluded score of each difference, carried
-    through the mean, whose weights sum to 1.  Measured on the MI355X: 3.00e-4, where the derived bound is 1.32e-1."""
+    stays within the project's derived bf16 bound of the fp64 oracle's (BF16_LOGP of tests/perturb_gpu.py), for the clean and the
+    occluded score of each difference, carried through the mean, whose weights sum to 1.  Measured on the MI355X: 3.00e-4, where the derived bound is 1.32e-1."""
     name = "16x32 stride 8x16"
     m, S, S0, cls = _mm_reference("spec", name)
-    ref_model, mine = FT._scaled_multimodal(torch.bfloat16)
-    eeg, spec = FT._mm_inputs()
-    with torch.no_grad():
-        scale = float(copy.deepcopy(ref_model).double()(eeg.double(), spec.double()).abs().max())
+    ref_model, mine = PG.scaled_multimodal(torch.bfloat16)
+    eeg, spec = PG.mm_inputs()
+    scale = PG.logp_scale(ref_model, eeg, spec)
     res = brainxai.occlusion(mine, eeg.to(DEV), spec.to(DEV), window=SPEC_GEOMS[name][0], stride=SPEC_GEOMS[name][1], return_parts=True)
     assert np.array_equal(res.classes.cpu().numpy(), cls)
     want = _guarded(S, S0, m, cls, "multimodal spec input (bf16 case)")[np.arange(3), cls]
     worst = float(np.abs(res.attribution.cpu().numpy().astype(np.float64) - want).max())
-    print(f"occlusion multimodal spec input {name}, bf16 storage: |map - reference| {worst:.2e} (bound {2 * 2e-2 * scale:.2e}, log-probability scale {scale:.2f})")
-    assert worst <= 2 * 2e-2 * scale
+    print(f"occlusion multimodal spec input {name}, bf16 storage: |map - reference| {worst:.2e} (bound {2 * PG.BF16_LOGP * scale:.2e}, log-probability scale {scale:.2f})")
+    assert worst <= 2 * PG.BF16_LOGP * scale
 
 
 # ---- 6. interface ---------------------------------------------------------------------------------------------------------------------------
-def _state(model):
-    return model.training, [p.requires_grad for p in model.parameters()]
-
-
 def test_interface_forms():
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     mine.train()
     for p in list(mine.parameters())[:3]:
         p.requires_grad_(False)
-    before = _state(mine)
+    before = PG.model_state(mine)
     kw = dict(window=(16, 32), stride=(8, 16))
     amap = brainxai.occlusion(mine, eeg, spec, **kw)
-    assert _state(mine) == before and all(mod.training for mod in mine.modules()) and all(p.grad is None for p in mine.parameters())
+    assert PG.model_state(mine) == before and all(mod.training for mod in mine.modules()) and all(p.grad is None for p in mine.parameters())
     assert amap.is_cuda and amap.dtype == torch.float32 and tuple(amap.shape) == (3, 64, 128) and bool(torch.isfinite(amap).all())
     full = brainxai.occlusion(mine, eeg, spec, return_parts=True, **kw)
     assert isinstance(full, brainxai.OcclusionResult) and torch.equal(full.attribution, amap) and full.grid == (7, 7)
@@ -379,19 +323,19 @@ def test_interface_forms():
     assert int(tiles.counts.min()) == 1 == int(tiles.counts.max())
     assert torch.equal(brainxai.occlusion(mine, eeg, spec, window=16, stride=8, return_parts=True).scores,
                        brainxai.occlusion(mine, eeg, spec, window=(16, 16), stride=(8, 8), return_parts=True).scores)
-    assert _state(mine) == before and all(p.grad is None for p in mine.parameters())
+    assert PG.model_state(mine) == before and all(p.grad is None for p in mine.parameters())
     # the EEG input of the multimodal model: the spectrogram branch runs once per sample; electrode ablation
     a = brainxai.occlusion(mine, eeg, spec, input="eeg", window=(1, 2000), max_batch=256, return_parts=True)
     b = brainxai.occlusion(mine, eeg, spec, input="eeg", window=(1, 2000), max_batch=9, return_parts=True)
     assert tuple(a.attribution.shape) == (3, 19, 2000) and a.grid == (19, 1) and tuple(a.drops.shape) == (3, 19, 1) and torch.equal(a.classes, want_cls)
     assert torch.equal(a.scores, b.scores) and torch.equal(a.attribution, b.attribution)
     assert torch.equal(a.attribution, a.drops.expand(3, 19, 2000)), "one window per electrode: the map repeats the per-electrode drop"
-    assert _state(mine) == before
+    assert PG.model_state(mine) == before
 
 
 def test_maps_fit_deletion_insertion_as_they_are():
-    _, mine = FT._scaled_multimodal()
-    eeg, spec = (t.to(DEV) for t in FT._mm_inputs())
+    _, mine = PG.scaled_multimodal()
+    eeg, spec = (t.to(DEV) for t in PG.mm_inputs())
     amap = brainxai.occlusion(mine, eeg, spec, window=(16, 32), stride=(8, 16))
     r = brainxai.deletion_insertion(mine, eeg, spec, amap, steps=8)
     assert tuple(r.deletion.shape) == (3, 9) and tuple(r.ranks.shape) == (3, 64 * 128) and bool(torch.isfinite(r.deletion).all())
