@@ -92,6 +92,72 @@ def _class_seed(out: torch.Tensor, class_mode: int, rows=None) -> torch.Tensor:
     return seed
 
 
+def _class_form(class_idx):
+    """``grad_cam``'s class_idx -> (class mode, stacked): None = -1 (each sample's arg-max), an int c = c, 'all' = -2 (every class; the
+    result then carries a class axis).  Any other string is refused."""
+    if class_idx is None:
+        return -1, False
+    if isinstance(class_idx, str):
+        if class_idx != "all":
+            raise ValueError(class_idx)
+        return -2, True
+    return int(class_idx), False
+
+
+def _class_grads(out, leaf, mode, read=None):
+    """d out[:, c] / d leaf for the class(es) of ``mode``: one seed launch and one backward pass per class, stacked to [B*nm, ...] with
+    map index = sample * nm + class.  ``read(g)`` replaces each returned gradient by the one to keep."""
+    seeds = [_class_seed(out, c) for c in (range(out.shape[1]) if mode == -2 else (mode,))]
+    grads = []
+    for sd in seeds:
+        (g,) = torch.autograd.grad(out, leaf, grad_outputs=sd, retain_graph=True)
+        grads.append(g if read is None else read(g))
+    return torch.stack(grads, dim=1).flatten(0, 1) if len(grads) > 1 else grads[0]
+
+
+def _class_axis(B, nm, stacked, cam, raw=None, wts=None):
+    """(cam, raw, wts), each [B*nm, ...] -> [B, nm, ...] when the result is stacked over the classes; None passes through."""
+    return tuple(t.reshape(B, nm, *t.shape[1:]) if stacked and t is not None else t for t in (cam, raw, wts))
+
+
+def _cam_result(B, nm, stacked, return_parts, cam, raw, wts, A, out):
+    """What every ``grad_cam`` path returns: the map, or with return_parts (cam, raw, weights, A, out)."""
+    cam, raw, wts = _class_axis(B, nm, stacked, cam, raw, wts)
+    return (cam, raw, wts, A, out) if return_parts else cam
+
+
+class _SpecTarget:
+    """Capture of a spectrogram target over the forward passes of a ``with`` body: the output of ``blk`` (conv_k = 0, a forward hook), or
+    the pre-ReLU output of its convolution conv_k in 1..3 (the block's own capture mode; ``want_input`` also keeps the block's input,
+    which is what autograd can differentiate against).  On exit, however the body ends, every hook is removed and the block is out
+    of capture mode."""
+
+    def __init__(self, blk, conv_k, want_input=False):
+        self.blk, self.conv_k, self.want_input, self.leaf, self.hooks = blk, conv_k, want_input, None, []
+
+    def __enter__(self):
+        if self.conv_k:
+            self.blk._preact, self.blk._capture = self.conv_k, {}
+            if self.want_input:
+                self.hooks.append(self.blk.register_forward_pre_hook(lambda _m, args: setattr(self, "leaf", args[0])))
+        else:
+            self.hooks.append(self.blk.register_forward_hook(lambda _m, _i, o: setattr(self, "leaf", o)))
+        return self
+
+    def __exit__(self, *exc):
+        for h in self.hooks:
+            h.remove()
+        self.blk._preact, self.blk._capture = 0, None
+
+    def act(self):
+        """The target's activation, NHWC."""
+        return self.blk._capture["act"] if self.conv_k else self.leaf.detach().permute(0, 2, 3, 1).contiguous()
+
+    def grad(self, g):
+        """The gradient at the target, NHWC, after the backward pass that returned ``g`` for ``leaf``."""
+        return self.blk._capture["grad"] if self.conv_k else g.permute(0, 2, 3, 1).contiguous()
+
+
 _METHODS = {"gradcam": L.BX_CAM_GRADCAM, "gradcam++": L.BX_CAM_GRADCAM_PP, "layercam": L.BX_CAM_LAYERCAM}
 
 
@@ -126,13 +192,26 @@ _EEG_TARGETS = {"conv1": L.BX_EEG_CAM_CONV1, "depthwiseConv": L.BX_EEG_CAM_DEPTH
 _EEG_TARGET = re.compile(r"^(?:eeg_model\.)?(" + "|".join(_EEG_TARGETS) + r")$")
 
 
+def _check_samples(em, f):
+    if f.shape[1] != em.dense.in_features:
+        raise RuntimeError(f"EEGNet: {f.shape[1]} features but dense expects {em.dense.in_features} (Samples mismatch)")
+
+
 def _eeg_head(em, f):
     """The EEG branch after block 2 on the features f (EEGNet: dense + LogSoftmax; EEGNetAttentionDeep: its head)."""
     if hasattr(em, "head"):
         return em.head(f)
-    if f.shape[1] != em.dense.in_features:
-        raise RuntimeError(f"EEGNet: {f.shape[1]} features but dense expects {em.dense.in_features} (Samples mismatch)")
+    _check_samples(em, f)
     return ops.LinearLsmFn.apply(f, em.dense.weight, em.dense.bias)
+
+
+def _eeg_target_plane(saved, desc, g, B, T, layer):
+    """The activation of EEG target ``layer`` cloned out of the byte arena ``saved`` of a forward pass (bx_eeg_saved_layout gives the
+    offsets): fp32 [B, F1*D, 1, T] for 'depthwiseConv', [B, F2, 1, T//P1] for 'separableConv'."""
+    off_d, off_s = C.c_size_t(0), C.c_size_t(0)
+    L.check(L.load().bx_eeg_saved_layout(C.byref(desc), C.byref(off_d), C.byref(off_s)), "bx_eeg_saved_layout")
+    off, ch, t = (off_d.value, g.F1 * g.D, T) if layer == "depthwiseConv" else (off_s.value, g.F2, T // g.P1)
+    return saved[off:off + B * ch * t * 4].view(torch.float32).reshape(B, ch, 1, t).clone()
 
 
 def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_parts, method=L.BX_CAM_GRADCAM):
@@ -147,20 +226,13 @@ def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_par
         raise ValueError(f"EEG Grad-CAM needs an EEGNet / EEGNetAttentionDeep branch, got {type(em).__name__}")
     if multimodal and spec is None:
         raise ValueError("EEG Grad-CAM on a MultimodalModel needs the spectrogram input too")
-    if class_idx is None:
-        modes = [-1]
-    elif isinstance(class_idx, str):
-        if class_idx != "all":
-            raise ValueError(class_idx)
-        modes = None                                     # every class, once the output width is known
-    else:
-        modes = [int(class_idx)]
+    mode, stacked = _class_form(class_idx)
     target = _EEG_TARGETS[layer]
     lib = L.load()
     g = em._geom
     B, T = eeg.shape[0], eeg.shape[-1]
     n_cls = model.fc2.out_features if multimodal else (em.dense2.out_features if hasattr(em, "dense2") else em.dense.out_features)
-    nm = n_cls if modes is None else 1
+    nm = n_cls if stacked else 1
     probe = L.EegDesc(B, eeg.shape[-2], T, g.F1, g.D, g.F2, g.K1, g.K2, g.P1, g.P2, 0, 1e-5, 0.1, 0.0, 0, L.BX_F32, 0, -1.0)
     if lib.bx_eeg_cam_workspace(C.byref(probe), nm, target, method) == 0:
         raise ValueError(f"EEG Grad-CAM supports the tuned EEGNet family only: F1=8, D=2, F2=16, K2=16, kernLength <= 64, Chans <= 64, "
@@ -175,9 +247,7 @@ def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_par
             out = _eeg_head(em, f)
             if multimodal:
                 out = ops.FusionHeadFn.apply(out, s_out, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
-        seeds = [_class_seed(out, c) for c in (range(out.shape[1]) if modes is None else modes)]
-        grads = [torch.autograd.grad(out, f, grad_outputs=sd, retain_graph=i + 1 < len(seeds))[0] for i, sd in enumerate(seeds)]
-        dfeat = (torch.stack(grads, dim=1).reshape(B * nm, -1) if nm > 1 else grads[0]).contiguous()
+        dfeat = _class_grads(out, f, mode).contiguous()
         Ch, T1 = desc.Chans, T // g.P1
         shape1, nw = {L.BX_EEG_CAM_CONV1: ((Ch, T), g.F1), L.BX_EEG_CAM_DEPTHWISE: ((1, T), g.F1 * g.D),
                       L.BX_EEG_CAM_SEPARABLE: ((1, T1), g.F2)}[target]
@@ -190,22 +260,10 @@ def _grad_cam_eeg(model, eeg, spec, layer, class_idx, upsample, relu, return_par
                                _p(cam), _p(raw), _p(wts), _p(ws), ws.numel(), _stream()), "bx_eeg_cam")
         if raw is None:
             raw = cam
-        A = None
-        if return_parts and target != L.BX_EEG_CAM_CONV1:
-            off_d, off_s = C.c_size_t(0), C.c_size_t(0)
-            L.check(lib.bx_eeg_saved_layout(C.byref(desc), C.byref(off_d), C.byref(off_s)), "bx_eeg_saved_layout")
-            if target == L.BX_EEG_CAM_DEPTHWISE:
-                A = saved[off_d.value:off_d.value + B * g.F1 * g.D * T * 4].view(torch.float32).reshape(B, g.F1 * g.D, 1, T).clone()
-            else:
-                A = saved[off_s.value:off_s.value + B * g.F2 * T1 * 4].view(torch.float32).reshape(B, g.F2, 1, T1).clone()
+        A = _eeg_target_plane(saved, desc, g, B, T, layer) if return_parts and target != L.BX_EEG_CAM_CONV1 else None
         if upsample and target == L.BX_EEG_CAM_SEPARABLE:
             cam = resize_bilinear(cam.reshape(B * nm, 1, T1), (1, T))
-    stacked = isinstance(class_idx, str)
-    def shape(t):
-        return t.reshape(B, nm, *t.shape[1:]) if stacked else t
-    if return_parts:
-        return shape(cam), shape(raw), None if wts is None else shape(wts), A, out.detach()
-    return shape(cam)
+    return _cam_result(B, nm, stacked, return_parts, cam, raw, wts, A, out.detach())
 
 
 def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_parts, method=L.BX_CAM_GRADCAM):
@@ -214,43 +272,30 @@ def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_par
     and the method's channel reduce; a second launch upsamples the maps."""
     lib = L.load()
     sm = model.spectrogram_model
-    if class_idx is None:
-        mode = -1
-    elif isinstance(class_idx, str):
-        if class_idx != "all":
-            raise ValueError(class_idx)
-        mode = -2
-    else:
-        mode = int(class_idx)
+    mode, stacked = _class_form(class_idx)
     with torch.no_grad():
         em = model.eeg_model
         H, W = spec.shape[-2:]
-        if upsample and not return_parts and W % 4 == 0 and hasattr(model, "_fusable") and model._fusable():
-            # sweep form: the EEG branch's dense + LogSoftmax and the up-sampling ride in the head launch (two launches fewer per batch)
-            # (the EEG branch beside the spectrogram branch, as the captured training step runs them, does not pay here: 440 vs 433 us
-            # per batch -- the evaluation-mode branch is 55 us of five launches and the fork / join costs about as much as it hides)
-            ef = em.features(eeg).contiguous()
-            A = sm.features(spec).permute(0, 2, 3, 1).contiguous()
-            B, h, w, C = A.shape
-            N, Hd = model.fc2.out_features, model.fc1.out_features
-            nm = N if mode == -2 else 1
-            if ef.shape[1] != em.dense.in_features:
-                raise RuntimeError(f"EEGNet: {ef.shape[1]} features but dense expects {em.dense.in_features} (Samples mismatch)")
+        # sweep form: the EEG branch's dense + LogSoftmax and the up-sampling ride in the head launch (two launches fewer per batch)
+        # (the EEG branch beside the spectrogram branch, as the captured training step runs them, does not pay here: 440 vs 433 us
+        # per batch -- the evaluation-mode branch is 55 us of five launches and the fork / join costs about as much as it hides)
+        sweep = upsample and not return_parts and W % 4 == 0 and hasattr(model, "_fusable") and model._fusable()
+        e = (em.features(eeg) if sweep else em(eeg)).contiguous()        # the branch's log-probabilities; sweep form: its features
+        A = sm.features(spec).permute(0, 2, 3, 1).contiguous()
+        B, h, w, C = A.shape
+        N, Hd = model.fc2.out_features, model.fc1.out_features
+        nm = N if stacked else 1
+        if sweep:
+            _check_samples(em, e)
             lds_floats = 2 * C + 2 * Hd + 5 * N + (256 // (C // 8)) * C + h * w
             if lds_floats * 4 <= 64 * 1024:
                 maps = torch.empty(B * nm, H, W, dtype=torch.float32, device=A.device)
-                L.check(lib.bx_cam_head_sweep(_p(A), _p(ef), _p(em.dense.weight), _p(em.dense.bias), ef.shape[1], _p(sm.fc.weight),
+                L.check(lib.bx_cam_head_sweep(_p(A), _p(e), _p(em.dense.weight), _p(em.dense.bias), e.shape[1], _p(sm.fc.weight),
                                               _p(sm.fc.bias), _p(model.fc1.weight), _p(model.fc1.bias), _p(model.fc2.weight),
                                               _p(model.fc2.bias), None, _p(maps), B, h, w, C, N, Hd, H, W, mode, method, 1 if relu else 0,
                                               ops.bx_dtype(A.dtype), _stream()), "bx_cam_head_sweep")
-                return maps.reshape(B, nm, H, W) if isinstance(class_idx, str) else maps
-            e = ops.LinearLsmFn.apply(ef, em.dense.weight, em.dense.bias).contiguous()
-        else:
-            e = em(eeg).contiguous()
-            A = sm.features(spec).permute(0, 2, 3, 1).contiguous()
-        B, h, w, C = A.shape
-        N, Hd = model.fc2.out_features, model.fc1.out_features
-        nm = N if mode == -2 else 1
+                return _class_axis(B, nm, stacked, maps)[0]
+            e = ops.LinearLsmFn.apply(e, em.dense.weight, em.dense.bias).contiguous()
         dev = A.device
         out = torch.empty(B, N, dtype=torch.float32, device=dev)
         cam = torch.empty(B * nm, h, w, dtype=torch.float32, device=dev)
@@ -261,11 +306,7 @@ def _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_par
                                 method, 1 if relu else 0, ops.bx_dtype(A.dtype), _stream()), "bx_cam_head")
         if upsample:
             cam = resize_bilinear(cam, spec.shape[-2:])
-    stacked = isinstance(class_idx, str)
-    shape = (lambda t: t.reshape(B, nm, *t.shape[1:])) if stacked else (lambda t: t)
-    if return_parts:
-        return shape(cam), shape(raw), None if wts is None else shape(wts), A, out
-    return shape(cam)
+    return _cam_result(B, nm, stacked, return_parts, cam, raw, wts, A, out)
 
 
 class GradCamSweep:
@@ -472,55 +513,19 @@ def grad_cam(model, eeg, spec, target_layer="spectrogram_model.block5", class_id
             return _grad_cam_last_stage(model, eeg, spec, class_idx, upsample, relu, return_parts, code)
         finally:
             model.train(was_training)
+    mode, stacked = _class_form(class_idx)
     with _eval_frozen(model):
         spec_in = spec.detach().clone().requires_grad_(True)
-        grabbed = {}
-        hooks = []
-        if conv_k:
-            blk._preact, blk._capture = conv_k, {}
-            hooks.append(blk.register_forward_pre_hook(lambda _m, args: grabbed.__setitem__("x", args[0])))
-        else:
-            hooks.append(blk.register_forward_hook(lambda _m, _i, o: grabbed.__setitem__("A", o)))
-        try:
+        with _SpecTarget(blk, conv_k, want_input=True) as tgt:
             out = model(eeg, spec_in) if hasattr(model, "spectrogram_model") else model(spec_in)
-        finally:
-            for h in hooks:
-                h.remove()
-        n_cls = out.shape[1]
-        B = out.shape[0]
-        if class_idx is None:
-            seeds = [_class_seed(out, -1)]
-        elif isinstance(class_idx, str):
-            if class_idx != "all":
-                raise ValueError(class_idx)
-            seeds = [_class_seed(out, c) for c in range(n_cls)]
-        else:
-            seeds = [_class_seed(out, int(class_idx))]
-        try:
-            grads = []
-            for sd in seeds:
-                if conv_k:
-                    torch.autograd.grad(out, grabbed["x"], grad_outputs=sd, retain_graph=True)
-                    grads.append(blk._capture["grad"])
-                else:
-                    (g,) = torch.autograd.grad(out, grabbed["A"], grad_outputs=sd, retain_graph=True)
-                    grads.append(g.permute(0, 2, 3, 1).contiguous())
-            A = blk._capture["act"] if conv_k else grabbed["A"].detach().permute(0, 2, 3, 1).contiguous()
-        finally:
-            blk._preact, blk._capture = 0, None
-        nm = len(grads)
-        # map index = sample * nm + class
-        G = torch.stack(grads, dim=1).reshape(B * nm, *grads[0].shape[1:]) if nm > 1 else grads[0]
+            G = _class_grads(out, tgt.leaf, mode, tgt.grad)
+            A = tgt.act()
+        B, nm = out.shape[0], out.shape[1] if stacked else 1
         cam, wts = _reduce(A, G, nm, relu, code)
         raw = _reduce(A, G, nm, False, code)[0] if (return_parts and relu) else cam
         if upsample:
             cam = resize_bilinear(cam, spec.shape[-2:])
-    stacked = isinstance(class_idx, str)
-    def shape(t):
-        return t.reshape(B, nm, *t.shape[1:]) if stacked else t
-    if return_parts:
-        return shape(cam), shape(raw), None if wts is None else shape(wts), A, out.detach()
-    return shape(cam)
+    return _cam_result(B, nm, stacked, return_parts, cam, raw, wts, A, out.detach())
 
 
 def _abs(t: torch.Tensor) -> torch.Tensor:
@@ -2069,30 +2074,12 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
             rp.fix_other()
             if eeg_target:
                 feat, saved, desc, _, _ = ops.eeg_features_keep(net, xs)
-                off_d, off_s = C.c_size_t(0), C.c_size_t(0)
-                L.check(lib.bx_eeg_saved_layout(C.byref(desc), C.byref(off_d), C.byref(off_s)), "bx_eeg_saved_layout")
-                if me.group(1) == "depthwiseConv":
-                    A = saved[off_d.value:off_d.value + B * g.F1 * g.D * T * 4].view(torch.float32).reshape(B, g.F1 * g.D, 1, T).clone()
-                else:
-                    T1 = T // g.P1
-                    A = saved[off_s.value:off_s.value + B * g.F2 * T1 * 4].view(torch.float32).reshape(B, g.F2, 1, T1).clone()
+                A = _eeg_target_plane(saved, desc, g, B, T, me.group(1))
                 clean = _eeg_head(net, feat)
             else:
-                blk = getattr(net, f"block{ms.group(1)}")
-                conv_k = int(ms.group(2)) if ms.group(2) else 0
-                grabbed = {}
-                if conv_k:
-                    blk._preact, blk._capture = conv_k, {}
-                    hook = None
-                else:
-                    hook = blk.register_forward_hook(lambda _m, _i, o_: grabbed.__setitem__("A", o_))
-                try:
+                with _SpecTarget(getattr(net, f"block{ms.group(1)}"), int(ms.group(2) or 0)) as tgt:
                     clean = net(xs)
-                    A = blk._capture["act"] if conv_k else grabbed["A"].detach().permute(0, 2, 3, 1).contiguous()
-                finally:
-                    blk._preact, blk._capture = 0, None
-                    if hook is not None:
-                        hook.remove()
+                    A = tgt.act()
             out = _fuse(model, multimodal, not eeg_target, clean, rp.fixed).float().contiguous()
         pl = _scorecam_plane(A, eeg_target)
         Cn, h, w = pl[5], pl[6], pl[7]
@@ -2125,12 +2112,10 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
                 cam = resize_bilinear(cam, (Hm, Wm))
     if eeg_target:
         cam, raw = cam.reshape(B * nm, 1, -1), raw.reshape(B * nm, 1, -1)
-
-    def shape(t):
-        return t.reshape(B, nm, *t.shape[1:]) if all_classes else t
+    cam, raw, wts = _class_axis(B, nm, all_classes, cam, raw, wts)
     if not return_parts:
-        return shape(cam)
-    return ScoreCamResult(shape(cam), shape(raw), shape(wts), A, out, P, lo, hi, valid, None if classes is None else classes.long())
+        return cam
+    return ScoreCamResult(cam, raw, wts, A, out, P, lo, hi, valid, None if classes is None else classes.long())
 
 
 # ------------------------------------------------------------------------------------------------

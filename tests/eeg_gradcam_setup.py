@@ -1,5 +1,5 @@
-"""The EEG-branch Grad-CAM setting shared by tests/test_gpu_eeg_gradcam.py and tests/test_gpu_heads.py: targets, BatchNorm
-statistics away from identity, and inputs."""
+"""The EEG-branch Grad-CAM setting shared by tests/test_gpu_eeg_gradcam.py, tests/test_gpu_cam_methods.py and tests/test_gpu_heads.py:
+targets, BatchNorm statistics away from identity, inputs and the relative error."""
 import torch
 
 from oracle import ref_torch as O
@@ -18,6 +18,13 @@ def bn_nontrivial(eeg_net, seed):
             bn.running_var.copy_(torch.rand(n, generator=g) * 2.8 + 0.2)
             bn.weight.copy_(torch.rand(n, generator=g) * 1.7 + 0.3)
             bn.bias.copy_(torch.rand(n, generator=g) * 1.0 - 0.5)
+
+
+def rel(a, b, scale=None):
+    """max |a - b| over ``scale`` (default: max |b|), in fp64 on the host."""
+    b = b.detach().double()
+    scale = float(b.abs().max()) if scale is None else scale
+    return float((a.detach().cpu().double() - b).abs().max()) / (scale + 1e-30)
 
 
 def inputs(B, chans, samples, seed=11):

@@ -13,6 +13,7 @@ import brainxai
 from brainxai import _lib as L
 from brainxai import ops
 from oracle import ref_torch as O
+from tests.eeg_gradcam_setup import bn_nontrivial, rel
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -39,18 +40,6 @@ def cam_fp64(A, G, method):
     sg = (S * G).abs()[counted]
     raw = (w.reshape(*w.shape, *([1] * len(dims))) * A).sum(1)
     return raw, w, float(cond.min()) if cond.numel() else 1.0, float(sg.max()) if sg.numel() else 0.0
-
-
-def _bn_nontrivial(eeg_net, seed):
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for name in ("batchnorm1", "batchnorm2", "batchnorm3"):
-            bn = getattr(eeg_net, name)
-            n = bn.num_features
-            bn.running_mean.copy_(torch.rand(n, generator=g) * 1.0 - 0.5)
-            bn.running_var.copy_(torch.rand(n, generator=g) * 2.8 + 0.2)
-            bn.weight.copy_(torch.rand(n, generator=g) * 1.7 + 0.3)
-            bn.bias.copy_(torch.rand(n, generator=g) * 1.0 - 0.5)
 
 
 def _resolve(model, dotted):
@@ -114,12 +103,6 @@ def clear_scale(ref64, fwd64, target, class_idx):
     return 2.0 ** -max(0, math.ceil(math.log2(max(sg, 1e-30) / 0.5)))
 
 
-def _rel(a, b, scale=None):
-    b = b.detach().double()
-    scale = float(b.abs().max()) if scale is None else scale
-    return float((a.detach().cpu().double() - b).abs().max()) / (scale + 1e-30)
-
-
 # ---- kernel level ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("nm", [1, 6])
@@ -147,9 +130,9 @@ def test_cam_reduce_against_fp64_definition(method, HW, C, nm, dtype):
                                   code, relu, ops.bx_dtype(dtype), ops._stream()), "bx_cam_reduce")
         torch.cuda.synchronize()
         want = raw_o.clamp_min(0) if relu else raw_o
-        assert _rel(cam, want, float(raw_o.abs().max())) <= 1e-5, (method, HW, C, nm, dtype, relu)
+        assert rel(cam, want, float(raw_o.abs().max())) <= 1e-5, (method, HW, C, nm, dtype, relu)
         if wts is not None:
-            assert _rel(wts, w_o) <= 1e-5
+            assert rel(wts, w_o) <= 1e-5
         # fixed-order sums: a second launch gives the same bits
         cam2 = torch.empty_like(cam)
         L.check(lib.bx_cam_reduce(Ad.data_ptr(), Gd.data_ptr(), cam2.data_ptr(), None, B * nm, nm, HW, C, code, relu, ops.bx_dtype(dtype),
@@ -161,7 +144,7 @@ def test_cam_reduce_against_fp64_definition(method, HW, C, nm, dtype):
 @pytest.fixture(scope="module")
 def pair():
     ref = O.fill_params(O.build_multimodal(19, 2000, 4, dropout=0.0), seed=5)
-    _bn_nontrivial(ref.eeg_model, 6)
+    bn_nontrivial(ref.eeg_model, 6)
     mine = brainxai.build_multimodal(19, 2000, 4, dropout=0.0)
     mine.load_state_dict(ref.state_dict())
     return copy.deepcopy(ref).double().eval(), mine.to(DEV)
@@ -181,12 +164,12 @@ def _check(ref64, fwd64, mine, args, target, class_idx, method):
         torch.cuda.synchronize()
     raw_o = raw_o.reshape(raw.shape)
     rs = float(raw_o.abs().max())
-    errs = [_rel(raw, raw_o), _rel(cam, raw_o.clamp_min(0), rs)]
+    errs = [rel(raw, raw_o), rel(cam, raw_o.clamp_min(0), rs)]
     if method == "layercam":
         assert w is None
     else:
         assert tuple(w.shape) == tuple(w_o.shape)
-        errs.append(_rel(w, w_o))
+        errs.append(rel(w, w_o))
     assert max(errs) < TOL, (target, class_idx, method, errs)
 
 
@@ -213,13 +196,13 @@ def test_sweep_form_matches_oracle(pair, method):
         e, s = eeg.to(DEV), spec.to(DEV)
         maps = brainxai.GradCamSweep(mine, e, s, class_idx="all", method=method)(e, s)
         torch.cuda.synchronize()
-        assert _rel(maps.flatten(0, 1), want, float(raw_o.abs().max())) < TOL
+        assert rel(maps.flatten(0, 1), want, float(raw_o.abs().max())) < TOL
 
 
 @pytest.mark.parametrize("method", METHODS)
 def test_standalone_nets(method):
     ref_net = O.fill_params(O.EEGNetAttentionDeep(6, Chans=19, Samples=2048, dropoutRate=0.0), seed=21)
-    _bn_nontrivial(ref_net, 22)
+    bn_nontrivial(ref_net, 22)
     mine = brainxai.EEGNetAttentionDeep(6, Chans=19, Samples=2048, dropoutRate=0.0)
     mine.load_state_dict(ref_net.state_dict())
     mine.to(DEV)

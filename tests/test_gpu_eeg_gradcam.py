@@ -6,17 +6,11 @@ import torch.nn.functional as F
 
 import brainxai
 from oracle import ref_torch as O
-from tests.eeg_gradcam_setup import TARGETS, bn_nontrivial, inputs
+from tests.eeg_gradcam_setup import TARGETS, bn_nontrivial, inputs, rel
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 TOL = 1e-3                     # north_star: 1e-3 relative fp32
-
-
-def _rel(a, b, scale=None):
-    b = b.detach().double()
-    scale = float(b.abs().max()) if scale is None else scale
-    return float((a.detach().cpu().double() - b).abs().max()) / (scale + 1e-30)
 
 
 def _mm_pair(chans, samples, seed=5, kern=64):
@@ -51,12 +45,12 @@ def _check(ref, mine, eeg, spec, target, class_idx):
     want = tuple(raw_r.shape)
     assert tuple(raw.shape) == want and tuple(cam.shape) == want and tuple(w.shape) == tuple(w_r.shape)
     rs = float(raw_r.abs().max())
-    e_raw, e_cam, e_w = _rel(raw, raw_r), _rel(cam, cam_r, rs), _rel(w, w_r)
+    e_raw, e_cam, e_w = rel(raw, raw_r), rel(cam, cam_r, rs), rel(w, w_r)
     assert max(e_raw, e_cam, e_w) < TOL, (target, class_idx, e_raw, e_cam, e_w)
     if target == "conv1":
         assert A is None
     else:
-        assert tuple(A.shape) == tuple(A_r.shape) and _rel(A, A_r) < TOL
+        assert tuple(A.shape) == tuple(A_r.shape) and rel(A, A_r) < TOL
 
 
 @pytest.fixture(scope="module")
@@ -112,7 +106,7 @@ def test_eeg_gradcam_standalone_nets(cls):
             # the prefix is optional for a stand-alone net
             cam, raw, w, _, _ = brainxai.grad_cam(mine, eeg.to(DEV), None, target, class_idx, upsample=False, return_parts=True)
             rs = float(raw_r.abs().max())
-            errs = (_rel(raw, raw_r), _rel(cam, cam_r, rs), _rel(w, w_r))
+            errs = (rel(raw, raw_r), rel(cam, cam_r, rs), rel(w, w_r))
             assert max(errs) < TOL, (cls, target, class_idx, errs)
 
 
@@ -123,7 +117,7 @@ def test_eeg_gradcam_upsample(bench_pair):
     up = brainxai.grad_cam(mine, eeg, spec, "eeg_model.separableConv", "all", upsample=True)
     assert tuple(small.shape) == (2, 6, 1, 500) and tuple(up.shape) == (2, 6, 1, 2000)
     want = F.interpolate(small.cpu().reshape(12, 1, 1, 500), size=(1, 2000), mode="bilinear", align_corners=False).reshape(up.shape)
-    assert _rel(up, want) <= 1e-6
+    assert rel(up, want) <= 1e-6
     for target in ("conv1", "depthwiseConv"):
         a = brainxai.grad_cam(mine, eeg, spec, "eeg_model." + target, 3, upsample=False)
         b = brainxai.grad_cam(mine, eeg, spec, "eeg_model." + target, 3, upsample=True)
@@ -140,7 +134,7 @@ def test_eeg_gradcam_bf16_storage():
     for target in TARGETS:
         _, r32, *_ = brainxai.grad_cam(mine32, eeg, spec, "eeg_model." + target, "all", upsample=False, return_parts=True, relu=False)
         _, r16, *_ = brainxai.grad_cam(mine16, eeg, spec, "eeg_model." + target, "all", upsample=False, return_parts=True, relu=False)
-        assert _rel(r16, r32.cpu()) <= 2e-2, target     # the bound the bf16 Grad-CAM of the spectrogram branch is held to
+        assert rel(r16, r32.cpu()) <= 2e-2, target     # the bound the bf16 Grad-CAM of the spectrogram branch is held to
 
 
 def test_eeg_gradcam_restores_state_and_leaves_spectrogram_path(bench_pair):
