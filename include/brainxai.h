@@ -524,7 +524,10 @@ int bx_spec_preprocess(const float* raw, const int* offsets, float* out, int B, 
  * normalize_signal (root/src/utils/data_utils.py:133-136: NaN -> nanmean of the sample, min-max with eps) -> per region
  * resample_spectrogram (data_utils.py:145-147: skimage.transform.resize(mode='reflect', anti_aliasing=True): gaussian_filter
  * with the host-supplied 1-D weights gauss_y[2*radius_y+1] / gauss_x[2*radius_x+1] ('mirror' boundary; radius 0 = no filter),
- * then order-1 zoom with grid_mode coordinates, mirrored indices).  fp64 arithmetic. */
+ * then order-1 zoom with grid_mode coordinates, mirrored indices).  fp64 arithmetic.
+ * A window without one finite value (every sample NaN, no zero padding): the reference's nanmean of an empty set is NaN and its
+ * output NaN everywhere; here the fill value is 0, as the reference's handle_nan takes it for an all-NaN row, so the plane is
+ * constant and the output 0.  A window wholly outside the recording is all padding: output 0 as well. */
 size_t bx_spec_regions_workspace(int B);
 int bx_spec_regions(const float* raw, const int* offsets, float* out, int B, int Trows, int C, int regions, int win, int Ho, int Wo,
                     const double* gauss_y, int radius_y, const double* gauss_x, int radius_x, float eps, void* workspace,
