@@ -810,6 +810,43 @@ int bx_expgrad_seed(const int* classes, int class_all, float* seed, int B, int n
 /* The reference's per-electrode reduction: out[r] = fl32( (sum_t |v[r,t]|) / L ) for v fp32 [R,L].  The sum is fp64 in an order that does
  * not depend on the launch: 64 partial sums over t = l, l + 64, ... (ascending), added by a fixed pairwise tree.  R * L < 2^31. */
 int bx_mean_abs_rows(const float* v, float* out, int R, int L, bxStream stream);
+/* ---- SmoothGrad, SmoothGrad^2 and VarGrad (Smilkov et al. 2017; Hooker et al. 2019; Adebayo et al. 2018; Captum's NoiseTunnel), batched.
+ * For the explained input x [B,per], n draws per sample, a noise scale sigma[b] and F_c the model's output log-probability of class c:
+ *     row[b,k,e] = fl32( x[b,e] + fl32( sigma[b] * z[b,k,e] ) )            (product and sum rounded separately, no fma)
+ *     g[b,k]     = dF_c/dx( row[b,k] ),    S1 = sum_k g,    S2 = sum_k g * g      (fp64, ascending k; g * g of a float is exact in fp64)
+ *     BX_SMOOTHGRAD_MEAN  S1 / n                              (SmoothGrad)
+ *     BX_SMOOTHGRAD_SQ    S2 / n                              (SmoothGrad^2)
+ *     BX_SMOOTHGRAD_VAR   max(0, (S2 - S1 * S1 / n) / n)      (VarGrad: the population variance; four fp64 operations, each rounded)
+ * each then rounded to fp32 once; the map is the largest |value| over the input's channels (saliency's convention).
+ * Noise.  For flat element e of a sample, q = e >> 2:
+ *     (w0,w1,w2,w3) = Philox4x32-10( counter = (q, k, b, 0), key = (seed & 0xffffffff, seed >> 32) )
+ * the Random123 generator (Salmon et al., SC 2011): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; a round maps the counter c to
+ * ( hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0) ); ten rounds, the key advanced by (0x9E3779B9, 0xBB67AE85) before
+ * every round but the first.  Box-Muller in fp32 on a word pair (wa, wb), every operation rounded on its own:
+ *     u = ((wa >> 8) + 1) 2^-24 in (0,1],  t = (wb >> 8) 2^-23 in [0,2)   (both exact),   r = sqrtf(-2 logf(u)),
+ *     z_even = r cospif(t),  z_odd = r sinpif(t);
+ * (w0,w1) gives elements 4q, 4q+1 and (w2,w3) gives 4q+2, 4q+3.  The draws of (b, k) depend on nothing else: a longer run extends a
+ * shorter one, and how the rows are split into calls does not matter.  logf, cospif and sinpif are the device library's: z is pinned
+ * to the exact Box-Muller value of (u, t) within a few units of 2^-24 max(1, r), not bit for bit; everything after z is.
+ * Rows are numbered globally j = b * n + k, sample-major; a call handles rows [row0, row0 + rows), which may start and end inside a
+ * sample.  The sums are carried between calls in S1 and S2.  No atomics.  B * n, B * per, rows * per and B * Kc * per stay below 2^31;
+ * every entry point refuses its limits with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+enum { BX_SMOOTHGRAD_MEAN = 0, BX_SMOOTHGRAD_SQ = 1, BX_SMOOTHGRAD_VAR = 2 };
+/* The paper's noise level: sigma[b] = fl32( level * | fl32( max_e x[b,e] - min_e x[b,e] ) | ), one workgroup per sample; the modulus only
+ * clears the sign of a zero range, so the bits do not depend on the order the extremes are found in.  x finite, level >= 0 finite. */
+int bx_smoothgrad_sigma(const float* x, float* sigma, int B, int per, float level, bxStream stream);
+/* The noisy rows: out fp32 [rows, per], row r = row[b,k] of global row row0 + r; sigma fp32 [B].  One Philox block serves four
+ * elements; 16-byte accesses when per % 4 == 0 and the pointers are 16-byte aligned, element by element otherwise; the noise lives in
+ * registers only.  Every element of every row is written exactly once.  With x == NULL (and sigma == NULL) the same kernel writes z
+ * itself: one code path computes z. */
+int bx_smoothgrad_rows(const float* x, const float* sigma, float* out, int B, int n, int per, uint64_t seed, int row0, int rows, bxStream stream);
+/* The running sums of one class slot: S1[b,slot,e] += sum of g[j - row0, e] and S2[b,slot,e] += sum of g[j - row0, e]^2 over the rows
+ * j = b * n + k of the call that belong to sample b, in ascending k.  S1, S2 fp64 [B,Kc,per] (Kc <= 32; the other slots are not
+ * touched), g fp32 [rows, per] the input gradient of the call's rows, read exactly once. */
+int bx_smoothgrad_accumulate(const float* g, double* S1, double* S2, int B, int n, int per, int Kc, int slot, int row0, int rows, bxStream stream);
+/* Values and map.  S1, S2 fp64 [BK,C,HW] -> values fp32 [BK,C,HW] of ``kind`` and map fp32 [BK,HW] = max over the C channels of
+ * |values| (map may be NULL).  A spectrogram passes its C and HW = H*W; an EEG input passes C = 1, HW = Chans*T.  BK = B * Kc <= 65535. */
+int bx_smoothgrad_finish(const double* S1, const double* S2, float* values, float* map, int BK, int C, int HW, int n, int kind, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

@@ -10,7 +10,8 @@ from .explain import (GradCamSweep, expected_gradients, generate_saliency_maps, 
                       predict_fn, shard_bounds, sharded_sweep, LimeExplanation, grid_segments, lime_image,
                       FaithfulnessCurves, attribution_ranks, deletion_insertion, RiseResult, rise, rise_masks, ScoreCamResult, score_cam,
                       OcclusionResult, occlusion, KernelShapResult, kernel_shap,
-                      GradientShapResult, gradient_shap, channel_importance, GradientExplainer)
+                      GradientShapResult, gradient_shap, channel_importance, GradientExplainer,
+                      SmoothGradResult, smooth_grad, smooth_grad_noise)
 from .data import (EEGStacker, stack_eeg, EEGMontageStacker, stack_eeg_montage,          # noqa: F401
                    SpectrogramPreprocessor, preprocess_spectrograms, SpectrogramRegionStacker, stack_spectrogram_regions, StagingRing)                                        # noqa: F401
 from .train import (FlatAdamW, DataParallel, GraphedTrainStep, AsyncCheckpointer, train_and_validate_combined, train_and_validate_eeg_distributed,   # noqa: F401

@@ -201,6 +201,10 @@ SIGNATURES = {
     "bx_expgrad_finish": (i32, [vp, vp, vp] + [i32] * 4 + [vp]),
     "bx_expgrad_seed": (i32, [vp, i32, vp] + [i32] * 5 + [vp]),
     "bx_mean_abs_rows": (i32, [vp, vp, i32, i32, vp]),
+    "bx_smoothgrad_sigma": (i32, [vp, vp, i32, i32, C.c_float, vp]),
+    "bx_smoothgrad_rows": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint64, i32, i32, vp]),
+    "bx_smoothgrad_accumulate": (i32, [vp, vp, vp] + [i32] * 7 + [vp]),
+    "bx_smoothgrad_finish": (i32, [vp] * 4 + [i32] * 5 + [vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

@@ -38,6 +38,13 @@
                                  channel-summed map (bx_expgrad_finish).  ``channel_importance`` is the reference's mean |.| per
                                  electrode (bx_mean_abs_rows), ``GradientExplainer`` SHAP's calling form.  ``expected_gradients`` is
                                  the same estimator as a host loop over one stand-alone model.
+* ``smooth_grad``             -- SmoothGrad, SmoothGrad^2 and VarGrad (Smilkov et al. 2017; Hooker et al. 2019; Captum's NoiseTunnel, which
+                                 the reference imports) of either input of the multimodal model or of a stand-alone branch: the
+                                 Gaussian noise is drawn in registers from Philox4x32-10 counters while the noisy rows of a pass are
+                                 written (bx_smoothgrad_sigma, bx_smoothgrad_rows) and never stored, one forward pass for all
+                                 classes, fp64 running sums of the gradient and its square in fixed draw order
+                                 (bx_smoothgrad_accumulate), the mean / mean square / variance and the channel-max map
+                                 (bx_smoothgrad_finish).  ``smooth_grad_noise`` returns the draws.
 """
 from __future__ import annotations
 
@@ -2316,3 +2323,194 @@ class GradientExplainer:
         res = gradient_shap(self.model, eeg, spec, self.background, input=self.input, nsamples=nsamples, class_idx="all", seed=seed, return_parts=True)
         vals = res.values.cpu().numpy()
         return [vals[:, c] for c in range(vals.shape[1])]
+
+
+# ------------------------------------------------------------------------------------------------
+# SmoothGrad, SmoothGrad^2 and VarGrad (Captum's NoiseTunnel over saliency; the reference imports Captum).  The definition is pinned in
+# include/brainxai.h; tests/smooth_grad_ref.py restates it.
+SmoothGradResult = collections.namedtuple("SmoothGradResult", "attribution values classes out sigma nsamples kind seed")
+SmoothGradResult.__doc__ = """What ``smooth_grad(..., return_parts=True)`` returns: ``attribution`` fp32 [B,H,W] / [B,Chans,T], with a class axis for
+class_idx='all' (what the plain call returns), ``values`` fp32 [B(,K),*x.shape[1:]] (the estimator element by element), ``classes`` int64
+[B] (None for class_idx='all'), ``out`` fp32 [B,K] (the log-probabilities of the clean input), ``sigma`` fp32 [B] (the noise scale of
+every sample), all on the device; ``nsamples``, ``kind`` and ``seed`` as given: ``stdev=sigma`` with them repeats the call."""
+
+_SMOOTHGRAD_KINDS = {"smoothgrad": 0, "smoothgrad_sq": 1, "vargrad": 2}          # BX_SMOOTHGRAD_MEAN / _SQ / _VAR
+
+
+def _smoothgrad_seed(who, seed):
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
+    return int(seed)
+
+
+def _smoothgrad_nsamples(who, nsamples):
+    if isinstance(nsamples, bool) or not isinstance(nsamples, numbers.Integral):
+        raise ValueError(f"{who}: nsamples must be an int, got {nsamples!r}")
+    if int(nsamples) < 1:
+        raise ValueError(f"{who}: nsamples = {int(nsamples)} < 1")
+    return int(nsamples)
+
+
+def _smoothgrad_scale(who, B, noise_level, stdev):
+    """-> (level, None) or (None, stdev fp32 host [B]): the paper's noise level (a fraction of each sample's range) or the caller's
+    absolute standard deviation, a number or one per sample; both None means a noise level of 0.15."""
+    if noise_level is not None and stdev is not None:
+        raise ValueError(f"{who}: give noise_level or stdev, not both")
+    if stdev is None:
+        level = 0.15 if noise_level is None else noise_level
+        if isinstance(level, bool) or not isinstance(level, numbers.Real) or not math.isfinite(level) or level < 0:
+            raise ValueError(f"{who}: noise_level must be a finite number >= 0, got {noise_level!r}")
+        if level > 3.0e38:
+            raise ValueError(f"{who}: noise_level {noise_level!r} is beyond fp32")
+        return float(level), None
+    if isinstance(stdev, torch.Tensor):
+        sd = stdev.detach().to("cpu", torch.float64).numpy()
+        if sd.shape != (B,):
+            raise ValueError(f"{who}: stdev of shape {tuple(stdev.shape)}; expected a number or [B] = [{B}]")
+    elif isinstance(stdev, numbers.Real) and not isinstance(stdev, bool):
+        sd = np.full(B, float(stdev), dtype=np.float64)
+    else:
+        raise ValueError(f"{who}: stdev must be a number or a tensor [B], got {type(stdev).__name__}")
+    if not np.isfinite(sd).all() or (sd < 0).any() or (sd > 3.0e38).any():
+        raise ValueError(f"{who}: stdev must be finite and >= 0")
+    return None, np.ascontiguousarray(sd.astype(np.float32))
+
+
+def smooth_grad_noise(shape, *, nsamples, seed=0, device=None):
+    """The standard normal draws of ``smooth_grad`` themselves, fp32 [B, n, *shape[1:]] on the device, for an explained input of
+    ``shape`` = [B, ...] -- for tests, plots and callers who want them; ``smooth_grad`` never stores them.  Written by the kernel that
+    writes the noisy rows (bx_smoothgrad_rows without an input), so row[b,k] = x[b] + sigma[b] * z[b,k] holds bit for bit.  The draws
+    of (b, k) depend on seed alone: a longer run extends a shorter one."""
+    who = "smooth_grad_noise"
+    try:
+        shape = tuple(int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: shape must be a sequence of ints [B, ...], got {shape!r}") from None
+    if len(shape) < 2 or min(shape) < 1:
+        raise ValueError(f"{who}: shape {shape}; expected [B, ...] with at least two axes, all >= 1")
+    n, seed = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed)
+    B, per = shape[0], int(np.prod(shape[1:]))
+    if B * n >= 1 << 31 or B * per >= 1 << 31:
+        raise ValueError(f"{who}: B * n = {B * n} or B * per = {B * per} beyond 32-bit offsets")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"brainxai.{who}: the noise is drawn on the GPU; there is no CPU path")
+    lib = L.load()
+    with torch.cuda.device(dev):
+        z = torch.empty(B * n, *shape[1:], dtype=torch.float32, device=dev)
+        step = max(1, ((1 << 31) - 1) // per)
+        for row0 in range(0, B * n, step):
+            rows = min(step, B * n - row0)
+            L.check(lib.bx_smoothgrad_rows(None, None, _p(z[row0:row0 + rows]), B, n, per, seed, row0, rows, _stream()), "bx_smoothgrad_rows")
+    return z.reshape(B, n, *shape[1:])
+
+
+def smooth_grad(model, eeg, spec, *, input="spec", nsamples=50, noise_level=None, stdev=None, kind="smoothgrad", class_idx=None, seed=0, max_batch=256,
+                return_parts=False):
+    """SmoothGrad (Smilkov et al. 2017), SmoothGrad^2 and VarGrad (Hooker et al. 2019; Adebayo et al. 2018) -- Captum's NoiseTunnel over
+    the input gradient -- for either input of the multimodal model or a stand-alone branch, batched over samples, draws and classes:
+        g[b,k] = dF_c/dx( x[b] + sigma[b] * z[b,k] ),   z standard normal,   F_c the model's output log-probability of class c
+        kind='smoothgrad': mean_k g;   'smoothgrad_sq': mean_k g^2;   'vargrad': the population variance of g over the draws.
+    The map is the largest |value| over the input's channels (``saliency``'s convention) and fits ``deletion_insertion`` and
+    ``attribution_ranks`` as it is.
+
+    input:       'spec': x = spec [B,C,H,W], map [B,H,W]; 'eeg': x = eeg [B,1,Chans,T], map [B,Chans,T].
+    model:       a MultimodalModel (the other input stays the sample's own); a stand-alone Spectrogram_Model (eeg=None, input='spec');
+                 a stand-alone EEGNet / EEGNetAttentionDeep (spec=None, input='eeg').
+    noise_level: the paper's noise level: sigma[b] = noise_level * (max x[b] - min x[b]) (bx_smoothgrad_sigma); 0.15 when neither
+                 noise_level nor stdev is given.
+    stdev:       the absolute standard deviation instead: a number, or one per sample (tensor [B]).  Giving both is refused.
+    nsamples:    n, the draws per sample.  The noise is drawn on the device from Philox4x32-10 counters (element, draw, sample) keyed by
+                 ``seed`` (0 <= seed < 2^64) and never stored; the draws of a sample depend neither on nsamples (a longer run extends a
+                 shorter one) nor on max_batch.  ``smooth_grad_noise`` returns them.
+    class_idx:   None = each sample's arg-max class on the clean input; an int; one class per sample (sequence / tensor [B]); 'all' =
+                 every class, the map gains a class axis [B,K,...] (K <= 32): one forward pass then serves K backward passes.
+    max_batch:   rows (noisy inputs) per pass, capped so that a pass addresses its largest activation with 32-bit offsets.  The sums
+                 over the draws are carried in fp64 between passes, so, given the same gradients, no bit of the result depends on it.
+    The rows of a pass are written by one launch (bx_smoothgrad_rows), the one-hot gradient seeds by one (bx_expgrad_seed); every backward
+    pass is followed by one bx_smoothgrad_accumulate (fp64 sums of g and g^2, ascending draw order, no atomics), and bx_smoothgrad_finish
+    forms the values and the map.  In a MultimodalModel the branch whose input does not change runs once per sample and its output is
+    gathered into the fusion head.  The training flag and every requires_grad are restored on return.  Returns the map (device, fp32),
+    or ``SmoothGradResult`` with return_parts."""
+    return _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, class_idx, seed, max_batch, return_parts)
+
+
+def _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, class_idx, seed, max_batch, return_parts, profile=None):
+    """``smooth_grad`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'sigma', 'rows',
+    'forward', 'backward', 'accumulate', 'finish' -- device events around every phase of the pass (tools/smooth_grad_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "smooth_grad"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if not isinstance(kind, str) or kind not in _SMOOTHGRAD_KINDS:
+        raise ValueError(f"{who}: unknown kind {kind!r}; use 'smoothgrad', 'smoothgrad_sq' or 'vargrad'")
+    n, seed, max_batch = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed), _max_batch(who, max_batch)
+    x = _input_tensor(who, input, eeg, spec)
+    B = int(x.shape[0])
+    if B < 1 or x.numel() == 0:
+        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
+    level, sd = _smoothgrad_scale(who, B, noise_level, stdev)
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    Kc = K if all_classes else 1
+    per = x.numel() // B
+    if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or B * Kc > 65535:
+        raise ValueError(f"{who}: B * n = {B * n} or B * Kc * per = {B * Kc * per} beyond 32-bit offsets, or B * Kc = {B * Kc} > 65535; use fewer samples per call")
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+
+    lib = L.load()
+    dev = x.device
+    is_spec = input == "spec"
+    dt = getattr(net, "compute_dtype", torch.float32) if is_spec else torch.float32
+    max_rows = min(_row_cap(x, input, dt, max_batch), ((1 << 31) - 1) // per)
+    total = B * n
+    Cc, HW = (int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])) if is_spec else (1, per)
+
+    with torch.cuda.device(dev), _eval_frozen(model):
+        xs = x.detach().to(torch.float32).contiguous()
+        with _lap(profile, "sigma"):
+            if sd is None:
+                sigma = torch.empty(B, dtype=torch.float32, device=dev)
+                L.check(lib.bx_smoothgrad_sigma(_p(xs), _p(sigma), B, per, level, _stream()), "bx_smoothgrad_sigma")
+            else:
+                sigma = torch.from_numpy(sd).to(dev)
+        fixed = None
+        with torch.no_grad(), _lap(profile, "forward"):
+            if multimodal:
+                fixed = _fixed_branch(model, other, is_spec)
+            out = _fuse(model, multimodal, is_spec, net(xs), fixed).float().contiguous()
+        classes = _class_tensor(cls_h, all_classes, out, dev)
+        S1 = torch.zeros(B, Kc, per, dtype=torch.float64, device=dev)
+        S2 = torch.zeros(B, Kc, per, dtype=torch.float64, device=dev)
+        for row0 in range(0, total, max_rows):
+            rows = min(max_rows, total - row0)
+            with _lap(profile, "rows"):
+                r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=dev)
+                L.check(lib.bx_smoothgrad_rows(_p(xs), _p(sigma), _p(r), B, n, per, seed, row0, rows, _stream()), "bx_smoothgrad_rows")
+            with _lap(profile, "forward"):
+                r.requires_grad_(True)
+                rep = None
+                if multimodal:                                      # the other branch's output of the sample each row belongs to
+                    rep = fixed.index_select(0, torch.div(torch.arange(row0, row0 + rows, device=dev), n, rounding_mode="floor"))
+                y = _fuse(model, multimodal, is_spec, net(r), rep).float()
+            seed_rows = torch.empty(rows, K, dtype=torch.float32, device=dev)
+            for slot in range(Kc):
+                with _lap(profile, "backward"):
+                    L.check(lib.bx_expgrad_seed(_p(classes), slot if all_classes else -1, _p(seed_rows), B, n, K, row0, rows, _stream()), "bx_expgrad_seed")
+                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows, retain_graph=slot + 1 < Kc)
+                    g = g.to(torch.float32).contiguous()
+                with _lap(profile, "accumulate"):
+                    L.check(lib.bx_smoothgrad_accumulate(_p(g), _p(S1), _p(S2), B, n, per, Kc, slot, row0, rows, _stream()), "bx_smoothgrad_accumulate")
+            del y, r
+        with _lap(profile, "finish"):
+            values = torch.empty(B, Kc, *xs.shape[1:], dtype=torch.float32, device=dev)
+            amap = torch.empty(B, Kc, int(x.shape[2]), int(x.shape[3]), dtype=torch.float32, device=dev)
+            L.check(lib.bx_smoothgrad_finish(_p(S1), _p(S2), _p(values), _p(amap), B * Kc, Cc, HW, n, _SMOOTHGRAD_KINDS[kind], _stream()), "bx_smoothgrad_finish")
+    if not all_classes:
+        amap, values = amap[:, 0], values[:, 0]
+    if not return_parts:
+        return amap
+    return SmoothGradResult(amap, values, None if classes is None else classes.long(), out, sigma, n, kind, seed)
