@@ -847,6 +847,55 @@ int bx_smoothgrad_accumulate(const float* g, double* S1, double* S2, int B, int 
 /* Values and map.  S1, S2 fp64 [BK,C,HW] -> values fp32 [BK,C,HW] of ``kind`` and map fp32 [BK,HW] = max over the C channels of
  * |values| (map may be NULL).  A spectrogram passes its C and HW = H*W; an EEG input passes C = 1, HW = Chans*T.  BK = B * Kc <= 65535. */
 int bx_smoothgrad_finish(const double* S1, const double* S2, float* values, float* map, int BK, int C, int HW, int n, int kind, bxStream stream);
+/* ---- Infidelity and max-sensitivity of an explanation (Yeh et al., NeurIPS 2019; Captum's metrics.infidelity and
+ * metrics.sensitivity_max).  Infidelity, for the explained input x [B,...], an attribution Phi [B,Kc,cells] whose cells are the features,
+ * n draws per sample, a noise scale sigma[b] and s_c the model's fp32 probability (or log-probability) of class c:
+ *     I[b,k,cell]  = fl32( sigma[b] * z[b,k,cell] )                       z: SmoothGrad's stream above, with `cell` as its element
+ *     row[b,k,e]   = fl32( x[b,e] - I[b,k,cell(e)] )                      (product and difference rounded separately, no fma)
+ *     d[b,c,k]     = sum_cell (double)I[b,k,cell] * (double)Phi[b,c,cell] (fp64; every product is exact)
+ *     Delta[b,c,k] = (double)s_c(x[b]) - (double)s_c(row[b,k])
+ *     infid[b,c]   = (1/n) sum_k ( beta d - Delta )^2                     (fp64, ascending k; product, difference, square, sum and the
+ *                                                                          division by n each rounded on their own)
+ *     beta = 1, or with `normalize` beta[b,c] = (sum_k d Delta) / (sum_k d d), 0 when the denominator is 0   (Captum's scaling)
+ * Cells.  A spectrogram [C,H,W]: elements (cells = C*H*W, cell = its NCHW offset in the sample) or pixels (cells = H*W, one draw moves
+ * the C channels of a pixel).  An EEG input [1,Chans,T]: elements (cells = Chans*T) or time columns (cells = T, one draw moves every
+ * electrode).  z[b,k,cell] is word cell & 3 of the Philox block of counter (cell >> 2, k, b, 0): bx_smoothgrad_rows with x == NULL and
+ * per = cells writes exactly these draws.
+ * Rows are written straight in the model's layouts -- spectrogram rows NHWC with Cp = 8 channels in `dtype` (channels C..7 zero, the
+ * rounding of bx_nchw_to_nhwc), EEG rows fp32 [rows,1,Chans,T] -- in the chunk form of the perturb-and-predict writers: a call writes
+ * samples b0 .. b0+nb-1 and draws n0 .. n0+n-1 of the N draws, row (b - b0) * n + (k - n0); x and sigma are the whole arrays.  The noise
+ * lives in registers only.  The order of the sum d is a function of `cells` alone: the noise is drawn again, thread t of one workgroup
+ * per (b, k) takes the Philox blocks t, t + 256, ... in ascending order and the 256 partial sums meet in a pairwise tree over the thread
+ * index (stride 128, 64, .., 1).  No atomics; no bit of d depends on how rows were split into calls.  Every entry point refuses its
+ * limits with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+/* out [nb*n,H,W,Cp] in dtype (16-byte aligned); per_pixel != 0: pixel cells.  1 <= C <= 4, Cp = 8; 16-byte loads when H*W % 4 == 0 and
+ * x is 16-byte aligned, element by element otherwise. */
+int bx_infidelity_rows_spec(const float* x, const float* sigma, void* out, int B, int C, int H, int W, int Cp, int per_pixel, int N, int b0,
+                            int nb, int n0, int n, uint64_t seed, int dtype, bxStream stream);
+/* out fp32 [nb*n,1,Chans,T]; per_column != 0: time-column cells. */
+int bx_infidelity_rows_eeg(const float* x, const float* sigma, float* out, int B, int Chans, int T, int per_column, int N, int b0, int nb, int n0,
+                           int n, uint64_t seed, bxStream stream);
+/* d fp64 [B,Kc,n]: the entries of the global rows j = b * n + k in [row0, row0 + rows) are written, every class of them (Kc <= 32);
+ * phi fp32 [B,Kc,cells], sigma fp32 [B]. */
+int bx_infidelity_dot(const float* phi, const float* sigma, double* d, int B, int n, int cells, int Kc, uint64_t seed, int row0, int rows,
+                      bxStream stream);
+/* One thread per explained (sample, class) pair q: classes i32 [B] on the device (Kc = 1; a class outside 0..K-1 counts as the nearest
+ * end) or NULL for every class (Kc = K <= 32).  d fp64 [B,Kc,n], S fp32 [B,n,K] the scores of the rows, clean fp32 [B,K] those of the
+ * unperturbed input -> infid, beta fp64 [B,Kc] and drops fp64 [B,Kc,n] = Delta. */
+int bx_infidelity_finish(const double* d, const float* S, const float* clean, const int* classes, double* infid, double* beta, double* drops, int B,
+                         int n, int K, int normalize, bxStream stream);
+/* Max-sensitivity, for an explanation function Phi, n draws per sample and a radius r[b]:
+ *     u[b,k,e]   = (float)(w >> 8) * 2^-23 - 1  in [-1, 1), exact;  w = word e & 3 of Philox4x32-10( counter = (e >> 2, k, b, 1), key as above )
+ *     row[b,k,e] = fl32( x[b,e] + fl32( r[b] * u[b,k,e] ) )         fp32 in the input's own layout, always elementwise
+ *     sens[b]    = max_k || Phi(row[b,k]) - Phi(x[b]) ||_2 / || Phi(x[b]) ||_2,   the denominator 1 when the norm is 0   (Captum's rule)
+ * Counter word 3 is 1: a stream apart from the normal one.  The uniformly perturbed rows, out fp32 [rows, per], row r = global row
+ * row0 + r = b * n + k; with x == NULL (and radius == NULL) the same kernel writes u itself. */
+int bx_sensitivity_rows(const float* x, const float* radius, float* out, int B, int n, int per, uint64_t seed, int row0, int rows, bxStream stream);
+/* dist[r] = sqrt( sum_e ( (double)a[r,e] - (double)ref[(row0 + r) / n, e] )^2 ) for a fp32 [rows, per], ref fp32 [B, per]; ref == NULL: the
+ * norm of a[r].  One workgroup per row; thread t sums e = t, t + 256, ... in ascending order, then the tree above: fixed order. */
+int bx_sensitivity_dist(const float* a, const float* ref, double* dist, int B, int n, int per, int row0, int rows, bxStream stream);
+/* sens[b] = max_k dist[b,k] / (norms[b] == 0 ? 1 : norms[b]); dist fp64 [B,n], norms and sens fp64 [B]. */
+int bx_sensitivity_finish(const double* dist, const double* norms, double* sens, int B, int n, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

@@ -11,7 +11,8 @@ from .explain import (GradCamSweep, expected_gradients, generate_saliency_maps, 
                       FaithfulnessCurves, attribution_ranks, deletion_insertion, RiseResult, rise, rise_masks, ScoreCamResult, score_cam,
                       OcclusionResult, occlusion, KernelShapResult, kernel_shap,
                       GradientShapResult, gradient_shap, channel_importance, GradientExplainer,
-                      SmoothGradResult, smooth_grad, smooth_grad_noise)
+                      SmoothGradResult, smooth_grad, smooth_grad_noise,
+                      InfidelityResult, infidelity, SensitivityResult, sensitivity_max)
 from .data import (EEGStacker, stack_eeg, EEGMontageStacker, stack_eeg_montage,          # noqa: F401
                    SpectrogramPreprocessor, preprocess_spectrograms, SpectrogramRegionStacker, stack_spectrogram_regions, StagingRing)                                        # noqa: F401
 from .train import (FlatAdamW, DataParallel, GraphedTrainStep, AsyncCheckpointer, train_and_validate_combined, train_and_validate_eeg_distributed,   # noqa: F401

@@ -205,6 +205,13 @@ SIGNATURES = {
     "bx_smoothgrad_rows": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint64, i32, i32, vp]),
     "bx_smoothgrad_accumulate": (i32, [vp, vp, vp] + [i32] * 7 + [vp]),
     "bx_smoothgrad_finish": (i32, [vp] * 4 + [i32] * 5 + [vp]),
+    "bx_infidelity_rows_spec": (i32, [vp, vp, vp] + [i32] * 11 + [C.c_uint64, i32, vp]),
+    "bx_infidelity_rows_eeg": (i32, [vp, vp, vp] + [i32] * 9 + [C.c_uint64, vp]),
+    "bx_infidelity_dot": (i32, [vp, vp, vp] + [i32] * 4 + [C.c_uint64, i32, i32, vp]),
+    "bx_infidelity_finish": (i32, [vp] * 7 + [i32] * 4 + [vp]),
+    "bx_sensitivity_rows": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint64, i32, i32, vp]),
+    "bx_sensitivity_dist": (i32, [vp, vp, vp] + [i32] * 5 + [vp]),
+    "bx_sensitivity_finish": (i32, [vp, vp, vp, i32, i32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

@@ -45,6 +45,12 @@
                                  classes, fp64 running sums of the gradient and its square in fixed draw order
                                  (bx_smoothgrad_accumulate), the mean / mean square / variance and the channel-max map
                                  (bx_smoothgrad_finish).  ``smooth_grad_noise`` returns the draws.
+* ``infidelity`` / ``sensitivity_max`` -- the two measures of Yeh et al. (NeurIPS 2019; Captum's metrics.infidelity and
+                                 metrics.sensitivity_max) for any of those maps: rows minus SmoothGrad's Gaussian stream written in the
+                                 model's layout (bx_infidelity_rows_*), the fp64 dot of the same noise with the attribution in fixed
+                                 order (bx_infidelity_dot), drops, beta and the mean square (bx_infidelity_finish); uniformly perturbed
+                                 rows (bx_sensitivity_rows), fp64 distances of the caller's explanations (bx_sensitivity_dist) and
+                                 the largest relative one (bx_sensitivity_finish).
 """
 from __future__ import annotations
 
@@ -2514,3 +2520,267 @@ def _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, cl
     if not return_parts:
         return amap
     return SmoothGradResult(amap, values, None if classes is None else classes.long(), out, sigma, n, kind, seed)
+
+
+# ------------------------------------------------------------------------------------------------
+# Infidelity and max-sensitivity (Yeh et al., NeurIPS 2019; Captum's metrics.infidelity and metrics.sensitivity_max): how well an
+# attribution predicts the effect of a small perturbation, and how stable it is around the input.  The definitions are pinned in
+# include/brainxai.h; tests/infidelity_ref.py restates them.
+InfidelityResult = collections.namedtuple("InfidelityResult", "infidelity beta dots drops clean classes sigma nsamples seed")
+InfidelityResult.__doc__ = """What ``infidelity(..., return_parts=True)`` returns: ``infidelity`` and ``beta`` fp64 [B] or [B,K] (beta is 1 without
+normalize), ``dots`` and ``drops`` fp64 [B,n] or [B,K,n] (d and Delta of every draw), ``clean`` fp32 [B,K] (the scores of the unperturbed
+input), ``classes`` int64 [B] (None for class_idx='all'), ``sigma`` fp32 [B], all on the device; ``nsamples`` and ``seed`` as given."""
+
+SensitivityResult = collections.namedtuple("SensitivityResult", "sensitivity distances norms radius nsamples seed")
+SensitivityResult.__doc__ = """What ``sensitivity_max(..., return_parts=True)`` returns: ``sensitivity`` fp64 [B], ``distances`` fp64 [B,n] (the L2
+distance of every perturbed explanation from the clean one), ``norms`` fp64 [B] (the L2 norm of the clean explanation), ``radius`` fp32
+[B], all on the device; ``nsamples`` and ``seed`` as given."""
+
+
+def _infidelity_cells(who, attribution, x, input_is_spec, all_classes, K):
+    """-> (grouped, cells): whether a draw moves a whole pixel / time column (else one element), and the cells of a sample."""
+    B = int(x.shape[0])
+    lead = (B, K) if all_classes else (B,)
+    shape = tuple(attribution.shape)
+    if input_is_spec:
+        Cc, H, W = (int(v) for v in x.shape[1:])
+        forms = {lead + (Cc, H, W): (False, Cc * H * W), lead + (H, W): (True, H * W)}
+        names = ("[B,K,C,H,W]", "[B,K,H,W]") if all_classes else ("[B,C,H,W]", "[B,H,W]")
+    else:
+        Chans, T = int(x.shape[2]), int(x.shape[3])
+        forms = {lead + (1, Chans, T): (False, Chans * T), lead + (Chans, T): (False, Chans * T), lead + (1, T): (True, T)}
+        names = ("[B,K,1,Chans,T]", "[B,K,Chans,T]", "[B,K,1,T]") if all_classes else ("[B,1,Chans,T]", "[B,Chans,T]", "[B,1,T]")
+    if shape not in forms:
+        if all_classes and shape in {s[:1] + s[2:] for s in forms}:
+            raise ValueError(f"{who}: class_idx='all' needs an attribution with a class axis after B; got {shape}, expected one of "
+                             + " or ".join(f"{nm} = {s}" for nm, s in zip(names, forms)))
+        raise ValueError(f"{who}: wrong map shape {shape} for input={'spec' if input_is_spec else 'eeg'!r}; expected "
+                         + " or ".join(f"{nm} = {s}" for nm, s in zip(names, forms)))
+    return forms[shape]
+
+
+def _infidelity_rows(x, sigma, grouped, N, seed, b0, nb, n0, n, dt, eeg_rows):
+    """Rows (b, j), b in b0..b0+nb-1, j in 0..n-1: sample b minus the noise of draw n0 + j.  x fp32 [B,C,H,W] -> internal layout
+    [nb*n,H,W,8] in dt (bx_infidelity_rows_spec), or with eeg_rows fp32 [B,1,Chans,T] -> [nb*n,1,Chans,T] (bx_infidelity_rows_eeg)."""
+    lib = L.load()
+    out, dims = _empty_rows(x, nb * n, dt, eeg_rows)
+    B = int(x.shape[0])
+    if not eeg_rows:
+        L.check(lib.bx_infidelity_rows_spec(_p(x), _p(sigma), _p(out), B, *dims, 1 if grouped else 0, N, b0, nb, n0, n, seed, ops.bx_dtype(dt), _stream()),
+                "bx_infidelity_rows_spec")
+    else:
+        L.check(lib.bx_infidelity_rows_eeg(_p(x), _p(sigma), _p(out), B, *dims, 1 if grouped else 0, N, b0, nb, n0, n, seed, _stream()),
+                "bx_infidelity_rows_eeg")
+    return out
+
+
+def infidelity(model, eeg, spec, attribution, *, input="spec", nsamples=10, noise_level=None, stdev=None, normalize=False, class_idx=None, score="prob",
+               seed=0, max_batch=256, return_parts=False):
+    """Infidelity of an attribution (Yeh et al., NeurIPS 2019; Captum's ``metrics.infidelity`` with Gaussian perturbations): how well the
+    attribution predicts the drop of the class score under a small perturbation of the input,
+        I[b,k] = sigma[b] * z[b,k],   d = <I, Phi>,   Delta = s_c(x) - s_c(x - I),   infid[b] = mean_k (beta d - Delta)^2
+    with z standard normal and s_c the probability (score='logprob': the log-probability) of the explained class.  Small is faithful.
+
+    attribution: the features are its cells.  input='spec': [B,C,H,W] (a cell is an element) or [B,H,W] (a cell is a pixel: one draw moves
+                 all its channels -- the maps every method here returns); input='eeg': [B,1,Chans,T] / [B,Chans,T] (elements) or [B,1,T]
+                 (a whole time column).  With class_idx='all' it carries a class axis after B, [B,K,...] (K <= 32).  The maps of
+                 grad_cam, saliency, smooth_grad, occlusion, rise, kernel_shap ... fit as they are.
+    model:       a MultimodalModel; a stand-alone Spectrogram_Model (eeg=None, input='spec'); a stand-alone EEGNet /
+                 EEGNetAttentionDeep (spec=None, input='eeg') -- the convention of grad_cam.
+    noise_level / stdev: the scale of the perturbation, as in ``smooth_grad``: sigma[b] = noise_level * the sample's range (0.15 when
+                 neither is given), or an absolute stdev, a number or one per sample.  Giving both is refused.
+    nsamples:    n, the draws per sample.  z is SmoothGrad's stream with the cell as its element: ``smooth_grad_noise((B, *cell_shape),
+                 nsamples=n, seed=seed)`` returns exactly these draws; those of (b, k) depend neither on nsamples nor on max_batch.
+    normalize:   Captum's scaling: beta[b] = sum_k d Delta / sum_k d^2 (0 when the denominator is 0) makes the result invariant to the
+                 scale of the attribution; otherwise beta = 1.
+    class_idx:   None = each sample's arg-max class on the clean input; an int; one class per sample; 'all' (``occlusion``'s conventions).
+    max_batch:   rows (perturbed inputs) per forward pass; no bit of ``dots`` depends on it.
+    (n + 1) * B forward evaluations in eval mode without autograd.  The rows are written straight in the model's layout with the noise
+    in registers (bx_infidelity_rows_*); the dot draws the noise again and sums in fp64 in an order that depends on the shapes alone
+    (bx_infidelity_dot); bx_infidelity_finish forms the drops, beta and the mean square.  In a MultimodalModel the branch whose input
+    does not change runs once per sample.  The training flag and every requires_grad are restored on return.  Returns fp64 [B] (or
+    [B,K]) on the device, or ``InfidelityResult`` with return_parts."""
+    return _infidelity(model, eeg, spec, attribution, input, nsamples, noise_level, stdev, normalize, class_idx, score, seed, max_batch, return_parts)
+
+
+def _infidelity(model, eeg, spec, attribution, input, nsamples, noise_level, stdev, normalize, class_idx, score, seed, max_batch, return_parts, profile=None):
+    """``infidelity`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'sigma', 'perturb',
+    'forward', 'dot', 'finish' -- device events around every phase of the pass (tools/infidelity_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "infidelity"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if score not in _FAITH_SCORES:
+        raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
+    n, seed, max_batch = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed), _max_batch(who, max_batch)
+    x = _input_tensor(who, input, eeg, spec)
+    if not isinstance(attribution, torch.Tensor):
+        raise ValueError(f"{who}: attribution must be a tensor")
+    B = int(x.shape[0])
+    if B < 1 or x.numel() == 0:
+        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
+    is_spec = input == "spec"
+    _per_cell(who, x, is_spec)
+    level, sd = _smoothgrad_scale(who, B, noise_level, stdev)
+    other = eeg if is_spec else spec
+    multimodal, K, net = _target_model(who, model, x, other, is_spec)
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    grouped, cells = _infidelity_cells(who, attribution, x, is_spec, all_classes, K)
+    Kc = K if all_classes else 1
+    per = x.numel() // B
+    if B * n * K >= 1 << 31 or B * Kc * cells >= 1 << 31 or B * per >= 1 << 31:
+        raise ValueError(f"{who}: B * n * K = {B * n * K}, B * Kc * cells = {B * Kc * cells} or B * per = {B * per} beyond 32-bit offsets; use fewer samples per call")
+    _need_gpu(who, "the model, its inputs and the attribution", model, x, attribution, other if multimodal else None)
+
+    lib = L.load()
+    dev = x.device
+    use_logprob = score == "logprob"
+    rp = _RowPass(model, net, multimodal, K, x, other, is_spec, 0, torch.zeros(1), max_batch, profile)
+
+    with rp.open():
+        with rp.lap("sigma"):
+            if sd is None:
+                sigma = torch.empty(B, dtype=torch.float32, device=dev)
+                L.check(lib.bx_smoothgrad_sigma(_p(rp.xs), _p(sigma), B, per, level, _stream()), "bx_smoothgrad_sigma")
+            else:
+                sigma = torch.from_numpy(sd).to(dev)
+        phi = attribution.detach().to(torch.float32).reshape(B, Kc, cells).contiguous()
+        with rp.lap("forward"):
+            rp.fix_other()
+            # the unperturbed input takes the path of the perturbed rows, in chunks of the same size
+            clean = torch.empty(B, K, dtype=torch.float32, device=dev)
+            for b0, nb in rp.groups():
+                clean[b0:b0 + nb] = rp.scores(rp.clean_rows(b0, nb), b0, nb, logprob=use_logprob)
+        classes = _class_tensor(cls_h, all_classes, clean, dev)
+        S = rp.sweep(n, lambda *chunk: _infidelity_rows(rp.xs, sigma, grouped, n, seed, *chunk, rp.dt, not is_spec), logprob=use_logprob)
+        with rp.lap("dot"):
+            dots = torch.empty(B, Kc, n, dtype=torch.float64, device=dev)
+            L.check(lib.bx_infidelity_dot(_p(phi), _p(sigma), _p(dots), B, n, cells, Kc, seed, 0, B * n, _stream()), "bx_infidelity_dot")
+        with rp.lap("finish"):
+            infid = torch.empty(B, Kc, dtype=torch.float64, device=dev)
+            beta, drops = torch.empty_like(infid), torch.empty_like(dots)
+            L.check(lib.bx_infidelity_finish(_p(dots), _p(S), _p(clean), _p(classes), _p(infid), _p(beta), _p(drops), B, n, K, 1 if normalize else 0,
+                                             _stream()), "bx_infidelity_finish")
+    if not all_classes:
+        infid, beta, dots, drops = infid[:, 0], beta[:, 0], dots[:, 0], drops[:, 0]
+    if not return_parts:
+        return infid
+    return InfidelityResult(infid, beta, dots, drops, clean, None if classes is None else classes.long(), sigma, n, seed)
+
+
+def _sensitivity_radius(who, B, radius, radius_level):
+    """-> (level, None) or (None, radius fp32 host [B]): a fraction of each sample's range or the caller's absolute radius, a number or
+    one per sample; both None means a level of 0.02 (Captum's radius on unit-range inputs)."""
+    if radius is not None and radius_level is not None:
+        raise ValueError(f"{who}: give radius or radius_level, not both")
+    if radius is None:
+        level = 0.02 if radius_level is None else radius_level
+        if isinstance(level, bool) or not isinstance(level, numbers.Real) or not math.isfinite(level) or level < 0 or level > 3.0e38:
+            raise ValueError(f"{who}: radius_level must be a finite number >= 0, got {radius_level!r}")
+        return float(level), None
+    if isinstance(radius, torch.Tensor):
+        r = radius.detach().to("cpu", torch.float64).numpy()
+        if r.shape != (B,):
+            raise ValueError(f"{who}: radius of shape {tuple(radius.shape)}; expected a number or [B] = [{B}]")
+    elif isinstance(radius, numbers.Real) and not isinstance(radius, bool):
+        r = np.full(B, float(radius), dtype=np.float64)
+    else:
+        raise ValueError(f"{who}: radius must be a number or a tensor [B], got {type(radius).__name__}")
+    if not np.isfinite(r).all() or (r < 0).any() or (r > 3.0e38).any():
+        raise ValueError(f"{who}: radius must be finite and >= 0")
+    return None, np.ascontiguousarray(r.astype(np.float32))
+
+
+def _sensitivity_explain(who, explain, eeg_rows, spec_rows, sample, trail):
+    """One call of the explanation function -> fp32 [rows, P] contiguous and its trailing shape, which must equal ``trail`` if given."""
+    rows = int(sample.shape[0])
+    phi = explain(eeg_rows, spec_rows, sample)
+    if not isinstance(phi, torch.Tensor) or not phi.is_cuda or phi.dim() < 2 or int(phi.shape[0]) != rows or not phi.dtype.is_floating_point:
+        raise ValueError(f"{who}: explain must return a floating-point device tensor [rows, ...] with rows = {rows}, got "
+                         + (f"{tuple(phi.shape)} {phi.dtype} on {phi.device}" if isinstance(phi, torch.Tensor) else type(phi).__name__))
+    if trail is not None and tuple(phi.shape[1:]) != trail:
+        raise ValueError(f"{who}: explain returned the trailing shape {tuple(phi.shape[1:])}, the clean call returned {trail}")
+    return phi.detach().to(torch.float32).reshape(rows, -1).contiguous(), tuple(phi.shape[1:])
+
+
+def sensitivity_max(explain, eeg, spec, *, input="spec", nsamples=10, radius=None, radius_level=None, seed=0, max_batch=256, return_parts=False):
+    """Max-sensitivity of an explanation function (Yeh et al., NeurIPS 2019; Captum's ``metrics.sensitivity_max``): how far the
+    explanation moves, relative to its norm, when the input moves inside a small L-infinity ball,
+        sens[b] = max_k || Phi(x[b] + r[b] * u[b,k]) - Phi(x[b]) ||_2 / || Phi(x[b]) ||_2,   u uniform in [-1, 1) per element
+    (the denominator is 1 when the norm is 0, Captum's rule).  Small is stable.
+
+    explain:     ``explain(eeg_rows, spec_rows, sample)`` -> a floating-point device tensor [rows, ...]: any of the package's attribution
+                 calls behind a lambda.  ``sample`` is int64 [rows] on the device and names the sample each row perturbs, so that a caller
+                 can pass ``class_idx=cls[sample]``; the input that is not perturbed is repeated per row (None stays None, for a
+                 stand-alone model).  It is called once on the clean batch, then on chunks of at most max_batch rows; the trailing
+                 shape of its result must be the same on every call.
+    input:       'spec': the spectrogram [B,C,H,W] is perturbed; 'eeg': the EEG input [B,1,Chans,T].  Rows are fp32 in the input's own
+                 layout, always perturbed element by element.
+    radius / radius_level: r[b]: an absolute radius, a number or one per sample (tensor [B]); or radius_level times the sample's range
+                 (bx_smoothgrad_sigma).  radius_level = 0.02 when neither is given; giving both is refused.
+    nsamples:    n, the draws per sample, from Philox4x32-10 counters (element, draw, sample, 1) keyed by ``seed``: a stream apart from
+                 smooth_grad's; the draws of (b, k) depend neither on nsamples nor on max_batch.
+    The rows of a chunk are written by one launch (bx_sensitivity_rows), the distances are fp64 sums in fixed order, one workgroup per row
+    (bx_sensitivity_dist; the norms of the clean explanation are the same kernel without a second operand), bx_sensitivity_finish takes
+    the maximum and divides.  Returns fp64 [B] on the device, or ``SensitivityResult`` with return_parts."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "sensitivity_max"
+    if not callable(explain):
+        raise ValueError(f"{who}: explain must be a callable (eeg_rows, spec_rows, sample) -> tensor, got {type(explain).__name__}")
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    n, seed, max_batch = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed), _max_batch(who, max_batch)
+    x = _input_tensor(who, input, eeg, spec)
+    B = int(x.shape[0])
+    if B < 1 or x.numel() == 0:
+        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
+    level, rad = _sensitivity_radius(who, B, radius, radius_level)
+    other = eeg if input == "spec" else spec
+    if other is not None and (not isinstance(other, torch.Tensor) or other.shape[0] != B):
+        raise ValueError(f"{who}: the other input must be None or a tensor with the same batch size")
+    per = x.numel() // B
+    if B * n >= 1 << 31 or B * per >= 1 << 31:
+        raise ValueError(f"{who}: B * n = {B * n} or B * per = {B * per} beyond 32-bit offsets; use fewer samples per call")
+    if not (x.is_cuda and (other is None or other.is_cuda)):
+        raise RuntimeError(f"brainxai.{who}: the inputs must live on the GPU; there is no CPU path")
+
+    lib = L.load()
+    dev = x.device
+    total = B * n
+    max_rows = max(1, min(max_batch, ((1 << 31) - 1) // per))
+
+    def call(rows_x, sample, trail):
+        """explain on rows of the perturbed input; the other input is the clean batch itself (trail None) or repeated per row"""
+        o = other if other is None or trail is None else other.index_select(0, sample)
+        return _sensitivity_explain(who, explain, *((o, rows_x) if input == "spec" else (rows_x, o)), sample, trail)
+
+    with torch.cuda.device(dev):
+        xs = x.detach().to(torch.float32).contiguous()
+        if rad is None:
+            r = torch.empty(B, dtype=torch.float32, device=dev)
+            L.check(lib.bx_smoothgrad_sigma(_p(xs), _p(r), B, per, level, _stream()), "bx_smoothgrad_sigma")
+        else:
+            r = torch.from_numpy(rad).to(dev)
+        phi0, trail = call(xs, torch.arange(B, dtype=torch.int64, device=dev), None)
+        P = int(phi0.shape[1])
+        if P < 1 or B * P >= 1 << 31:
+            raise ValueError(f"{who}: explain returned {P} values per row; B * P must stay within 1..2^31 - 1")
+        norms = torch.empty(B, dtype=torch.float64, device=dev)
+        L.check(lib.bx_sensitivity_dist(_p(phi0), None, _p(norms), B, 1, P, 0, B, _stream()), "bx_sensitivity_dist")
+        dist = torch.empty(total, dtype=torch.float64, device=dev)
+        max_rows = max(1, min(max_rows, ((1 << 31) - 1) // P))
+        for row0 in range(0, total, max_rows):
+            rows = min(max_rows, total - row0)
+            rx = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=dev)
+            L.check(lib.bx_sensitivity_rows(_p(xs), _p(r), _p(rx), B, n, per, seed, row0, rows, _stream()), "bx_sensitivity_rows")
+            sample = torch.div(torch.arange(row0, row0 + rows, dtype=torch.int64, device=dev), n, rounding_mode="floor")
+            phi, _ = call(rx, sample, trail)
+            L.check(lib.bx_sensitivity_dist(_p(phi), _p(phi0), _p(dist[row0:row0 + rows]), B, n, P, row0, rows, _stream()), "bx_sensitivity_dist")
+            del phi, rx
+        sens = torch.empty(B, dtype=torch.float64, device=dev)
+        L.check(lib.bx_sensitivity_finish(_p(dist), _p(norms), _p(sens), B, n, _stream()), "bx_sensitivity_finish")
+    if not return_parts:
+        return sens
+    return SensitivityResult(sens, dist.reshape(B, n), norms, r, n, seed)
