@@ -1088,6 +1088,65 @@ def _max_batch(who, v):
     return v
 
 
+def _draw_count(who, nsamples):
+    if isinstance(nsamples, bool) or not isinstance(nsamples, numbers.Integral):
+        raise ValueError(f"{who}: nsamples must be an int, got {nsamples!r}")
+    if int(nsamples) < 1:
+        raise ValueError(f"{who}: nsamples = {int(nsamples)} < 1")
+    return int(nsamples)
+
+
+def _stream_seed(who, seed):
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
+    return int(seed)
+
+
+def _nonempty(who, x):
+    """-> B, the samples of an input that has elements."""
+    B = int(x.shape[0])
+    if B < 1 or x.numel() == 0:
+        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
+    return B
+
+
+def _level_or_absolute(who, B, level_name, level, absolute_name, absolute, default, level_first):
+    """-> (level, None) or (None, absolute fp32 host [B]): a scale given as a fraction of each sample's range (``default`` when neither
+    is given) or as the caller's absolute value, a number or one per sample.  smooth_grad's wording (level_first) names the level
+    first and reports a level beyond fp32 in a message of its own; sensitivity_max's folds that case into its one message."""
+    if level is not None and absolute is not None:
+        raise ValueError(f"{who}: give {level_name if level_first else absolute_name} or {absolute_name if level_first else level_name}, not both")
+    if absolute is None:
+        lv = default if level is None else level
+        if isinstance(lv, bool) or not isinstance(lv, numbers.Real) or not math.isfinite(lv) or lv < 0 or (lv > 3.0e38 and not level_first):
+            raise ValueError(f"{who}: {level_name} must be a finite number >= 0, got {level!r}")
+        if lv > 3.0e38:
+            raise ValueError(f"{who}: {level_name} {level!r} is beyond fp32")
+        return float(lv), None
+    if isinstance(absolute, torch.Tensor):
+        a = absolute.detach().to("cpu", torch.float64).numpy()
+        if a.shape != (B,):
+            raise ValueError(f"{who}: {absolute_name} of shape {tuple(absolute.shape)}; expected a number or [B] = [{B}]")
+    elif isinstance(absolute, numbers.Real) and not isinstance(absolute, bool):
+        a = np.full(B, float(absolute), dtype=np.float64)
+    else:
+        raise ValueError(f"{who}: {absolute_name} must be a number or a tensor [B], got {type(absolute).__name__}")
+    if not np.isfinite(a).all() or (a < 0).any() or (a > 3.0e38).any():
+        raise ValueError(f"{who}: {absolute_name} must be finite and >= 0")
+    return None, np.ascontiguousarray(a.astype(np.float32))
+
+
+def _range_scale(xs, level, host_values):
+    """fp32 [B] on the device of xs (fp32, contiguous): ``level`` times each sample's range (bx_smoothgrad_sigma), or the caller's own
+    values uploaded -- the two results of ``_level_or_absolute``."""
+    if host_values is not None:
+        return torch.from_numpy(host_values).to(xs.device)
+    B = int(xs.shape[0])
+    scale = torch.empty(B, dtype=torch.float32, device=xs.device)
+    L.check(L.load().bx_smoothgrad_sigma(_p(xs), _p(scale), B, xs.numel() // B, level, _stream()), "bx_smoothgrad_sigma")
+    return scale
+
+
 def _per_cell(who, x, input_is_spec):
     """-> (per_len, what): the length and the name of a one-value-per-channel / per-electrode baseline; a spectrogram has 1..4 channels."""
     if not input_is_spec:
@@ -1262,6 +1321,93 @@ class _RowPass:
             with self.lap("forward"):
                 out[b0:b0 + nb, n0:n0 + n] = self.scores(rows, b0, nb, n, logprob).reshape(nb, n, self.K)
         return out
+
+
+def _sample_chunks(total, max_rows):
+    """(row0, rows): sample-major rows j = b * n + k in windows of at most max_rows, which may begin and end inside a sample."""
+    for row0 in range(0, total, max_rows):
+        yield row0, min(max_rows, total - row0)
+
+
+def _sample_of(row0, rows, n, dev):
+    """int64 [rows] on the device: the sample b = j // n of rows j = row0..row0+rows-1."""
+    return torch.div(torch.arange(row0, row0 + rows, dtype=torch.int64, device=dev), n, rounding_mode="floor")
+
+
+class _GradPass:
+    """What the sampled-gradient drivers (gradient_shap, smooth_grad) do alike once their arguments are checked: n sampled rows per
+    sample, sample-major, run through the branch that reads them with the other branch's per-sample output gathered into the fusion
+    head, and one backward pass per explained class from a one-hot seed (bx_expgrad_seed).  A driver brings its row writer, its
+    accumulate and its finish; the chunking by max_batch, the clean pass, the fp64 sums and the 'forward' / 'rows' / 'backward' /
+    'accumulate' laps of ``profile`` are here.  Inside ``open()``, ``xs`` is the explained input (fp32, contiguous); ``clean`` sets
+    ``out``, ``classes`` and ``fixed`` (None for a stand-alone model).  Cc, HW: the channels and pixels a finish launch reduces over."""
+
+    def __init__(self, model, net, multimodal, K, x, other, input_is_spec, n, cls_h, all_classes, max_batch, profile):
+        self.model, self.net, self.multimodal, self.K, self.other, self.input_is_spec = model, net, multimodal, K, other, input_is_spec
+        self.xs, self.n, self.cls_h, self.all_classes, self.profile, self.fixed = x, n, cls_h, all_classes, profile, None
+        self.dev, self.B = x.device, int(x.shape[0])
+        self.per, self.Kc, self.total = x.numel() // self.B, K if all_classes else 1, self.B * n
+        self.dt = getattr(net, "compute_dtype", torch.float32) if input_is_spec else torch.float32
+        self.max_rows = min(_row_cap(x, "spec" if input_is_spec else "eeg", self.dt, max_batch), ((1 << 31) - 1) // self.per)
+        self.Cc, self.HW = (int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])) if input_is_spec else (1, self.per)
+
+    @contextlib.contextmanager
+    def open(self):
+        """The pass's device, eval mode with frozen parameters; autograd stays on, for the gradients with respect to the rows."""
+        with torch.cuda.device(self.dev), _eval_frozen(self.model):
+            self.xs = self.xs.detach().to(torch.float32).contiguous()
+            yield self
+
+    def lap(self, name):
+        return _lap(self.profile, name)
+
+    def clean(self):
+        """The clean pass: the branch whose input does not change (once per sample), ``out`` fp32 [B,K] and the explained classes."""
+        with torch.no_grad(), self.lap("forward"):
+            if self.multimodal:
+                self.fixed = _fixed_branch(self.model, self.other, self.input_is_spec)
+            self.out = _fuse(self.model, self.multimodal, self.input_is_spec, self.net(self.xs), self.fixed).float().contiguous()
+        self.classes = _class_tensor(self.cls_h, self.all_classes, self.out, self.dev)
+
+    def sums(self, count):
+        """``count`` fp64 zero sums [B,Kc,per]: what is carried between chunks, so that no bit depends on max_batch."""
+        return [torch.zeros(self.B, self.Kc, self.per, dtype=torch.float64, device=self.dev) for _ in range(count)]
+
+    def sweep(self, write, accumulate):
+        """For every chunk: ``write(row0, rows)`` returns the fp32 rows in the input's own layout; one forward pass; then per class slot
+        one backward pass and ``accumulate(g, slot, row0, rows)``, g fp32 contiguous: the gradient of the slot's class by the rows."""
+        lib = L.load()
+        for row0, rows in _sample_chunks(self.total, self.max_rows):
+            with self.lap("rows"):
+                r = write(row0, rows)
+            with self.lap("forward"):
+                r.requires_grad_(True)
+                rep = None
+                if self.multimodal:                                 # the other branch's output of the sample each row belongs to
+                    rep = self.fixed.index_select(0, _sample_of(row0, rows, self.n, self.dev))
+                y = _fuse(self.model, self.multimodal, self.input_is_spec, self.net(r), rep).float()
+            seed_rows = torch.empty(rows, self.K, dtype=torch.float32, device=self.dev)
+            for slot in range(self.Kc):
+                with self.lap("backward"):
+                    L.check(lib.bx_expgrad_seed(_p(self.classes), slot if self.all_classes else -1, _p(seed_rows), self.B, self.n, self.K, row0, rows,
+                                                _stream()), "bx_expgrad_seed")
+                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows, retain_graph=slot + 1 < self.Kc)
+                    g = g.to(torch.float32).contiguous()
+                with self.lap("accumulate"):
+                    accumulate(g, slot, row0, rows)
+            del y, r
+
+    def empty(self, *trail):
+        """fp32 [B,Kc,*trail], empty: ``empty(*xs.shape[1:])`` is the estimator element by element, for the driver's finish launch."""
+        return torch.empty(self.B, self.Kc, *trail, dtype=torch.float32, device=self.dev)
+
+    def result(self, return_parts, parts, amap, values, *rest):
+        """The map alone, or ``parts(map, values, classes int64 [B] or None, out, *rest)``; the class axis stays for class_idx='all' only."""
+        if not self.all_classes:
+            amap, values = amap[:, 0], values[:, 0]
+        if not return_parts:
+            return amap
+        return parts(amap, values, None if self.classes is None else self.classes.long(), self.out, *rest)
 
 
 def deletion_insertion(model, eeg, spec, attribution, *, input="spec", mode="both", steps=32, baseline=0.0, class_idx=None, score="prob",
@@ -2199,17 +2345,9 @@ def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, see
     who = "gradient_shap"
     if input not in _FAITH_INPUTS:
         raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
-    if isinstance(nsamples, bool) or not isinstance(nsamples, numbers.Integral):
-        raise ValueError(f"{who}: nsamples must be an int, got {nsamples!r}")
-    n, max_batch = int(nsamples), int(max_batch)
-    if n < 1:
-        raise ValueError(f"{who}: nsamples = {n} < 1")
-    if max_batch < 1:
-        raise ValueError(f"{who}: max_batch = {max_batch} < 1")
+    n, max_batch = _draw_count(who, nsamples), _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
-    B = int(x.shape[0])
-    if B < 1 or x.numel() == 0:
-        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
+    B = _nonempty(who, x)
     if not isinstance(background, torch.Tensor) or background.dim() != 4 or tuple(background.shape[1:]) != tuple(x.shape[1:]):
         got = tuple(background.shape) if isinstance(background, torch.Tensor) else type(background).__name__
         raise ValueError(f"{who}: background of shape {got}; expected [Nb, {', '.join(str(int(v)) for v in x.shape[1:])}] like the {input} input")
@@ -2226,60 +2364,32 @@ def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, see
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or Nb * per >= 1 << 31:
         raise ValueError(f"{who}: B * n = {B * n}, B * Kc * per = {B * Kc * per} or Nb * per = {Nb * per} beyond 32-bit offsets; use fewer samples per call")
     idx, alpha = _gradshap_draws(who, B, Nb, n, seed, draws)
-    if not (x.is_cuda and background.is_cuda and (not multimodal or other.is_cuda) and next(model.parameters()).is_cuda):
-        raise RuntimeError(f"brainxai.{who}: the model, its inputs and the background must live on the GPU; there is no CPU path")
+    _need_gpu(who, "the model, its inputs and the background", model, x, background, other if multimodal else None)
 
     lib = L.load()
-    dev = x.device
-    is_spec = input == "spec"
-    dt = getattr(net, "compute_dtype", torch.float32) if is_spec else torch.float32
-    max_rows = min(_row_cap(x, input, dt, max_batch), ((1 << 31) - 1) // per)
-    total = B * n
-    Cc, HW = (int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])) if is_spec else (1, per)
+    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", n, cls_h, all_classes, max_batch, profile)
 
-    with torch.cuda.device(dev), _eval_frozen(model):
-        xs = x.detach().to(torch.float32).contiguous()
-        bgs = background.detach().to(dev, torch.float32).contiguous()
-        idx_d, alpha_d = torch.from_numpy(idx).to(dev), torch.from_numpy(alpha).to(dev)
-        fixed = None
-        with torch.no_grad(), _lap(profile, "forward"):
-            if multimodal:
-                fixed = _fixed_branch(model, other, is_spec)
-            out = _fuse(model, multimodal, is_spec, net(xs), fixed).float().contiguous()
-        classes = _class_tensor(cls_h, all_classes, out, dev)
-        acc = torch.zeros(B, Kc, per, dtype=torch.float64, device=dev)
-        for row0 in range(0, total, max_rows):
-            rows = min(max_rows, total - row0)
-            with _lap(profile, "rows"):
-                r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=dev)
-                L.check(lib.bx_expgrad_rows(_p(xs), _p(bgs), _p(idx_d), _p(alpha_d), _p(r), B, Nb, n, per, row0, rows, _stream()), "bx_expgrad_rows")
-            with _lap(profile, "forward"):
-                r.requires_grad_(True)
-                rep = None
-                if multimodal:                                      # the other branch's output of the sample each row belongs to
-                    rep = fixed.index_select(0, torch.div(torch.arange(row0, row0 + rows, device=dev), n, rounding_mode="floor"))
-                y = _fuse(model, multimodal, is_spec, net(r), rep).float()
-            seed_rows = torch.empty(rows, K, dtype=torch.float32, device=dev)
-            for slot in range(Kc):
-                with _lap(profile, "backward"):
-                    L.check(lib.bx_expgrad_seed(_p(classes), slot if all_classes else -1, _p(seed_rows), B, n, K, row0, rows, _stream()), "bx_expgrad_seed")
-                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows, retain_graph=slot + 1 < Kc)
-                    g = g.to(torch.float32).contiguous()
-                with _lap(profile, "accumulate"):
-                    L.check(lib.bx_expgrad_accumulate(_p(xs), _p(bgs), _p(idx_d), _p(g), _p(acc), B, Nb, n, per, Kc, slot, row0, rows, _stream()),
-                            "bx_expgrad_accumulate")
-            del y, r
-        with _lap(profile, "finish"):
-            values = torch.empty(B, Kc, *xs.shape[1:], dtype=torch.float32, device=dev)
-            amap = torch.empty(B, Kc, int(x.shape[2]), int(x.shape[3]), dtype=torch.float32, device=dev) if is_spec else None
-            L.check(lib.bx_expgrad_finish(_p(acc), _p(values), _p(amap), B * Kc, Cc, HW, n, _stream()), "bx_expgrad_finish")
-            if amap is None:
+    with gp.open():
+        xs = gp.xs
+        bgs = background.detach().to(gp.dev, torch.float32).contiguous()
+        idx_d, alpha_d = torch.from_numpy(idx).to(gp.dev), torch.from_numpy(alpha).to(gp.dev)
+        gp.clean()
+        acc, = gp.sums(1)
+
+        def write(row0, rows):
+            r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=gp.dev)
+            L.check(lib.bx_expgrad_rows(_p(xs), _p(bgs), _p(idx_d), _p(alpha_d), _p(r), B, Nb, n, per, row0, rows, _stream()), "bx_expgrad_rows")
+            return r
+
+        gp.sweep(write, lambda g, slot, row0, rows: L.check(lib.bx_expgrad_accumulate(
+            _p(xs), _p(bgs), _p(idx_d), _p(g), _p(acc), B, Nb, n, per, Kc, slot, row0, rows, _stream()), "bx_expgrad_accumulate"))
+        with gp.lap("finish"):
+            values = gp.empty(*xs.shape[1:])
+            amap = gp.empty(*xs.shape[2:]) if gp.input_is_spec else None
+            L.check(lib.bx_expgrad_finish(_p(acc), _p(values), _p(amap), B * Kc, gp.Cc, gp.HW, n, _stream()), "bx_expgrad_finish")
+            if amap is None:                                        # an EEG input has one channel: the map is the values
                 amap = values[:, :, 0]
-    if not all_classes:
-        amap, values = amap[:, 0], values[:, 0]
-    if not return_parts:
-        return amap
-    return GradientShapResult(amap, values, None if classes is None else classes.long(), out, idx, alpha, n)
+    return gp.result(return_parts, GradientShapResult, amap, values, idx, alpha, n)
 
 
 def channel_importance(values, top=None):
@@ -2343,45 +2453,6 @@ every sample), all on the device; ``nsamples``, ``kind`` and ``seed`` as given: 
 _SMOOTHGRAD_KINDS = {"smoothgrad": 0, "smoothgrad_sq": 1, "vargrad": 2}          # BX_SMOOTHGRAD_MEAN / _SQ / _VAR
 
 
-def _smoothgrad_seed(who, seed):
-    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 1 << 64:
-        raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
-    return int(seed)
-
-
-def _smoothgrad_nsamples(who, nsamples):
-    if isinstance(nsamples, bool) or not isinstance(nsamples, numbers.Integral):
-        raise ValueError(f"{who}: nsamples must be an int, got {nsamples!r}")
-    if int(nsamples) < 1:
-        raise ValueError(f"{who}: nsamples = {int(nsamples)} < 1")
-    return int(nsamples)
-
-
-def _smoothgrad_scale(who, B, noise_level, stdev):
-    """-> (level, None) or (None, stdev fp32 host [B]): the paper's noise level (a fraction of each sample's range) or the caller's
-    absolute standard deviation, a number or one per sample; both None means a noise level of 0.15."""
-    if noise_level is not None and stdev is not None:
-        raise ValueError(f"{who}: give noise_level or stdev, not both")
-    if stdev is None:
-        level = 0.15 if noise_level is None else noise_level
-        if isinstance(level, bool) or not isinstance(level, numbers.Real) or not math.isfinite(level) or level < 0:
-            raise ValueError(f"{who}: noise_level must be a finite number >= 0, got {noise_level!r}")
-        if level > 3.0e38:
-            raise ValueError(f"{who}: noise_level {noise_level!r} is beyond fp32")
-        return float(level), None
-    if isinstance(stdev, torch.Tensor):
-        sd = stdev.detach().to("cpu", torch.float64).numpy()
-        if sd.shape != (B,):
-            raise ValueError(f"{who}: stdev of shape {tuple(stdev.shape)}; expected a number or [B] = [{B}]")
-    elif isinstance(stdev, numbers.Real) and not isinstance(stdev, bool):
-        sd = np.full(B, float(stdev), dtype=np.float64)
-    else:
-        raise ValueError(f"{who}: stdev must be a number or a tensor [B], got {type(stdev).__name__}")
-    if not np.isfinite(sd).all() or (sd < 0).any() or (sd > 3.0e38).any():
-        raise ValueError(f"{who}: stdev must be finite and >= 0")
-    return None, np.ascontiguousarray(sd.astype(np.float32))
-
-
 def smooth_grad_noise(shape, *, nsamples, seed=0, device=None):
     """The standard normal draws of ``smooth_grad`` themselves, fp32 [B, n, *shape[1:]] on the device, for an explained input of
     ``shape`` = [B, ...] -- for tests, plots and callers who want them; ``smooth_grad`` never stores them.  Written by the kernel that
@@ -2394,7 +2465,7 @@ def smooth_grad_noise(shape, *, nsamples, seed=0, device=None):
         raise ValueError(f"{who}: shape must be a sequence of ints [B, ...], got {shape!r}") from None
     if len(shape) < 2 or min(shape) < 1:
         raise ValueError(f"{who}: shape {shape}; expected [B, ...] with at least two axes, all >= 1")
-    n, seed = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed)
+    n, seed = _draw_count(who, nsamples), _stream_seed(who, seed)
     B, per = shape[0], int(np.prod(shape[1:]))
     if B * n >= 1 << 31 or B * per >= 1 << 31:
         raise ValueError(f"{who}: B * n = {B * n} or B * per = {B * per} beyond 32-bit offsets")
@@ -2404,9 +2475,7 @@ def smooth_grad_noise(shape, *, nsamples, seed=0, device=None):
     lib = L.load()
     with torch.cuda.device(dev):
         z = torch.empty(B * n, *shape[1:], dtype=torch.float32, device=dev)
-        step = max(1, ((1 << 31) - 1) // per)
-        for row0 in range(0, B * n, step):
-            rows = min(step, B * n - row0)
+        for row0, rows in _sample_chunks(B * n, max(1, ((1 << 31) - 1) // per)):
             L.check(lib.bx_smoothgrad_rows(None, None, _p(z[row0:row0 + rows]), B, n, per, seed, row0, rows, _stream()), "bx_smoothgrad_rows")
     return z.reshape(B, n, *shape[1:])
 
@@ -2450,12 +2519,10 @@ def _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, cl
         raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
     if not isinstance(kind, str) or kind not in _SMOOTHGRAD_KINDS:
         raise ValueError(f"{who}: unknown kind {kind!r}; use 'smoothgrad', 'smoothgrad_sq' or 'vargrad'")
-    n, seed, max_batch = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed), _max_batch(who, max_batch)
+    n, seed, max_batch = _draw_count(who, nsamples), _stream_seed(who, seed), _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
-    B = int(x.shape[0])
-    if B < 1 or x.numel() == 0:
-        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
-    level, sd = _smoothgrad_scale(who, B, noise_level, stdev)
+    B = _nonempty(who, x)
+    level, sd = _level_or_absolute(who, B, "noise_level", noise_level, "stdev", stdev, 0.15, True)
     other = eeg if input == "spec" else spec
     multimodal, K, net = _target_model(who, model, x, other, input == "spec")
     if K > _RISE_MAX_K:
@@ -2468,58 +2535,27 @@ def _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, cl
     _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
 
     lib = L.load()
-    dev = x.device
-    is_spec = input == "spec"
-    dt = getattr(net, "compute_dtype", torch.float32) if is_spec else torch.float32
-    max_rows = min(_row_cap(x, input, dt, max_batch), ((1 << 31) - 1) // per)
-    total = B * n
-    Cc, HW = (int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])) if is_spec else (1, per)
+    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", n, cls_h, all_classes, max_batch, profile)
 
-    with torch.cuda.device(dev), _eval_frozen(model):
-        xs = x.detach().to(torch.float32).contiguous()
-        with _lap(profile, "sigma"):
-            if sd is None:
-                sigma = torch.empty(B, dtype=torch.float32, device=dev)
-                L.check(lib.bx_smoothgrad_sigma(_p(xs), _p(sigma), B, per, level, _stream()), "bx_smoothgrad_sigma")
-            else:
-                sigma = torch.from_numpy(sd).to(dev)
-        fixed = None
-        with torch.no_grad(), _lap(profile, "forward"):
-            if multimodal:
-                fixed = _fixed_branch(model, other, is_spec)
-            out = _fuse(model, multimodal, is_spec, net(xs), fixed).float().contiguous()
-        classes = _class_tensor(cls_h, all_classes, out, dev)
-        S1 = torch.zeros(B, Kc, per, dtype=torch.float64, device=dev)
-        S2 = torch.zeros(B, Kc, per, dtype=torch.float64, device=dev)
-        for row0 in range(0, total, max_rows):
-            rows = min(max_rows, total - row0)
-            with _lap(profile, "rows"):
-                r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=dev)
-                L.check(lib.bx_smoothgrad_rows(_p(xs), _p(sigma), _p(r), B, n, per, seed, row0, rows, _stream()), "bx_smoothgrad_rows")
-            with _lap(profile, "forward"):
-                r.requires_grad_(True)
-                rep = None
-                if multimodal:                                      # the other branch's output of the sample each row belongs to
-                    rep = fixed.index_select(0, torch.div(torch.arange(row0, row0 + rows, device=dev), n, rounding_mode="floor"))
-                y = _fuse(model, multimodal, is_spec, net(r), rep).float()
-            seed_rows = torch.empty(rows, K, dtype=torch.float32, device=dev)
-            for slot in range(Kc):
-                with _lap(profile, "backward"):
-                    L.check(lib.bx_expgrad_seed(_p(classes), slot if all_classes else -1, _p(seed_rows), B, n, K, row0, rows, _stream()), "bx_expgrad_seed")
-                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows, retain_graph=slot + 1 < Kc)
-                    g = g.to(torch.float32).contiguous()
-                with _lap(profile, "accumulate"):
-                    L.check(lib.bx_smoothgrad_accumulate(_p(g), _p(S1), _p(S2), B, n, per, Kc, slot, row0, rows, _stream()), "bx_smoothgrad_accumulate")
-            del y, r
-        with _lap(profile, "finish"):
-            values = torch.empty(B, Kc, *xs.shape[1:], dtype=torch.float32, device=dev)
-            amap = torch.empty(B, Kc, int(x.shape[2]), int(x.shape[3]), dtype=torch.float32, device=dev)
-            L.check(lib.bx_smoothgrad_finish(_p(S1), _p(S2), _p(values), _p(amap), B * Kc, Cc, HW, n, _SMOOTHGRAD_KINDS[kind], _stream()), "bx_smoothgrad_finish")
-    if not all_classes:
-        amap, values = amap[:, 0], values[:, 0]
-    if not return_parts:
-        return amap
-    return SmoothGradResult(amap, values, None if classes is None else classes.long(), out, sigma, n, kind, seed)
+    with gp.open():
+        xs = gp.xs
+        with gp.lap("sigma"):
+            sigma = _range_scale(xs, level, sd)
+        gp.clean()
+        S1, S2 = gp.sums(2)
+
+        def write(row0, rows):
+            r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=gp.dev)
+            L.check(lib.bx_smoothgrad_rows(_p(xs), _p(sigma), _p(r), B, n, per, seed, row0, rows, _stream()), "bx_smoothgrad_rows")
+            return r
+
+        gp.sweep(write, lambda g, slot, row0, rows: L.check(lib.bx_smoothgrad_accumulate(
+            _p(g), _p(S1), _p(S2), B, n, per, Kc, slot, row0, rows, _stream()), "bx_smoothgrad_accumulate"))
+        with gp.lap("finish"):
+            values, amap = gp.empty(*xs.shape[1:]), gp.empty(*xs.shape[2:])
+            L.check(lib.bx_smoothgrad_finish(_p(S1), _p(S2), _p(values), _p(amap), B * Kc, gp.Cc, gp.HW, n, _SMOOTHGRAD_KINDS[kind], _stream()),
+                    "bx_smoothgrad_finish")
+    return gp.result(return_parts, SmoothGradResult, amap, values, sigma, n, kind, seed)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2612,16 +2648,14 @@ def _infidelity(model, eeg, spec, attribution, input, nsamples, noise_level, std
         raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
-    n, seed, max_batch = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed), _max_batch(who, max_batch)
+    n, seed, max_batch = _draw_count(who, nsamples), _stream_seed(who, seed), _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
     if not isinstance(attribution, torch.Tensor):
         raise ValueError(f"{who}: attribution must be a tensor")
-    B = int(x.shape[0])
-    if B < 1 or x.numel() == 0:
-        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
+    B = _nonempty(who, x)
     is_spec = input == "spec"
     _per_cell(who, x, is_spec)
-    level, sd = _smoothgrad_scale(who, B, noise_level, stdev)
+    level, sd = _level_or_absolute(who, B, "noise_level", noise_level, "stdev", stdev, 0.15, True)
     other = eeg if is_spec else spec
     multimodal, K, net = _target_model(who, model, x, other, is_spec)
     if K > _RISE_MAX_K:
@@ -2641,11 +2675,7 @@ def _infidelity(model, eeg, spec, attribution, input, nsamples, noise_level, std
 
     with rp.open():
         with rp.lap("sigma"):
-            if sd is None:
-                sigma = torch.empty(B, dtype=torch.float32, device=dev)
-                L.check(lib.bx_smoothgrad_sigma(_p(rp.xs), _p(sigma), B, per, level, _stream()), "bx_smoothgrad_sigma")
-            else:
-                sigma = torch.from_numpy(sd).to(dev)
+            sigma = _range_scale(rp.xs, level, sd)
         phi = attribution.detach().to(torch.float32).reshape(B, Kc, cells).contiguous()
         with rp.lap("forward"):
             rp.fix_other()
@@ -2668,29 +2698,6 @@ def _infidelity(model, eeg, spec, attribution, input, nsamples, noise_level, std
     if not return_parts:
         return infid
     return InfidelityResult(infid, beta, dots, drops, clean, None if classes is None else classes.long(), sigma, n, seed)
-
-
-def _sensitivity_radius(who, B, radius, radius_level):
-    """-> (level, None) or (None, radius fp32 host [B]): a fraction of each sample's range or the caller's absolute radius, a number or
-    one per sample; both None means a level of 0.02 (Captum's radius on unit-range inputs)."""
-    if radius is not None and radius_level is not None:
-        raise ValueError(f"{who}: give radius or radius_level, not both")
-    if radius is None:
-        level = 0.02 if radius_level is None else radius_level
-        if isinstance(level, bool) or not isinstance(level, numbers.Real) or not math.isfinite(level) or level < 0 or level > 3.0e38:
-            raise ValueError(f"{who}: radius_level must be a finite number >= 0, got {radius_level!r}")
-        return float(level), None
-    if isinstance(radius, torch.Tensor):
-        r = radius.detach().to("cpu", torch.float64).numpy()
-        if r.shape != (B,):
-            raise ValueError(f"{who}: radius of shape {tuple(radius.shape)}; expected a number or [B] = [{B}]")
-    elif isinstance(radius, numbers.Real) and not isinstance(radius, bool):
-        r = np.full(B, float(radius), dtype=np.float64)
-    else:
-        raise ValueError(f"{who}: radius must be a number or a tensor [B], got {type(radius).__name__}")
-    if not np.isfinite(r).all() or (r < 0).any() or (r > 3.0e38).any():
-        raise ValueError(f"{who}: radius must be finite and >= 0")
-    return None, np.ascontiguousarray(r.astype(np.float32))
 
 
 def _sensitivity_explain(who, explain, eeg_rows, spec_rows, sample, trail):
@@ -2731,12 +2738,10 @@ def sensitivity_max(explain, eeg, spec, *, input="spec", nsamples=10, radius=Non
         raise ValueError(f"{who}: explain must be a callable (eeg_rows, spec_rows, sample) -> tensor, got {type(explain).__name__}")
     if input not in _FAITH_INPUTS:
         raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
-    n, seed, max_batch = _smoothgrad_nsamples(who, nsamples), _smoothgrad_seed(who, seed), _max_batch(who, max_batch)
+    n, seed, max_batch = _draw_count(who, nsamples), _stream_seed(who, seed), _max_batch(who, max_batch)
     x = _input_tensor(who, input, eeg, spec)
-    B = int(x.shape[0])
-    if B < 1 or x.numel() == 0:
-        raise ValueError(f"{who}: empty input of shape {tuple(x.shape)}")
-    level, rad = _sensitivity_radius(who, B, radius, radius_level)
+    B = _nonempty(who, x)
+    level, rad = _level_or_absolute(who, B, "radius_level", radius_level, "radius", radius, 0.02, False)
     other = eeg if input == "spec" else spec
     if other is not None and (not isinstance(other, torch.Tensor) or other.shape[0] != B):
         raise ValueError(f"{who}: the other input must be None or a tensor with the same batch size")
@@ -2758,11 +2763,7 @@ def sensitivity_max(explain, eeg, spec, *, input="spec", nsamples=10, radius=Non
 
     with torch.cuda.device(dev):
         xs = x.detach().to(torch.float32).contiguous()
-        if rad is None:
-            r = torch.empty(B, dtype=torch.float32, device=dev)
-            L.check(lib.bx_smoothgrad_sigma(_p(xs), _p(r), B, per, level, _stream()), "bx_smoothgrad_sigma")
-        else:
-            r = torch.from_numpy(rad).to(dev)
+        r = _range_scale(xs, level, rad)
         phi0, trail = call(xs, torch.arange(B, dtype=torch.int64, device=dev), None)
         P = int(phi0.shape[1])
         if P < 1 or B * P >= 1 << 31:
@@ -2771,12 +2772,10 @@ def sensitivity_max(explain, eeg, spec, *, input="spec", nsamples=10, radius=Non
         L.check(lib.bx_sensitivity_dist(_p(phi0), None, _p(norms), B, 1, P, 0, B, _stream()), "bx_sensitivity_dist")
         dist = torch.empty(total, dtype=torch.float64, device=dev)
         max_rows = max(1, min(max_rows, ((1 << 31) - 1) // P))
-        for row0 in range(0, total, max_rows):
-            rows = min(max_rows, total - row0)
+        for row0, rows in _sample_chunks(total, max_rows):
             rx = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=dev)
             L.check(lib.bx_sensitivity_rows(_p(xs), _p(r), _p(rx), B, n, per, seed, row0, rows, _stream()), "bx_sensitivity_rows")
-            sample = torch.div(torch.arange(row0, row0 + rows, dtype=torch.int64, device=dev), n, rounding_mode="floor")
-            phi, _ = call(rx, sample, trail)
+            phi, _ = call(rx, _sample_of(row0, rows, n, dev), trail)
             L.check(lib.bx_sensitivity_dist(_p(phi), _p(phi0), _p(dist[row0:row0 + rows]), B, n, P, row0, rows, _stream()), "bx_sensitivity_dist")
             del phi, rx
         sens = torch.empty(B, dtype=torch.float64, device=dev)

@@ -41,6 +41,21 @@ def bits(t):
     return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
 
 
+def np_bits(a):
+    """A numpy array's bits as integers of its item size: equality then tells -0.0 from 0.0 and compares NaNs."""
+    a = np.ascontiguousarray(a)
+    return a.view({2: np.int16, 4: np.int32, 8: np.int64}[a.dtype.itemsize])
+
+
+def misaligned(t):
+    """A copy of t that starts 4 bytes past a 16-byte boundary: the entry points then take the element-by-element path."""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
+    view = buf[1:].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
 def model_state(model):
     return model.training, [q.requires_grad for q in model.parameters()]
 

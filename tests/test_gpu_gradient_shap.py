@@ -23,6 +23,7 @@ from brainxai import _lib as L
 from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
+from tests import grad_gpu as GG
 from tests import gradient_shap_ref as R
 from tests import perturb_gpu as PG
 from tests.golden_util import matched_oracle
@@ -152,56 +153,30 @@ def test_channel_importance_top_with_exact_ties():
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------------------
-def _per_pair_max(t):
-    t = torch.as_tensor(t).detach().double().cpu()
-    return t.abs().flatten(2).max(2).values                                # [B, K]
-
-
 def _guard(what, f64, want, x, bg, idx, alpha, other, input):
     """Reference side alone: the inputs discriminate the background gather and the interpolation points."""
     Nb = bg.shape[0]
-    scale = _per_pair_max(want)
-    shifted = _per_pair_max(R.values(f64, x, bg, (idx + 1) % Nb, alpha, other, input) - want) / scale
-    rolled = _per_pair_max(R.values(f64, x, bg, idx, np.roll(alpha, 1, axis=1), other, input) - want) / scale
+    scale = GG.per_pair_max(want)
+    shifted = GG.per_pair_max(R.values(f64, x, bg, (idx + 1) % Nb, alpha, other, input) - want) / scale
+    rolled = GG.per_pair_max(R.values(f64, x, bg, idx, np.roll(alpha, 1, axis=1), other, input) - want) / scale
     print(f"{what}: reference with idx shifted {float(shifted.min()):.3f}, with alpha rolled {float(rolled.min()):.3f} of the per-(sample, class) maximum (least)")
     assert float(shifted.min()) > 100 * TOL, f"{what}: shifting the background indices moves the reference by only {float(shifted.min()):.3e}"
     assert float(rolled.min()) > 50 * TOL, f"{what}: rolling alpha moves the reference by only {float(rolled.min()):.3e}"
 
 
-def _worst(got, want):
-    """max over (sample, class) of max|got - want| / max|want|"""
-    assert tuple(got.shape) == tuple(want.shape), (tuple(got.shape), tuple(want.shape))
-    assert bool(torch.isfinite(torch.as_tensor(got)).all())
-    return float((_per_pair_max(torch.as_tensor(got).detach().double().cpu() - want.double()) / _per_pair_max(want)).max())
-
-
-def _mm_inputs():
-    return O.seeded((2, 1, 19, 2000), 12, "randn"), O.seeded((2, 4, 32, 64), 11, "rand")
-
-
 @functools.lru_cache(maxsize=None)
 def _eeg_case(kind):
     """(ref, mine, x, bg, other, n, seed, max_batch, idx, alpha, want fp64 [B,K,1,Chans,T]); computed once, never written to."""
-    if kind == "eegnet":                                                  # the inputs of test_gpu_parity.test_expected_gradients_shap_style
-        ref = O.fill_params(O.EEGNet(6, Chans=19, Samples=2000, dropoutRate=0.0), seed=31).eval()
-        mine = brainxai.EEGNet(6, Chans=19, Samples=2000, dropoutRate=0.0)
-        x, bg, other, n, seed, max_batch = O.seeded((2, 1, 19, 2000), 91, "randn"), O.seeded((5, 1, 19, 2000), 92, "randn"), None, 12, 3, 8
-    elif kind == "deep":
-        ref = O.fill_params(O.EEGNetAttentionDeep(6, Chans=19, Samples=2000, dropoutRate=0.0), seed=61).eval()
-        mine = brainxai.EEGNetAttentionDeep(6, Chans=19, Samples=2000, dropoutRate=0.0)
-        x, bg, other, n, seed, max_batch = _mm_inputs()[0], O.seeded((3, 1, 19, 2000), 14, "randn"), None, 6, 3, 256
+    ref, mine, f64, x, other = GG.eeg_models(kind)
+    if kind == "eegnet":
+        bg, n, seed, max_batch = O.seeded((5, 1, 19, 2000), 92, "randn"), 12, 3, 8
     else:
-        ref, mine = PG.scaled_multimodal()
-        (x, other), bg, n, seed, max_batch = _mm_inputs(), O.seeded((3, 1, 19, 2000), 14, "randn"), 6, 3, 256
-    if kind != "multimodal":
-        mine.load_state_dict(ref.state_dict())
-        mine = mine.to(DEV).eval()
-    f64 = copy.deepcopy(ref).double().eval()
+        bg, n, seed, max_batch = O.seeded((3, 1, 19, 2000), 14, "randn"), 6, 3, 256
     idx, alpha = R.draws(seed, x.shape[0], bg.shape[0], n)
     want = R.values(f64, x, bg, idx, alpha, other, "eeg")
     if kind == "eegnet":                                                  # the oracle's own estimator, run in fp64, is the target there
         oracle = O.expected_gradients(f64, x.double(), bg.double(), nsamples=n, seed=seed).double()
-        assert _worst(want, oracle) <= 1e-6, "the restatement and the oracle's estimator disagree"
+        assert GG.worst(want, oracle) <= 1e-6, "the restatement and the oracle's estimator disagree"
         want = oracle
     _guard(f"gradient_shap eeg input, {kind}", f64, want, x, bg, idx, alpha, other, "eeg")
     return ref, mine, x, bg, other, n, seed, max_batch, idx, alpha, want
@@ -215,19 +190,19 @@ def test_eeg_input_against_the_fp64_oracle(kind):
     assert res.values.shape == want.shape == (2, 6, 1, 19, 2000) and res.attribution.shape == (2, 6, 19, 2000) and res.classes is None
     assert np.array_equal(res.idx, idx) and np.array_equal(res.alpha, alpha) and res.nsamples == n
     assert torch.equal(res.attribution, res.values[:, :, 0])
-    err = _worst(res.values, want)
+    err = GG.worst(res.values, want)
     line = f"gradient_shap eeg input, {kind}: worst per-(sample, class) error {err:.3e} of the maximum (bound {TOL})"
     assert err <= TOL, line
     if other is None:                                                     # the host-loop estimator on the same seed: the same draws
         old = brainxai.expected_gradients(mine, x.to(DEV), bg.to(DEV), nsamples=n, seed=seed, max_batch=max_batch)
-        eo, eb = _worst(old, want), _worst(res.values, old.cpu())
+        eo, eb = GG.worst(old, want), GG.worst(res.values, old.cpu())
         line += f"; expected_gradients {eo:.3e}; between the two {eb:.3e}"
         assert eb <= TOL, line
     print(line)
 
 
 def _spec_case():
-    (eeg, spec), bg = _mm_inputs(), O.seeded((3, 4, 32, 64), 13, "rand")
+    (eeg, spec), bg = GG.mm_inputs(), O.seeded((3, 4, 32, 64), 13, "rand")
     idx, alpha = R.draws(3, 2, 3, 6)
     return eeg, spec, bg, idx, alpha
 
@@ -311,21 +286,18 @@ def test_spec_input_against_the_fp64_oracle():
     for c in range(y.shape[1]):
         (g,) = torch.autograd.grad(y[:, c].sum(), xi, retain_graph=True)
         want[:, c] = (g * d).reshape(B, n, *spec.shape[1:]).sum(1) / n
-    err, err_plain = _worst(res.values, want), _worst(res.values, plain)
+    err, err_plain = GG.worst(res.values, want), GG.worst(res.values, plain)
     line = (f"gradient_shap spec input, multimodal 4x32x64: {len(flips)} decision flips; worst per-(sample, class) error {err:.3e} against the "
             f"decision-matched fp64 oracle, {err_plain:.3e} against the plain one (bound {TOL})")
     print(line)
     assert err <= TOL, line
     want_map = want.sum(2)
-    assert _worst(res.attribution, want_map) <= TOL
+    assert GG.worst(res.attribution, want_map) <= TOL
 
 
 # ---- interface --------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
 def _iface():
-    _, mine = PG.scaled_multimodal()
-    eeg, spec, bg, idx, alpha = _spec_case()
-    return mine, eeg.to(DEV), spec.to(DEV), O.seeded((3, 1, 19, 2000), 14, "randn").to(DEV), bg.to(DEV)
+    return GG.iface() + GG.backgrounds()
 
 
 def test_repeatable_draws_and_max_batch():
@@ -339,7 +311,7 @@ def test_repeatable_draws_and_max_batch():
     other = brainxai.gradient_shap(mine, eeg, spec, bge, input="eeg", nsamples=6, class_idx="all", seed=4)
     assert not torch.equal(a.attribution, other)
     small = brainxai.gradient_shap(mine, eeg, spec, bge, max_batch=5, **kw)
-    err = _worst(small, a.attribution.cpu())
+    err = GG.worst(small, a.attribution.cpu())
     print(f"gradient_shap max_batch 5 vs 256: {err:.3e} of the per-(sample, class) maximum, bit for bit: {torch.equal(small, a.attribution)}")
     assert err <= TOL
     s_kw = dict(input="spec", nsamples=4, class_idx="all", seed=1)

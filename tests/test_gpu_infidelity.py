@@ -23,7 +23,6 @@ class) -- a kernel that dropped the noise, its sign, its scale or the attributio
 score at noise level 0.15 (1.0 for the multimodal model), and the score is the log-probability: with probabilities the least likely class of EEGNet (p ~ 1e-3) has
 drops so small against e that -z moves its reference by only 40 bounds and -Phi by 18 (10 and 134 at level 0.05); with
 log-probabilities every class moves by more than 5000.  Probabilities are compared in the composed-pass test.  Observed worst figures are printed by each test (run with -s) and recorded in DESIGN.md section 6."""
-import copy
 import functools
 
 import numpy as np
@@ -35,6 +34,7 @@ from brainxai import _lib as L
 from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
+from tests import grad_gpu as GG
 from tests import infidelity_ref as R
 from tests import perturb_gpu as PG
 from tests import smooth_grad_ref as SG
@@ -54,11 +54,6 @@ WINDOWS = [(0, 15), (2, 10), (14, 1)]              # all rows; from inside sampl
 SEED = 0x9E3779B97F4A7C15                           # both key words in use
 LEVEL = 0.15
 FORMS = ["element", "grouped"]                      # grouped: a pixel with all its channels / a time column with all its electrodes
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({2: np.int16, 4: np.int32, 8: np.int64}[a.dtype.itemsize])
 
 
 def _is_eeg(name):
@@ -91,15 +86,6 @@ def _dump(name, grouped):
     z = brainxai.smooth_grad_noise((KB, *cs), nsamples=KN, seed=SEED, device=DEV)
     assert z.shape == (KB, KN, *cs) and z.dtype == torch.float32
     return z.cpu().numpy().reshape(KB, KN, -1)
-
-
-def _misaligned(t):
-    """A copy of t that starts 4 bytes past a 16-byte boundary: the entry points then take the element-by-element path."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4
-    return view
 
 
 def _chunks_of_window(row0, rows):
@@ -147,17 +133,17 @@ def test_infidelity_rows_bit_for_bit(name, form):
     row_shape = shape if eeg else (shape[1], shape[2], 8)
     for dt in ([torch.float32] if eeg else [torch.float32, torch.bfloat16]):
         want = _layout(want32, name, dt)
-        inputs = [("aligned", xd, False), ("misaligned input", _misaligned(xd), False)] + ([("misaligned output", xd, True)] if eeg else [])
+        inputs = [("aligned", xd, False), ("misaligned input", PG.misaligned(xd), False)] + ([("misaligned output", xd, True)] if eeg else [])
         for what, xin, mis_out in inputs:
             for row0, rows in WINDOWS:                                                   # a window of rows, sample by sample
                 out = torch.full((rows, *row_shape), float("nan"), dtype=dt, device=DEV)
-                out = _misaligned(out) if mis_out else out
+                out = PG.misaligned(out) if mis_out else out
                 for at, b0, nb, n0, n in _chunks_of_window(row0, rows):
                     _launch_inf_rows(name, xin, sd, out[at:at + n], grouped, dt, b0, nb, n0, n)
                 PG.assert_same_rows(out.cpu(), want[row0:row0 + rows], f"{name} {form} {dt} rows {row0}..{row0 + rows}, {what}", None if eeg else shape[0])
             for b0, nb, n0, n in ((0, KB, 0, KN), (1, 2, 1, 3), (2, 1, 4, 1)):           # rectangles of samples x draws: the chunks of a sweep
                 out = torch.full((nb * n, *row_shape), float("nan"), dtype=dt, device=DEV)
-                out = _misaligned(out) if mis_out else out
+                out = PG.misaligned(out) if mis_out else out
                 _launch_inf_rows(name, xin, sd, out, grouped, dt, b0, nb, n0, n)
                 pick = [b * KN + k for b in range(b0, b0 + nb) for k in range(n0, n0 + n)]
                 PG.assert_same_rows(out.cpu(), want[pick], f"{name} {form} {dt} chunk {(b0, nb, n0, n)}, {what}", None if eeg else shape[0])
@@ -181,16 +167,16 @@ def test_uniform_draws_and_rows_bit_for_bit(name):
     for row0, rows in WINDOWS:
         for mis in (False, True):
             out = torch.full((rows, per), float("nan"), dtype=torch.float32, device=DEV)
-            out = _misaligned(out) if mis else out
+            out = PG.misaligned(out) if mis else out
             L.check(lib.bx_sensitivity_rows(None, None, PG.p(out), KB, KN, per, SEED, row0, rows, PG.stream()), "bx_sensitivity_rows")
-            assert np.array_equal(_bits(out.cpu().numpy()), _bits(full[row0:row0 + rows])), f"{name} draws {row0}..{row0 + rows}, misaligned {mis}"
-        for what, xin, mis_out in (("aligned", xd, False), ("misaligned input", _misaligned(xd), False), ("misaligned output", xd, True)):
+            assert np.array_equal(PG.np_bits(out.cpu().numpy()), PG.np_bits(full[row0:row0 + rows])), f"{name} draws {row0}..{row0 + rows}, misaligned {mis}"
+        for what, xin, mis_out in (("aligned", xd, False), ("misaligned input", PG.misaligned(xd), False), ("misaligned output", xd, True)):
             out = torch.full((rows, per), float("nan"), dtype=torch.float32, device=DEV)
-            out = _misaligned(out) if mis_out else out
+            out = PG.misaligned(out) if mis_out else out
             L.check(lib.bx_sensitivity_rows(PG.p(xin), PG.p(rd), PG.p(out), KB, KN, per, SEED, row0, rows, PG.stream()), "bx_sensitivity_rows")
             got = out.cpu().numpy()
             assert not np.isnan(got).any(), f"{name} rows {row0}..{row0 + rows}, {what}: elements left unwritten"
-            assert np.array_equal(_bits(got), _bits(want[row0:row0 + rows])), f"{name} rows {row0}..{row0 + rows}, {what}"
+            assert np.array_equal(PG.np_bits(got), PG.np_bits(want[row0:row0 + rows])), f"{name} rows {row0}..{row0 + rows}, {what}"
     out = torch.empty(KB * KN, per, dtype=torch.float32, device=DEV)
     L.check(lib.bx_sensitivity_rows(None, None, PG.p(out), KB, KN, per, SEED + 1, 0, KB * KN, PG.stream()), "bx_sensitivity_rows")
     assert per < 8 or not np.array_equal(out.cpu().numpy(), full), "another seed is another stream"
@@ -225,11 +211,11 @@ def test_dot_against_numpy_and_across_windows(name, form, Kc):
     for row0, rows in WINDOWS[1:]:
         part = run(PG.dev(phi), row0, rows).transpose(0, 2, 1).reshape(KB * KN, Kc)
         ref = full.transpose(0, 2, 1).reshape(KB * KN, Kc)
-        assert np.array_equal(_bits(part[row0:row0 + rows]), _bits(ref[row0:row0 + rows])), f"{name}: window {row0}..{row0 + rows} differs from the full call"
+        assert np.array_equal(PG.np_bits(part[row0:row0 + rows]), PG.np_bits(ref[row0:row0 + rows])), f"{name}: window {row0}..{row0 + rows} differs from the full call"
         assert np.isnan(part[:row0]).all() and np.isnan(part[row0 + rows:]).all(), "rows outside the window were written"
-    mis = run(_misaligned(PG.dev(phi)), 0, KB * KN)
+    mis = run(PG.misaligned(PG.dev(phi)), 0, KB * KN)
     assert cells < 4 or np.abs(mis - want).max() <= bound.max(), "the element-by-element path"
-    assert np.array_equal(_bits(mis), _bits(full)), "both paths add in the same order"
+    assert np.array_equal(PG.np_bits(mis), PG.np_bits(full)), "both paths add in the same order"
     print(f"dot {name} {form} Kc={Kc}: cells {cells}, worst |d - numpy| = {ratio:.3e} x cells u sum|I Phi|; windows and both load paths bit for bit")
 
 
@@ -266,12 +252,12 @@ def test_finish_against_numpy(classes, normalize):
     delta = R.drops(clean, S)
     if classes is not None:
         delta = np.stack([delta[b, c][None] for b, c in enumerate(classes)])
-    assert np.array_equal(_bits(drops), _bits(delta)), "a drop is one exact-operand fp64 subtraction"
+    assert np.array_equal(PG.np_bits(drops), PG.np_bits(delta)), "a drop is one exact-operand fp64 subtraction"
     want, wbeta = R.finish(d, delta, normalize)
     assert (beta[1] == 0).all() if normalize else (beta == 1).all()
     E = _finish_bound(d, delta, wbeta, want, normalize)
     ratio = float((np.abs(infid - want) / (2 * E)).max())
-    same = bool(np.array_equal(_bits(infid), _bits(want)) and np.array_equal(_bits(beta), _bits(wbeta)))
+    same = bool(np.array_equal(PG.np_bits(infid), PG.np_bits(want)) and np.array_equal(PG.np_bits(beta), PG.np_bits(wbeta)))
     print(f"finish {'all classes' if classes is None else 'one class per sample'}, normalize {normalize}: {ratio:.3e} x the bound, bit for bit: {same}")
     assert ratio <= 1.0 and np.allclose(beta, wbeta, rtol=1e-12, atol=0)
     assert np.allclose(infid[1], (delta[1] ** 2).sum(-1) / n, rtol=1e-14, atol=0), "zero dots leave the mean square of the drops"
@@ -294,7 +280,7 @@ def test_distance_and_sensitivity_finish_against_numpy(P):
         for mis in (False, True):
             part = torch.full((rows,), float("nan"), dtype=torch.float64, device=DEV)
             rows_a = ad[row0:row0 + rows].contiguous()
-            L.check(lib.bx_sensitivity_dist(PG.p(_misaligned(rows_a) if mis else rows_a), PG.p(rd), PG.p(part), Bn, n, P, row0, rows, PG.stream()), "bx_sensitivity_dist")
+            L.check(lib.bx_sensitivity_dist(PG.p(PG.misaligned(rows_a) if mis else rows_a), PG.p(rd), PG.p(part), Bn, n, P, row0, rows, PG.stream()), "bx_sensitivity_dist")
             assert torch.equal(part, full[row0:row0 + rows]), f"window {row0}..{row0 + rows} differs from the full call"
     norms_h, dist_h = norms.cpu().numpy(), full.cpu().numpy().reshape(Bn, n)
     rel = 2 * (P / 2 + 2) * U
@@ -311,10 +297,6 @@ def test_distance_and_sensitivity_finish_against_numpy(P):
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------------------
 EN, ESEED = 6, 3
-
-
-def _mm_inputs():
-    return O.seeded((2, 1, 19, 2000), 12, "randn"), O.seeded((2, 4, 32, 64), 11, "rand")
 
 
 def _device_noise(shape, n=EN, seed=ESEED):
@@ -345,7 +327,7 @@ def test_spec_input_against_the_same_pass_from_pieces(dt, form):
     """The scores are then the same launches on the same bits: the drops are equal bit for bit, what remains is the dot and finish bound."""
     grouped = form == "grouped"
     _, mine = PG.scaled_multimodal(dt)
-    eeg, spec = _mm_inputs()
+    eeg, spec = GG.mm_inputs()
     eeg_d, spec_d = eeg.to(DEV), spec.to(DEV)
     B, n, max_batch = 2, EN, 5
     cs = (32, 64) if grouped else (4, 32, 64)
@@ -356,7 +338,7 @@ def test_spec_input_against_the_same_pass_from_pieces(dt, form):
     zd, sd = PG.dev(z), PG.dev(sig)
     I_d = sd[:, None, None, None, None] * (zd[:, :, None] if grouped else zd)
     rows_all = (spec_d[:, None] - I_d).reshape(B * n, 4, 32, 64)
-    assert np.array_equal(_bits(rows_all.cpu().numpy()), _bits(R.rows(spec, sig, z, grouped, False))), "the composed rows are not the restatement's"
+    assert np.array_equal(PG.np_bits(rows_all.cpu().numpy()), PG.np_bits(R.rows(spec, sig, z, grouped, False))), "the composed rows are not the restatement's"
     clean, S = _composed_scores(mine, eeg_d, spec_d, rows_all, n, max_batch, dt)
     I = R.perturbation(sig, z)
     d, absum = R.dots(I, phi.reshape(B, 6, -1).numpy())
@@ -368,8 +350,8 @@ def test_spec_input_against_the_same_pass_from_pieces(dt, form):
                                   seed=ESEED, max_batch=max_batch, return_parts=True)
         assert res.infidelity.shape == res.beta.shape == (B, 6) and res.dots.shape == res.drops.shape == (B, 6, n) and res.classes is None
         assert res.infidelity.dtype == res.dots.dtype == torch.float64 and (res.nsamples, res.seed) == (n, ESEED)
-        assert np.array_equal(_bits(res.sigma.cpu().numpy()), _bits(sig)) and np.array_equal(_bits(res.clean.cpu().numpy()), _bits(clean))
-        assert np.array_equal(_bits(res.drops.cpu().numpy()), _bits(delta)), "drops must be bit for bit those of the composed pass"
+        assert np.array_equal(PG.np_bits(res.sigma.cpu().numpy()), PG.np_bits(sig)) and np.array_equal(PG.np_bits(res.clean.cpu().numpy()), PG.np_bits(clean))
+        assert np.array_equal(PG.np_bits(res.drops.cpu().numpy()), PG.np_bits(delta)), "drops must be bit for bit those of the composed pass"
         got_d = res.dots.cpu().numpy()
         rd = float((np.abs(got_d - d) / ed).max())
         want, wbeta = R.finish(d, delta, normalize)
@@ -381,24 +363,6 @@ def test_spec_input_against_the_same_pass_from_pieces(dt, form):
                                     seed=ESEED, return_parts=True)
         assert torch.equal(whole.dots, res.dots), "no bit of the dots may depend on max_batch"
     print(f"infidelity spec input ({form} cells) vs composed pass, {dt}: " + "; ".join(line))
-
-
-def _oracle_case(kind):
-    if kind == "eegnet":
-        ref = O.fill_params(O.EEGNet(6, Chans=19, Samples=2000, dropoutRate=0.0), seed=31).eval()
-        mine = brainxai.EEGNet(6, Chans=19, Samples=2000, dropoutRate=0.0)
-        x, other = O.seeded((2, 1, 19, 2000), 91, "randn"), None
-    elif kind == "deep":
-        ref = O.fill_params(O.EEGNetAttentionDeep(6, Chans=19, Samples=2000, dropoutRate=0.0), seed=61).eval()
-        mine = brainxai.EEGNetAttentionDeep(6, Chans=19, Samples=2000, dropoutRate=0.0)
-        x, other = _mm_inputs()[0], None
-    else:
-        ref, mine = PG.scaled_multimodal()
-        x, other = _mm_inputs()
-    if kind != "multimodal":
-        mine.load_state_dict(ref.state_dict())
-        mine = mine.to(DEV).eval()
-    return copy.deepcopy(ref).double().eval(), mine, x, other
 
 
 def _oracle_reference(f64, x, other, grouped, z, sig, phi=None, logprob=True):
@@ -445,7 +409,7 @@ def _oracle_guard(what, f64, x, other, grouped, z, z_other, sig, phi, want, boun
 @pytest.mark.parametrize("kind,form,level", [("eegnet", "element", LEVEL), ("deep", "element", LEVEL), ("multimodal", "grouped", 1.0)])
 def test_eeg_input_against_the_fp64_oracle(kind, form, level):
     grouped = form == "grouped"
-    f64, mine, x, other = _oracle_case(kind)
+    _, mine, f64, x, other = GG.eeg_models(kind)
     B = x.shape[0]
     cs = (2000,) if grouped else (1, 19, 2000)
     z, z_other, sig = _device_noise((B, *cs)), _device_noise((B, *cs), seed=ESEED + 1), SG.sigma(x, level)
@@ -470,9 +434,8 @@ def test_eeg_input_against_the_fp64_oracle(kind, form, level):
 # ---- interface --------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _iface():
-    _, mine = PG.scaled_multimodal()
-    eeg, spec = _mm_inputs()
-    return mine, eeg.to(DEV), spec.to(DEV), PG.dev(O.seeded((2, 6, 32, 64), 19, "randn")), PG.dev(O.seeded((2, 6, 1, 2000), 20, "randn"))
+    """GG.iface() and an attribution for either input, [B,K,H,W] and [B,K,1,T]."""
+    return GG.iface() + (PG.dev(O.seeded((2, 6, 32, 64), 19, "randn")), PG.dev(O.seeded((2, 6, 1, 2000), 20, "randn")))
 
 
 def test_repeatable_prefix_and_seed():
@@ -571,7 +534,7 @@ def test_sensitivity_max_of_saliency_against_the_rows_composed_in_torch():
         return brainxai.saliency(mine, e, s)[1]
     res = brainxai.sensitivity_max(explain, eeg, spec, input="spec", nsamples=n, seed=ESEED, max_batch=5, return_parts=True)
     assert res.sensitivity.shape == (B,) and res.distances.shape == (B, n) and res.norms.shape == (B,) and res.sensitivity.dtype == torch.float64
-    assert np.array_equal(_bits(res.radius.cpu().numpy()), _bits(SG.sigma(spec.cpu(), 0.02))), "the default radius is 0.02 of the sample's range"
+    assert np.array_equal(PG.np_bits(res.radius.cpu().numpy()), PG.np_bits(SG.sigma(spec.cpu(), 0.02))), "the default radius is 0.02 of the sample's range"
     want_samples = torch.arange(B).repeat_interleave(n)
     assert torch.equal(seen[0].cpu(), torch.arange(B)) and [len(s) for s in seen[1:]] == [5, 5, 2]
     assert torch.equal(torch.cat(seen[1:]).cpu(), want_samples) and seen[1].dtype == torch.int64 and seen[1].is_cuda
@@ -579,10 +542,10 @@ def test_sensitivity_max_of_saliency_against_the_rows_composed_in_torch():
     per = spec[0].numel()
     u = torch.empty(B * n, per, dtype=torch.float32, device=DEV)
     L.check(L.load().bx_sensitivity_rows(None, None, PG.p(u), B, n, per, ESEED, 0, B * n, PG.stream()), "bx_sensitivity_rows")
-    assert np.array_equal(_bits(u.cpu().numpy()), _bits(R.uniform(B, n, per, ESEED).reshape(B * n, per)))
+    assert np.array_equal(PG.np_bits(u.cpu().numpy()), PG.np_bits(R.uniform(B, n, per, ESEED).reshape(B * n, per)))
     dl = res.radius[:, None, None] * u.reshape(B, n, per)
     rows = (spec.reshape(B, 1, per) + dl).reshape(B * n, *spec.shape[1:])
-    assert np.array_equal(_bits(rows.cpu().numpy()), _bits(R.uniform_rows(spec.cpu(), res.radius.cpu().numpy(), u.cpu().numpy().reshape(B, n, *spec.shape[1:]))))
+    assert np.array_equal(PG.np_bits(rows.cpu().numpy()), PG.np_bits(R.uniform_rows(spec.cpu(), res.radius.cpu().numpy(), u.cpu().numpy().reshape(B, n, *spec.shape[1:]))))
     clean = brainxai.saliency(mine, eeg, spec)[1]
     phis = torch.cat([brainxai.saliency(mine, eeg[want_samples[i:i + 5]], rows[i:i + 5])[1] for i in range(0, B * n, 5)])
     want_dist, want_norm = R.distances(phis.cpu().numpy(), clean.cpu().numpy(), n)

@@ -28,6 +28,7 @@ from brainxai import _lib as L
 from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
+from tests import grad_gpu as GG
 from tests import perturb_gpu as PG
 from tests import smooth_grad_ref as R
 from tests.golden_util import matched_oracle
@@ -55,10 +56,6 @@ SEED = 0x9E3779B97F4A7C15                           # both key words in use
 LEVEL = 0.15
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
 def _kernel_case(name):
     shape = SHAPES[name]
     x = O.seeded((KB, *shape), 200 + sorted(SHAPES).index(name), "randn")
@@ -79,15 +76,6 @@ def _launch_rows(x, sigma, out, per, row0, rows, seed=SEED):
     L.check(L.load().bx_smoothgrad_rows(PG.p(x), PG.p(sigma), PG.p(out), KB, KN, per, seed, row0, rows, PG.stream()), "bx_smoothgrad_rows")
 
 
-def _misaligned(t):
-    """A copy of t that starts 4 bytes past a 16-byte boundary: the entry points then take the element-by-element path."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4
-    return view
-
-
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_noise_against_the_fp64_restatement(name):
     shape = SHAPES[name]
@@ -103,13 +91,13 @@ def test_noise_against_the_fp64_restatement(name):
     for row0, rows in WINDOWS:
         out = torch.full((rows, per), float("nan"), dtype=torch.float32, device=DEV)
         _launch_rows(None, None, out, per, row0, rows)
-        assert np.array_equal(_bits(out.cpu().numpy()), _bits(full[row0:row0 + rows])), f"{name} window {row0}..{row0 + rows}"
-        mis = _misaligned(torch.full((rows, per), float("nan"), dtype=torch.float32, device=DEV))
+        assert np.array_equal(PG.np_bits(out.cpu().numpy()), PG.np_bits(full[row0:row0 + rows])), f"{name} window {row0}..{row0 + rows}"
+        mis = PG.misaligned(torch.full((rows, per), float("nan"), dtype=torch.float32, device=DEV))
         _launch_rows(None, None, mis, per, row0, rows)
-        assert np.array_equal(_bits(mis.cpu().numpy()), _bits(full[row0:row0 + rows])), f"{name} window {row0}..{row0 + rows}, misaligned"
+        assert np.array_equal(PG.np_bits(mis.cpu().numpy()), PG.np_bits(full[row0:row0 + rows])), f"{name} window {row0}..{row0 + rows}, misaligned"
     # a shorter run is a prefix; another seed is another stream
     short = brainxai.smooth_grad_noise((KB, *shape), nsamples=3, seed=SEED, device=DEV).cpu().numpy()
-    assert np.array_equal(_bits(short), _bits(_dump(name)[:, :3]))
+    assert np.array_equal(PG.np_bits(short), PG.np_bits(_dump(name)[:, :3]))
     other = brainxai.smooth_grad_noise((KB, *shape), nsamples=KN, seed=SEED + 1, device=DEV).cpu().numpy()
     assert not np.array_equal(other, _dump(name))
 
@@ -123,10 +111,10 @@ def test_sigma_bit_for_bit(name):
     x = torch.cat([x, zeros])
     want = R.sigma(x, LEVEL)
     assert want[1] == 0 and want[3] == 0 and not np.signbit(want).any() and (per == 1 or (want[[0, 2]] > 0).all())
-    for xd in (PG.dev(x), _misaligned(PG.dev(x))):
+    for xd in (PG.dev(x), PG.misaligned(PG.dev(x))):
         sig = torch.full((4,), float("nan"), dtype=torch.float32, device=DEV)
         L.check(L.load().bx_smoothgrad_sigma(PG.p(xd), PG.p(sig), 4, per, LEVEL, PG.stream()), "bx_smoothgrad_sigma")
-        assert np.array_equal(_bits(sig.cpu().numpy()), _bits(want)), f"{name}: {sig.cpu().numpy()} against {want}"
+        assert np.array_equal(PG.np_bits(sig.cpu().numpy()), PG.np_bits(want)), f"{name}: {sig.cpu().numpy()} against {want}"
 
 
 @pytest.mark.parametrize("name", sorted(SHAPES))
@@ -141,15 +129,15 @@ def test_rows_bit_for_bit(name):
     want = R.rows(x, sig, _dump(name))
     assert not np.isnan(want).any() and np.array_equal(want.reshape(KB, KN, per)[1], np.full((KN, per), 2.5, dtype=np.float32))
     xd, sd = PG.dev(x), PG.dev(sig)
-    paths = [("aligned", xd, False), ("misaligned input", _misaligned(xd), False), ("misaligned output", xd, True)]
+    paths = [("aligned", xd, False), ("misaligned input", PG.misaligned(xd), False), ("misaligned output", xd, True)]
     for row0, rows in WINDOWS:
         for what, xin, mis_out in paths:
             out = torch.full((rows, *shape), float("nan"), dtype=torch.float32, device=DEV)
-            out = _misaligned(out) if mis_out else out
+            out = PG.misaligned(out) if mis_out else out
             _launch_rows(xin, sd, out, per, row0, rows)
             got = out.cpu().numpy()
             assert not np.isnan(got).any(), f"{name} rows {row0}..{row0 + rows}, {what}: elements left unwritten"
-            assert np.array_equal(_bits(got), _bits(want[row0:row0 + rows])), f"{name} rows {row0}..{row0 + rows}, {what}"
+            assert np.array_equal(PG.np_bits(got), PG.np_bits(want[row0:row0 + rows])), f"{name} rows {row0}..{row0 + rows}, {what}"
     print(f"rows {name}: per {per} ({'16-byte and ' if per % 4 == 0 else ''}element-by-element path), windows {WINDOWS} bit for bit")
 
 
@@ -231,18 +219,13 @@ def test_exact_cases(n):
                                          PG.stream()), "bx_smoothgrad_finish")
         got[kind] = values.cpu().numpy()[:, 0], amap.cpu().numpy()[:, 0]
     g1 = g1.numpy()[:, 0]
-    assert np.array_equal(_bits(got["smoothgrad"][0]), _bits(g1)) and np.array_equal(_bits(got["smoothgrad"][1]), _bits(np.abs(g1).max(1)))
-    assert np.array_equal(_bits(got["smoothgrad_sq"][0]), _bits((g1.astype(np.float64) ** 2).astype(np.float32)))
+    assert np.array_equal(PG.np_bits(got["smoothgrad"][0]), PG.np_bits(g1)) and np.array_equal(PG.np_bits(got["smoothgrad"][1]), PG.np_bits(np.abs(g1).max(1)))
+    assert np.array_equal(PG.np_bits(got["smoothgrad_sq"][0]), PG.np_bits((g1.astype(np.float64) ** 2).astype(np.float32)))
     assert not got["vargrad"][0].any() and not got["vargrad"][1].any() and not np.signbit(got["vargrad"][0]).any()
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------------------
 EN, ESEED = 6, 3
-
-
-def _per_pair_max(t):
-    t = torch.as_tensor(t).detach().double().cpu()
-    return t.abs().flatten(2).max(2).values                                # [B, K]
 
 
 def _device_noise(x, n=EN, seed=ESEED):
@@ -256,34 +239,16 @@ def _guard(what, f64, want, x, z, sig, other, input):
     least = {}
     for how, alt in moved.items():
         for kind, a, w in zip(R.KINDS, alt, want):
-            least[how, kind] = float((_per_pair_max(a - w) / _per_pair_max(w)).min())
+            least[how, kind] = float((GG.per_pair_max(a - w) / GG.per_pair_max(w)).min())
     print(f"{what}: the reference moves by (least over (sample, class), of its maximum) " + ", ".join(f"{how} / {kind} {v:.3f}" for (how, kind), v in least.items()))
     for key, v in least.items():
         assert v > 100 * TOL, f"{what}: {key} moves the reference by only {v:.3e}"
 
 
-def _mm_inputs():
-    return O.seeded((2, 1, 19, 2000), 12, "randn"), O.seeded((2, 4, 32, 64), 11, "rand")
-
-
 @functools.lru_cache(maxsize=None)
 def _eeg_case(kind):
     """(mine, x, other, z, sigma, (mean, sq, var) fp64 [B,K,1,Chans,T], M fp64 [B,K]); computed once, never written to."""
-    if kind == "eegnet":
-        ref = O.fill_params(O.EEGNet(6, Chans=19, Samples=2000, dropoutRate=0.0), seed=31).eval()
-        mine = brainxai.EEGNet(6, Chans=19, Samples=2000, dropoutRate=0.0)
-        x, other = O.seeded((2, 1, 19, 2000), 91, "randn"), None
-    elif kind == "deep":
-        ref = O.fill_params(O.EEGNetAttentionDeep(6, Chans=19, Samples=2000, dropoutRate=0.0), seed=61).eval()
-        mine = brainxai.EEGNetAttentionDeep(6, Chans=19, Samples=2000, dropoutRate=0.0)
-        x, other = _mm_inputs()[0], None
-    else:
-        ref, mine = PG.scaled_multimodal()
-        x, other = _mm_inputs()
-    if kind != "multimodal":
-        mine.load_state_dict(ref.state_dict())
-        mine = mine.to(DEV).eval()
-    f64 = copy.deepcopy(ref).double().eval()
+    _, mine, f64, x, other = GG.eeg_models(kind)
     z, sig = _device_noise(x), R.sigma(x, LEVEL)
     *want, M = R.values(f64, x, z, sig, other, "eeg", with_gmax=True)
     _guard(f"smooth_grad eeg input, {kind}", f64, want, x, z, sig, other, "eeg")
@@ -296,10 +261,10 @@ def _check_kinds(what, results, want, M):
     for kind, w in zip(R.KINDS, want):
         got = results[kind].detach().double().cpu()
         assert got.shape == w.shape and bool(torch.isfinite(got).all())
-        err = _per_pair_max(got - w)
-        bound = {"smoothgrad": TOL * _per_pair_max(w), "smoothgrad_sq": (2 * TOL + TOL * TOL) * M * M, "vargrad": 2 * (2 * TOL + TOL * TOL) * M * M}[kind]
+        err = GG.per_pair_max(got - w)
+        bound = {"smoothgrad": TOL * GG.per_pair_max(w), "smoothgrad_sq": (2 * TOL + TOL * TOL) * M * M, "vargrad": 2 * (2 * TOL + TOL * TOL) * M * M}[kind]
         ratio = float((err / bound).max())
-        line.append(f"{kind} {ratio:.3e} x bound (error {float((err / _per_pair_max(w)).max()):.3e} of the maximum)")
+        line.append(f"{kind} {ratio:.3e} x bound (error {float((err / GG.per_pair_max(w)).max()):.3e} of the maximum)")
         assert ratio <= 1.0, f"{what}: {kind} {ratio:.3f} x the bound"
     print(f"{what}: " + "; ".join(line))
 
@@ -313,14 +278,14 @@ def test_eeg_input_against_the_fp64_oracle(kind):
                                    class_idx="all", seed=ESEED, return_parts=True)
         assert res.values.shape == (2, 6, 1, 19, 2000) and res.attribution.shape == (2, 6, 19, 2000) and res.classes is None
         assert (res.nsamples, res.kind, res.seed) == (EN, k, ESEED)
-        assert np.array_equal(_bits(res.sigma.cpu().numpy()), _bits(sig))
+        assert np.array_equal(PG.np_bits(res.sigma.cpu().numpy()), PG.np_bits(sig))
         assert torch.equal(res.attribution, res.values[:, :, 0].abs())
         results[k] = res.values
     _check_kinds(f"smooth_grad eeg input, {kind}", results, want, M)
 
 
 def _spec_case():
-    eeg, spec = _mm_inputs()
+    eeg, spec = GG.mm_inputs()
     return eeg, spec, _device_noise(spec), R.sigma(spec, LEVEL)
 
 
@@ -364,7 +329,7 @@ def test_spec_input_against_the_same_pass_from_pieces(dt):
     eeg_d, spec_d = eeg.to(DEV), spec.to(DEV)
     max_batch, n = 5, EN                                                  # three passes; the first two end inside a sample
     r_all, S1, S2, A1 = _composed(mine, eeg_d, spec_d, PG.dev(z), PG.dev(sig), max_batch)
-    assert np.array_equal(_bits(r_all.cpu().numpy()), _bits(R.rows(spec, sig, z))), "the composed rows are not the restatement's"
+    assert np.array_equal(PG.np_bits(r_all.cpu().numpy()), PG.np_bits(R.rows(spec, sig, z))), "the composed rows are not the restatement's"
     S1, S2, A1 = S1.cpu().numpy(), S2.cpu().numpy(), A1.cpu().numpy()
     assert float(np.abs(S1).max()) > 0
     line = []
@@ -418,27 +383,15 @@ def test_spec_input_against_the_fp64_oracle():
 
 
 # ---- interface --------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _iface():
-    _, mine = PG.scaled_multimodal()
-    eeg, spec = _mm_inputs()
-    return mine, eeg.to(DEV), spec.to(DEV)
-
-
-def _worst(got, want):
-    assert tuple(got.shape) == tuple(want.shape) and bool(torch.isfinite(got).all())
-    return float((_per_pair_max(got.double().cpu() - want.double().cpu()) / _per_pair_max(want)).max())
-
-
 def test_repeatable_prefix_and_max_batch():
-    mine, eeg, spec = _iface()
+    mine, eeg, spec = GG.iface()
     kw = dict(input="eeg", nsamples=EN, class_idx="all", seed=ESEED)
     a = brainxai.smooth_grad(mine, eeg, spec, return_parts=True, **kw)
     b = brainxai.smooth_grad(mine, eeg, spec, **kw)
     assert torch.equal(a.attribution, b), "two calls differ"
     assert not torch.equal(a.attribution, brainxai.smooth_grad(mine, eeg, spec, input="eeg", nsamples=EN, class_idx="all", seed=ESEED + 1))
     small = brainxai.smooth_grad(mine, eeg, spec, max_batch=5, return_parts=True, **kw)
-    err = _worst(small.values, a.values)
+    err = GG.worst(small.values, a.values)
     print(f"smooth_grad max_batch 5 vs 256: {err:.3e} of the per-(sample, class) maximum, bit for bit: {torch.equal(small.values, a.values)}")
     assert err <= TOL
     # nsamples = 3 sees the first three draws of nsamples = 6: the mean over the first three rows of the dumped noise, from pieces
@@ -449,9 +402,9 @@ def test_repeatable_prefix_and_max_batch():
         y = mine(r, spec.repeat_interleave(3, dim=0))
         (g,) = torch.autograd.grad(y[:, 2].sum(), r)
     gg = g.double().reshape(2, 3, 1, 19, 2000)
-    err3 = _worst(three.values[:, None], gg.mean(1)[:, None])
+    err3 = GG.worst(three.values[:, None], gg.mean(1)[:, None])
     flipped = gg * torch.tensor([1.0, 1.0, -1.0], device=DEV, dtype=torch.float64).view(1, 3, 1, 1, 1)
-    wrong = _worst(three.values[:, None], flipped.mean(1)[:, None])
+    wrong = GG.worst(three.values[:, None], flipped.mean(1)[:, None])
     print(f"smooth_grad nsamples 3 against the first three dumped draws from pieces: {err3:.3e} of the maximum (one draw's sign flipped: {wrong:.3e})")
     assert err3 <= TOL < wrong
     s_kw = dict(input="spec", nsamples=4, class_idx="all", seed=1, kind="vargrad")
@@ -459,7 +412,7 @@ def test_repeatable_prefix_and_max_batch():
 
 
 def test_class_forms():
-    mine, eeg, spec = _iface()
+    mine, eeg, spec = GG.iface()
     for input, shape in (("eeg", (19, 2000)), ("spec", (32, 64))):
         kw = dict(input=input, nsamples=4, seed=5, kind="smoothgrad_sq" if input == "spec" else "smoothgrad")
         every = brainxai.smooth_grad(mine, eeg, spec, class_idx="all", return_parts=True, **kw)
@@ -480,7 +433,7 @@ def test_class_forms():
 
 
 def test_stdev_modes_and_downstream():
-    mine, eeg, spec = _iface()
+    mine, eeg, spec = GG.iface()
     mine.train()
     frozen = mine.fc1.bias
     frozen.requires_grad_(False)
@@ -490,14 +443,14 @@ def test_stdev_modes_and_downstream():
     finally:
         frozen.requires_grad_(True)
         mine.eval()
-    assert level.sigma.shape == (2,) and np.array_equal(_bits(level.sigma.cpu().numpy()), _bits(R.sigma(spec.cpu(), 0.15))), "the default noise level is 0.15"
+    assert level.sigma.shape == (2,) and np.array_equal(PG.np_bits(level.sigma.cpu().numpy()), PG.np_bits(R.sigma(spec.cpu(), 0.15))), "the default noise level is 0.15"
     # the absolute scale: per sample as a tensor, and one number for all
     per = brainxai.smooth_grad(mine, eeg, spec, input="spec", nsamples=4, seed=2, class_idx="all", stdev=level.sigma, return_parts=True)
     assert torch.equal(per.values, level.values) and torch.equal(per.sigma, level.sigma)
     s0 = float(level.sigma[0])
     one = brainxai.smooth_grad(mine, eeg, spec, input="spec", nsamples=4, seed=2, class_idx="all", stdev=s0, return_parts=True)
     assert torch.equal(one.sigma, torch.full((2,), s0, device=DEV))
-    assert _worst(one.values[:1], level.values[:1]) <= TOL, "sample 0 has the same scale in both calls"
+    assert GG.worst(one.values[:1], level.values[:1]) <= TOL, "sample 0 has the same scale in both calls"
     both = brainxai.smooth_grad(mine, eeg, spec, input="spec", nsamples=4, seed=2, class_idx="all", stdev=torch.tensor([s0, s0], dtype=torch.float64))
     assert torch.equal(both, one.attribution)
     # without noise every draw is the plain gradient of the same row: the variance stays within its end-to-end bound of zero
@@ -518,7 +471,7 @@ def test_stdev_modes_and_downstream():
 
 
 def test_stand_alone_spectrogram_model():
-    mine, eeg, spec = _iface()
+    mine, eeg, spec = GG.iface()
     sm = mine.spectrogram_model
     res = brainxai.smooth_grad(sm, None, spec, nsamples=4, class_idx="all", seed=2, return_parts=True)
     assert res.values.shape == (2, 6, 4, 32, 64) and res.attribution.shape == (2, 6, 32, 64) and bool(torch.isfinite(res.values).all())
