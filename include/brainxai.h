@@ -896,6 +896,58 @@ int bx_sensitivity_rows(const float* x, const float* radius, float* out, int B, 
 int bx_sensitivity_dist(const float* a, const float* ref, double* dist, int B, int n, int per, int row0, int rows, bxStream stream);
 /* sens[b] = max_k dist[b,k] / (norms[b] == 0 ? 1 : norms[b]); dist fp64 [B,n], norms and sens fp64 [B]. */
 int bx_sensitivity_finish(const double* dist, const double* norms, double* sens, int B, int n, bxStream stream);
+/* ---- Blur Integrated Gradients (Xu, Venugopalan, Sundararajan, CVPR 2020; PAIR's saliency.BlurIG) and the Gaussian blur behind it.
+ * For the explained input x [B,C,H,W] (an EEG input [B,1,Chans,T] is C = 1, H = Chans, W = T), n steps, max_sigma, grad_step = eps and
+ * F_c the model's output log-probability of class c:
+ *   Schedule (host, Python floats, as saliency computes it): sigma_i = i * max_sigma / n, or sqrt(i * max_sigma / n), i = 0..n;
+ *     w_i = -(sigma_{i+1} - sigma_i).
+ *   Taps (host, numpy fp64, rounded once to fp32; scipy.ndimage.gaussian_filter's with truncate 4): R(s) = int(4 s + 0.5),
+ *     g_s[t] = exp(-0.5 / s^2 * t^2) / sum_t exp(..), t = -R..R; g_0 is the identity (R = 0).  Per step a = g_{sigma_i},
+ *     b = g_{sigma_i + eps}, d = (b - a) / eps formed in fp64 with a zero-padded to b's radius.
+ *   Rows: zero padding outside the image (scipy's mode="constant"), per channel, filters along `axes`.  With A, B, D the filters of
+ *     the taps a, b, d along x (W) or y (H):
+ *       both axes:  X_i = A_y A_x x,   D_i = B_y (D_x x) + D_y (A_x x)      -- exactly ( blur_{sigma_i+eps}(x) - X_i ) / eps in real
+ *                   arithmetic (B_y B_x - A_y A_x = B_y (B_x - A_x) + (B_y - A_y) A_x), without the cancellation of the literal form
+ *       one axis:   X_i = A x,         D_i = D x
+ *     Every filter is a chain of fmaf(tap, input, sum) from +0 in ascending tap order over the taps that can land inside the image
+ *     (a tap beyond a filter's radius, where the chain reaches one, counts as 0); the horizontal results Ha = A_x x and Hd = D_x x are
+ *     rounded to fp32 once; D's vertical chain is one accumulator that takes, for each tap t in ascending order, b[t] Hd[y+t] and then
+ *     d[t] Ha[y+t].  Where R_b = 0 the row is x bit for bit (signs of zero included) and D is +0.
+ *   Attribution: values[b,c] = sum_{i<n} w_i * dF_c/dx(X_i) (.) D_i  (fp64: g * D of two floats is exact, w_i * (g * D) and the sum are one
+ *     rounding each, ascending i, carried between calls), rounded to fp32 once (bx_expgrad_finish with n = 1, which also gives the
+ *     channel-summed map).  endpoint[b] = F(blur_{sigma_n}(x[b])); delta[b,c] = sum_e values - (F_c(x) - endpoint_c): the completeness
+ *     error of the left Riemann sum, reported, not minimised.
+ * The tap table.  taps fp32 [entries, 3, tap_width]: filters a, b, d of an entry, tap t at index tap_width / 2 + t; tap_width is odd and
+ * at least 2 max R_b + 1.  radius i32 [entries, 2] = (R_a, R_b) of an entry, R_a <= R_b <= tap_width / 2 (values outside are clamped);
+ * the kernel reads a only within R_a and b, d only within R_b, so what the table holds beyond them does not matter.  Both on the
+ * device.  Rows are numbered globally j = b * n + i, sample-major; a call handles rows [row0, row0 + rows), which may start and end
+ * inside a sample.  Row j uses entry i (per_sample == 0: entries = n, the schedule shared by the samples) or entry j (per_sample != 0:
+ * entries = B * n, a sigma of its own for every sample; bx_blur_rows with n = 1 is then a Gaussian blur with one sigma per sample).
+ * B * n, B * per, rows * per and B * Kc * per stay below 2^31; every entry point refuses its limits with BX_EINVAL / BX_EUNSUPPORTED
+ * before any pointer is touched. */
+enum { BX_BLUR_AXES_HW = 0, BX_BLUR_AXES_H = 1, BX_BLUR_AXES_W = 2 };
+#define BX_BLUR_MAX_RADIUS 16384
+/* The rows: rows_out fp32 [rows,C,H,W] = X and deriv_out fp32 [rows,C,H,W] = D (NULL: X alone, the filters b and d are not read).  Every
+ * element of every row is written exactly once; 16-byte accesses when W % 4 == 0 and x, rows_out and deriv_out are 16-byte aligned,
+ * element by element otherwise.  Both axes: a workgroup owns (row, channel, strip of 16, 8 or 4 columns), keeps Ha and Hd of its strip
+ * for all H image rows in LDS and filters vertically from there -- no global intermediate; the widest strip is taken for which
+ *     4 * ( 6 TP + (2, or 1 without D) * 4 ceil(H / 4) * (strip + 4) ) <= 65536 bytes,   TP = 4 ceil((RC + 3) / 4) + 4,
+ * RC = min(tap_width / 2, max(H, W) - 1): only taps that can join two points of the image are staged.  A shape whose 4-column strip
+ * does not fit returns BX_EUNSUPPORTED (with D and radius 200: H <= 944).  One axis: no intermediate, 16 TP <= 65536 with RC from the
+ * filtered extent.
+ * A thread produces four adjacent outputs along the filter axis from each loaded group of four inputs; the taps of a row are staged in
+ * LDS once per workgroup.  tap_width / 2 <= BX_BLUR_MAX_RADIUS, C <= 65535 (BX_EUNSUPPORTED above). */
+int bx_blur_rows(const float* x, const float* taps, const int* radius, float* rows_out, float* deriv_out, int B, int n, int C, int H, int W, int axes,
+                 int tap_width, int per_sample, int row0, int rows, bxStream stream);
+/* The running sum of one class slot: acc[b,slot,e] += sum of w[i] * ( (double)g[j - row0, e] * (double)deriv[j - row0, e] ) over the rows
+ * j = b * n + i of the call that belong to sample b, in ascending i.  acc fp64 [B,Kc,per] (Kc <= 32; the other slots are not touched),
+ * w fp64 [n] on the device, g and deriv fp32 [rows, per]: the input gradient and D of the call's rows.  One thread per element, no
+ * atomics: no bit depends on how the rows were split into calls. */
+int bx_blurig_accumulate(const float* g, const float* deriv, const double* w, double* acc, int B, int n, int per, int Kc, int slot, int row0, int rows,
+                         bxStream stream);
+/* out[r] = sum_t (double)v[r,t] for v fp32 [R,L], out fp64 [R]: the sum behind delta, one row per (sample, class), in the order of
+ * bx_mean_abs_rows -- 64 partial sums over t = l, l + 64, ... (ascending), added by a fixed pairwise tree.  R * L < 2^31. */
+int bx_blurig_sum_rows(const float* v, double* out, int R, int L, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

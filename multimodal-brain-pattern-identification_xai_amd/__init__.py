@@ -12,6 +12,7 @@ from .explain import (GradCamSweep, expected_gradients, generate_saliency_maps, 
                       OcclusionResult, occlusion, KernelShapResult, kernel_shap,
                       GradientShapResult, gradient_shap, channel_importance, GradientExplainer,
                       SmoothGradResult, smooth_grad, smooth_grad_noise,
+                      BlurIGResult, blur_ig, blur_path, gaussian_blur,
                       InfidelityResult, infidelity, SensitivityResult, sensitivity_max)
 from .data import (EEGStacker, stack_eeg, EEGMontageStacker, stack_eeg_montage,          # noqa: F401
                    SpectrogramPreprocessor, preprocess_spectrograms, SpectrogramRegionStacker, stack_spectrogram_regions, StagingRing)                                        # noqa: F401

@@ -20,6 +20,8 @@ BX_TAIL_SYNC_WORDS = 8192
 BX_EEG_CAM_CONV1, BX_EEG_CAM_DEPTHWISE, BX_EEG_CAM_SEPARABLE = 0, 1, 2
 BX_CAM_GRADCAM, BX_CAM_GRADCAM_PP, BX_CAM_LAYERCAM = 0, 1, 2
 BX_SCORECAM_PROB, BX_SCORECAM_INCREASE = 0, 1
+BX_BLUR_AXES_HW, BX_BLUR_AXES_H, BX_BLUR_AXES_W = 0, 1, 2
+BX_BLUR_MAX_RADIUS = 16384
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -212,6 +214,9 @@ SIGNATURES = {
     "bx_sensitivity_rows": (i32, [vp, vp, vp, i32, i32, i32, C.c_uint64, i32, i32, vp]),
     "bx_sensitivity_dist": (i32, [vp, vp, vp] + [i32] * 5 + [vp]),
     "bx_sensitivity_finish": (i32, [vp, vp, vp, i32, i32, vp]),
+    "bx_blur_rows": (i32, [vp] * 5 + [i32] * 10 + [vp]),
+    "bx_blurig_accumulate": (i32, [vp] * 4 + [i32] * 7 + [vp]),
+    "bx_blurig_sum_rows": (i32, [vp, vp, i32, i32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

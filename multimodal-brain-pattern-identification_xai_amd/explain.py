@@ -45,6 +45,12 @@
                                  classes, fp64 running sums of the gradient and its square in fixed draw order
                                  (bx_smoothgrad_accumulate), the mean / mean square / variance and the channel-max map
                                  (bx_smoothgrad_finish).  ``smooth_grad_noise`` returns the draws.
+* ``blur_ig``                 -- Blur Integrated Gradients (Xu et al., CVPR 2020; saliency.BlurIG; not in the reference): integrated
+                                 gradients along the path through Gaussian scale space, without a baseline, of either input; the
+                                 blurred rows of a pass and their scale derivative come from one launch of separable filters
+                                 (bx_blur_rows), an fp64 running sum of w * gradient * derivative in fixed step order
+                                 (bx_blurig_accumulate), the completeness error from fp64 row sums (bx_blurig_sum_rows).
+                                 ``blur_path`` returns the rows, ``gaussian_blur`` is the same kernel as a plain blur.
 * ``infidelity`` / ``sensitivity_max`` -- the two measures of Yeh et al. (NeurIPS 2019; Captum's metrics.infidelity and
                                  metrics.sensitivity_max) for any of those maps: rows minus SmoothGrad's Gaussian stream written in the
                                  model's layout (bx_infidelity_rows_*), the fp64 dot of the same noise with the attribution in fixed
@@ -1214,12 +1220,13 @@ def _explained_classes(who, class_idx, B, K, allow_all):
     return cls_h, False
 
 
-def _row_cap(x, input, dt, max_batch):
+def _row_cap(x, input, dt, max_batch, beside=0):
     """Rows per forward pass: max_batch, capped so that a pass addresses its largest activation with 32-bit byte offsets -- stage 1's
-    H x W x 16 channels in dt for a spectrogram [B,C,H,W], EEGNet's F1 x Chans x T in fp32 for an EEG input [B,1,Chans,T]."""
+    H x W x 16 channels in dt for a spectrogram [B,C,H,W], EEGNet's F1 x Chans x T in fp32 for an EEG input [B,1,Chans,T].  beside: the
+    bytes per row of a buffer the driver keeps beside the rows (blur_ig's D), addressed within the same limit."""
     cells = int(x.shape[2]) * int(x.shape[3])
     row_bytes = cells * 16 * (2 if dt == torch.bfloat16 else 4) if input == "spec" else 8 * cells * 4
-    return max(1, min(max_batch, ((1 << 31) - 1) // row_bytes))
+    return max(1, min(max_batch, ((1 << 31) - 1) // max(row_bytes, beside)))
 
 
 def _fixed_branch(model, other, input_is_spec):
@@ -1335,20 +1342,20 @@ def _sample_of(row0, rows, n, dev):
 
 
 class _GradPass:
-    """What the sampled-gradient drivers (gradient_shap, smooth_grad) do alike once their arguments are checked: n sampled rows per
+    """What the sampled-gradient drivers (gradient_shap, smooth_grad, blur_ig) do alike once their arguments are checked: n sampled rows per
     sample, sample-major, run through the branch that reads them with the other branch's per-sample output gathered into the fusion
     head, and one backward pass per explained class from a one-hot seed (bx_expgrad_seed).  A driver brings its row writer, its
     accumulate and its finish; the chunking by max_batch, the clean pass, the fp64 sums and the 'forward' / 'rows' / 'backward' /
     'accumulate' laps of ``profile`` are here.  Inside ``open()``, ``xs`` is the explained input (fp32, contiguous); ``clean`` sets
     ``out``, ``classes`` and ``fixed`` (None for a stand-alone model).  Cc, HW: the channels and pixels a finish launch reduces over."""
 
-    def __init__(self, model, net, multimodal, K, x, other, input_is_spec, n, cls_h, all_classes, max_batch, profile):
+    def __init__(self, model, net, multimodal, K, x, other, input_is_spec, n, cls_h, all_classes, max_batch, profile, beside=0):
         self.model, self.net, self.multimodal, self.K, self.other, self.input_is_spec = model, net, multimodal, K, other, input_is_spec
         self.xs, self.n, self.cls_h, self.all_classes, self.profile, self.fixed = x, n, cls_h, all_classes, profile, None
         self.dev, self.B = x.device, int(x.shape[0])
         self.per, self.Kc, self.total = x.numel() // self.B, K if all_classes else 1, self.B * n
         self.dt = getattr(net, "compute_dtype", torch.float32) if input_is_spec else torch.float32
-        self.max_rows = min(_row_cap(x, "spec" if input_is_spec else "eeg", self.dt, max_batch), ((1 << 31) - 1) // self.per)
+        self.max_rows = min(_row_cap(x, "spec" if input_is_spec else "eeg", self.dt, max_batch, beside), ((1 << 31) - 1) // self.per)
         self.Cc, self.HW = (int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])) if input_is_spec else (1, self.per)
 
     @contextlib.contextmanager
@@ -1425,8 +1432,8 @@ def deletion_insertion(model, eeg, spec, attribution, *, input="spec", mode="bot
                  saliency, a channel-reduced IG result and LimeExplanation.heatmap(label)[None] fit as they are.
     model:       a MultimodalModel; a stand-alone Spectrogram_Model (eeg=None, input='spec'); a stand-alone EEGNet /
                  EEGNetAttentionDeep (spec=None, input='eeg') -- the convention of grad_cam.
-    baseline:    a number; one value per channel (spec) / electrode (eeg); or a tensor of the input's shape (a blurred copy, a
-                 per-sample mean: the package does not blur).
+    baseline:    a number; one value per channel (spec) / electrode (eeg); or a tensor of the input's shape (a per-sample mean, or a
+                 blurred copy: ``gaussian_blur(x, sigma)`` returns one).
     class_idx:   None = each sample's arg-max class on the unperturbed input; an int; or one class per sample (sequence / tensor [B]).
     mode:        'both', 'deletion' or 'insertion'; the fields of the other mode are None.
     max_batch:   rows (perturbed samples) per forward pass.
@@ -2557,6 +2564,273 @@ def _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, cl
                     "bx_smoothgrad_finish")
     return gp.result(return_parts, SmoothGradResult, amap, values, sigma, n, kind, seed)
 
+
+# ------------------------------------------------------------------------------------------------
+# Blur Integrated Gradients (Xu, Venugopalan, Sundararajan, CVPR 2020; PAIR's saliency.BlurIG) and the Gaussian blur behind it.  The
+# definition is pinned in include/brainxai.h; tests/blur_ig_ref.py restates it.
+BlurIGResult = collections.namedtuple("BlurIGResult", "map values classes out endpoint delta sigmas steps max_sigma sqrt grad_step axes")
+BlurIGResult.__doc__ = """What ``blur_ig(..., return_parts=True)`` returns: ``map`` fp32 [B,H,W] / [B,Chans,T], with a class axis for class_idx='all'
+(what the plain call returns), ``values`` fp32 [B(,K),*x.shape[1:]] (the attribution element by element), ``classes`` int64 [B] (None
+for class_idx='all'), ``out`` fp32 [B,K] (the log-probabilities of the clean input), ``endpoint`` fp32 [B,K] (those of the input blurred
+with the last sigma), ``delta`` fp64 [B] or [B,K] (sum of the values - (F_c(x) - endpoint_c): the completeness error of the left
+Riemann sum), all on the device; ``sigmas`` the n + 1 Python floats of the schedule; the other fields as given."""
+
+_BLUR_AXES = {"hw": L.BX_BLUR_AXES_HW, "h": L.BX_BLUR_AXES_H, "w": L.BX_BLUR_AXES_W}
+_BLUR_LDS = 65536                                                                  # the row kernel's LDS budget (include/brainxai.h)
+
+
+def blur_sigmas(steps, max_sigma, sqrt=False):
+    """The n + 1 scales of the blur path in Python floats, exactly as saliency computes them: i * max_sigma / n, or its square root."""
+    if sqrt:
+        return [math.sqrt(float(i) * max_sigma / float(steps)) for i in range(0, steps + 1)]
+    return [float(i) * max_sigma / float(steps) for i in range(0, steps + 1)]
+
+
+def _blur_radius(sigma):
+    return int(4.0 * float(sigma) + 0.5)                                           # scipy.ndimage.gaussian_filter1d, truncate = 4
+
+
+def gaussian_taps(sigma):
+    """fp64 [2 R + 1]: the taps of scipy.ndimage.gaussian_filter1d(sigma, truncate=4), R = int(4 sigma + 0.5); the identity for
+    sigma = 0 (and wherever R = 0)."""
+    R = _blur_radius(sigma)
+    if R == 0:
+        return np.ones(1, dtype=np.float64)
+    t = np.arange(-R, R + 1)
+    phi = np.exp(-0.5 / (float(sigma) * float(sigma)) * t ** 2)
+    return phi / phi.sum()
+
+
+def blur_taps(sigmas, grad_step=None):
+    """The tap table of bx_blur_rows for the scales ``sigmas``: (taps fp32 [E,3,TW], radius int32 [E,2]) on the host.  Per entry
+    a = g_sigma, b = g_{sigma+eps} and d = (b - a) / eps, formed in fp64 with a zero-padded to b's radius and rounded to fp32 once, tap t at
+    index TW // 2 + t; radius = (R_a, R_b).  grad_step None: a alone (b and d stay zero, R_b = R_a)."""
+    E = len(sigmas)
+    ab = []
+    for s in sigmas:
+        a = gaussian_taps(s)
+        b = a if grad_step is None else gaussian_taps(float(s) + grad_step)
+        ab.append((a, b))
+    Rmax = max(len(b) // 2 for _, b in ab)
+    TW = 2 * Rmax + 1
+    taps, radius = np.zeros((E, 3, TW), dtype=np.float32), np.zeros((E, 2), dtype=np.int32)
+    for e, (a, b) in enumerate(ab):
+        Ra, Rb = len(a) // 2, len(b) // 2
+        radius[e] = Ra, Rb
+        a_pad = np.zeros(2 * Rb + 1, dtype=np.float64)
+        a_pad[Rb - Ra:Rb + Ra + 1] = a
+        taps[e, 0, Rmax - Rb:Rmax + Rb + 1] = a_pad
+        if grad_step is not None:
+            taps[e, 1, Rmax - Rb:Rmax + Rb + 1] = b
+            taps[e, 2, Rmax - Rb:Rmax + Rb + 1] = (b - a_pad) / grad_step
+    return taps, radius
+
+
+def _blur_axes(who, axes, eeg_input):
+    if axes is None:
+        return "w" if eeg_input else "hw"
+    if not isinstance(axes, str) or axes not in _BLUR_AXES:
+        raise ValueError(f"{who}: unknown axes {axes!r}; use 'hw', 'h' or 'w'")
+    if eeg_input and axes != "w":
+        raise ValueError(f"{who}: axes {axes!r} for the EEG input; the electrode order carries no geometry, only 'w' (time) is filtered")
+    return axes
+
+
+def _blur_steps(who, steps, max_sigma, sqrt, grad_step):
+    if isinstance(steps, bool) or not isinstance(steps, numbers.Integral):
+        raise ValueError(f"{who}: steps must be an int, got {steps!r}")
+    if int(steps) < 1:
+        raise ValueError(f"{who}: steps = {int(steps)} < 1")
+    for name, v in (("max_sigma", max_sigma), ("grad_step", grad_step)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
+            raise ValueError(f"{who}: {name} must be a finite number > 0, got {v!r}")
+    return int(steps), float(max_sigma), bool(sqrt), float(grad_step)
+
+
+def _blur_fits(who, x, axes, Rmax, deriv):
+    """Refuses what bx_blur_rows would: a radius beyond the kernel's, and two filtered axes whose 4-column strip does not fit its LDS."""
+    if Rmax > L.BX_BLUR_MAX_RADIUS:
+        raise ValueError(f"{who}: filter radius {Rmax} (4 sigma), supported up to {L.BX_BLUR_MAX_RADIUS}; use a smaller sigma")
+    H, W = int(x.shape[2]), int(x.shape[3])
+    RC = min(Rmax, {"hw": max(H, W), "h": H, "w": W}[axes] - 1)                    # only taps that can join two points of the image are staged
+    TP = 4 * ((RC + 6) // 4) + 4
+    if 16 * TP > _BLUR_LDS or (axes == "hw" and 4 * (6 * TP + (2 if deriv else 1) * 4 * ((H + 3) // 4) * 8) > _BLUR_LDS):
+        raise ValueError(f"{who}: H x W = {H} x {W} with filter radius {Rmax}: the taps and a strip of the intermediates do not fit the kernel's "
+                         f"{_BLUR_LDS} bytes of LDS")
+    if int(x.shape[1]) > 65535:
+        raise ValueError(f"{who}: {int(x.shape[1])} channels, supported 1..65535")
+
+
+def _blur_rows(lib, xs, taps_d, rad_d, TW, out, deriv, n, axes, per_sample, row0, rows):
+    B, Cc, H, W = (int(v) for v in xs.shape)
+    L.check(lib.bx_blur_rows(_p(xs), _p(taps_d), _p(rad_d), _p(out), _p(deriv), B, n, Cc, H, W, _BLUR_AXES[axes], TW, per_sample, row0, rows, _stream()),
+            "bx_blur_rows")
+
+
+def _blur_input(who, x):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be a tensor [B,C,H,W] (an EEG input [B,1,Chans,T] with axes='w')")
+    return _nonempty(who, x)
+
+
+def blur_path(x, *, steps, max_sigma, sqrt=False, grad_step=0.01, axes=None):
+    """The rows of ``blur_ig`` themselves: (rows fp32 [B,n,*x.shape[1:]], deriv fp32 [B,n,*x.shape[1:]], sigmas) -- X_i = x blurred with
+    sigma_i and D_i = (blur_{sigma_i + grad_step}(x) - X_i) / grad_step for i = 0..n-1, written by the kernel that writes the rows of a
+    pass (bx_blur_rows) -- for scale-space plots and tests; ``blur_ig`` never stores more than a pass of them.  x [B,C,H,W]; axes
+    'hw' (default), 'h' or 'w' (an EEG input [B,1,Chans,T] is blurred along time with axes='w')."""
+    who = "blur_path"
+    B = _blur_input(who, x)
+    axes = _blur_axes(who, axes, False)
+    n, max_sigma, sqrt, eps = _blur_steps(who, steps, max_sigma, sqrt, grad_step)
+    per = x.numel() // B
+    if B * n >= 1 << 31 or B * per >= 1 << 31:
+        raise ValueError(f"{who}: B * n = {B * n} or B * per = {B * per} beyond 32-bit offsets")
+    sigmas = blur_sigmas(n, max_sigma, sqrt)
+    taps, radius = blur_taps(sigmas[:n], eps)
+    _blur_fits(who, x, axes, taps.shape[2] // 2, True)
+    if not x.is_cuda:
+        raise RuntimeError(f"brainxai.{who}: the rows are written on the GPU; there is no CPU path")
+    lib = L.load()
+    with torch.cuda.device(x.device):
+        xs = x.detach().to(torch.float32).contiguous()
+        taps_d, rad_d = torch.from_numpy(taps).to(xs.device), torch.from_numpy(radius).to(xs.device)
+        rows_out = torch.empty(B * n, *xs.shape[1:], dtype=torch.float32, device=xs.device)
+        deriv = torch.empty_like(rows_out)
+        for row0, rows in _sample_chunks(B * n, max(1, ((1 << 31) - 1) // per)):
+            _blur_rows(lib, xs, taps_d, rad_d, taps.shape[2], rows_out[row0:row0 + rows], deriv[row0:row0 + rows], n, axes, 0, row0, rows)
+    return rows_out.reshape(B, n, *xs.shape[1:]), deriv.reshape(B, n, *xs.shape[1:]), sigmas
+
+
+def gaussian_blur(x, sigma, *, axes=None):
+    """x [B,C,H,W] blurred with a Gaussian of standard deviation ``sigma`` (a number, or one per sample: a sequence or tensor [B]), fp32
+    in the input's shape: scipy.ndimage.gaussian_filter's taps (truncate 4) and zero padding (mode='constant'), per channel, along
+    ``axes`` = 'hw' (default), 'h' or 'w' (an EEG input [B,1,Chans,T] is blurred along time with axes='w').  sigma = 0 returns the
+    input bit for bit.  The kernel of ``blur_ig``'s rows with one row per sample (bx_blur_rows).  The result passes as the tensor
+    ``baseline=`` of deletion_insertion, rise, occlusion, kernel_shap and score_cam."""
+    who = "gaussian_blur"
+    B = _blur_input(who, x)
+    axes = _blur_axes(who, axes, False)
+    if isinstance(sigma, numbers.Real) and not isinstance(sigma, bool):
+        sig = [float(sigma)]
+    else:
+        try:
+            sig_a = sigma.detach().to("cpu", torch.float64).numpy() if isinstance(sigma, torch.Tensor) else np.asarray(sigma, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: sigma must be a number or one per sample [B], got {type(sigma).__name__}") from None
+        if sig_a.shape != (B,):
+            raise ValueError(f"{who}: sigma of shape {tuple(sig_a.shape)}; expected a number or [B] = [{B}]")
+        sig = [float(v) for v in sig_a]
+    if any(not math.isfinite(v) or v < 0 for v in sig):
+        raise ValueError(f"{who}: sigma must be finite and >= 0")
+    per = x.numel() // B
+    if B * per >= 1 << 31:
+        raise ValueError(f"{who}: B * per = {B * per} beyond 32-bit offsets")
+    taps, radius = blur_taps(sig)
+    _blur_fits(who, x, axes, taps.shape[2] // 2, False)
+    if not x.is_cuda:
+        raise RuntimeError(f"brainxai.{who}: the blur runs on the GPU; there is no CPU path")
+    lib = L.load()
+    with torch.cuda.device(x.device):
+        xs = x.detach().to(torch.float32).contiguous()
+        out = torch.empty_like(xs)
+        _blur_rows(lib, xs, torch.from_numpy(taps).to(xs.device), torch.from_numpy(radius).to(xs.device), taps.shape[2], out, None, 1, axes,
+                   int(len(sig) > 1), 0, B)
+    return out
+
+
+def blur_ig(model, eeg, spec, *, input="spec", steps=50, max_sigma=50.0, sqrt=False, grad_step=0.01, axes=None, class_idx=None, max_batch=256,
+            return_parts=False):
+    """Blur Integrated Gradients (Xu, Venugopalan, Sundararajan, CVPR 2020; saliency.BlurIG): integrated gradients along the path through
+    Gaussian scale space from the input to a heavily blurred copy of it -- no baseline -- for either input of the multimodal model or a
+    stand-alone branch, batched over samples, steps and classes:
+        values[b,c] = sum_{i<n} w_i * dF_c/dx( X_i ) * D_i,      X_i = blur_{sigma_i}(x[b]),   D_i = (blur_{sigma_i + grad_step}(x[b]) - X_i) / grad_step,
+        sigma_i = i * max_sigma / n (sqrt: its square root),  w_i = -(sigma_{i+1} - sigma_i),  F_c the model's output log-probability of class c
+    with scipy.ndimage.gaussian_filter's taps (truncate 4) and zero padding, per channel.  The map is the values summed over the
+    input's channels (attributions stay additive) and fits ``deletion_insertion`` and ``attribution_ranks`` as it is.
+
+    input:       'spec': x = spec [B,C,H,W], map [B,H,W]; 'eeg': x = eeg [B,1,Chans,T], map [B,Chans,T].
+    model:       a MultimodalModel (the other input stays the sample's own); a stand-alone Spectrogram_Model (eeg=None, input='spec');
+                 a stand-alone EEGNet / EEGNetAttentionDeep (spec=None, input='eeg').
+    axes:        the filtered axes: 'hw' (the default for a spectrogram, saliency's [sigma, sigma, 0]), 'h' or 'w'; the EEG input is
+                 blurred along time only ('w', its default): a progressive low-pass.
+    steps, max_sigma, sqrt, grad_step: saliency's arguments; the filter radius int(4 (max_sigma + grad_step) + 0.5) is at most 16384.
+    class_idx:   None = each sample's arg-max class on the clean input; an int; one class per sample (sequence / tensor [B]); 'all' =
+                 every class, the map gains a class axis [B,K,...] (K <= 32): one forward pass then serves K backward passes.
+    max_batch:   rows (blurred inputs) per pass, capped so that a pass addresses its largest activation and its D with 32-bit offsets.
+                 The sum over the steps is carried in fp64 between passes, so, given the same gradients, no bit depends on it.
+    The rows of a pass and their D are written by one launch (bx_blur_rows: separable filters, D as B_y(D_x x) + D_y(A_x x), no global
+    intermediate), the one-hot gradient seeds by one (bx_expgrad_seed); every backward pass is followed by one bx_blurig_accumulate
+    (fp64, ascending step order, no atomics), and bx_expgrad_finish rounds the values and sums the channels.  ``endpoint`` is the
+    model's output on the input blurred with sigma_n and ``delta`` the completeness error sum(values) - (F_c(x) - endpoint_c) of the
+    left Riemann sum (bx_blurig_sum_rows: fp64, fixed order); it is reported, not minimised.  In a MultimodalModel the branch whose
+    input does not change runs once per sample.  The training flag and every requires_grad are restored on return.  Returns the map
+    (device, fp32), or ``BlurIGResult`` with return_parts."""
+    return _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, class_idx, max_batch, return_parts)
+
+
+def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, class_idx, max_batch, return_parts, profile=None):
+    """``blur_ig`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'rows', 'forward',
+    'backward', 'accumulate', 'finish' -- device events around every phase of the pass (tools/blur_ig_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "blur_ig"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    axes = _blur_axes(who, axes, input == "eeg")
+    n, max_sigma, sqrt, eps = _blur_steps(who, steps, max_sigma, sqrt, grad_step)
+    max_batch = _max_batch(who, max_batch)
+    x = _input_tensor(who, input, eeg, spec)
+    B = _nonempty(who, x)
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    Kc = K if all_classes else 1
+    per = x.numel() // B
+    if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or B * Kc > 65535:
+        raise ValueError(f"{who}: B * n = {B * n} or B * Kc * per = {B * Kc * per} beyond 32-bit offsets, or B * Kc = {B * Kc} > 65535; use fewer samples per call")
+    sigmas = blur_sigmas(n, max_sigma, sqrt)
+    taps, radius = blur_taps(sigmas[:n], eps)
+    end_taps, end_radius = blur_taps(sigmas[n:])
+    _blur_fits(who, x, axes, max(taps.shape[2], end_taps.shape[2]) // 2, True)
+    w = np.array([-(sigmas[i + 1] - sigmas[i]) for i in range(n)], dtype=np.float64)
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+
+    lib = L.load()
+    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", n, cls_h, all_classes, max_batch, profile, beside=per * 4)
+
+    with gp.open():
+        xs = gp.xs
+        taps_d, rad_d, w_d = torch.from_numpy(taps).to(gp.dev), torch.from_numpy(radius).to(gp.dev), torch.from_numpy(w).to(gp.dev)
+        gp.clean()
+        acc, = gp.sums(1)
+        kept = {}                                                   # the chunk's D, written beside its rows, read by its accumulates
+
+        def write(row0, rows):
+            r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=gp.dev)
+            kept["D"] = torch.empty_like(r)
+            _blur_rows(lib, xs, taps_d, rad_d, taps.shape[2], r, kept["D"], n, axes, 0, row0, rows)
+            return r
+
+        gp.sweep(write, lambda g, slot, row0, rows: L.check(lib.bx_blurig_accumulate(
+            _p(g), _p(kept["D"]), _p(w_d), _p(acc), B, n, per, Kc, slot, row0, rows, _stream()), "bx_blurig_accumulate"))
+        with gp.lap("finish"):
+            values = gp.empty(*xs.shape[1:])
+            amap = gp.empty(*xs.shape[2:]) if gp.input_is_spec else None
+            L.check(lib.bx_expgrad_finish(_p(acc), _p(values), _p(amap), B * Kc, gp.Cc, gp.HW, 1, _stream()), "bx_expgrad_finish")
+            if amap is None:                                        # an EEG input has one channel: the map is the values
+                amap = values[:, :, 0]
+            last = torch.empty_like(xs)                             # the end of the path: x blurred with sigma_n
+            _blur_rows(lib, xs, torch.from_numpy(end_taps).to(gp.dev), torch.from_numpy(end_radius).to(gp.dev), end_taps.shape[2], last, None, 1, axes, 0, 0, B)
+            with torch.no_grad():
+                endpoint = _fuse(model, multimodal, gp.input_is_spec, net(last), gp.fixed).float().contiguous()
+            total = torch.empty(B, Kc, dtype=torch.float64, device=gp.dev)
+            L.check(lib.bx_blurig_sum_rows(_p(values), _p(total), B * Kc, per, _stream()), "bx_blurig_sum_rows")
+            drop = gp.out.double() - endpoint.double()
+            delta = total - (drop if all_classes else drop.gather(1, gp.classes.long()[:, None]))
+            if not all_classes:
+                delta = delta[:, 0]
+    return gp.result(return_parts, BlurIGResult, amap, values, endpoint, delta, sigmas, n, max_sigma, sqrt, eps, axes)
 
 # ------------------------------------------------------------------------------------------------
 # Infidelity and max-sensitivity (Yeh et al., NeurIPS 2019; Captum's metrics.infidelity and metrics.sensitivity_max): how well an
