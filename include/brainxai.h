@@ -948,6 +948,52 @@ int bx_blurig_accumulate(const float* g, const float* deriv, const double* w, do
 /* out[r] = sum_t (double)v[r,t] for v fp32 [R,L], out fp64 [R]: the sum behind delta, one row per (sample, class), in the order of
  * bx_mean_abs_rows -- 64 partial sums over t = l, l + 64, ... (ascending), added by a fixed pairwise tree.  R * L < 2^31. */
 int bx_blurig_sum_rows(const float* v, double* out, int R, int L, bxStream stream);
+/* ---- Spectral attributions of the EEG input: amplitude gradients and spectral occlusion (Schirrmeister et al., Hum. Brain Mapp. 2017;
+ * braindecode's compute_amplitude_gradients).  For a row x[0..T) (one electrode of one sample), F = T / 2 + 1 bins (integer division):
+ *   Transform:  X_f = sum_t x_t (cos th - i sin th),  th = 2 pi ((f t) mod T) / T,  f = 0..F-1.
+ *   Weights:    c_0 = 1; c_{T/2} = 1 when T is even; c_f = 2 otherwise (the bins a real signal's spectrum holds twice).
+ *   Phase:      u_f = X_f / |X_f|, and 1 + 0i when X_f is exactly zero (numpy's angle(0) = 0).
+ *   With g the gradient of the explained log-probability F_c by the row and G its transform:
+ *     amplitude gradient    dF_c/dA_f     = (c_f / T) Re(u_f conj(G_f))    -- autograd through irfft(A e^{i phi}) by A, braindecode's
+ *     gradient x amplitude  A_f dF_c/dA_f = (c_f / T) Re(X_f conj(G_f))    -- per electrode it sums over f to sum_t g_t x_t (Parseval)
+ *   Path form (steps = n > 1): g = sum_k w_k dF_c/dx(alpha_k x) with (alpha, w) the n Gauss-Legendre nodes and weights on [0, 1]
+ *     (integrated_gradients' ig_nodes); the points alpha x share x's phase, so gradient x amplitude is integrated gradients from the
+ *     zero-amplitude baseline per frequency: sum_{e,f} values = F_c(x) - F_c(0) up to the quadrature error (delta, reported).
+ *   Band component:  y_q[t] = (1 / T) sum_{f in [lo_q, hi_q)} c_f (Re X_f cos th - Im X_f sin th); a band-stopped row is fl32(x - y_q).
+ *   Bands: bin f belongs to (lo, hi) iff lo <= f fs / T < hi, decided on the host in fp64 as lo T <= f fs < hi T: one bin range
+ *     [f_lo, f_hi) per band (fs absent: edges in cycles per sample).  A band without a bin sums to 0 and stops nothing.
+ * The twiddle table tw fp64 [T,2] = (cos, sin)(2 pi j / T), j = 0..T-1, is computed on the host in fp64 and lives on the device; the
+ * kernels walk j = (f t) mod T by integer add-and-wrap: no sincos and no fp32 angle on the device.  Every sum is fp64, one fma per
+ * term, in an order that depends on T or the bin range alone (ascending t, ascending f); no atomics.  1 <= T <= BX_SPECTRAL_MAX_T
+ * (BX_EUNSUPPORTED above); a workgroup transforms 8 rows at once, one table entry serving all of them: the table is staged in LDS
+ * (T <= 4096; read from global memory above), the row values, which are the same for every lane of a wave, come through the scalar cache.  Every entry point refuses its limits with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+enum { BX_SPECTRAL_AMPLITUDE_GRADIENT = 0, BX_SPECTRAL_GRADIENT_X_AMPLITUDE = 1 };
+enum { BX_SPECTRAL_CELLS_BAND = 0, BX_SPECTRAL_CELLS_ELECTRODE_BAND = 1 };
+#define BX_SPECTRAL_MAX_T 8192
+/* x fp32 [R,T] -> re, im fp64 [R,F].  A workgroup owns (8 rows, 256 bins), a thread one bin of each, ascending t.  Per bin
+ * |error| <= (T + 4) 2^-53 sum_t |x_t|; a zero row gives exactly 0.  R * T < 2^31. */
+int bx_rdft_rows(const float* x, const double* tw, double* re, double* im, int R, int T, bxStream stream);
+/* The running sum of one class slot: acc[b,slot,e] += w[k] * (double)g[j - row0, e] over the rows j = b * n + k of the call that belong
+ * to sample b, in ascending k (the product and the sum are one fp64 rounding each).  acc fp64 [B,Kc,per] (Kc <= 32; the other slots are
+ * not touched), w fp64 [n] on the device, g fp32 [rows,per].  Rows are numbered globally, sample-major; a call handles rows
+ * [row0, row0 + rows), which may start and end inside a sample.  One thread per element, no atomics: no bit depends on how the rows
+ * were split into calls. */
+int bx_spectral_accumulate(const float* g, const double* w, double* acc, int B, int n, int per, int Kc, int slot, int row0, int rows, bxStream stream);
+/* values fp32 [B,Kc,Chans,F] from the fp64 gradient sums gsum [B,Kc,Chans,T] and X = (re, im) fp64 [B*Chans,F] of the samples, by
+ * `kind`.  G_f is computed in registers with the transform body of bx_rdft_rows and never stored; the value is formed in fp64 and
+ * rounded to fp32 once. */
+int bx_spectral_values(const double* gsum, const double* re, const double* im, const double* tw, float* values, int B, int Kc, int Chans, int T, int kind,
+                       bxStream stream);
+/* out fp64 [R,nb]: out[r,q] = sum of (double)values[r,f] over f in [bins[q,0], bins[q,1]) in ascending f, from +0; bins int32 [nb,2] on
+ * the device (ranges are clamped to 0 <= lo <= hi <= F).  values fp32 [R,F]. */
+int bx_band_sum(const float* values, const int* bins, double* out, int R, int F, int nb, bxStream stream);
+/* The rows of spectral occlusion in the EEG layout: out fp32 [B*n,1,Chans,T], rows (b, j) for j in [n0, n0 + n), sample-major.
+ * cells = BAND: N = nb, row j = q has every electrode band-stopped.  cells = ELECTRODE_BAND: N = nb * Chans, row j = q * Chans + e has
+ * electrode e band-stopped; every other electrode is x bit for bit, zero signs included, as is every electrode for a band without a
+ * bin.  x fp32 [B,1,Chans,T], (re, im) fp64 [B*Chans,F] its transform.  y_q is summed in fp64 in ascending f, divided by T and
+ * subtracted from double(x); the result is rounded to fp32 once. */
+int bx_bandstop_rows(const float* x, const double* re, const double* im, const double* tw, const int* bins, float* out, int B, int Chans, int T, int nb,
+                     int cells, int n0, int n, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

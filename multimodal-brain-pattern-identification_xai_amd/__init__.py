@@ -13,6 +13,8 @@ from .explain import (GradCamSweep, expected_gradients, generate_saliency_maps, 
                       GradientShapResult, gradient_shap, channel_importance, GradientExplainer,
                       SmoothGradResult, smooth_grad, smooth_grad_noise,
                       BlurIGResult, blur_ig, blur_path, gaussian_blur,
+                      SpectralGradientsResult, spectral_gradients, SpectralOcclusionResult, spectral_occlusion, eeg_spectrum, band_sums,
+                      spectral_band_bins, spectral_twiddles, CLINICAL_BANDS,
                       InfidelityResult, infidelity, SensitivityResult, sensitivity_max)
 from .data import (EEGStacker, stack_eeg, EEGMontageStacker, stack_eeg_montage,          # noqa: F401
                    SpectrogramPreprocessor, preprocess_spectrograms, SpectrogramRegionStacker, stack_spectrogram_regions, StagingRing)                                        # noqa: F401

@@ -22,6 +22,9 @@ BX_CAM_GRADCAM, BX_CAM_GRADCAM_PP, BX_CAM_LAYERCAM = 0, 1, 2
 BX_SCORECAM_PROB, BX_SCORECAM_INCREASE = 0, 1
 BX_BLUR_AXES_HW, BX_BLUR_AXES_H, BX_BLUR_AXES_W = 0, 1, 2
 BX_BLUR_MAX_RADIUS = 16384
+BX_SPECTRAL_AMPLITUDE_GRADIENT, BX_SPECTRAL_GRADIENT_X_AMPLITUDE = 0, 1
+BX_SPECTRAL_CELLS_BAND, BX_SPECTRAL_CELLS_ELECTRODE_BAND = 0, 1
+BX_SPECTRAL_MAX_T = 8192
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -217,6 +220,11 @@ SIGNATURES = {
     "bx_blur_rows": (i32, [vp] * 5 + [i32] * 10 + [vp]),
     "bx_blurig_accumulate": (i32, [vp] * 4 + [i32] * 7 + [vp]),
     "bx_blurig_sum_rows": (i32, [vp, vp, i32, i32, vp]),
+    "bx_rdft_rows": (i32, [vp] * 4 + [i32, i32, vp]),
+    "bx_spectral_accumulate": (i32, [vp] * 3 + [i32] * 7 + [vp]),
+    "bx_spectral_values": (i32, [vp] * 5 + [i32] * 5 + [vp]),
+    "bx_band_sum": (i32, [vp] * 3 + [i32] * 3 + [vp]),
+    "bx_bandstop_rows": (i32, [vp] * 6 + [i32] * 7 + [vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

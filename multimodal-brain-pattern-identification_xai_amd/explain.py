@@ -51,6 +51,13 @@
                                  (bx_blur_rows), an fp64 running sum of w * gradient * derivative in fixed step order
                                  (bx_blurig_accumulate), the completeness error from fp64 row sums (bx_blurig_sum_rows).
                                  ``blur_path`` returns the rows, ``gaussian_blur`` is the same kernel as a plain blur.
+* ``spectral_gradients`` / ``spectral_occlusion`` -- the EEG input explained by frequency (Schirrmeister et al. 2017; braindecode's
+                                 compute_amplitude_gradients; not in the reference): a real DFT of any length as a direct fp64 sum over a
+                                 host-made twiddle table (bx_rdft_rows), the path-weighted gradient summed in fp64 in fixed step order
+                                 (bx_spectral_accumulate), amplitude gradient / gradient x amplitude per bin with the gradient's
+                                 transform in registers (bx_spectral_values), band sums (bx_band_sum); forward-only, the drop of the
+                                 score with a band removed, rows written in the EEG layout (bx_bandstop_rows).  ``eeg_spectrum``
+                                 returns the transform, ``band_sums`` reduces any per-bin map.
 * ``infidelity`` / ``sensitivity_max`` -- the two measures of Yeh et al. (NeurIPS 2019; Captum's metrics.infidelity and
                                  metrics.sensitivity_max) for any of those maps: rows minus SmoothGrad's Gaussian stream written in the
                                  model's layout (bx_infidelity_rows_*), the fp64 dot of the same noise with the attribution in fixed
@@ -2831,6 +2838,326 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
             if not all_classes:
                 delta = delta[:, 0]
     return gp.result(return_parts, BlurIGResult, amap, values, endpoint, delta, sigmas, n, max_sigma, sqrt, eps, axes)
+
+
+# ------------------------------------------------------------------------------------------------
+# Spectral attributions of the EEG input: amplitude gradients and spectral occlusion (Schirrmeister et al., Hum. Brain Mapp. 2017;
+# braindecode's compute_amplitude_gradients).  The definition is pinned in include/brainxai.h; tests/spectral_ref.py restates it.
+SpectralGradientsResult = collections.namedtuple("SpectralGradientsResult", "map bands gradient classes out freqs band_bins delta kind steps")
+SpectralGradientsResult.__doc__ = """What ``spectral_gradients(..., return_parts=True)`` returns: ``map`` fp32 [B,Chans,F], with a class axis for
+class_idx='all' (what the plain call returns), ``bands`` fp64 [B(,K),Chans,nb] (the map summed over each band's bins; None without
+bands), ``gradient`` fp32 [B(,K),1,Chans,T] (the time-domain, path-weighted gradient the map was formed from), ``classes`` int64 [B]
+(None for class_idx='all'), ``out`` fp32 [B,K] (the log-probabilities of the clean input), all on the device; ``freqs`` numpy fp64 [F]
+(the bins' frequencies f fs / T, cycles per sample without fs), ``band_bins`` the bands' bin ranges [(f_lo, f_hi), ...] (None without
+bands), ``delta`` fp64 [B] or [B,K] (sum of the map - (F_c(x) - F_c(0)), the completeness error of the quadrature; only for steps > 1
+with kind='gradient_x_amplitude', None otherwise); ``kind`` and ``steps`` as given."""
+SpectralOcclusionResult = collections.namedtuple("SpectralOcclusionResult", "drops scores clean classes band_bins")
+SpectralOcclusionResult.__doc__ = """What ``spectral_occlusion(..., return_parts=True)`` returns: ``drops`` fp32 [B(,K),nb] or [B(,K),Chans,nb] (what
+the plain call returns), ``scores`` fp32 [B,N,K] (the score of every class for every band-stopped input; row j = q for cells='band',
+j = q * Chans + e for 'electrode_band'), ``clean`` fp32 [B,K], ``classes`` int64 [B] (None for class_idx='all'), all on the device;
+``band_bins`` the bands' bin ranges [(f_lo, f_hi), ...]."""
+
+_SPECTRAL_KINDS = {"amplitude_gradient": L.BX_SPECTRAL_AMPLITUDE_GRADIENT, "gradient_x_amplitude": L.BX_SPECTRAL_GRADIENT_X_AMPLITUDE}
+_SPECTRAL_CELLS = {"band": L.BX_SPECTRAL_CELLS_BAND, "electrode_band": L.BX_SPECTRAL_CELLS_ELECTRODE_BAND}
+CLINICAL_BANDS = {"delta": (0.5, 4.0), "theta": (4.0, 8.0), "alpha": (8.0, 13.0), "beta": (13.0, 30.0)}       # Hz
+
+
+def spectral_twiddles(T):
+    """fp64 numpy [T,2]: (cos, sin)(2 pi j / T), j = 0..T-1 -- the table the transform kernels walk.  The angle is reduced to an octant
+    in integers first, so that sin and cos are only evaluated on [0, pi/4]: multiples of a quarter turn are exact (a Nyquist bin has
+    no imaginary part) and every entry is within about one unit in the last place."""
+    j = np.arange(T, dtype=np.int64)
+    octant, rem = np.divmod(8 * j, T)
+    odd = (octant & 1).astype(bool)
+    phi = np.pi * np.where(odd, T - rem, rem).astype(np.float64) / (4.0 * T)
+    c, s = np.cos(phi), np.sin(phi)
+    major, minor = np.where(odd, s, c), np.where(odd, c, s)               # (cos, sin) of the angle folded into the first quadrant
+    quad = octant >> 1
+    cos = np.select([quad == 0, quad == 1, quad == 2], [major, -minor, -major], minor)
+    sin = np.select([quad == 0, quad == 1, quad == 2], [minor, major, -minor], -major)
+    return np.ascontiguousarray(np.stack([cos, sin], axis=1))
+
+
+def _spectral_fs(who, fs):
+    if fs is None:
+        return None
+    if isinstance(fs, bool) or not isinstance(fs, numbers.Real) or not math.isfinite(fs) or fs <= 0:
+        raise ValueError(f"{who}: fs must be a finite number > 0 or None, got {fs!r}")
+    return float(fs)
+
+
+def spectral_band_bins(bands, T, fs=None, who="spectral_band_bins"):
+    """-> [(f_lo, f_hi), ...]: the bin range of every band of a length-T transform.  Bin f belongs to (lo, hi) iff lo <= f fs / T < hi,
+    decided in fp64 as lo T <= f fs < hi T.  bands: 'clinical' (delta, theta, alpha, beta of CLINICAL_BANDS; needs fs in Hz) or a
+    sequence of (lo, hi) with 0 <= lo <= hi; fs None: edges in cycles per sample.  A band may hold no bin."""
+    fs = _spectral_fs(who, fs)
+    if isinstance(bands, str):
+        if bands != "clinical":
+            raise ValueError(f"{who}: unknown bands {bands!r}; use 'clinical' or a sequence of (lo, hi)")
+        if fs is None:
+            raise ValueError(f"{who}: bands='clinical' are in Hz and need fs (the stacker's 19 x 2000 traces are 40 Hz, the montage's 37 x 3000 are 200 Hz)")
+        edges = list(CLINICAL_BANDS.values())
+    else:
+        try:
+            edges = [(lo, hi) for lo, hi in bands]
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: bands must be 'clinical' or a sequence of (lo, hi) pairs, got {bands!r}") from None
+    if not edges:
+        raise ValueError(f"{who}: no bands given")
+    f = np.arange(int(T) // 2 + 1, dtype=np.float64) * (1.0 if fs is None else fs)
+    bins = []
+    for lo, hi in edges:
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) for v in (lo, hi)):
+            raise ValueError(f"{who}: band edges must be finite numbers, got {(lo, hi)!r}")
+        if lo < 0 or hi < lo:
+            raise ValueError(f"{who}: band {(lo, hi)!r} has a negative or inverted edge; use 0 <= lo <= hi")
+        bins.append((int(np.count_nonzero(f < float(lo) * T)), int(np.count_nonzero(f < float(hi) * T))))
+    return bins
+
+
+def _spectral_shape(who, x):
+    """-> (B, Chans, T, F) of an EEG input within the transform's limit."""
+    B = _nonempty(who, x)
+    Chans, T = int(x.shape[2]), int(x.shape[3])
+    if T > L.BX_SPECTRAL_MAX_T:
+        raise ValueError(f"{who}: T = {T}, supported 1..{L.BX_SPECTRAL_MAX_T}")
+    return B, Chans, T, T // 2 + 1
+
+
+def _rdft(lib, xs, tw_d, T):
+    """(re, im) fp64 [R,F] of fp32 rows xs [..., T] (R = the other axes flattened), bx_rdft_rows."""
+    R = xs.numel() // T
+    re = torch.empty(R, T // 2 + 1, dtype=torch.float64, device=xs.device)
+    im = torch.empty_like(re)
+    L.check(lib.bx_rdft_rows(_p(xs), _p(tw_d), _p(re), _p(im), R, T, _stream()), "bx_rdft_rows")
+    return re, im
+
+
+def _band_sum(lib, values, bins_d, nb):
+    F = int(values.shape[-1])
+    out = torch.empty(*values.shape[:-1], nb, dtype=torch.float64, device=values.device)
+    L.check(lib.bx_band_sum(_p(values), _p(bins_d), _p(out), values.numel() // F, F, nb, _stream()), "bx_band_sum")
+    return out
+
+
+def eeg_spectrum(x, *, fs=None):
+    """(re, im, freqs): the real DFT of every electrode's trace, fp64 [B,Chans,F] each on the device, F = T // 2 + 1, and the bins'
+    frequencies (numpy fp64 [F]: f fs / T, cycles per sample without fs) -- X_f = sum_t x_t exp(-2 pi i f t / T), numpy's rfft, by the
+    kernel ``spectral_gradients`` and ``spectral_occlusion`` transform their input with (bx_rdft_rows: a direct fp64 sum in ascending t for
+    any 1 <= T <= 8192, twiddles from a host-made fp64 table).  x: an EEG input [B,1,Chans,T] or [B,Chans,T]."""
+    who = "eeg_spectrum"
+    fs = _spectral_fs(who, fs)
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[1] != 1):
+        raise ValueError(f"{who}: x must be a tensor [B,1,Chans,T] or [B,Chans,T]")
+    x4 = x if x.dim() == 4 else x[:, None]
+    B, Chans, T, F = _spectral_shape(who, x4)
+    if B * Chans * T >= 1 << 31:
+        raise ValueError(f"{who}: B * Chans * T = {B * Chans * T} beyond 32-bit offsets")
+    if not x.is_cuda:
+        raise RuntimeError(f"brainxai.{who}: the transform runs on the GPU; there is no CPU path")
+    lib = L.load()
+    with torch.cuda.device(x.device):
+        xs = x4.detach().to(torch.float32).contiguous()
+        re, im = _rdft(lib, xs, torch.from_numpy(spectral_twiddles(T)).to(xs.device), T)
+    return re.reshape(B, Chans, F), im.reshape(B, Chans, F), np.arange(F, dtype=np.float64) * (1.0 if fs is None else fs) / T
+
+
+def band_sums(map, bands, *, T, fs=None):
+    """fp64 [..., nb]: a map [..., F] of a length-T transform (F = T // 2 + 1; ``spectral_gradients``' map, or anything per bin) summed
+    over each band's bins in ascending f (bx_band_sum).  bands and fs as in ``spectral_band_bins``."""
+    who = "band_sums"
+    if isinstance(T, bool) or not isinstance(T, numbers.Integral) or T < 1:
+        raise ValueError(f"{who}: T must be an int >= 1, got {T!r}")
+    bins = spectral_band_bins(bands, int(T), fs, who)
+    if not isinstance(map, torch.Tensor) or map.dim() < 1 or int(map.shape[-1]) != int(T) // 2 + 1 or map.numel() == 0:
+        raise ValueError(f"{who}: map must be a tensor [..., F] with F = T // 2 + 1 = {int(T) // 2 + 1}")
+    if map.numel() >= 1 << 31:
+        raise ValueError(f"{who}: {map.numel()} elements, beyond 32-bit offsets")
+    if not map.is_cuda:
+        raise RuntimeError(f"brainxai.{who}: the sums are taken on the GPU; there is no CPU path")
+    lib = L.load()
+    with torch.cuda.device(map.device):
+        return _band_sum(lib, map.detach().to(torch.float32).contiguous(), torch.tensor(bins, dtype=torch.int32, device=map.device), len(bins))
+
+
+def spectral_gradients(model, eeg, spec, *, kind="amplitude_gradient", steps=1, fs=None, bands=None, class_idx=None, max_batch=256, return_parts=False):
+    """The EEG input explained by frequency: amplitude gradients (Schirrmeister et al. 2017; braindecode's
+    compute_amplitude_gradients) in closed form.  With X the real DFT of an electrode's trace x (F = T // 2 + 1 bins), u = X / |X| its
+    phase, g the gradient of the explained log-probability F_c by the trace and G its DFT, c_f = 1 for f = 0 and the Nyquist bin, 2
+    otherwise:
+        kind='amplitude_gradient':    dF_c/dA_f     = (c_f / T) Re(u_f conj(G_f))   -- what autograd through irfft(A e^{i phi}) gives by A
+        kind='gradient_x_amplitude':  A_f dF_c/dA_f = (c_f / T) Re(X_f conj(G_f))   -- per electrode it sums over f to sum_t g_t x_t
+    steps = n > 1 replaces g by sum_k w_k dF_c/dx(alpha_k x) with ``ig_nodes(n)``: the path from zero amplitude to x at x's phase, so
+    that gradient x amplitude is integrated gradients per frequency and sums to F_c(x) - F_c(0) up to the quadrature error ``delta``.
+
+    model:       a MultimodalModel (the spectrogram stays the sample's own, its branch runs once per sample); a stand-alone EEGNet /
+                 EEGNetAttentionDeep (spec=None).  eeg [B,1,Chans,T], T <= 8192, any length (no power of two needed).
+    fs, bands:   the sampling rate (Hz) and the bands of ``spectral_band_bins``: 'clinical' or (lo, hi) pairs; with bands the parts
+                 carry the map summed per band.  fs has no default: the stacker's 19 x 2000 traces are 40 Hz, the montage's 200 Hz.
+    class_idx:   None = each sample's arg-max class on the clean input; an int; one class per sample (sequence / tensor [B]); 'all' =
+                 every class, the map gains a class axis [B,K,Chans,F] (K <= 32): one forward pass then serves K backward passes.
+    max_batch:   rows (path points) per pass.  The gradient sum is carried in fp64 between passes, so, given the same gradients, no
+                 bit depends on it.
+    X is transformed once per call (bx_rdft_rows); the path rows are bx_expgrad_rows against a zero background (exactly fl32(alpha x)),
+    the seeds bx_expgrad_seed; every backward pass is followed by one bx_spectral_accumulate (fp64, ascending step order, no atomics);
+    bx_spectral_values transforms the gradient sums in registers and forms the map; bx_band_sum the bands.  All transforms are direct
+    fp64 sums in a fixed order over a host-made twiddle table.  The training flag and every requires_grad are restored on return.
+    Returns the map (device, fp32), or ``SpectralGradientsResult`` with return_parts."""
+    return _spectral_gradients(model, eeg, spec, kind, steps, fs, bands, class_idx, max_batch, return_parts)
+
+
+def _spectral_gradients(model, eeg, spec, kind, steps, fs, bands, class_idx, max_batch, return_parts, profile=None):
+    """``spectral_gradients`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'transform',
+    'rows', 'forward', 'backward', 'accumulate', 'values' -- device events around every phase (tools/spectral_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "spectral_gradients"
+    if not isinstance(kind, str) or kind not in _SPECTRAL_KINDS:
+        raise ValueError(f"{who}: unknown kind {kind!r}; use 'amplitude_gradient' or 'gradient_x_amplitude'")
+    if isinstance(steps, bool) or not isinstance(steps, numbers.Integral):
+        raise ValueError(f"{who}: steps must be an int, got {steps!r}")
+    n = int(steps)
+    if n < 1:
+        raise ValueError(f"{who}: steps = {n} < 1")
+    max_batch = _max_batch(who, max_batch)
+    x = _input_tensor(who, "eeg", eeg, spec)
+    B, Chans, T, F = _spectral_shape(who, x)
+    fs = _spectral_fs(who, fs)
+    band_bins = None if bands is None else spectral_band_bins(bands, T, fs, who)
+    multimodal, K, net = _target_model(who, model, x, spec, False)
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    Kc = K if all_classes else 1
+    per = Chans * T
+    if B * n >= 1 << 31 or B * Kc * per >= 1 << 31:
+        raise ValueError(f"{who}: B * n = {B * n} or B * Kc * per = {B * Kc * per} beyond 32-bit offsets; use fewer samples per call")
+    _need_gpu(who, "the model and its inputs", model, x, spec if multimodal else None)
+
+    lib = L.load()
+    alpha, w = (np.ones(1), np.ones(1)) if n == 1 else ig_nodes(n)
+    gp = _GradPass(model, net, multimodal, K, x, spec, False, n, cls_h, all_classes, max_batch, profile)
+
+    with gp.open():
+        xs, dev = gp.xs, gp.dev
+        tw_d = torch.from_numpy(spectral_twiddles(T)).to(dev)
+        w_d = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
+        alpha_d = torch.from_numpy(np.tile(alpha.astype(np.float32), B)).to(dev)
+        zero_bg = torch.zeros(1, per, dtype=torch.float32, device=dev)
+        idx_d = torch.zeros(B * n, dtype=torch.int32, device=dev)
+        gp.clean()
+        with gp.lap("transform"):
+            re, im = _rdft(lib, xs, tw_d, T)                        # X once per call, whatever the classes
+        acc, = gp.sums(1)
+
+        def write(row0, rows):
+            r = torch.empty(rows, *xs.shape[1:], dtype=torch.float32, device=dev)
+            L.check(lib.bx_expgrad_rows(_p(xs), _p(zero_bg), _p(idx_d), _p(alpha_d), _p(r), B, 1, n, per, row0, rows, _stream()), "bx_expgrad_rows")
+            return r
+
+        gp.sweep(write, lambda g, slot, row0, rows: L.check(lib.bx_spectral_accumulate(
+            _p(g), _p(w_d), _p(acc), B, n, per, Kc, slot, row0, rows, _stream()), "bx_spectral_accumulate"))
+        with gp.lap("values"):
+            amap = gp.empty(Chans, F)
+            L.check(lib.bx_spectral_values(_p(acc), _p(re), _p(im), _p(tw_d), _p(amap), B, Kc, Chans, T, _SPECTRAL_KINDS[kind], _stream()),
+                    "bx_spectral_values")
+        if not return_parts:
+            return amap if all_classes else amap[:, 0]
+        gradient = gp.empty(*xs.shape[1:])
+        L.check(lib.bx_expgrad_finish(_p(acc), _p(gradient), None, B * Kc, 1, per, 1, _stream()), "bx_expgrad_finish")
+        band_vals = None if band_bins is None else _band_sum(lib, amap, torch.tensor(band_bins, dtype=torch.int32, device=dev), len(band_bins))
+        delta = None
+        if n > 1 and kind == "gradient_x_amplitude":
+            with torch.no_grad():                                   # F(0): EEGNet in eval mode treats every row alike, one row serves all samples
+                at_zero = net(torch.zeros_like(xs[:1]))
+                at_zero = _fuse(model, multimodal, False, at_zero.expand(B, -1).contiguous(), gp.fixed).float()
+            total = torch.empty(B, Kc, dtype=torch.float64, device=dev)
+            L.check(lib.bx_blurig_sum_rows(_p(amap), _p(total), B * Kc, Chans * F, _stream()), "bx_blurig_sum_rows")
+            drop = gp.out.double() - at_zero.double()
+            delta = total - (drop if all_classes else drop.gather(1, gp.classes.long()[:, None]))
+        if not all_classes:
+            amap, gradient = amap[:, 0], gradient[:, 0]
+            band_vals = None if band_vals is None else band_vals[:, 0]
+            delta = None if delta is None else delta[:, 0]
+    freqs = np.arange(F, dtype=np.float64) * (1.0 if fs is None else fs) / T
+    return SpectralGradientsResult(amap, band_vals, gradient, None if gp.classes is None else gp.classes.long(), gp.out, freqs, band_bins, delta, kind, n)
+
+
+def spectral_occlusion(model, eeg, spec, *, bands, fs=None, cells="band", class_idx=None, score="prob", max_batch=256, return_parts=False):
+    """Spectral perturbation of the EEG input (Schirrmeister et al. 2017, forward-only): remove one frequency band from the traces and
+    record how much the class score drops.  drops[b,k,q] = S0[b,k] - S[b,j,k], with S0 the score of the clean input and S[b,j,.] that
+    of the input whose band q is stopped: x - y_q, y_q the band's component of x (the inverse transform of X restricted to the band's
+    bins, formed in fp64 and subtracted before one rounding to fp32).
+
+    bands, fs:   the bands of ``spectral_band_bins``: 'clinical' (needs fs in Hz) or (lo, hi) pairs; a band without a bin leaves the
+                 input as it is and drops 0.
+    cells:       'band': every electrode loses the band, drops [B(,K),nb]; 'electrode_band': one electrode at a time,
+                 drops [B(,K),Chans,nb] -- "which band, at which electrode".
+    model, class_idx, max_batch: as ``spectral_gradients``;  score: 'prob' or 'logprob'.
+    (N + 1) * B forward evaluations in eval mode without autograd, N = nb or Chans * nb; the clean input takes the path of the rows, as
+    in ``occlusion``.  X is transformed once (bx_rdft_rows); the rows are written straight in the EEG layout (bx_bandstop_rows: an
+    electrode the row does not select is x bit for bit).  The training flag and every requires_grad are restored on return.  Returns
+    the drops (device, fp32), or ``SpectralOcclusionResult`` with return_parts."""
+    return _spectral_occlusion(model, eeg, spec, bands, fs, cells, class_idx, score, max_batch, return_parts)
+
+
+def _spectral_occlusion(model, eeg, spec, bands, fs, cells, class_idx, score, max_batch, return_parts, profile=None):
+    """``spectral_occlusion`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'transform',
+    'perturb', 'forward'."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "spectral_occlusion"
+    if not isinstance(cells, str) or cells not in _SPECTRAL_CELLS:
+        raise ValueError(f"{who}: unknown cells {cells!r}; use 'band' or 'electrode_band'")
+    if score not in _FAITH_SCORES:
+        raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
+    max_batch = _max_batch(who, max_batch)
+    x = _input_tensor(who, "eeg", eeg, spec)
+    B, Chans, T, F = _spectral_shape(who, x)
+    band_bins = spectral_band_bins(bands, T, fs, who)
+    nb = len(band_bins)
+    N = nb if cells == "band" else nb * Chans
+    multimodal, K, net = _target_model(who, model, x, spec, False)
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    if B * N * K >= 1 << 31 or B * Chans * T >= 1 << 31:
+        raise ValueError(f"{who}: B * N * K = {B * N * K} or B * Chans * T = {B * Chans * T} beyond 32-bit offsets; use fewer samples per call")
+    _need_gpu(who, "the model and its inputs", model, x, spec if multimodal else None)
+
+    lib = L.load()
+    dev = x.device
+    use_logprob = score == "logprob"
+    rp = _RowPass(model, net, multimodal, K, x, spec, False, 0, torch.zeros(1), max_batch, profile)
+
+    with rp.open():
+        xs = rp.xs
+        with rp.lap("forward"):
+            rp.fix_other()
+            clean = torch.empty(B, K, dtype=torch.float32, device=dev)
+            for b0, ng in rp.groups():                              # the clean input takes the path of the rows, in chunks of the same size
+                clean[b0:b0 + ng] = rp.scores(rp.clean_rows(b0, ng), b0, ng, logprob=use_logprob)
+        classes = _class_tensor(cls_h, all_classes, clean, dev)
+        with rp.lap("transform"):
+            tw_d = torch.from_numpy(spectral_twiddles(T)).to(dev)
+            bins_d = torch.tensor(band_bins, dtype=torch.int32, device=dev)
+            re, im = _rdft(lib, xs, tw_d, T)
+
+        def write(b0, ng, n0, n):
+            out = torch.empty(ng * n, 1, Chans, T, dtype=torch.float32, device=dev)
+            L.check(lib.bx_bandstop_rows(_p(xs[b0:b0 + ng]), _p(re[b0 * Chans:(b0 + ng) * Chans]), _p(im[b0 * Chans:(b0 + ng) * Chans]), _p(tw_d), _p(bins_d),
+                                         _p(out), ng, Chans, T, nb, _SPECTRAL_CELLS[cells], n0, n, _stream()), "bx_bandstop_rows")
+            return out
+
+        S = rp.sweep(N, write, logprob=use_logprob)
+        d = clean[:, None, :] - S                                   # [B,N,K]
+        if not all_classes:
+            d = d.gather(2, classes.long().reshape(B, 1, 1).expand(B, N, 1))
+        d = d.permute(0, 2, 1)                                      # [B,K or 1,N]
+        drops = (d if cells == "band" else d.reshape(B, -1, nb, Chans).transpose(2, 3)).contiguous()
+        if not all_classes:
+            drops = drops[:, 0]
+    if not return_parts:
+        return drops
+    return SpectralOcclusionResult(drops, S, clean, None if classes is None else classes.long(), band_bins)
 
 # ------------------------------------------------------------------------------------------------
 # Infidelity and max-sensitivity (Yeh et al., NeurIPS 2019; Captum's metrics.infidelity and metrics.sensitivity_max): how well an
