@@ -13,6 +13,7 @@ import brainxai
 from brainxai import _lib as L
 from brainxai import ops
 from oracle import ref_torch as O
+from tests.cam_ref import cam as cam_fp64
 from tests.eeg_gradcam_setup import bn_nontrivial, rel
 
 pytestmark = pytest.mark.gpu
@@ -23,23 +24,6 @@ METHODS = ("gradcam++", "layercam")
 SPEC_TARGETS = ("spectrogram_model.block5", "spectrogram_model.block5.conv3", "spectrogram_model.block3", "spectrogram_model.block1",
                 "spectrogram_model.block2.conv1")
 EEG_TARGETS = ("eeg_model.conv1", "eeg_model.depthwiseConv", "eeg_model.separableConv")
-
-
-def cam_fp64(A, G, method):
-    """A, G [B, K, *spatial] fp64 -> (raw [B, *spatial], w [B, K] or None, worst conditioning of a counted element, the largest
-    |S G| of a counted element)."""
-    dims = tuple(range(2, A.dim()))
-    if method == "layercam":
-        return (G.clamp_min(0) * A).sum(1), None, 1.0, 0.0
-    S = A.sum(dims, keepdim=True)
-    den = 2 * G ** 2 + S * G ** 3 + EPS
-    alpha = torch.where(G == 0, torch.zeros_like(G), G ** 2 / den)
-    w = (G.clamp_min(0) * alpha).sum(dims)
-    counted = G > 0
-    cond = (den.abs() / (2 * G ** 2 + (S * G ** 3).abs() + EPS))[counted]
-    sg = (S * G).abs()[counted]
-    raw = (w.reshape(*w.shape, *([1] * len(dims))) * A).sum(1)
-    return raw, w, float(cond.min()) if cond.numel() else 1.0, float(sg.max()) if sg.numel() else 0.0
 
 
 def _resolve(model, dotted):

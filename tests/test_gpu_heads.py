@@ -34,6 +34,7 @@ import brainxai
 from brainxai import _lib as L
 from brainxai import explain, ops
 from oracle import ref_torch as O
+from tests.cam_ref import _fusion_ref, _gen, _lsm, _uniform          # (the fp64 LogSoftmax whose backward does not cancel lives there)
 from tests.golden_util import grad_close, matched_oracle, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -70,39 +71,6 @@ def _cmp_bf16(got, want, head, n, label):
     bad = ~(d <= ulp + OP_TOL * scale)                             # (NaN fails)
     assert not bool(bad.any()), f"{head} N={n} {label}: {int(bad.sum())} elements beyond one bf16 ulp (worst {float((d - ulp).max()) / scale:.3e})"
     _note(head + " (bf16: beyond 1 ulp)", n, float((d - ulp).clamp_min(0).max()) / scale)
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _uniform(shape, bound, g):
-    return (torch.rand(shape, generator=g) * 2 - 1) * bound
-
-
-class _LogSoftmax64(torch.autograd.Function):
-    """LogSoftmax over dim 1 whose backward forms 1 - p_n as the sum of the OTHER probabilities:
-        dz_n = dy_n sum_{j != n} p_j - p_n sum_{j != n} dy_j.
-    torch's own backward, dy - p sum(dy), cancels in fp64 too: once p_n > 1 - 1e-16 it returns dz_n = 0 where the true value is
-    -sum_{j != n} p_j (the confident regime below reaches p_n = 1 - e^-45, and a two-class model at 1 - 1.6e-6 already costs the
-    fp32 oracle 1e-2 of its Grad-CAM weights)."""
-
-    @staticmethod
-    def forward(ctx, z):
-        y = z - torch.logsumexp(z, dim=1, keepdim=True)
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (y,) = ctx.saved_tensors
-        p = y.exp()
-        off = 1.0 - torch.eye(y.shape[1], dtype=y.dtype)                 # off[n, j] = (j != n)
-        return dy * (p @ off.T) - p * (dy @ off.T)
-
-
-def _lsm(z):
-    return _LogSoftmax64.apply(z)
 
 
 def _upstream(regime, B, N, c0, g):
@@ -269,10 +237,6 @@ def _fusion_case(B, N, Hd, regime, seed):
     if regime == "confident":
         _confident(_fusion_ref, (e, s, w1, b1, w2, b2), 5, c0)
     return (e, s, w1, b1, w2, b2), _upstream(regime, B, N, c0, g)
-
-
-def _fusion_ref(e, s, w1, b1, w2, b2):
-    return _lsm(torch.relu(torch.cat((e, s), 1) @ w1.T + b1) @ w2.T + b2)
 
 
 def _fusion_hds(N):

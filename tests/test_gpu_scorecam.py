@@ -25,7 +25,9 @@ from brainxai import explain as X
 from brainxai import ops
 from oracle import ref_torch as O
 from tests import perturb_gpu as PG
+from tests import cam_ref
 from tests import scorecam_ref as S
+from tests.attrib_cases import RESIZE_BOUND
 from tests.perturb_gpu import DEV, TOL
 
 pytestmark = pytest.mark.gpu
@@ -259,6 +261,15 @@ def _nchw(A):
     return A.float().permute(0, 3, 1, 2).contiguous().cpu().numpy()
 
 
+def _against_fp64_resize(cam, low, size, label):
+    """The up-sampled map against the fp64 resize of the low-resolution one (tests/cam_ref.py), at the bound of
+    tests/test_gpu_attrib_kernels.py::test_resize_bilinear: the comparison beside it is the kernel against itself."""
+    want = cam_ref.resize(low.cpu().numpy(), *size)
+    err = float(np.abs(cam.cpu().numpy().astype(np.float64) - want).max()) / (float(low.abs().max()) + 1e-30)
+    print(f"score_cam {label}: up-sampled map {err:.2e} of max|map| from the fp64 resize (bound {RESIZE_BOUND:.1e})")
+    assert tuple(cam.shape) == want.shape and err <= RESIZE_BOUND
+
+
 @functools.lru_cache(maxsize=None)
 def _mm_setting(dt=torch.float32):
     ref_model, mine = PG.scaled_multimodal(dt)
@@ -291,6 +302,7 @@ def test_spectrogram_targets_against_fp64_oracle(target):
     _compare(res.raw, ref, "prob", target)
     low = brainxai.score_cam(mine, e, s, target, upsample=False)
     assert torch.equal(low, res.raw.clamp_min(0)) and torch.equal(res.cam, X.resize_bilinear(low, (64, 128)) if (h, w) != (64, 128) else low)
+    _against_fp64_resize(res.cam, low, (64, 128), target)
     # the paper's weighting: P_base exceeds every P[k, c] on these inputs, so the map is compared before the ReLU
     inc = brainxai.score_cam(mine, e, s, target, weights="increase", relu=False, upsample=False, return_parts=True)
     assert torch.equal(inc.probs, res.probs) and torch.equal(inc.cam, inc.raw)
@@ -331,6 +343,7 @@ def test_eeg_targets_stand_alone_against_fp64_oracle(target):
     _compare(res.raw.reshape(2, 1, w), ref, "prob", f"EEGNet {target}")
     low = brainxai.score_cam(mine, xe.to(DEV), None, target, upsample=False)
     assert tuple(low.shape) == (2, 1, w) and torch.equal(res.cam, X.resize_bilinear(low, (1, 2000)) if w != 2000 else low)
+    _against_fp64_resize(res.cam, low, (1, 2000), f"EEGNet {target}")
     inc = brainxai.score_cam(mine, xe.to(DEV), None, target, weights="increase", relu=False, return_parts=True, max_batch=5)
     assert torch.equal(inc.probs, res.probs)
     _compare(inc.raw.reshape(2, 1, w), ref, "increase", f"EEGNet {target}")
