@@ -1,14 +1,13 @@
 // Blur Integrated Gradients (Xu, Venugopalan, Sundararajan, CVPR 2020; PAIR's saliency.BlurIG) and the Gaussian blur behind it: the rows
 // X_i = blur_{sigma_i}(x) of every (sample, step) pair and the scale-space derivative D_i beside them, written in one launch by
-// separable filters whose taps the host computes; the fp64 running sum of w_i * gradient * D_i in fixed step order; and the fp64 row
-// sums behind the completeness error.  The forward and backward passes between rows and accumulate are the model's own kernels; the
-// one-hot gradient seeds are bx_expgrad_seed and the finish is bx_expgrad_finish with n = 1.  See include/brainxai.h for the
-// definition, the tap table and each entry point.
+// separable filters whose taps the host computes; the fp64 running sum of w_i * gradient * D_i in fixed step order and the fp64 row
+// sums behind the completeness error (the walk and the wave row sum of sample_rows.h).  The forward and backward passes between rows
+// and accumulate are the model's own kernels; the one-hot gradient seeds are bx_expgrad_seed and the finish is bx_expgrad_finish with
+// n = 1.  See include/brainxai.h for the definition, the tap table and each entry point.
 // The file is compiled with -ffp-contract=off: every filter step is an explicit fmaf in ascending tap order, and the accumulate's
 // g * D (exact), w * (g * D) and the sum are separate fp64 roundings, so that a numpy restatement matches the sums bit for bit.
-#include "bx_common.h"
+#include "sample_rows.h"
 
-#define BI_MAX_K 32
 #define BI_THREADS 128
 #define BI_LDS_LIMIT 65536
 
@@ -353,7 +352,7 @@ extern "C" int bx_blur_rows(const float* x, const float* taps, const int* radius
               BI_LDS_LIMIT);
   }
   BX_REQUIRE(x && taps && radius && rows_out, "bx_blur_rows: null pointer");
-  const bool v4 = W % 4 == 0 && ((((uintptr_t)x | (uintptr_t)rows_out | (uintptr_t)deriv_out) & 15) == 0);
+  const bool v4 = sample_vec4(W, x, rows_out, deriv_out);
   const BiLaunch L = {x, taps, radius, rows_out, deriv_out, {n, C, H, W, SW, tap_width, RC, per_sample, row0}, rows, axes, lds, (hipStream_t)stream};
   if (v4 && deriv_out) bi_launch<4, true>(L);
   else if (v4) bi_launch<4, false>(L);
@@ -363,83 +362,35 @@ extern "C" int bx_blur_rows(const float* x, const float* taps, const int* radius
   return BX_OK;
 }
 
-// ---- the running sum --------------------------------------------------------------------------------------------------------------------
-// A thread owns V consecutive elements of one sample (blockIdx.y walks the samples the call touches) and loops over that sample's steps
-// inside the call in ascending i.  g * D of two floats is exact in fp64; w[i] * (g * D) and the sum are one fp64 rounding each.  One
-// thread per element and no atomics: the bits are a function of the inputs alone, and a sum carried between calls equals one call's.
-#define BI_ACC_THREADS 64
-template <int V>
-__global__ __launch_bounds__(BI_ACC_THREADS) void k_blurig_accumulate(const float* __restrict__ g, const float* __restrict__ deriv, const double* __restrict__ w,
-                                                                      double* __restrict__ acc, int n, int per, int Kc, int slot, int row0, int rows, int b_first,
-                                                                      int b_count) {
-  const int e = (blockIdx.x * BI_ACC_THREADS + threadIdx.x) * V;
-  if (e >= per) return;
-  for (int bi = blockIdx.y; bi < b_count; bi += gridDim.y) {
-    const int b = b_first + bi;
-    const int j0 = b * n > row0 ? b * n : row0;
-    const int j1 = (b + 1) * n < row0 + rows ? (b + 1) * n : row0 + rows;
-    const size_t at = ((size_t)b * Kc + slot) * per + e;
-    double s[V];
-#pragma unroll
-    for (int q = 0; q < V; ++q) s[q] = acc[at + q];
-    for (int j = j0; j < j1; ++j) {
-      float gv[V], dv[V];
-      const size_t o = (size_t)(j - row0) * per + e;
-      if (V == 4) { ld4(g, o, gv); ld4(deriv, o, dv); } else { gv[0] = g[o]; dv[0] = deriv[o]; }
-      const double wi = w[j - b * n];
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        const double gd = (double)gv[q] * (double)dv[q];
-        const double term = wi * gd;
-        s[q] += term;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < V; ++q) acc[at + q] = s[q];
+// ---- the running sum: w[i] * (g * D).  g * D of two floats is exact in fp64; w[i] * (g * D) and the sum are one fp64 rounding each. ---------
+struct BiTerm {
+  const float* deriv; const double* w; double* acc;
+  static constexpr int SUMS = 1;
+  template <int V> struct Keep {};
+  template <int V> struct Row { float d[V]; double w; };
+  double* sum(int) const { return acc; }
+  template <int V> __device__ __forceinline__ void sample(Keep<V>&, int, int, int) const {}
+  template <int V> __device__ __forceinline__ void row(Row<V>& r, int, int i, int rr, int per, int e) const {
+    sample_ld<V>(deriv + (size_t)rr * per + e, r.d);
+    r.w = w[i];
   }
-}
+  template <int V> __device__ __forceinline__ void add(double (&s)[1][V], int q, const Keep<V>&, float g, const Row<V>& r) const {
+    const double gd = (double)g * (double)r.d[q];
+    const double term = r.w * gd;
+    s[0][q] += term;
+  }
+};
 extern "C" int bx_blurig_accumulate(const float* g, const float* deriv, const double* w, double* acc, int B, int n, int per, int Kc, int slot, int row0, int rows,
                                     bxStream stream) {
-  BX_REQUIRE(B > 0 && n > 0 && per > 0, "bx_blurig_accumulate: bad shape B=%d n=%d per=%d", B, n, per);
-  BX_REQUIRE((long long)B * n < (1ll << 31) && (long long)B * per < (1ll << 31), "bx_blurig_accumulate: B * n or B * per beyond 32-bit offsets");
-  BX_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= (long long)B * n, "bx_blurig_accumulate: rows row0 = %d, rows = %d outside 0..B * n = %d", row0,
-             rows, B * n);
-  BX_REQUIRE((long long)rows * per < (1ll << 31), "bx_blurig_accumulate: rows * per beyond 32-bit offsets");
-  BX_REQUIRE(Kc >= 1 && slot >= 0 && slot < Kc, "bx_blurig_accumulate: class slot %d outside 0..Kc = %d", slot, Kc);
-  if (Kc > BI_MAX_K) BX_FAIL(BX_EUNSUPPORTED, "bx_blurig_accumulate: %d classes, supported 1..%d", Kc, BI_MAX_K);
-  BX_REQUIRE((long long)B * Kc * per < (1ll << 31), "bx_blurig_accumulate: B * Kc * per beyond 32-bit offsets");
-  BX_REQUIRE(g && deriv && w && acc, "bx_blurig_accumulate: null pointer");
-  BX_REQUIRE((((uintptr_t)acc | (uintptr_t)w) & 7) == 0, "bx_blurig_accumulate: w and acc must be 8-byte aligned");
-  const int b_first = row0 / n, b_count = (row0 + rows - 1) / n - b_first + 1;
-  const int gy = b_count < 65535 ? b_count : 65535;
-  if (per % 4 == 0 && ((((uintptr_t)g | (uintptr_t)deriv) & 15) == 0))
-    hipLaunchKernelGGL((k_blurig_accumulate<4>), dim3(bx_ceil_div(per / 4, BI_ACC_THREADS), gy), dim3(BI_ACC_THREADS), 0, (hipStream_t)stream, g, deriv, w, acc, n,
-                       per, Kc, slot, row0, rows, b_first, b_count);
-  else
-    hipLaunchKernelGGL((k_blurig_accumulate<1>), dim3(bx_ceil_div(per, BI_ACC_THREADS), gy), dim3(BI_ACC_THREADS), 0, (hipStream_t)stream, g, deriv, w, acc, n,
-                       per, Kc, slot, row0, rows, b_first, b_count);
-  BX_CHECK_LAUNCH("bx_blurig_accumulate");
-  return BX_OK;
+  const char* who = "bx_blurig_accumulate";
+  SAMPLE_TRY(sample_rows_ok(who, B, n, per, row0, rows));
+  SAMPLE_TRY(sample_slot_ok(who, B, per, Kc, slot));
+  BX_REQUIRE(g && deriv && w && acc, "%s: null pointer", who);
+  BX_REQUIRE((((uintptr_t)acc | (uintptr_t)w) & 7) == 0, "%s: w and acc must be 8-byte aligned", who);
+  return sample_accumulate<64, 4, 1>(who, stream, g, sample_vec4(per, g, deriv), BiTerm{deriv, w, acc}, n, per, Kc, slot, row0, rows);
 }
 
-// ---- the sum of a row -------------------------------------------------------------------------------------------------------------------
-// One wave per row, whatever the launch (the order of bx_mean_abs_rows): lane l adds v[r,t] for t = l, l + 64, ... in ascending t in
-// fp64, the 64 lane sums are added by the xor butterfly (offsets 32, 16, .., 1: the same tree in every lane).
-__global__ __launch_bounds__(256) void k_blurig_sum_rows(const float* __restrict__ v, double* __restrict__ out, int R, int L) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (r >= R) return;                                          // wave-uniform
-  const float* row = v + (size_t)r * L;
-  double s = 0.0;
-  for (int t = lane; t < L; t += 64) s += (double)row[t];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) out[r] = s;
-}
+// ---- the sum of a row: the wave row sum of sample_rows.h, in the order of bx_mean_abs_rows -----------------------------------------------
 extern "C" int bx_blurig_sum_rows(const float* v, double* out, int R, int L, bxStream stream) {
-  BX_REQUIRE(R > 0 && L > 0, "bx_blurig_sum_rows: bad shape R=%d L=%d", R, L);
-  BX_REQUIRE((long long)R * L < (1ll << 31), "bx_blurig_sum_rows: R * L beyond 32-bit offsets");
-  BX_REQUIRE(v && out, "bx_blurig_sum_rows: null pointer");
-  BX_REQUIRE(((uintptr_t)out & 7) == 0, "bx_blurig_sum_rows: out must be 8-byte aligned");
-  hipLaunchKernelGGL(k_blurig_sum_rows, dim3(bx_ceil_div(R, 4)), dim3(256), 0, (hipStream_t)stream, v, out, R, L);
-  BX_CHECK_LAUNCH("bx_blurig_sum_rows");
-  return BX_OK;
+  return sample_row_sum<false>("bx_blurig_sum_rows", stream, v, out, R, L);
 }

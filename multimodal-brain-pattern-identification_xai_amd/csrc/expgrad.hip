@@ -1,39 +1,20 @@
 // Expected gradients (SHAP's GradientExplainer; Erion et al. 2021), batched: the interpolants of every (sample, draw) pair written in one
-// launch, the fp64 running sum of (x - background) * gradient in fixed draw order, the mean and the channel-summed map, the one-hot
-// gradient seeds of sample-major rows and the reference's mean |.| per electrode.  The forward and backward passes between rows and
-// accumulate are the model's own kernels.  See include/brainxai.h for the definition and the contract of each entry point.
+// launch, the fp64 running sum of (x - background) * gradient in fixed draw order (the walk of sample_rows.h), the mean and the
+// channel-summed map, the one-hot gradient seeds of sample-major rows and the reference's mean |.| per electrode.  The forward and
+// backward passes between rows and accumulate are the model's own kernels.  See include/brainxai.h for each entry point.
 // The file is compiled with -ffp-contract=off: d = x - bg, alpha * d and bg + (alpha * d) are three separate fp32 roundings, so that a
 // numpy float32 restatement matches the rows bit for bit.
-#include "bx_common.h"
+#include "sample_rows.h"
 
-#define EG_MAX_K 32
-
-// global row j = b * n + k (sample-major); a call handles rows [row0, row0 + rows), which may start and end inside a sample
+// the window of sample_rows_ok, and the background's Nb rows
 static int eg_rows_ok(const char* who, int B, int Nb, int n, int per, int row0, int rows) {
   BX_REQUIRE(B > 0 && Nb > 0 && n > 0 && per > 0, "%s: bad shape B=%d Nb=%d n=%d per=%d", who, B, Nb, n, per);
   BX_REQUIRE((long long)B * n < (1ll << 31) && (long long)B * per < (1ll << 31) && (long long)Nb * per < (1ll << 31),
              "%s: B * n, B * per or Nb * per beyond 32-bit offsets", who);
-  BX_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= (long long)B * n, "%s: rows row0 = %d, rows = %d outside 0..B * n = %d", who, row0, rows,
-             B * n);
-  BX_REQUIRE((long long)rows * per < (1ll << 31), "%s: rows * per beyond 32-bit offsets", who);
-  return BX_OK;
-}
-static inline bool eg_vec4(int per, const void* a, const void* b, const void* c, const void* d) {
-  return per % 4 == 0 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0);
+  SAMPLE_TRY(sample_window_ok(who, B, n, row0, rows));
+  return sample_out_ok(who, rows, per);
 }
 __device__ __forceinline__ int eg_clamp(int v, int hi) { return v < 0 ? 0 : (v >= hi ? hi - 1 : v); }
-
-template <int V> struct EgVec;
-template <> struct EgVec<1> {
-  float v[1];
-  __device__ __forceinline__ void load(const float* p) { v[0] = p[0]; }
-  __device__ __forceinline__ void store(float* p) const { p[0] = v[0]; }
-};
-template <> struct EgVec<4> {
-  float v[4];
-  __device__ __forceinline__ void load(const float* p) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
 
 // ---- the interpolants -------------------------------------------------------------------------------------------------------------------
 // A thread owns V consecutive elements of a row and walks the rows of its workgroup row; every element of every row is written once.
@@ -46,25 +27,26 @@ __global__ __launch_bounds__(256) void k_expgrad_rows(const float* __restrict__ 
     const int j = row0 + r, b = j / n;
     const int i = eg_clamp(idx[j], Nb);
     const float a = alpha[j];
-    EgVec<V> xv, bv, o;
-    xv.load(x + (size_t)b * per + e);
-    bv.load(bg + (size_t)i * per + e);
+    float xv[V], bv[V], o[V];
+    sample_ld<V>(x + (size_t)b * per + e, xv);
+    sample_ld<V>(bg + (size_t)i * per + e, bv);
 #pragma unroll
     for (int q = 0; q < V; ++q) {
-      const float d = xv.v[q] - bv.v[q];
+      const float d = xv[q] - bv[q];
       const float ad = a * d;
-      o.v[q] = bv.v[q] + ad;
+      o[q] = bv[q] + ad;
     }
-    o.store(out + (size_t)r * per + e);
+    float* dst = out + (size_t)r * per + e;
+    if (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[V > 1 ? 1 : 0], o[V > 2 ? 2 : 0], o[V > 3 ? 3 : 0]);
+    else dst[0] = o[0];
   }
 }
 extern "C" int bx_expgrad_rows(const float* x, const float* bg, const int* idx, const float* alpha, float* out, int B, int Nb, int n, int per, int row0,
                                int rows, bxStream stream) {
-  const int rc = eg_rows_ok("bx_expgrad_rows", B, Nb, n, per, row0, rows);
-  if (rc) return rc;
+  SAMPLE_TRY(eg_rows_ok("bx_expgrad_rows", B, Nb, n, per, row0, rows));
   BX_REQUIRE(x && bg && idx && alpha && out, "bx_expgrad_rows: null pointer");
   const int gy = rows < 65535 ? rows : 65535;
-  if (eg_vec4(per, x, bg, out, nullptr))
+  if (sample_vec4(per, x, bg, out))
     hipLaunchKernelGGL((k_expgrad_rows<4>), dim3(bx_ceil_div(per / 4, 256), gy), dim3(256), 0, (hipStream_t)stream, x, bg, idx, alpha, out, Nb, n, per, row0, rows);
   else
     hipLaunchKernelGGL((k_expgrad_rows<1>), dim3(bx_ceil_div(per, 256), gy), dim3(256), 0, (hipStream_t)stream, x, bg, idx, alpha, out, Nb, n, per, row0, rows);
@@ -73,76 +55,31 @@ extern "C" int bx_expgrad_rows(const float* x, const float* bg, const int* idx, 
 }
 
 // ---- the running sum --------------------------------------------------------------------------------------------------------------------
-// A thread owns V consecutive elements of one sample (blockIdx.y walks the samples the call touches) and loops over that sample's draws
-// inside the call in ascending k, four rows' loads (gradient and gathered background) in flight.  d is one fp32 rounding; the product of
-// two floats is exact in fp64; the sum is fp64.  One thread per element and no atomics: the bits are a function of the inputs alone, and
-// a sum carried through acc between calls equals the sum of one call.
-#define EG_ACC_THREADS 64
-template <int V>
-__global__ __launch_bounds__(EG_ACC_THREADS) void k_expgrad_accumulate(const float* __restrict__ x, const float* __restrict__ bg, const int* __restrict__ idx,
-                                                                        const float* __restrict__ g, double* __restrict__ acc, int Nb, int n, int per, int Kc,
-                                                                        int slot, int row0, int rows, int b_first, int b_count) {
-  const int e = (blockIdx.x * EG_ACC_THREADS + threadIdx.x) * V;
-  if (e >= per) return;
-  for (int bi = blockIdx.y; bi < b_count; bi += gridDim.y) {
-    const int b = b_first + bi;
-    const int j0 = b * n > row0 ? b * n : row0;
-    const int j1 = (b + 1) * n < row0 + rows ? (b + 1) * n : row0 + rows;
-    EgVec<V> xv;
-    xv.load(x + (size_t)b * per + e);
-    double* ap = acc + ((size_t)b * Kc + slot) * per + e;
-    double s[V];
-#pragma unroll
-    for (int q = 0; q < V; ++q) s[q] = ap[q];
-    int j = j0;
-    for (; j + 4 <= j1; j += 4) {
-      EgVec<V> gv[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        gv[u].load(g + (size_t)(j + u - row0) * per + e);
-        bv[u].load(bg + (size_t)eg_clamp(idx[j + u], Nb) * per + e);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-          const float d = xv.v[q] - bv[u].v[q];
-          s[q] += (double)d * (double)gv[u].v[q];
-        }
-    }
-    for (; j < j1; ++j) {
-      EgVec<V> gv, bv;
-      gv.load(g + (size_t)(j - row0) * per + e);
-      bv.load(bg + (size_t)eg_clamp(idx[j], Nb) * per + e);
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        const float d = xv.v[q] - bv.v[q];
-        s[q] += (double)d * (double)gv.v[q];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < V; ++q) ap[q] = s[q];
+// The term of row j is (x - bg[idx[j]]) * g: a thread keeps its elements of x, the gathered background is loaded beside g.  d is one fp32
+// rounding; the product of two floats is exact in fp64.
+struct EgTerm {
+  const float* x; const float* bg; const int* idx; double* acc; int Nb;
+  static constexpr int SUMS = 1;
+  template <int V> struct Keep { float x[V]; };
+  template <int V> struct Row { float bg[V]; };
+  double* sum(int) const { return acc; }
+  template <int V> __device__ __forceinline__ void sample(Keep<V>& k, int b, int per, int e) const { sample_ld<V>(x + (size_t)b * per + e, k.x); }
+  template <int V> __device__ __forceinline__ void row(Row<V>& r, int j, int, int, int per, int e) const {
+    sample_ld<V>(bg + (size_t)eg_clamp(idx[j], Nb) * per + e, r.bg);
   }
-}
+  template <int V> __device__ __forceinline__ void add(double (&s)[1][V], int q, const Keep<V>& k, float g, const Row<V>& r) const {
+    const float d = k.x[q] - r.bg[q];
+    s[0][q] += (double)d * (double)g;
+  }
+};
 extern "C" int bx_expgrad_accumulate(const float* x, const float* bg, const int* idx, const float* g, double* acc, int B, int Nb, int n, int per, int Kc,
                                      int slot, int row0, int rows, bxStream stream) {
-  const int rc = eg_rows_ok("bx_expgrad_accumulate", B, Nb, n, per, row0, rows);
-  if (rc) return rc;
-  BX_REQUIRE(Kc >= 1 && slot >= 0 && slot < Kc, "bx_expgrad_accumulate: class slot %d outside 0..Kc = %d", slot, Kc);
-  if (Kc > EG_MAX_K) BX_FAIL(BX_EUNSUPPORTED, "bx_expgrad_accumulate: %d classes, supported 1..%d", Kc, EG_MAX_K);
-  BX_REQUIRE((long long)B * Kc * per < (1ll << 31), "bx_expgrad_accumulate: B * Kc * per beyond 32-bit offsets");
-  BX_REQUIRE(x && bg && idx && g && acc, "bx_expgrad_accumulate: null pointer");
-  BX_REQUIRE(((uintptr_t)acc & 7) == 0, "bx_expgrad_accumulate: acc must be 8-byte aligned");
-  const int b_first = row0 / n, b_count = (row0 + rows - 1) / n - b_first + 1;
-  const int gy = b_count < 65535 ? b_count : 65535;
-  if (eg_vec4(per, x, bg, g, nullptr))
-    hipLaunchKernelGGL((k_expgrad_accumulate<4>), dim3(bx_ceil_div(per / 4, EG_ACC_THREADS), gy), dim3(EG_ACC_THREADS), 0, (hipStream_t)stream, x, bg, idx, g,
-                       acc, Nb, n, per, Kc, slot, row0, rows, b_first, b_count);
-  else
-    hipLaunchKernelGGL((k_expgrad_accumulate<1>), dim3(bx_ceil_div(per, EG_ACC_THREADS), gy), dim3(EG_ACC_THREADS), 0, (hipStream_t)stream, x, bg, idx, g, acc,
-                       Nb, n, per, Kc, slot, row0, rows, b_first, b_count);
-  BX_CHECK_LAUNCH("bx_expgrad_accumulate");
-  return BX_OK;
+  const char* who = "bx_expgrad_accumulate";
+  SAMPLE_TRY(eg_rows_ok(who, B, Nb, n, per, row0, rows));
+  SAMPLE_TRY(sample_slot_ok(who, B, per, Kc, slot));
+  BX_REQUIRE(x && bg && idx && g && acc, "%s: null pointer", who);
+  BX_REQUIRE(((uintptr_t)acc & 7) == 0, "%s: acc must be 8-byte aligned", who);
+  return sample_accumulate<64, 4, 4>(who, stream, g, sample_vec4(per, x, bg, g), EgTerm{x, bg, idx, acc, Nb}, n, per, Kc, slot, row0, rows);
 }
 
 // ---- mean and map -----------------------------------------------------------------------------------------------------------------------
@@ -193,23 +130,7 @@ extern "C" int bx_expgrad_seed(const int* classes, int class_all, float* seed, i
   return BX_OK;
 }
 
-// ---- mean |.| per row -------------------------------------------------------------------------------------------------------------------
-// One wave per row, whatever the launch: lane l adds |v[r,t]| for t = l, l + 64, ... in ascending t in fp64, the 64 lane sums are added
-// by the xor butterfly (offsets 32, 16, .., 1: the same tree in every lane), the quotient by L is fp64 and rounded to fp32 once.
-__global__ __launch_bounds__(256) void k_mean_abs_rows(const float* __restrict__ v, float* __restrict__ out, int R, int L) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (r >= R) return;                                          // wave-uniform
-  const float* row = v + (size_t)r * L;
-  double s = 0.0;
-  for (int t = lane; t < L; t += 64) s += (double)fabsf(row[t]);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) out[r] = (float)(s / (double)L);
-}
+// ---- mean |.| per row: the wave row sum of sample_rows.h, |.| and the fp32 mean ------------------------------------------------------------
 extern "C" int bx_mean_abs_rows(const float* v, float* out, int R, int L, bxStream stream) {
-  BX_REQUIRE(R > 0 && L > 0, "bx_mean_abs_rows: bad shape R=%d L=%d", R, L);
-  BX_REQUIRE((long long)R * L < (1ll << 31), "bx_mean_abs_rows: R * L beyond 32-bit offsets");
-  BX_REQUIRE(v && out, "bx_mean_abs_rows: null pointer");
-  hipLaunchKernelGGL(k_mean_abs_rows, dim3(bx_ceil_div(R, 4)), dim3(256), 0, (hipStream_t)stream, v, out, R, L);
-  BX_CHECK_LAUNCH("bx_mean_abs_rows");
-  return BX_OK;
+  return sample_row_sum<true>("bx_mean_abs_rows", stream, v, out, R, L);
 }

@@ -6,7 +6,7 @@
 // point.  The file is compiled with -ffp-contract=off: sigma * z and x - (sigma * z) are two separate fp32 roundings, beta * d - drop two
 // fp64 ones, so that a numpy restatement matches the rows bit for bit given z.
 #include "perturb_rows.h"
-#include "bx_philox.h"
+#include "sample_rows.h"
 
 #define INF_MAX_K 32
 #define INF_DOT_CK 4                    // classes a dot workgroup serves with one pass over the noise (one class alone: 1)
@@ -17,15 +17,6 @@ static int inf_chunk_ok(const char* who, int B, int N, int b0, int nb, int n0, i
   BX_REQUIRE(n0 >= 0 && n >= 1 && (long long)n0 + n <= N, "%s: draws n0 = %d, n = %d outside 0..N = %d", who, n0, n, N);
   return BX_OK;
 }
-// global row j = b * n + k (sample-major); a call handles rows [row0, row0 + rows), which may start and end inside a sample
-static int inf_rows_ok(const char* who, int B, int n, int per, int row0, int rows) {
-  BX_REQUIRE(B > 0 && n > 0 && per > 0, "%s: bad shape B=%d n=%d per=%d", who, B, n, per);
-  BX_REQUIRE((long long)B * n < (1ll << 31) && (long long)B * per < (1ll << 31), "%s: B * n or B * per beyond 32-bit offsets", who);
-  BX_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= (long long)B * n, "%s: rows row0 = %d, rows = %d outside 0..B * n = %d", who, row0, rows,
-             B * n);
-  return BX_OK;
-}
-static inline bool inf_aligned16(const void* a, const void* b) { return ((((uintptr_t)a | (uintptr_t)b) & 15) == 0); }
 
 // ---- infidelity: the rows ---------------------------------------------------------------------------------------------------------------
 // I[i] = fl32(sigma * z) of the cells cell0 .. cell0 + 3 of draw k of sample b.  cell0 % 4 == 0: one Philox block; otherwise the cells
@@ -111,7 +102,7 @@ extern "C" int bx_infidelity_rows_spec(const float* x, const float* sigma, void*
   const int HW = H * W;
   const dim3 grid = perturb_grid(bx_ceil_div(HW, 4), 256, n, nb);
   const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
-  const bool vec = HW % 4 == 0 && inf_aligned16(x, nullptr);
+  const bool vec = sample_vec4(HW, x);
   BX_DISPATCH_DTYPE(dtype, T, {
     if (vec) hipLaunchKernelGGL((k_infid_rows_spec<T, 4>), grid, dim3(256), 0, (hipStream_t)stream, x, sigma, (T*)out, HW, C, per_pixel ? 1 : 0, b0, n0, n, k0, k1);
     else hipLaunchKernelGGL((k_infid_rows_spec<T, 1>), grid, dim3(256), 0, (hipStream_t)stream, x, sigma, (T*)out, HW, C, per_pixel ? 1 : 0, b0, n0, n, k0, k1);
@@ -177,7 +168,7 @@ extern "C" int bx_infidelity_rows_eeg(const float* x, const float* sigma, float*
   const int E = per_column ? Chans : 1, L = per_column ? T : Chans * T;
   const dim3 grid = perturb_grid(bx_ceil_div(L, 4), 256, n, nb);
   const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
-  if (L % 4 == 0 && inf_aligned16(x, out))
+  if (sample_vec4(L, x, out))
     hipLaunchKernelGGL((k_infid_rows_eeg<4>), grid, dim3(256), 0, (hipStream_t)stream, x, sigma, out, E, L, b0, n0, n, k0, k1);
   else
     hipLaunchKernelGGL((k_infid_rows_eeg<1>), grid, dim3(256), 0, (hipStream_t)stream, x, sigma, out, E, L, b0, n0, n, k0, k1);
@@ -240,15 +231,14 @@ __global__ __launch_bounds__(256) void k_infid_dot(const float* __restrict__ phi
 extern "C" int bx_infidelity_dot(const float* phi, const float* sigma, double* d, int B, int n, int cells, int Kc, uint64_t seed, int row0, int rows,
                                  bxStream stream) {
   const char* who = "bx_infidelity_dot";
-  const int rc = inf_rows_ok(who, B, n, cells, row0, rows);
-  if (rc) return rc;
+  SAMPLE_TRY(sample_rows_ok(who, B, n, cells, row0, rows, false));
   BX_REQUIRE(Kc >= 1, "%s: bad class count Kc=%d", who, Kc);
   if (Kc > INF_MAX_K) BX_FAIL(BX_EUNSUPPORTED, "%s: %d classes, supported 1..%d", who, Kc, INF_MAX_K);
   BX_REQUIRE((long long)B * Kc * cells < (1ll << 31) && (long long)B * Kc * n < (1ll << 31), "%s: B * Kc * cells or B * Kc * n beyond 32-bit offsets", who);
   BX_REQUIRE(phi && sigma && d, "%s: null pointer", who);
   BX_REQUIRE(((uintptr_t)d & 7) == 0, "%s: d must be 8-byte aligned", who);
   const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
-  const int vec = cells % 4 == 0 && inf_aligned16(phi, nullptr);
+  const int vec = sample_vec4(cells, phi);
   if (Kc == 1)
     hipLaunchKernelGGL((k_infid_dot<1>), dim3(rows, 1), dim3(256), 0, (hipStream_t)stream, phi, sigma, d, n, cells, Kc, k0, k1, row0, vec);
   else
@@ -304,58 +294,14 @@ extern "C" int bx_infidelity_finish(const double* d, const float* S, const float
 }
 
 // ---- sensitivity_max: the rows -----------------------------------------------------------------------------------------------------------
-// The uniform twin of k_smoothgrad_rows: row = fl32(x + fl32(radius * u)), u in [-1, 1) from word e & 3 of the block of counter
-// (e >> 2, k, b, 1).  x == nullptr: the row is u itself.
-template <int V>
-__global__ __launch_bounds__(256) void k_sens_rows(const float* __restrict__ x, const float* __restrict__ radius, float* __restrict__ out, int n, int per,
-                                                   uint32_t k0, uint32_t k1, int row0, int rows) {
-  const int q = blockIdx.x * 256 + threadIdx.x, e = q * 4;
-  if (e >= per) return;
-  for (int r = blockIdx.y; r < rows; r += gridDim.y) {
-    const int j = row0 + r, b = j / n, k = j - b * n;
-    float u[4];
-    sg_uniform4((uint32_t)q, (uint32_t)k, (uint32_t)b, k0, k1, u);
-    float* o = out + (size_t)r * per + e;
-    const float rad = x ? radius[b] : 0.f;
-    if (V == 4) {
-      if (x) {
-        float xv[4];
-        ld4(x + (size_t)b * per + e, 0, xv);
-        const float d0 = rad * u[0], d1 = rad * u[1], d2 = rad * u[2], d3 = rad * u[3];
-        *reinterpret_cast<float4*>(o) = make_float4(xv[0] + d0, xv[1] + d1, xv[2] + d2, xv[3] + d3);
-      } else {
-        *reinterpret_cast<float4*>(o) = make_float4(u[0], u[1], u[2], u[3]);
-      }
-    } else {
-      const int m = per - e < 4 ? per - e : 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < m) {
-          if (x) {
-            const float dl = rad * u[i];
-            o[i] = x[(size_t)b * per + e + i] + dl;
-          } else {
-            o[i] = u[i];
-          }
-        }
-    }
-  }
-}
+// The noise rows of sample_rows.h with the uniform draw: row = fl32(x + fl32(radius * u)), u in [-1, 1) from word e & 3 of the block of
+// counter (e >> 2, k, b, 1).  x == nullptr: the row is u itself.
 extern "C" int bx_sensitivity_rows(const float* x, const float* radius, float* out, int B, int n, int per, uint64_t seed, int row0, int rows,
                                    bxStream stream) {
   const char* who = "bx_sensitivity_rows";
-  const int rc = inf_rows_ok(who, B, n, per, row0, rows);
-  if (rc) return rc;
-  BX_REQUIRE((long long)rows * per < (1ll << 31), "%s: rows * per beyond 32-bit offsets", who);
+  SAMPLE_TRY(sample_rows_ok(who, B, n, per, row0, rows));
   BX_REQUIRE(out && (x == nullptr) == (radius == nullptr), "%s: null pointer (x and radius are given or omitted together)", who);
-  const int gy = rows < 65535 ? rows : 65535, quads = bx_ceil_div(per, 4);
-  const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
-  if (per % 4 == 0 && inf_aligned16(x, out))
-    hipLaunchKernelGGL((k_sens_rows<4>), dim3(bx_ceil_div(quads, 256), gy), dim3(256), 0, (hipStream_t)stream, x, radius, out, n, per, k0, k1, row0, rows);
-  else
-    hipLaunchKernelGGL((k_sens_rows<1>), dim3(bx_ceil_div(quads, 256), gy), dim3(256), 0, (hipStream_t)stream, x, radius, out, n, per, k0, k1, row0, rows);
-  BX_CHECK_LAUNCH(who);
-  return BX_OK;
+  return sample_noise_rows<SampleUniform>(who, stream, x, radius, out, n, per, seed, row0, rows);
 }
 
 // ---- sensitivity_max: distances and the result --------------------------------------------------------------------------------------------
@@ -378,9 +324,7 @@ __global__ __launch_bounds__(256) void k_sens_dist(const float* __restrict__ a, 
 }
 extern "C" int bx_sensitivity_dist(const float* a, const float* ref, double* dist, int B, int n, int per, int row0, int rows, bxStream stream) {
   const char* who = "bx_sensitivity_dist";
-  const int rc = inf_rows_ok(who, B, n, per, row0, rows);
-  if (rc) return rc;
-  BX_REQUIRE((long long)rows * per < (1ll << 31), "%s: rows * per beyond 32-bit offsets", who);
+  SAMPLE_TRY(sample_rows_ok(who, B, n, per, row0, rows));
   BX_REQUIRE(a && dist, "%s: null pointer", who);
   BX_REQUIRE(((uintptr_t)dist & 7) == 0, "%s: dist must be 8-byte aligned", who);
   hipLaunchKernelGGL(k_sens_dist, dim3(rows), dim3(256), 0, (hipStream_t)stream, a, ref, dist, n, per, row0);

@@ -1,15 +1,14 @@
 // Spectral attributions of the EEG input (amplitude gradients and spectral perturbation: Schirrmeister et al., Hum. Brain Mapp. 2017;
 // braindecode's compute_amplitude_gradients): the real DFT of every electrode's trace for any length 1..8192 as a direct fp64 sum over a
-// host-made twiddle table, the fp64 running sum of the path-weighted gradient in fixed step order, the amplitude gradient / gradient x
-// amplitude per frequency bin with the gradient's transform kept in registers, band sums, and the band-stopped rows of spectral
-// occlusion written in the EEG layout.  The forward and backward passes are the model's own kernels; the path rows are
-// bx_expgrad_rows, the seeds bx_expgrad_seed.  See include/brainxai.h for the definition and each entry point.
+// host-made twiddle table, the fp64 running sum of the path-weighted gradient in fixed step order (the walk of sample_rows.h), the
+// amplitude gradient / gradient x amplitude per frequency bin with the gradient's transform kept in registers, band sums, and the
+// band-stopped rows of spectral occlusion written in the EEG layout.  The forward and backward passes are the model's own kernels; the
+// path rows are bx_expgrad_rows, the seeds bx_expgrad_seed.  See include/brainxai.h for the definition and each entry point.
 // The file is compiled with -ffp-contract=off: the accumulate's w * g and its sum are two separate fp64 roundings (numpy's, bit for
 // bit); the transforms ask for their fused multiply-adds by name (fma), one rounding per term, in ascending t or f.
 // No sum here uses an atomic or depends on the launch geometry: a thread owns its output and walks its terms in ascending order.
-#include "bx_common.h"
+#include "sample_rows.h"
 
-#define SP_MAX_K 32
 #define SP_LDS 65536                  // dynamic LDS of a workgroup: the twiddle table where it fits (and a tile of bins in the band-stop kernel)
 #define SP_TILE 1024                  // bins of a band staged at a time by the band-stop kernel (16 KiB)
 typedef double2 sp_c;                 // (cos, sin) of a table entry; (re, im) of a staged bin
@@ -110,60 +109,27 @@ extern "C" int bx_rdft_rows(const float* x, const double* tw, double* re, double
   return BX_OK;
 }
 
-// ---- the running sum --------------------------------------------------------------------------------------------------------------------
-// global row j = b * n + k (sample-major); a call handles rows [row0, row0 + rows), which may start and end inside a sample.  A thread
-// owns one element of one sample and walks that sample's rows of the call in ascending k, four loads in flight.
-static int sp_rows_ok(const char* who, int B, int n, int per, int row0, int rows) {
-  BX_REQUIRE(B > 0 && n > 0 && per > 0, "%s: bad shape B=%d n=%d per=%d", who, B, n, per);
-  BX_REQUIRE((long long)B * n < (1ll << 31) && (long long)B * per < (1ll << 31), "%s: B * n or B * per beyond 32-bit offsets", who);
-  BX_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= (long long)B * n, "%s: rows row0 = %d, rows = %d outside 0..B * n = %d", who, row0, rows,
-             B * n);
-  BX_REQUIRE((long long)rows * per < (1ll << 31), "%s: rows * per beyond 32-bit offsets", who);
-  return BX_OK;
-}
-__global__ __launch_bounds__(256) void k_spectral_accumulate(const float* __restrict__ g, const double* __restrict__ w, double* __restrict__ acc, int n, int per,
-                                                             int Kc, int slot, int row0, int rows, int b_first, int b_count) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= per) return;
-  for (int bi = blockIdx.y; bi < b_count; bi += gridDim.y) {
-    const int b = b_first + bi;
-    const int j0 = b * n > row0 ? b * n : row0;
-    const int j1 = (b + 1) * n < row0 + rows ? (b + 1) * n : row0 + rows;
-    const size_t at = ((size_t)b * Kc + slot) * per + e;
-    double s = acc[at];
-    int j = j0;
-    for (; j + 4 <= j1; j += 4) {
-      float gv[4];
-      double wv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { gv[u] = g[(size_t)(j + u - row0) * per + e]; wv[u] = w[j + u - b * n]; }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const double p = wv[u] * (double)gv[u];
-        s = s + p;
-      }
-    }
-    for (; j < j1; ++j) {
-      const double p = w[j - b * n] * (double)g[(size_t)(j - row0) * per + e];
-      s = s + p;
-    }
-    acc[at] = s;
+// ---- the running sum: w[k] * g, the walk of sample_rows.h with one element per thread -----------------------------------------------------
+struct SpTerm {
+  const double* w; double* acc;
+  static constexpr int SUMS = 1;
+  template <int V> struct Keep {};
+  template <int V> struct Row { double w; };
+  double* sum(int) const { return acc; }
+  template <int V> __device__ __forceinline__ void sample(Keep<V>&, int, int, int) const {}
+  template <int V> __device__ __forceinline__ void row(Row<V>& r, int, int k, int, int, int) const { r.w = w[k]; }
+  template <int V> __device__ __forceinline__ void add(double (&s)[1][V], int q, const Keep<V>&, float g, const Row<V>& r) const {
+    const double p = r.w * (double)g;
+    s[0][q] = s[0][q] + p;
   }
-}
+};
 extern "C" int bx_spectral_accumulate(const float* g, const double* w, double* acc, int B, int n, int per, int Kc, int slot, int row0, int rows, bxStream stream) {
-  const int rc = sp_rows_ok("bx_spectral_accumulate", B, n, per, row0, rows);
-  if (rc) return rc;
-  BX_REQUIRE(Kc >= 1 && slot >= 0 && slot < Kc, "bx_spectral_accumulate: class slot %d outside 0..Kc = %d", slot, Kc);
-  if (Kc > SP_MAX_K) BX_FAIL(BX_EUNSUPPORTED, "bx_spectral_accumulate: %d classes, supported 1..%d", Kc, SP_MAX_K);
-  BX_REQUIRE((long long)B * Kc * per < (1ll << 31), "bx_spectral_accumulate: B * Kc * per beyond 32-bit offsets");
-  BX_REQUIRE(g && w && acc, "bx_spectral_accumulate: null pointer");
-  BX_REQUIRE((((uintptr_t)acc | (uintptr_t)w) & 7) == 0, "bx_spectral_accumulate: w and acc must be 8-byte aligned");
-  const int b_first = row0 / n, b_count = (row0 + rows - 1) / n - b_first + 1;
-  const int gy = b_count < 65535 ? b_count : 65535;
-  hipLaunchKernelGGL(k_spectral_accumulate, dim3(bx_ceil_div(per, 256), gy), dim3(256), 0, (hipStream_t)stream, g, w, acc, n, per, Kc, slot, row0, rows, b_first,
-                     b_count);
-  BX_CHECK_LAUNCH("bx_spectral_accumulate");
-  return BX_OK;
+  const char* who = "bx_spectral_accumulate";
+  SAMPLE_TRY(sample_rows_ok(who, B, n, per, row0, rows));
+  SAMPLE_TRY(sample_slot_ok(who, B, per, Kc, slot));
+  BX_REQUIRE(g && w && acc, "%s: null pointer", who);
+  BX_REQUIRE((((uintptr_t)acc | (uintptr_t)w) & 7) == 0, "%s: w and acc must be 8-byte aligned", who);
+  return sample_accumulate<256, 1, 4>(who, stream, g, false, SpTerm{w, acc}, n, per, Kc, slot, row0, rows);
 }
 
 // ---- the values -------------------------------------------------------------------------------------------------------------------------
@@ -206,7 +172,7 @@ __global__ __launch_bounds__(256) void k_spectral_values(const double* __restric
 extern "C" int bx_spectral_values(const double* gsum, const double* re, const double* im, const double* tw, float* values, int B, int Kc, int Chans, int T,
                                   int kind, bxStream stream) {
   BX_REQUIRE(B > 0 && Kc > 0 && Chans > 0, "bx_spectral_values: bad shape B=%d Kc=%d Chans=%d", B, Kc, Chans);
-  if (Kc > SP_MAX_K) BX_FAIL(BX_EUNSUPPORTED, "bx_spectral_values: %d classes, supported 1..%d", Kc, SP_MAX_K);
+  if (Kc > SAMPLE_MAX_K) BX_FAIL(BX_EUNSUPPORTED, "bx_spectral_values: %d classes, supported 1..%d", Kc, SAMPLE_MAX_K);
   const long long RL = (long long)B * Kc * Chans;
   const int rc = sp_shape_ok("bx_spectral_values", RL, T);
   if (rc) return rc;

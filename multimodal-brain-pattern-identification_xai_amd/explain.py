@@ -1415,6 +1415,14 @@ class _GradPass:
         """fp32 [B,Kc,*trail], empty: ``empty(*xs.shape[1:])`` is the estimator element by element, for the driver's finish launch."""
         return torch.empty(self.B, self.Kc, *trail, dtype=torch.float32, device=self.dev)
 
+    def completeness(self, values, per, reference):
+        """fp64 [B] or [B,K]: the sum of the ``per`` values of each (sample, class) row (bx_blurig_sum_rows: fp64, fixed order) minus
+        out - ``reference`` (fp32 [B,K], the model's output at the path's other end) of the row's class."""
+        total = torch.empty(self.B, self.Kc, dtype=torch.float64, device=self.dev)
+        L.check(L.load().bx_blurig_sum_rows(_p(values), _p(total), self.B * self.Kc, per, _stream()), "bx_blurig_sum_rows")
+        drop = self.out.double() - reference.double()
+        return total - drop if self.all_classes else (total - drop.gather(1, self.classes.long()[:, None]))[:, 0]
+
     def result(self, return_parts, parts, amap, values, *rest):
         """The map alone, or ``parts(map, values, classes int64 [B] or None, out, *rest)``; the class axis stays for class_idx='all' only."""
         if not self.all_classes:
@@ -2831,12 +2839,7 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
             _blur_rows(lib, xs, torch.from_numpy(end_taps).to(gp.dev), torch.from_numpy(end_radius).to(gp.dev), end_taps.shape[2], last, None, 1, axes, 0, 0, B)
             with torch.no_grad():
                 endpoint = _fuse(model, multimodal, gp.input_is_spec, net(last), gp.fixed).float().contiguous()
-            total = torch.empty(B, Kc, dtype=torch.float64, device=gp.dev)
-            L.check(lib.bx_blurig_sum_rows(_p(values), _p(total), B * Kc, per, _stream()), "bx_blurig_sum_rows")
-            drop = gp.out.double() - endpoint.double()
-            delta = total - (drop if all_classes else drop.gather(1, gp.classes.long()[:, None]))
-            if not all_classes:
-                delta = delta[:, 0]
+            delta = gp.completeness(values, per, endpoint)
     return gp.result(return_parts, BlurIGResult, amap, values, endpoint, delta, sigmas, n, max_sigma, sqrt, eps, axes)
 
 
@@ -3070,14 +3073,10 @@ def _spectral_gradients(model, eeg, spec, kind, steps, fs, bands, class_idx, max
             with torch.no_grad():                                   # F(0): EEGNet in eval mode treats every row alike, one row serves all samples
                 at_zero = net(torch.zeros_like(xs[:1]))
                 at_zero = _fuse(model, multimodal, False, at_zero.expand(B, -1).contiguous(), gp.fixed).float()
-            total = torch.empty(B, Kc, dtype=torch.float64, device=dev)
-            L.check(lib.bx_blurig_sum_rows(_p(amap), _p(total), B * Kc, Chans * F, _stream()), "bx_blurig_sum_rows")
-            drop = gp.out.double() - at_zero.double()
-            delta = total - (drop if all_classes else drop.gather(1, gp.classes.long()[:, None]))
+            delta = gp.completeness(amap, Chans * F, at_zero)
         if not all_classes:
             amap, gradient = amap[:, 0], gradient[:, 0]
             band_vals = None if band_vals is None else band_vals[:, 0]
-            delta = None if delta is None else delta[:, 0]
     freqs = np.arange(F, dtype=np.float64) * (1.0 if fs is None else fs) / T
     return SpectralGradientsResult(amap, band_vals, gradient, None if gp.classes is None else gp.classes.long(), gp.out, freqs, band_bins, delta, kind, n)
 

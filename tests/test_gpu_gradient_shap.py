@@ -85,16 +85,18 @@ def test_accumulate_and_finish_against_numpy(name, Kc):
     xd, bd, idx_d, gd = PG.dev(x), PG.dev(bg), PG.dev(IDX), PG.dev(g)
     SENTINEL = 7.25
 
-    def run(splits):
+    def run(splits, mis=False):
         acc = torch.full((KB, Kc, per), SENTINEL, dtype=torch.float64, device=DEV)
         acc[:, slot] = 0.0
         for row0, rows in splits:
             gs = gd[row0:row0 + rows].contiguous()
-            L.check(lib.bx_expgrad_accumulate(PG.p(xd), PG.p(bd), PG.p(idx_d), PG.p(gs), PG.p(acc), KB, KNB, KN, per, Kc, slot, row0, rows, PG.stream()),
-                    "bx_expgrad_accumulate")
+            L.check(lib.bx_expgrad_accumulate(PG.p(xd), PG.p(bd), PG.p(idx_d), PG.p(PG.misaligned(gs) if mis else gs), PG.p(acc), KB, KNB, KN, per, Kc, slot,
+                                              row0, rows, PG.stream()), "bx_expgrad_accumulate")
         return acc
     one, two = run([(0, rows_all)]), run([(0, 7), (7, rows_all - 7)])                    # row 7 is inside sample 1
     assert torch.equal(one, two), f"{name}: two calls split inside a sample differ from one call"
+    mis = run([(0, 7), (7, rows_all - 7)], mis=True)                                     # element by element, whatever per % 4
+    assert torch.equal(one.view(torch.int64), mis.view(torch.int64)), f"{name}: a misaligned g changes the sum"
     others = [k for k in range(Kc) if k != slot]
     assert bool((one[:, others] == SENTINEL).all()), "the slots of other classes were touched"
     want_acc, absacc = R.accumulate(x, bg, IDX, g.numpy())

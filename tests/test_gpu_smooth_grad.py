@@ -158,16 +158,20 @@ def test_accumulate_and_finish_against_numpy(name, Kc):
     gd = PG.dev(g)
     SENTINEL = 7.25
 
-    def run(splits):
+    def run(splits, mis=False):
         S1 = torch.full((KB, Kc, per), SENTINEL, dtype=torch.float64, device=DEV)
         S2 = torch.full((KB, Kc, per), SENTINEL, dtype=torch.float64, device=DEV)
         S1[:, slot], S2[:, slot] = 0.0, 0.0
         for row0, rows in splits:
             gs = gd[row0:row0 + rows].contiguous()
-            L.check(lib.bx_smoothgrad_accumulate(PG.p(gs), PG.p(S1), PG.p(S2), KB, n, per, Kc, slot, row0, rows, PG.stream()), "bx_smoothgrad_accumulate")
+            L.check(lib.bx_smoothgrad_accumulate(PG.p(PG.misaligned(gs) if mis else gs), PG.p(S1), PG.p(S2), KB, n, per, Kc, slot, row0, rows, PG.stream()),
+                    "bx_smoothgrad_accumulate")
         return S1, S2
     one, two = run([(0, rows_all)]), run([(0, 7), (7, rows_all - 7)])                    # row 7 is inside sample 1
     assert torch.equal(one[0], two[0]) and torch.equal(one[1], two[1]), f"{name}: two calls split inside a sample differ from one call"
+    mis = run([(0, 7), (7, rows_all - 7)], mis=True)                                     # element by element, whatever per % 4
+    assert torch.equal(one[0].view(torch.int64), mis[0].view(torch.int64)) and torch.equal(one[1].view(torch.int64), mis[1].view(torch.int64)), \
+        f"{name}: a misaligned g changes the sums"
     others = [k for k in range(Kc) if k != slot]
     assert bool((one[0][:, others] == SENTINEL).all()) and bool((one[1][:, others] == SENTINEL).all()), "the slots of other classes were touched"
     w1, w2, abs1 = R.accumulate(g.numpy(), KB, n)
