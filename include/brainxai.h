@@ -994,6 +994,67 @@ int bx_band_sum(const float* values, const int* bins, double* out, int R, int F,
  * subtracted from double(x); the result is rounded to fp32 once. */
 int bx_bandstop_rows(const float* x, const double* re, const double* im, const double* tw, const int* bins, float* out, int B, int Chans, int T, int nb,
                      int cells, int n0, int n, bxStream stream);
+/* ---- Similarity of two attribution maps and the model parameter randomization test (Adebayo et al., "Sanity Checks for Saliency
+ * Maps", NeurIPS 2018; Ghorbani et al., AAAI 2019; scipy.stats.spearmanr / pearsonr, scikit-image's structural_similarity).  A map is a
+ * row of N = H * W cells, 1 <= N < 2^20 (the limit of bx_rank_desc; BX_EUNSUPPORTED above, before any pointer is touched); R rows.
+ * With `abs` every kernel reads |v| in registers.
+ *   pearson   r = sum (x - mx)(y - my) / sqrt( sum (x - mx)^2 * sum (y - my)^2 ), clamped to [-1, 1] as scipy does; fp64, two
+ *             passes (means first), every product and sum rounded on its own.  One workgroup of 256 per row: thread t takes the cells
+ *             t, t + 256, ... in ascending order and the 256 partial sums meet in a pairwise tree over the thread index (stride 128,
+ *             64, .., 1), the order of bx_infidelity_dot: a function of N alone, no atomics.  NaN when either centred sum of squares
+ *             is 0 (scipy's result for a constant input).
+ *   spearman  the same correlation over tie-averaged ranks (scipy.stats.rankdata(method="average") of the negated keys, minus 1):
+ *             avg[i] = #{key > key_i} + (#{key == key_i} - 1) / 2, key as in bx_rank_desc (NaN counts as -inf, -0.0 equals +0.0): a
+ *             half-integer below 2^20, exact in fp32.
+ *   topk      |{i : rank_a[i] < k and rank_b[i] < k}| / k over the stable ranks of bx_rank_desc: an exact integer divided once.
+ *   ssim      the mean of S over the positions whose whole window lies inside the map (scikit-image's crop of (win - 1) / 2 per side,
+ *             so no padding rule enters).  F is the separable filter of the `win` taps (odd) along each map axis of extent > 1; an axis
+ *             of extent 1 is not filtered, and such a map is a line of H * W cells.  NP = win^(filtered axes).  With the cells X, Y:
+ *               ux = F(X), uy = F(Y), uxx = F(X X), uyy = F(Y Y), uxy = F(X Y)
+ *               vx = c (uxx - ux^2), vy = c (uyy - uy^2), vxy = c (uxy - ux uy)         c = cov_norm: NP / (NP - 1) for the uniform
+ *               C1 = (0.01 R)^2, C2 = (0.03 R)^2, R = data_range                         window, 1 for the Gaussian one
+ *               S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2))
+ *             Cells: with the four range arrays X = ((double)x - lo) / ((double)hi - (double)lo) per row, 0 everywhere when hi == lo
+ *             (the rescaling to [0, 1] of Adebayo et al.; pass data_range = 1); without them the raw values.  All fp64: a moment is
+ *             the sum of tap * value in ascending tap order along the row, then of tap * moment down the column.
+ *   re-initialisation  p[e] = fl32( bound * u ), u = (float)(w >> 8) * 2^-23 - 1 in [-1, 1), w = word e & 3 of
+ *             Philox4x32-10( counter = (e >> 2, j, s, 2), key = (seed & 0xffffffff, seed >> 32) ): j the tensor's position in its
+ *             layer's parameters, s the layer's position in the test's list.  Counter word 3 is 2: a stream apart from the Gaussian
+ *             (0) and the uniform (1) one.  bound = 1 / sqrt(fan_in) is torch's default for Conv2d / Linear weights and biases.
+ * Every entry point refuses its limits with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched. */
+#define BX_SSIM_MAX_WIN 63
+/* avg fp32 [R,N] from values fp32 [R,N] and ranks i32 [R,N] = bx_rank_desc of the same keys (of |values| with abs: bx_rank_desc has no
+ * flag, the caller ranks a copy of |values|; here |v| is formed in registers).  The keys are scattered to sorted order, then every cell
+ * finds the two ends of its tie run by binary search.  workspace: bx_rank_average_workspace bytes (0 for refused shapes), 4-byte
+ * aligned.  R <= 65535. */
+size_t bx_rank_average_workspace(int R, int N);
+int bx_rank_average(const float* values, const int* ranks, float* avg, int R, int N, int abs, void* workspace, size_t workspace_bytes, bxStream stream);
+/* r fp64 [R]: pearson of the rows of a and b fp32 [R,N], values or ranks. */
+int bx_map_corr(const float* a, const float* b, double* r, int R, int N, int abs, bxStream stream);
+/* out fp64 [R]: topk of the rank rows ranks_a, ranks_b i32 [R,N]; 1 <= k <= N. */
+int bx_topk_overlap(const int* ranks_a, const int* ranks_b, double* out, int R, int N, int k, bxStream stream);
+/* lo, hi fp32 [R]: the extremes of every row of v fp32 [R,N] (of |v| with abs); a NaN cell is skipped.  (bx_smoothgrad_sigma returns
+ * only level * (max - min) and bx_scorecam_range the extremes of bilinearly up-sampled planes: neither gives lo and hi of a row as it
+ * stands.) */
+int bx_row_minmax(const float* v, float* lo, float* hi, int R, int N, int abs, bxStream stream);
+/* out fp64 [R]: ssim of the maps a, b fp32 [R,H,W].  taps fp64 [win] on the device; lo_a, hi_a, lo_b, hi_b fp32 [R] (all four or none).
+ * A workgroup owns (map, strip of SW columns of positions): it keeps the five moments filtered along the rows, for all H rows of its
+ * strip, in LDS as fp64 and filters down the columns from there -- no global intermediate; thread t adds S of the strip's positions
+ * t, t + 256, ... (row-major) and the 256 partials meet in the butterfly and then in wave order.  A map's mean is the sum of its strip
+ * sums in ascending strip order (a second launch) divided by the number of positions.  No atomics.
+ * SW = bx_ssim_strip(H, W, win): the widest of 64, 32, 16, 8, 4 with H * SW <= 1624 (five planes of H * SW doubles beside the taps in
+ * 65536 bytes), halved while half of it still covers all W - win + 1 columns; a line (an axis of extent 1) counts as H = 1.  The largest
+ * map with two filtered axes therefore has H <= 406 rows (any W within N < 2^20); above, BX_EUNSUPPORTED (bx_ssim_strip: 0).
+ * win odd, <= BX_SSIM_MAX_WIN and <= every filtered extent (BX_EINVAL: scikit-image refuses such a window too); R <= 65535.
+ * workspace: bx_ssim_rows_workspace bytes (0 for refused shapes), 8-byte aligned. */
+int bx_ssim_strip(int H, int W, int win);
+size_t bx_ssim_rows_workspace(int R, int H, int W, int win);
+int bx_ssim_rows(const float* a, const float* b, const double* taps, const float* lo_a, const float* hi_a, const float* lo_b, const float* hi_b,
+                 double data_range, double cov_norm, double* out, int R, int H, int W, int win, int abs, void* workspace, size_t workspace_bytes,
+                 bxStream stream);
+/* p fp32 [n] on the device, 1 <= n < 2^31: the re-initialisation above.  One Philox block serves four elements; 16-byte stores when p is
+ * 16-byte aligned, the partial last block element by element. */
+int bx_param_uniform(float* p, size_t n, float bound, uint64_t seed, uint32_t j, uint32_t s, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

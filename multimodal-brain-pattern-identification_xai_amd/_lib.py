@@ -25,6 +25,7 @@ BX_BLUR_MAX_RADIUS = 16384
 BX_SPECTRAL_AMPLITUDE_GRADIENT, BX_SPECTRAL_GRADIENT_X_AMPLITUDE = 0, 1
 BX_SPECTRAL_CELLS_BAND, BX_SPECTRAL_CELLS_ELECTRODE_BAND = 0, 1
 BX_SPECTRAL_MAX_T = 8192
+BX_SSIM_MAX_WIN = 63
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -225,6 +226,15 @@ SIGNATURES = {
     "bx_spectral_values": (i32, [vp] * 5 + [i32] * 5 + [vp]),
     "bx_band_sum": (i32, [vp] * 3 + [i32] * 3 + [vp]),
     "bx_bandstop_rows": (i32, [vp] * 6 + [i32] * 7 + [vp]),
+    "bx_rank_average_workspace": (sz, [i32, i32]),
+    "bx_rank_average": (i32, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "bx_map_corr": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "bx_topk_overlap": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "bx_row_minmax": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "bx_ssim_strip": (i32, [i32, i32, i32]),
+    "bx_ssim_rows_workspace": (sz, [i32] * 4),
+    "bx_ssim_rows": (i32, [vp] * 7 + [C.c_double, C.c_double, vp] + [i32] * 5 + [vp, sz, vp]),
+    "bx_param_uniform": (i32, [vp, sz, f32, C.c_uint64, u32, u32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),
     "bx_seed_next2": (i32, [vp, vp, vp, vp, vp]),

@@ -128,6 +128,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(bx_lane(v, 0), bx_lane(v, 16)), fmaxf(bx_lane(v, 32), bx_lane(v, 48)));
 }
 
+// The sort key of bx_rank_desc, shared with the tie-averaged ranks of similarity.hip: ascending key order is descending value order.
+__device__ __forceinline__ uint32_t bx_rank_key(float v) {
+  if (v != v) v = -INFINITY;                                        // NaN ranks with -inf
+  if (v == 0.f) v = 0.f;                                            // -0.0 == +0.0
+  const uint32_t u = __float_as_uint(v);
+  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+}
+
 // Grad-CAM++ (include/brainxai.h, BX_CAM_GRADCAM_PP): one position's share of the channel weight, max(g, 0) * alpha(g, S) with
 // alpha = g^2 / (2 g^2 + S g^3 + eps) and alpha = 0 where g == 0; S = sum_s A[k, s] of the channel
 #define BX_CAM_EPS 1e-6f

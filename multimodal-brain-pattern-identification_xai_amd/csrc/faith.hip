@@ -15,12 +15,6 @@
 //            take consecutive slots behind the wave's counter in lane order, and the last of them advances the counter.
 // Nothing depends on scheduling: every cell's slot is a function of the row alone.  Pass 0 keys the values itself (flat index =
 // position), pass 3 writes ranks[idx] = slot instead of another (key, idx) image.
-__device__ __forceinline__ uint32_t rank_key(float v) {
-  if (v != v) v = -INFINITY;                                        // NaN ranks with -inf
-  if (v == 0.f) v = 0.f;                                            // -0.0 == +0.0
-  const uint32_t u = __float_as_uint(v);
-  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-}
 
 template <bool FIRST, bool LAST>
 __global__ __launch_bounds__(1024) void k_rank_pass(const float* __restrict__ values, const uint32_t* __restrict__ kin, const uint32_t* __restrict__ iin,
@@ -31,7 +25,7 @@ __global__ __launch_bounds__(1024) void k_rank_pass(const float* __restrict__ va
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const size_t row = (size_t)blockIdx.x * N;
   const int lo = w * chunk < N ? w * chunk : N, hi = lo + chunk < N ? lo + chunk : N;
-  auto key_at = [&](int i) -> uint32_t { return FIRST ? rank_key(values[row + i]) : kin[row + i]; };
+  auto key_at = [&](int i) -> uint32_t { return FIRST ? bx_rank_key(values[row + i]) : kin[row + i]; };
   for (int i = tid; i < 256 * RANK_WAVES; i += 1024) cnt[i] = 0u;
   __syncthreads();
   for (int i0 = lo; i0 < hi; i0 += 256) {

@@ -64,6 +64,12 @@
                                  order (bx_infidelity_dot), drops, beta and the mean square (bx_infidelity_finish); uniformly perturbed
                                  rows (bx_sensitivity_rows), fp64 distances of the caller's explanations (bx_sensitivity_dist) and
                                  the largest relative one (bx_sensitivity_finish).
+* ``map_similarity`` / ``agreement_matrix`` / ``randomization_test`` -- the sanity checks of Adebayo et al. (NeurIPS 2018): Spearman's
+                                 correlation over tie-averaged ranks (bx_rank_desc, bx_rank_average), Pearson's in fp64 (bx_map_corr), the
+                                 overlap of the top-k cells (bx_topk_overlap) and the mean windowed SSIM of scikit-image
+                                 (bx_row_minmax, bx_ssim_rows) of two maps; the model parameter randomization test re-initialises
+                                 the layers from the output towards the input with counter-based draws (bx_param_uniform), compares
+                                 every stage's map with the trained model's and restores the parameters bit for bit.
 """
 from __future__ import annotations
 
@@ -3383,3 +3389,413 @@ def sensitivity_max(explain, eeg, spec, *, input="spec", nsamples=10, radius=Non
     if not return_parts:
         return sens
     return SensitivityResult(sens, dist.reshape(B, n), norms, r, n, seed)
+
+
+# ---- similarity of two maps and the model parameter randomization test ------------------------------------------------------------------
+_SIM_METRICS = ("spearman", "pearson", "ssim", "topk")
+_SIM_WINDOWS = ("uniform", "gaussian")
+_SIM_ORDERS = ("cascade", "independent")
+
+MapSimilarityResult = collections.namedtuple("MapSimilarityResult", "spearman pearson ssim topk ranks_a ranks_b k lo hi args",
+                                             defaults=(None,) * 10)
+MapSimilarityResult.__doc__ = """What ``map_similarity`` returns: ``spearman``, ``pearson``, ``ssim``, ``topk`` fp64 tensors of the maps' leading shape on the
+device (None for a metric that was not asked for).  With return_parts also ``ranks_a`` / ``ranks_b`` (the tie-averaged ranks, fp32, the
+maps' shape; None without 'spearman'), ``k`` (the top-k count; None without 'topk'), ``lo`` / ``hi`` (fp32 [2, *leading]: the extremes of
+a and of b that SSIM rescaled by; None with a data_range or without 'ssim') and ``args`` (the options as a dict)."""
+
+RandomizationResult = collections.namedtuple("RandomizationResult", "layers similarity original maps order seed")
+RandomizationResult.__doc__ = """What ``randomization_test`` returns: ``layers`` (the names, output first; a group is a tuple), ``similarity`` {metric:
+fp64 [*leading, n]} on the device (stage s compares the original map with the map after layer s was re-initialised), ``original`` (the
+map of the trained model), ``maps`` (the n stage maps with keep_maps, else None), ``order`` and ``seed`` as given."""
+
+
+def _sim_taps(window, win):
+    """fp64 [win]: 1 / win, or the taps of scipy.ndimage.gaussian_filter1d(sigma=1.5, truncate=3.5) (radius 5)."""
+    if window == "uniform":
+        return np.full(win, 1.0 / win, dtype=np.float64)
+    t = np.arange(-(win // 2), win // 2 + 1)
+    phi = np.exp(-0.5 / (1.5 * 1.5) * t ** 2)
+    return phi / phi.sum()
+
+
+def _sim_options(who, shape, metrics, window, win_size, data_range, topk):
+    """Everything about the options that can be refused, refused; -> (metrics, H, W, N, win, cov_norm, k)."""
+    if isinstance(metrics, str):
+        metrics = (metrics,)
+    metrics = tuple(metrics)
+    bad = [m for m in metrics if m not in _SIM_METRICS]
+    if bad or not metrics:
+        raise ValueError(f"{who}: unknown metric {bad[0] if bad else metrics!r}; use any of {_SIM_METRICS}")
+    if len(shape) < 2:
+        raise ValueError(f"{who}: a map needs at least two axes, [..., H, W]; got the shape {tuple(shape)}")
+    H, W = int(shape[-2]), int(shape[-1])
+    N = H * W
+    if not 1 <= N <= _FAITH_MAX_N or any(int(v) < 1 for v in shape):
+        raise ValueError(f"{who}: {N} cells per map (shape {tuple(shape)}), supported 1..{_FAITH_MAX_N}")
+    win = cov = k = None
+    if "ssim" in metrics:
+        if window not in _SIM_WINDOWS:
+            raise ValueError(f"{who}: unknown window {window!r}; use 'uniform' or 'gaussian'")
+        if window == "gaussian":
+            if win_size is not None:
+                raise ValueError(f"{who}: win_size is fixed by window='gaussian' (sigma 1.5, truncate 3.5: 11); do not pass it")
+            win = 11
+        else:
+            win = 7 if win_size is None else win_size
+            if not isinstance(win, numbers.Integral) or isinstance(win, bool) or win < 1 or win % 2 == 0:
+                raise ValueError(f"{who}: win_size must be an odd int >= 1, got {win_size!r}")
+            win = int(win)
+        if win > L.BX_SSIM_MAX_WIN:
+            raise ValueError(f"{who}: win_size = {win}, supported 1..{L.BX_SSIM_MAX_WIN}")
+        filtered = [v for v in (H, W) if v > 1]
+        if not filtered:
+            raise ValueError(f"{who}: ssim of a map of one cell is not defined")
+        if min(filtered) < win:
+            raise ValueError(f"{who}: win_size = {win} exceeds a filtered axis of the map [{H}, {W}]")
+        NP = win ** len(filtered)
+        if window == "uniform" and NP < 2:
+            raise ValueError(f"{who}: the uniform window needs win_size >= 3 (the sample covariance of one cell is not defined)")
+        cov = NP / (NP - 1.0) if window == "uniform" else 1.0
+        if data_range is not None and (not isinstance(data_range, numbers.Real) or isinstance(data_range, bool) or not 0 < float(data_range) < math.inf):
+            raise ValueError(f"{who}: data_range must be None or a finite number > 0, got {data_range!r}")
+        if len(filtered) == 2 and H * 4 > 1624:
+            raise ValueError(f"{who}: ssim supports maps of at most 406 rows, got [{H}, {W}]")
+    if "topk" in metrics:
+        if isinstance(topk, bool) or not isinstance(topk, numbers.Real):
+            raise ValueError(f"{who}: topk must be a fraction in (0, 1] or an int in 1..N, got {topk!r}")
+        if isinstance(topk, numbers.Integral):
+            if not 1 <= topk <= N:
+                raise ValueError(f"{who}: topk = {topk} outside 1..N = {N}")
+            k = int(topk)
+        else:
+            if not 0 < float(topk) <= 1:
+                raise ValueError(f"{who}: the fraction topk = {topk!r} lies outside (0, 1]")
+            k = min(N, max(1, math.ceil(float(topk) * N)))
+    return metrics, H, W, N, win, cov, k
+
+
+class _SimMap:
+    """One map tensor [*leading, H, W] as fp32 rows [R,N] on the device, with what the metrics need of it computed once: the stable
+    ranks, the tie-averaged ranks and the extremes."""
+
+    def __init__(self, t, abs):
+        self.lead = tuple(t.shape[:-2])
+        self.R = int(np.prod(self.lead, dtype=np.int64)) if self.lead else 1
+        self.N = int(t.shape[-2]) * int(t.shape[-1])
+        self.shape = tuple(t.shape)
+        self.v = t.detach().to(torch.float32).reshape(self.R, self.N).contiguous()
+        self.abs = 1 if abs else 0
+        self._ranks = self._avg = self._range = None
+
+    def ranks(self):
+        if self._ranks is None:
+            lib, v = L.load(), self.v
+            if self.abs:                                              # bx_rank_desc has no flag: it ranks a copy of |v|
+                v = torch.empty_like(self.v)
+                L.check(lib.bx_abs(_p(self.v), _p(v), self.v.numel(), _stream()), "bx_abs")
+            self._ranks = torch.empty(self.R, self.N, dtype=torch.int32, device=v.device)
+            nbytes = lib.bx_rank_desc_workspace(self.R, self.N)
+            if nbytes == 0:
+                L.check(-1, "bx_rank_desc_workspace")
+            ws = torch.empty(nbytes // 4, dtype=torch.int32, device=v.device)
+            L.check(lib.bx_rank_desc(_p(v), _p(self._ranks), self.R, self.N, _p(ws), nbytes, _stream()), "bx_rank_desc")
+        return self._ranks
+
+    def average_ranks(self):
+        if self._avg is None:
+            lib, ranks = L.load(), self.ranks()
+            self._avg = torch.empty(self.R, self.N, dtype=torch.float32, device=self.v.device)
+            nbytes = lib.bx_rank_average_workspace(self.R, self.N)
+            if nbytes == 0:
+                L.check(-1, "bx_rank_average_workspace")
+            ws = torch.empty(nbytes // 4, dtype=torch.int32, device=self.v.device)
+            L.check(lib.bx_rank_average(_p(self.v), _p(ranks), _p(self._avg), self.R, self.N, self.abs, _p(ws), nbytes, _stream()), "bx_rank_average")
+        return self._avg
+
+    def extremes(self):
+        if self._range is None:
+            lo = torch.empty(self.R, dtype=torch.float32, device=self.v.device)
+            hi = torch.empty_like(lo)
+            L.check(L.load().bx_row_minmax(_p(self.v), _p(lo), _p(hi), self.R, self.N, self.abs, _stream()), "bx_row_minmax")
+            self._range = (lo, hi)
+        return self._range
+
+
+def _sim_metric(metric, A, B, H, W, win, cov, k, taps_d, data_range):
+    """fp64 [*leading] of one metric for two prepared maps."""
+    lib = L.load()
+    out = torch.empty(A.R, dtype=torch.float64, device=A.v.device)
+    if metric == "pearson":
+        L.check(lib.bx_map_corr(_p(A.v), _p(B.v), _p(out), A.R, A.N, A.abs, _stream()), "bx_map_corr")
+    elif metric == "spearman":
+        L.check(lib.bx_map_corr(_p(A.average_ranks()), _p(B.average_ranks()), _p(out), A.R, A.N, 0, _stream()), "bx_map_corr")
+    elif metric == "topk":
+        L.check(lib.bx_topk_overlap(_p(A.ranks()), _p(B.ranks()), _p(out), A.R, A.N, k, _stream()), "bx_topk_overlap")
+    else:
+        rng = (None,) * 4 if data_range is not None else A.extremes() + B.extremes()
+        nbytes = lib.bx_ssim_rows_workspace(A.R, H, W, win)
+        if nbytes == 0:
+            L.check(-1, "bx_ssim_rows_workspace")
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=A.v.device)
+        L.check(lib.bx_ssim_rows(_p(A.v), _p(B.v), _p(taps_d), *(_p(t) for t in rng), 1.0 if data_range is None else float(data_range), cov, _p(out),
+                                 A.R, H, W, win, A.abs, _p(ws), nbytes, _stream()), "bx_ssim_rows")
+    return out.reshape(A.lead)
+
+
+def _sim_check_maps(who, maps):
+    first = maps[0]
+    for t in maps:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: the maps must be tensors, got {type(t).__name__}")
+        if tuple(t.shape) != tuple(first.shape):
+            raise ValueError(f"{who}: the maps must have equal shapes, got {tuple(first.shape)} and {tuple(t.shape)}")
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{who}: the maps must be floating-point tensors, got {t.dtype}")
+
+
+def _sim_need_gpu(who, maps):
+    if not all(t.is_cuda for t in maps):
+        raise RuntimeError(f"brainxai.{who}: the maps must live on the GPU; there is no CPU path")
+    if len({t.device for t in maps}) != 1:
+        raise ValueError(f"{who}: the maps live on different devices")
+    R = maps[0].numel() // (int(maps[0].shape[-2]) * int(maps[0].shape[-1]))
+    if R > 65535 or maps[0].numel() >= 1 << 31:
+        raise ValueError(f"{who}: {R} maps per call, supported 1..65535 (and fewer than 2^31 cells in all)")
+
+
+def map_similarity(a, b, *, metrics=_SIM_METRICS, abs=False, window="uniform", win_size=None, data_range=None, topk=0.1, return_parts=False):
+    """How alike two attribution maps are, by the measures of Adebayo et al. ("Sanity Checks for Saliency Maps", NeurIPS 2018) and
+    Ghorbani et al. (AAAI 2019): Spearman's rank correlation, Pearson's correlation, the mean structural similarity and the overlap of
+    the top-k cells.  Everything runs on the device; only the result leaves it.
+
+    a, b:        fp32 device tensors of equal shape [..., H, W]: the last two axes are the map ([H,W], [Chans,T] or [1,T]), all leading
+                 axes are batch, so [B,H,W] and the class-axis form [B,K,H,W] fit as the package returns them.  1 <= H * W < 2^20.
+    metrics:     any of 'spearman', 'pearson', 'ssim', 'topk'.
+    abs:         compare |a| and |b| (Adebayo et al. report both forms); the modulus is taken in registers.
+    spearman:    Pearson's correlation of the tie-averaged ranks, ``scipy.stats.spearmanr``; the keys are ``attribution_ranks``'s (NaN
+                 counts as -inf, -0.0 equals +0.0).  NaN for a constant map, as scipy returns.
+    pearson:     fp64, two passes, in an order that depends on H * W alone (``scipy.stats.pearsonr``).
+    topk:        |{cells among the k largest of both maps}| / k over the stable ranks; k = max(1, ceil(topk * N)) for a fraction in
+                 (0, 1], topk itself for an int.
+    ssim:        the mean SSIM of scikit-image's ``structural_similarity`` over the positions whose window lies inside the map.
+                 window='uniform': win_size (odd, default 7) equal taps and the sample covariance -- skimage's defaults;
+                 window='gaussian': sigma 1.5 truncated at 3.5 sigma (11 taps) and the population covariance -- Wang et al.'s setting
+                 (skimage's gaussian_weights=True, use_sample_covariance=False).  An axis of extent 1 is not filtered: [1,T] maps get
+                 1-D SSIM.  data_range=None rescales each map to [0, 1] by its own extremes first (a constant map becomes zeros), the
+                 procedure of Adebayo et al.; a number compares the raw values with that dynamic range.  A filtered axis shorter
+                 than the window is refused, as skimage does; with two filtered axes H <= 406.
+    Returns ``MapSimilarityResult``: one fp64 tensor of the leading shape per requested metric."""
+    who = "map_similarity"
+    _sim_check_maps(who, [a, b])
+    metrics, H, W, N, win, cov, k = _sim_options(who, a.shape, metrics, window, win_size, data_range, topk)
+    _sim_need_gpu(who, [a, b])
+    with torch.cuda.device(a.device):
+        A, B = _SimMap(a, abs), _SimMap(b, abs)
+        taps_d = torch.from_numpy(_sim_taps(window, win)).to(a.device) if "ssim" in metrics else None
+        vals = {m: _sim_metric(m, A, B, H, W, win, cov, k, taps_d, data_range) for m in metrics}
+        if not return_parts:
+            return MapSimilarityResult(**vals)
+        parts = dict(k=k, args=dict(metrics=metrics, abs=bool(abs), window=window, win_size=win, data_range=data_range, topk=topk))
+        if "spearman" in metrics:
+            parts.update(ranks_a=A.average_ranks().reshape(A.shape), ranks_b=B.average_ranks().reshape(A.shape))
+        if "ssim" in metrics and data_range is None:
+            (la, ha), (lb, hb) = A.extremes(), B.extremes()
+            parts.update(lo=torch.stack([la, lb]).reshape(2, *A.lead), hi=torch.stack([ha, hb]).reshape(2, *A.lead))
+    return MapSimilarityResult(**vals, **parts)
+
+
+def agreement_matrix(maps, *, metric="spearman", abs=False, window="uniform", win_size=None, data_range=None, topk=0.1):
+    """The "do my methods agree" table: ``metric`` of ``map_similarity`` for every pair of the maps {name: tensor [..., H, W]}, all of one
+    shape.  Each map is ranked once and each pair compared once; the matrix is symmetric with a unit diagonal.
+    Returns (fp64 [M, M, *leading] on the device, the names in the dict's order); entry [i, j] equals
+    ``map_similarity(maps[i], maps[j], metrics=(metric,), ...)`` bit for bit."""
+    who = "agreement_matrix"
+    if not isinstance(maps, dict) or not maps:
+        raise ValueError(f"{who}: maps must be a non-empty dict name -> tensor")
+    if not isinstance(metric, str):
+        raise ValueError(f"{who}: metric must be one name, got {metric!r}")
+    names, tensors = list(maps), list(maps.values())
+    _sim_check_maps(who, tensors)
+    _, H, W, N, win, cov, k = _sim_options(who, tensors[0].shape, (metric,), window, win_size, data_range, topk)
+    _sim_need_gpu(who, tensors)
+    dev = tensors[0].device
+    with torch.cuda.device(dev):
+        prepared = [_SimMap(t, abs) for t in tensors]
+        taps_d = torch.from_numpy(_sim_taps(window, win)).to(dev) if metric == "ssim" else None
+        M = len(names)
+        out = torch.ones(M, M, *prepared[0].lead, dtype=torch.float64, device=dev)
+        for i in range(M):
+            for j in range(i + 1, M):
+                out[i, j] = _sim_metric(metric, prepared[i], prepared[j], H, W, win, cov, k, taps_d, data_range)
+                out[j, i] = out[i, j]
+    return out, names
+
+
+def _rand_branch(prefix, net):
+    """The stages of a stand-alone branch, output first; a convolution brings the BatchNorm that follows it."""
+    from . import models as M
+    p = prefix + "." if prefix else ""
+    if isinstance(net, M.Spectrogram_Model):
+        return [p + "fc"] + [f"{p}block{i}" for i in range(5, 0, -1)]
+    trunk = [(p + "separableConv", p + "batchnorm3"), (p + "depthwiseConv", p + "batchnorm2"), (p + "conv1", p + "batchnorm1")]
+    if isinstance(net, M.EEGNetAttentionDeep):
+        return [p + "dense2", p + "dense1", p + "attention_layer", (p + "conv2", p + "batchnorm4")] + trunk
+    if isinstance(net, M.EEGNet):
+        return [p + "dense"] + trunk
+    raise ValueError(f"randomization_layers: no default layer list for a {type(net).__name__}; pass layers=")
+
+
+def randomization_layers(model, input="spec"):
+    """The default stages of ``randomization_test``, output first: for a MultimodalModel ``fc2``, ``fc1``, then the explained branch's
+    head and stages from last to first (the other branch is not touched); for a stand-alone branch its own list.  An entry is a dotted
+    module name, or a tuple of names re-initialised together (a convolution of the EEG nets with the BatchNorm that follows it)."""
+    from . import models as M
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"randomization_layers: unknown input {input!r}; use 'spec' or 'eeg'")
+    if isinstance(model, M.MultimodalModel):
+        return ["fc2", "fc1"] + (_rand_branch("spectrogram_model", model.spectrogram_model) if input == "spec" else _rand_branch("eeg_model", model.eeg_model))
+    if isinstance(model, M.Spectrogram_Model) != (input == "spec"):
+        raise ValueError(f"randomization_layers: input={input!r} does not fit a stand-alone {type(model).__name__}")
+    return _rand_branch("", model)
+
+
+def _rand_fan_in(weight):
+    """torch.nn.init._calculate_fan_in_and_fan_out's fan_in: the input features times the receptive field."""
+    return int(weight.shape[1]) * int(np.prod(weight.shape[2:], dtype=np.int64))
+
+
+def _rand_plan(who, model, layers):
+    """-> per layer the list of actions ('uniform', tensor, bound, j) / ('fill', tensor, value) and the list of every tensor the layer
+    owns.  j is the parameter's position in the layer's named_parameters() (a group: its modules' lists one after the other)."""
+    plans = []
+    seen = set()
+    for layer in layers:
+        names = (layer,) if isinstance(layer, str) else tuple(layer)
+        if not names or not all(isinstance(n, str) for n in names):
+            raise ValueError(f"{who}: a layer is a dotted module name or a tuple of names, got {layer!r}")
+        mods = []
+        for n in names:
+            try:
+                mods.append(_resolve(model, n))
+            except AttributeError:
+                raise ValueError(f"{who}: unknown layer {n!r}: the model has no such module") from None
+            if not isinstance(mods[-1], torch.nn.Module):
+                raise ValueError(f"{who}: unknown layer {n!r}: not a module")
+        position = {}
+        for m in mods:
+            for _, q in m.named_parameters():
+                position.setdefault(id(q), len(position))
+        actions, owned = [], []
+        for m in mods:
+            for sub in m.modules():
+                own = list(sub.parameters(recurse=False))
+                if isinstance(sub, (torch.nn.Conv2d, torch.nn.Linear)):
+                    bound = 1.0 / math.sqrt(_rand_fan_in(sub.weight))
+                    actions += [("uniform", q, bound, position[id(q)]) for q in (sub.weight, sub.bias) if q is not None]
+                elif isinstance(sub, torch.nn.modules.batchnorm._BatchNorm):
+                    actions += [("fill", t, v) for t, v in ((sub.weight, 1.0), (sub.bias, 0.0), (sub.running_mean, 0.0), (sub.running_var, 1.0),
+                                                            (sub.num_batches_tracked, 0)) if t is not None]
+                elif own:
+                    raise ValueError(f"{who}: layer {layer!r} holds parameters of a {type(sub).__name__}; only Conv2d, Linear and BatchNorm are re-initialised")
+                owned += own + list(sub.buffers(recurse=False))
+        if not actions:
+            raise ValueError(f"{who}: layer {layer!r} has no parameters to re-initialise")
+        for t in owned:
+            if id(t) in seen:
+                raise ValueError(f"{who}: layer {layer!r} repeats a tensor of an earlier layer")
+            seen.add(id(t))
+        for a in actions:
+            if a[0] == "uniform" and a[1].dtype != torch.float32:
+                raise ValueError(f"{who}: layer {layer!r} has a {a[1].dtype} parameter; parameters must be float32")
+        plans.append((actions, owned))
+    return plans
+
+
+def _rand_apply(actions, seed, stage):
+    lib = L.load()
+    for a in actions:
+        if a[0] == "uniform":
+            _, q, bound, j = a
+            t = q.data
+            if not t.is_contiguous():
+                raise ValueError("randomization_test: a parameter is not contiguous")
+            L.check(lib.bx_param_uniform(_p(t), t.numel(), bound, seed, j, stage, _stream()), "bx_param_uniform")
+        else:
+            a[1].data.fill_(a[2])
+    ops.bump_param_epoch()                                # the writes bump no version counter: packed weights are stale from here
+
+
+def _rand_restore(saved):
+    for t, copy in saved:
+        t.data.copy_(copy)
+    ops.bump_param_epoch()
+
+
+def randomization_test(model, explain, eeg, spec, *, input="spec", layers=None, order="cascade", metrics=("spearman", "ssim"), abs=False, seed=0,
+                       keep_maps=False, window="uniform", win_size=None, data_range=None, topk=0.1):
+    """The model parameter randomization test of Adebayo et al. ("Sanity Checks for Saliency Maps", NeurIPS 2018): the weights are
+    re-initialised layer by layer from the output towards the input, after each stage the map is recomputed and compared with the map of
+    the trained model.  A method whose maps do not change does not explain the model.
+
+    explain:     ``explain(model, eeg, spec)`` -> a map tensor as ``map_similarity`` accepts it: any of the package's attribution calls
+                 behind a lambda, e.g. ``lambda m, e, s: brainxai.grad_cam(m, e, s)``.
+    layers:      dotted module names, output first; a tuple of names is one stage.  Default ``randomization_layers(model, input)``.
+    order:       'cascade': stage s has layers 0..s re-initialised; 'independent': layer s alone, the rest keeps its trained values.
+                 A layer's draws do not depend on the order.
+    metrics, abs, window, win_size, data_range, topk: ``map_similarity``'s.
+    Re-initialisation, deterministic in ``seed``: every Conv2d / Linear weight and bias of the layer gets fl32(bound * u), bound =
+    1 / sqrt(fan_in) (torch's default kaiming_uniform_(a=sqrt(5)) and its bias bound), u uniform in [-1, 1) from Philox4x32-10 counters
+    (element >> 2, j, s, 2) keyed by seed -- j the tensor's position in the layer's named_parameters(), s the layer's position in
+    ``layers`` (bx_param_uniform); BatchNorm gets weight 1, bias 0, running mean 0, running variance 1 and num_batches_tracked 0.
+    Every parameter and buffer of the listed modules is copied on the device first and restored bit for bit in a ``finally``; the
+    parameter epoch is bumped after every write (ops.bump_param_epoch), so ``pack_reuse`` scopes and a ``GradCamSweep`` repack.
+    Returns ``RandomizationResult``."""
+    who = "randomization_test"
+    if not callable(explain):
+        raise ValueError(f"{who}: explain must be a callable (model, eeg, spec) -> tensor, got {type(explain).__name__}")
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if order not in _SIM_ORDERS:
+        raise ValueError(f"{who}: unknown order {order!r}; use 'cascade' or 'independent'")
+    seed = _stream_seed(who, seed)
+    if isinstance(metrics, str):
+        metrics = (metrics,)
+    metrics = tuple(metrics)
+    bad = [m for m in metrics if m not in _SIM_METRICS]
+    if bad or not metrics:
+        raise ValueError(f"{who}: unknown metric {bad[0] if bad else metrics!r}; use any of {_SIM_METRICS}")
+    layers = list(randomization_layers(model, input) if layers is None else layers)
+    if not layers:
+        raise ValueError(f"{who}: layers is empty")
+    plans = _rand_plan(who, model, layers)
+    if not all(t.is_cuda for _, owned in plans for t in owned):
+        raise RuntimeError(f"brainxai.{who}: the model must live on the GPU; there is no CPU path")
+    options = dict(metrics=metrics, abs=abs, window=window, win_size=win_size, data_range=data_range, topk=topk)
+
+    phi0 = explain(model, eeg, spec)
+    if not isinstance(phi0, torch.Tensor):
+        raise ValueError(f"{who}: explain must return a tensor, got {type(phi0).__name__}")
+    _sim_check_maps(who, [phi0])
+    _sim_options(who, phi0.shape, **{k: v for k, v in options.items() if k != "abs"})
+    phi0 = phi0.detach().clone()
+    sims = {m: [] for m in metrics}
+    maps = [] if keep_maps else None
+    with torch.cuda.device(phi0.device):
+        saved = [[(t, t.detach().clone()) for t in owned] for _, owned in plans]
+        try:
+            for s, (actions, _) in enumerate(plans):
+                if order == "independent" and s > 0:
+                    _rand_restore(saved[s - 1])
+                _rand_apply(actions, seed, s)
+                phi = explain(model, eeg, spec)
+                if not isinstance(phi, torch.Tensor) or tuple(phi.shape) != tuple(phi0.shape):
+                    raise ValueError(f"{who}: explain returned {tuple(phi.shape) if isinstance(phi, torch.Tensor) else type(phi).__name__} at stage {s}, "
+                                     f"{tuple(phi0.shape)} for the trained model")
+                res = map_similarity(phi0, phi, **options)
+                for m in metrics:
+                    sims[m].append(getattr(res, m))
+                if keep_maps:
+                    maps.append(phi.detach().clone())
+        finally:
+            _rand_restore([pair for group in saved for pair in group])
+    return RandomizationResult(layers, {m: torch.stack(v, dim=-1) for m, v in sims.items()}, phi0, maps, order, seed)
