@@ -125,14 +125,21 @@ __global__ __launch_bounds__(256) void k_cam(const T* __restrict__ A, const T* _
   }
 }
 
-extern "C" int bx_cam_reduce(const void* A, const void* G, float* cam, float* weights_out, int n_maps, int maps_per_act, int HW, int C,
-                             int method, int relu, int dtype, bxStream stream) {
-  const char* who = method == BX_CAM_GRADCAM ? "bx_gradcam_reduce" : "bx_cam_reduce";
+// What the CAM entry points check first, in this order: the method, Layer-CAM's absent channel weights, the dtype.
+static int cam_check(const char* who, int method, const void* weights_out, int dtype) {
   BX_REQUIRE(method >= BX_CAM_GRADCAM && method <= BX_CAM_LAYERCAM, "%s: unknown method %d (0 = Grad-CAM, 1 = Grad-CAM++, 2 = Layer-CAM)", who, method);
   BX_REQUIRE(method != BX_CAM_LAYERCAM || !weights_out, "%s: Layer-CAM has no channel weights (weights_out must be NULL)", who);
   BX_DTYPE_OK(dtype);
+  return BX_OK;
+}
+static bool cam_c_ok(int C) { return C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0; }
+
+extern "C" int bx_cam_reduce(const void* A, const void* G, float* cam, float* weights_out, int n_maps, int maps_per_act, int HW, int C,
+                             int method, int relu, int dtype, bxStream stream) {
+  const char* who = method == BX_CAM_GRADCAM ? "bx_gradcam_reduce" : "bx_cam_reduce";
+  if (const int e = cam_check(who, method, weights_out, dtype)) return e;
   BX_REQUIRE(A && G && cam && n_maps > 0 && HW > 0 && maps_per_act > 0 && n_maps % maps_per_act == 0, "%s: bad arguments", who);
-  BX_REQUIRE(C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0, "%s: C=%d must be 8*2^k, <= 2048", who, C);
+  BX_REQUIRE(cam_c_ok(C), "%s: C=%d must be 8*2^k, <= 2048", who, C);
   hipStream_t s = (hipStream_t)stream;
   if (method == BX_CAM_GRADCAM) {
     const size_t lds = ((size_t)(256 / (C / 8)) * C + C) * sizeof(float);
@@ -225,14 +232,7 @@ __global__ __launch_bounds__(256) void k_gradcam_head(const T* __restrict__ A, c
       if (lane == 0) dz[n] = acc + ex.db[n];              // logits parked in dz
     }
     __syncthreads();
-    if (tid == 0) {
-      float mx = -INFINITY;
-      for (int n = 0; n < N; ++n) mx = fmaxf(mx, dz[n]);
-      float se = 0.f;
-      for (int n = 0; n < N; ++n) se += expf(dz[n] - mx);
-      const float lse = mx + logf(se);
-      for (int n = 0; n < N; ++n) cat[n] = dz[n] - lse;
-    }
+    if (tid == 0) bx_lsm_row(dz, N, cat);
   } else if (tid < N) cat[tid] = e_lp[(size_t)b * N + tid];
   __syncthreads();
   // ---- fc + LogSoftmax (spectrogram branch head)
@@ -249,14 +249,7 @@ __global__ __launch_bounds__(256) void k_gradcam_head(const T* __restrict__ A, c
     if (lane == 0) ds[n] = acc + fcb[n];             // logits parked in ds
   }
   __syncthreads();
-  if (tid == 0) {
-    float mx = -INFINITY;
-    for (int n = 0; n < N; ++n) mx = fmaxf(mx, ds[n]);
-    float se = 0.f;
-    for (int n = 0; n < N; ++n) se += expf(ds[n] - mx);
-    const float lse = mx + logf(se);
-    for (int n = 0; n < N; ++n) cat[N + n] = ds[n] - lse;
-  }
+  if (tid == 0) bx_lsm_row(ds, N, cat + N);
   __syncthreads();
   // ---- fusion head forward
   for (int j = tid; j < Hd; j += 256) {                 // (rows of small matrices: all of a batch's loads before the first FMA -- a rolled
@@ -279,12 +272,9 @@ __global__ __launch_bounds__(256) void k_gradcam_head(const T* __restrict__ A, c
   }
   __syncthreads();
   if (tid == 0) {
-    float mx = -INFINITY;
-    for (int n = 0; n < N; ++n) mx = fmaxf(mx, dz[n]);
-    float se = 0.f;
-    for (int n = 0; n < N; ++n) se += expf(dz[n] - mx);
-    const float lse = mx + logf(se);
-    for (int n = 0; n < N; ++n) { lp[n] = dz[n] - lse; if (out_lp && blockIdx.y == 0) out_lp[(size_t)b * N + n] = lp[n]; }
+    bx_lsm_row(dz, N, lp);
+    if (out_lp && blockIdx.y == 0)
+      for (int n = 0; n < N; ++n) out_lp[(size_t)b * N + n] = lp[n];
   }
   __syncthreads();
   int first = class_mode, nm = 1;
@@ -443,26 +433,26 @@ __global__ __launch_bounds__(256) void k_gradcam_head(const T* __restrict__ A, c
   }
 }
 
-#define BX_CAM_HEAD_LAUNCH(METHOD, ...) do { switch (METHOD) {                                                                  \
-  case BX_CAM_GRADCAM:    BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_gradcam_head<T>), __VA_ARGS__)); break;                        \
-  case BX_CAM_GRADCAM_PP: BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_gradcam_head<T, BX_CAM_GRADCAM_PP>), __VA_ARGS__)); break;     \
-  default:                BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_gradcam_head<T, BX_CAM_LAYERCAM>), __VA_ARGS__)); break; } } while (0)
+// The two head forms: the sizes (dims: the form's own positive counts), then the launch of the method's and dtype's kernel.
+static int cam_head_sizes(const char* who, bool dims, int C, int N, int Hd) {
+  BX_REQUIRE(dims && cam_c_ok(C) && N > 0 && N <= 64 && Hd > 0 && Hd <= 4096,
+             "%s: unsupported sizes (C=%d must be 8*2^k <= 2048, N=%d <= 64, Hd=%d <= 4096)", who, C, N, Hd);
+  return BX_OK;
+}
+static size_t cam_head_lds(int C, int N, int Hd) { return ((size_t)2 * C + 2 * Hd + 5 * N + (size_t)(256 / (C / 8)) * C) * sizeof(float); }
+#define BX_CAM_HEAD_LAUNCH(...) BX_DISPATCH_CAM(method, M, BX_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((k_gradcam_head<T, M>), __VA_ARGS__)))
 
 extern "C" int bx_cam_head(const void* A, const float* eeg_logp, const float* fc_w, const float* fc_b, const float* w1, const float* b1,
                            const float* w2, const float* b2, float* out_logp, float* cam, float* raw, float* weights_out, int B, int HW,
                            int C, int N, int Hd, int class_mode, int method, int relu, int dtype, bxStream stream) {
   const char* who = method == BX_CAM_GRADCAM ? "bx_gradcam_head" : "bx_cam_head";
-  BX_REQUIRE(method >= BX_CAM_GRADCAM && method <= BX_CAM_LAYERCAM, "%s: unknown method %d (0 = Grad-CAM, 1 = Grad-CAM++, 2 = Layer-CAM)", who, method);
-  BX_REQUIRE(method != BX_CAM_LAYERCAM || !weights_out, "%s: Layer-CAM has no channel weights (weights_out must be NULL)", who);
-  BX_DTYPE_OK(dtype);
+  if (const int e = cam_check(who, method, weights_out, dtype)) return e;
   BX_REQUIRE(A && eeg_logp && fc_w && fc_b && w1 && b1 && w2 && b2 && cam, "%s: null pointer", who);
-  BX_REQUIRE(B > 0 && HW > 0 && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0 && N > 0 && N <= 64 && Hd > 0 && Hd <= 4096,
-             "%s: unsupported sizes (C=%d must be 8*2^k <= 2048, N=%d <= 64, Hd=%d <= 4096)", who, C, N, Hd);
+  if (const int e = cam_head_sizes(who, B > 0 && HW > 0, C, N, Hd)) return e;
   BX_REQUIRE(class_mode >= -2 && class_mode < N, "%s: class %d out of range", who, class_mode);
-  const size_t lds = ((size_t)2 * C + 2 * Hd + 5 * N + (size_t)(256 / (C / 8)) * C) * sizeof(float);
   const GcExtra none = {nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0};
-  BX_CAM_HEAD_LAUNCH(method, dim3(B, class_mode == -2 ? N : 1), dim3(256), lds, (hipStream_t)stream, (const T*)A, eeg_logp, fc_w, fc_b, w1, b1,
-                     w2, b2, out_logp, cam, raw, weights_out, HW, C, N, Hd, class_mode, relu, none);
+  BX_CAM_HEAD_LAUNCH(dim3(B, class_mode == -2 ? N : 1), dim3(256), cam_head_lds(C, N, Hd), (hipStream_t)stream, (const T*)A, eeg_logp, fc_w, fc_b,
+                     w1, b1, w2, b2, out_logp, cam, raw, weights_out, HW, C, N, Hd, class_mode, relu, none);
   BX_CHECK_LAUNCH(who);
   return BX_OK;
 }
@@ -477,18 +467,16 @@ extern "C" int bx_cam_head_sweep(const void* A, const float* eeg_feat, const flo
                                  float* maps, int B, int h, int w, int C, int N, int Hd, int H, int W, int class_mode, int method, int relu,
                                  int dtype, bxStream stream) {
   const char* who = method == BX_CAM_GRADCAM ? "bx_gradcam_head_sweep" : "bx_cam_head_sweep";
-  BX_REQUIRE(method >= BX_CAM_GRADCAM && method <= BX_CAM_LAYERCAM, "%s: unknown method %d (0 = Grad-CAM, 1 = Grad-CAM++, 2 = Layer-CAM)", who, method);
-  BX_DTYPE_OK(dtype);
+  if (const int e = cam_check(who, method, nullptr, dtype)) return e;
   BX_REQUIRE(A && eeg_feat && dense_w && dense_b && fc_w && fc_b && w1 && b1 && w2 && b2 && maps, "%s: null pointer", who);
   const int HW = h * w;
-  BX_REQUIRE(B > 0 && h > 0 && w > 0 && C % 8 == 0 && C >= 8 && C <= 2048 && 256 % (C / 8) == 0 && N > 0 && N <= 64 && Hd > 0 && Hd <= 4096 && Fe > 0,
-             "%s: unsupported sizes (C=%d must be 8*2^k <= 2048, N=%d <= 64, Hd=%d <= 4096)", who, C, N, Hd);
+  if (const int e = cam_head_sizes(who, B > 0 && h > 0 && w > 0 && Fe > 0, C, N, Hd)) return e;
   BX_REQUIRE(H > 0 && W > 0 && W % 4 == 0 && ((uintptr_t)maps & 15) == 0, "%s: W must be a multiple of 4 and maps 16-byte aligned", who);
   BX_REQUIRE(class_mode >= -2 && class_mode < N, "%s: class %d out of range", who, class_mode);
-  const size_t lds = ((size_t)2 * C + 2 * Hd + 5 * N + (size_t)(256 / (C / 8)) * C + HW) * sizeof(float);
+  const size_t lds = cam_head_lds(C, N, Hd) + HW * sizeof(float);
   BX_REQUIRE(lds <= 64 * 1024, "%s: stage output of %d positions x %d channels does not fit the workgroup's LDS", who, HW, C);
   const GcExtra ex = {eeg_feat, dense_w, dense_b, Fe, maps, h, w, H, W};
-  BX_CAM_HEAD_LAUNCH(method, dim3(B, class_mode == -2 ? N : 1), dim3(256), lds, (hipStream_t)stream, (const T*)A, (const float*)nullptr, fc_w,
+  BX_CAM_HEAD_LAUNCH(dim3(B, class_mode == -2 ? N : 1), dim3(256), lds, (hipStream_t)stream, (const T*)A, (const float*)nullptr, fc_w,
                      fc_b, w1, b1, w2, b2, out_logp, (float*)nullptr, (float*)nullptr, (float*)nullptr, HW, C, N, Hd, class_mode, relu, ex);
   BX_CHECK_LAUNCH(who);
   return BX_OK;

@@ -144,6 +144,15 @@ __device__ __forceinline__ float campp_term(float g, float S) {
   return g > 0.f ? g3 / (2.f * g2 + S * g3 + BX_CAM_EPS) : 0.f;
 }
 
+// LogSoftmax of one row by one thread (max, sum of exp, subtract): the heads' N is a handful of classes.  out may be logit.
+__device__ __forceinline__ void bx_lsm_row(const float* logit, int N, float* out) {
+  float m = -INFINITY;
+  for (int n = 0; n < N; ++n) m = fmaxf(m, logit[n]);
+  float se = 0.f;
+  for (int n = 0; n < N; ++n) se += expf(logit[n] - m);
+  const float lse = m + logf(se);
+  for (int n = 0; n < N; ++n) out[n] = logit[n] - lse;
+}
 // LogSoftmax backward for one row, dz_n = dy_n - softmax_n * sum_j dy_j, evaluated WITHOUT its cancellation:
 //     dz_n = dy_n * (sum_{j != n} p_j)  -  p_n * (sum_{j != n} dy_j),      p = exp(logp).
 // The textbook form computes (1 - p_n) by subtraction; with a one-hot seed on a confident sample (saliency / Grad-CAM of the
@@ -499,3 +508,8 @@ static inline int bx_partial_slices(int n, int nchunk) { return (n >= 16384 || n
 
 #define BX_DISPATCH_DTYPE(dtype, T, ...) \
   do { if ((dtype) == BX_F32) { typedef float T; __VA_ARGS__; } else { typedef bf16_t T; __VA_ARGS__; } } while (0)
+// the same for a class-activation method (BX_CAM_*; the caller has checked its range): M is the method as a constant expression
+#define BX_DISPATCH_CAM(method, M, ...) do { switch (method) {                                     \
+  case BX_CAM_GRADCAM:    { constexpr int M = BX_CAM_GRADCAM;    __VA_ARGS__; } break;                \
+  case BX_CAM_GRADCAM_PP: { constexpr int M = BX_CAM_GRADCAM_PP; __VA_ARGS__; } break;                \
+  default:                { constexpr int M = BX_CAM_LAYERCAM;   __VA_ARGS__; } break; } } while (0)

@@ -359,14 +359,6 @@ extern "C" int bx_kldiv_fwd_bwd(const float* logp, const float* target, float* l
 #define MMH_MAXC 1024
 #define MMH_MAXHD 256
 
-__device__ __forceinline__ void mmh_lsm(const float* logit, int N, float* out) {      // serial, N <= HEAD_MAX_N
-  float m = -INFINITY;
-  for (int n = 0; n < N; ++n) m = fmaxf(m, logit[n]);
-  float se = 0.f;
-  for (int n = 0; n < N; ++n) se += expf(logit[n] - m);
-  const float lse = m + logf(se);
-  for (int n = 0; n < N; ++n) out[n] = logit[n] - lse;
-}
 // dot of a global row with an LDS vector by one wave (all loads of a lane issued before the adds)
 __device__ __forceinline__ float mmh_wave_dot(const float* __restrict__ wrow, const float* vec, int n, int lane) {
   float acc = 0.f;
@@ -457,7 +449,7 @@ __global__ __launch_bounds__(256) void k_mm_head_fwd(const T* __restrict__ feat,
     }
   }
   __syncthreads();
-  if (tid < 2) mmh_lsm(lg + tid * N, N, z + tid * N);
+  if (tid < 2) bx_lsm_row(lg + tid * N, N, z + tid * N);
   __syncthreads();
   if (tid < 2 * N) (tid < N ? e_logp : s_logp)[(size_t)b * N + (tid < N ? tid : tid - N)] = z[tid];
   if (FAST) {
@@ -500,7 +492,7 @@ __global__ __launch_bounds__(256) void k_mm_head_fwd(const T* __restrict__ feat,
     }
   }
   __syncthreads();
-  if (tid == 0) mmh_lsm(lo, N, lg);
+  if (tid == 0) bx_lsm_row(lo, N, lg);
   __syncthreads();
   if (tid < N) logp[(size_t)b * N + tid] = lg[tid];
 }

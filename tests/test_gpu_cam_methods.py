@@ -15,6 +15,7 @@ from brainxai import ops
 from oracle import ref_torch as O
 from tests.cam_ref import cam as cam_fp64
 from tests.eeg_gradcam_setup import bn_nontrivial, rel
+from tests.eeg_gradcam_setup import inputs as eeg_inputs
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -164,6 +165,22 @@ def test_methods_match_oracle(pair, method, target, class_idx):
     ref64, mine = pair
     eeg, spec = _inputs(2)
     _check(ref64, lambda: ref64(eeg.double(), spec.double()), mine, (eeg.to(DEV), spec.to(DEV)), target, class_idx, method)
+
+
+@pytest.mark.parametrize("chans,samples,B", [(3, 1030, 2), (2, 40, 1)])
+@pytest.mark.parametrize("method", METHODS)
+def test_methods_match_oracle_ragged_and_tiny_eeg(method, chans, samples, B):
+    """The EEG targets off the multiples of four (the last two geometries of test_eeg_gradcam_pool_tails_and_native_geometry in
+    tests/test_gpu_eeg_gradcam.py, with its weights and inputs).  At 1030 Layer-CAM's zero tail is the two positions behind
+    T1 P1 = 1028."""
+    ref = O.fill_params(O.build_multimodal(chans, samples, 4, dropout=0.0), seed=7)
+    bn_nontrivial(ref.eeg_model, 8)
+    mine = brainxai.build_multimodal(chans, samples, 4, dropout=0.0)
+    mine.load_state_dict(ref.state_dict())
+    ref64, mine = copy.deepcopy(ref).double().eval(), mine.to(DEV)
+    eeg, spec = eeg_inputs(B, chans, samples, seed=13)
+    for target in EEG_TARGETS:
+        _check(ref64, lambda: ref64(eeg.double(), spec.double()), mine, (eeg.to(DEV), spec.to(DEV)), target, "all", method)
 
 
 @pytest.mark.parametrize("method", METHODS)

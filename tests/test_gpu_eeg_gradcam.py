@@ -66,9 +66,12 @@ def test_eeg_gradcam_matches_oracle(bench_pair, target, class_idx):
     _check(ref, mine, eeg, spec, target, class_idx)
 
 
-@pytest.mark.parametrize("chans,samples,B", [(19, 2100, 2), (5, 300, 1), (37, 3000, 2)])
+@pytest.mark.parametrize("chans,samples,B", [(19, 2100, 2), (5, 300, 1), (37, 3000, 2), (3, 1030, 2), (2, 40, 1)])
 def test_eeg_gradcam_pool_tails_and_native_geometry(chans, samples, B):
     # 2100 and 300: T//4 is not a multiple of 8, so the second pooling drops a tail (T2*P2 < T1)
+    # 1030: T % 4 = 2 (scalar stores in the conv1 map kernel, no 16-byte dmap loads), T1 = 257 (a second tile with one live step),
+    #       T2 P2 = 256 < T1, T1 P1 = 1028 < T, and a second conv1 workgroup of six steps
+    # 40:   T1 = 10, T2 = 1: one pooled column, fewer steps than threads everywhere, the tile halo mostly outside the row
     ref, mine = _mm_pair(chans, samples, seed=7)
     eeg, spec = inputs(B, chans, samples, seed=13)
     for target in TARGETS:
