@@ -948,6 +948,53 @@ int bx_blurig_accumulate(const float* g, const float* deriv, const double* w, do
 /* out[r] = sum_t (double)v[r,t] for v fp32 [R,L], out fp64 [R]: the sum behind delta, one row per (sample, class), in the order of
  * bx_mean_abs_rows -- 64 partial sums over t = l, l + 64, ... (ascending), added by a fixed pairwise tree.  R * L < 2^31. */
 int bx_blurig_sum_rows(const float* v, double* out, int R, int L, bxStream stream);
+/* ---- Guided Integrated Gradients (Kapishnikov et al., CVPR 2021; PAIR's saliency.GuidedIG): the adaptive path from a baseline to the
+ * input that moves, at every step, only the cells with the smallest |gradient|.
+ * One row is one (sample b, explained class c) pair of P cells, row r = b * Kc + slot.  fp32: the input x_in, the baseline x_base, the
+ * moving point x (it starts at x_base) and g, the gradient of F_c (the model's output log-probability of class c) at x.  fp64: attr [P],
+ * which starts at 0.  n steps, fraction in (0, 1], max_dist in [0, 1]; k = floor((P - 1) * fraction), computed by the host in fp64
+ * (numpy's quantile(.., 'lower') index).  Every difference below is taken in fp64 from the fp32 values.
+ *   L_total = SUM_e |x_in - x_base|.  A row with L_total = 0 never moves: its values are 0.
+ *   X(alpha)_e = fl32( x_base_e + alpha * (x_in_e - x_base_e) ), alpha fp64; the product and the sum are one fp64 rounding each (no fma),
+ *     then one rounding to fp32.  X(alpha) is x_in bit for bit for alpha >= 1 and x_base bit for bit for alpha <= 0.
+ *   Step i = 0..n-1, with g taken once at the top of the step:  alpha = (i + 1) / n,  a_min = max(alpha - max_dist, 0),
+ *     a_max = min(alpha + max_dist, 1),  X_min = X(a_min),  X_max = X(a_max),  L_target = L_total * (1 - alpha).  A NaN among the row's g
+ *     stops the row before anything of the step is written (status BX_GUIDED_NAN).  Otherwise repeat (one repetition is a pass):
+ *     1. x_old = x.
+ *     2. a_e = (x_e - x_base_e) / (x_in_e - x_base_e) in fp64, a_max for a cell with x_in_e == x_base_e; where a_e < a_min, x_e = X_min_e.
+ *     3. L_cur = SUM_e |x_in_e - x_e|.
+ *     4. If |L_target - L_cur| <= max(1e-9 * max(|L_target|, |L_cur|), 1e-9) (Python's math.isclose): attr_e += (x_e - x_old_e) * g_e and
+ *        the step ends.
+ *     5. A cell has arrived when x_e == X_max_e (fp32 equality).  key_e = |g_e| for a cell that has not arrived, +inf for one that has;
+ *        theta = the k-th smallest key (0-based, duplicates counted); S = { e not arrived : key_e <= theta }: every tie of theta is in S,
+ *        theta = +inf selects every cell that has not arrived.
+ *     6. L_S = SUM_e ( e in S ? |X_max_e - x_e| : 0 );  gamma = (L_cur - L_target) / L_S if L_S > 0, else +inf.
+ *     7. On S:  gamma > 1: x_e = X_max_e;  0 < gamma <= 1: x_e = fl32( x_e + gamma * (X_max_e - x_e) ), product and sum one fp64 rounding
+ *        each;  gamma <= 0 (rounding alone): nothing moves.
+ *     8. attr_e += (x_e - x_old_e) * g_e: product and sum one fp64 rounding each; g is the gradient itself, not the key.
+ *     9. Go on while gamma > 1 and L_S > 0.  L_S = 0 means that S is empty, which means that every cell has arrived: no further pass can
+ *        move anything, the step ends.  (With max_dist = 0 every step ends this way once fp32 rounding keeps L_cur from meeting
+ *        L_target to nine digits; the result is then the left Riemann sum SUM_i g(X(i/n)) * (X((i+1)/n) - X(i/n)).)
+ *   Every pass that goes on makes at least min(k + 1, cells left) further cells arrive, so a step has at most ceil(P / (k + 1)) + 2
+ *   passes; the host passes that number as `cap`, and a row that has made cap passes and would go on stops with BX_GUIDED_CAP.
+ *   A row whose status is not 0 is left alone by every later step.  values = fl32(attr) (bx_expgrad_finish with n = 1).
+ * Sums (L_total, L_cur, L_S), fp64 in an order that depends on P alone: 1024 partial sums over e = t, t + 1024, ... (ascending); inside
+ * each group of 64 consecutive partials the xor butterfly (offsets 32, 16, .., 1: p_l += p_{l ^ o}); the 16 group totals added in
+ * ascending order.
+ * The kernel: one workgroup per row, a cell is owned by one thread through all sweeps of all passes; theta by an exact radix select
+ * over the keys' bit patterns (non-negative fp32 values and +inf order as unsigned integers), four digits of eight bits, integer LDS
+ * counters.  No loop is unbounded, no workgroup waits for another.  1 <= P < 2^20, R = B * Kc <= 65535, R * P < 2^31 and R * n < 2^31:
+ * anything else is BX_EUNSUPPORTED before a pointer is touched. */
+enum { BX_GUIDED_OK = 0, BX_GUIDED_CAP = 1, BX_GUIDED_NAN = 2 };
+/* x fp32 [R,P] = the baseline of the row's sample, attr fp64 [R,P] = 0, L_total fp64 [R], status i32 [R] = 0.  x_in fp32 [B,P]; base
+ * fp32 [B,P] (base_rows != 0) or one value for every cell (base_rows == 0, base[0]). */
+int bx_guided_ig_init(const float* x_in, const float* base, int base_rows, float* x, double* attr, double* L_total, int* status, int B, int Kc, int P,
+                      bxStream stream);
+/* All passes of step i for rows row0 .. row0+rows-1 in one launch.  x_in, x_base fp32 [B,P]; x fp32 [R,P], attr fp64 [R,P], L_total
+ * fp64 [R], status i32 [R] and iters i32 [R,n] are the whole arrays; g fp32 [rows,P] holds the gradients of the call's rows.  iters[r,i]
+ * = the passes row r made in this step (0 for a row that is stopped, stops with BX_GUIDED_NAN or has L_total = 0). */
+int bx_guided_ig_step(const float* x_in, const float* x_base, float* x, const float* g, double* attr, const double* L_total, int* status, int* iters,
+                      int B, int Kc, int P, int i, int n, int k, double max_dist, int cap, int row0, int rows, bxStream stream);
 /* ---- Spectral attributions of the EEG input: amplitude gradients and spectral occlusion (Schirrmeister et al., Hum. Brain Mapp. 2017;
  * braindecode's compute_amplitude_gradients).  For a row x[0..T) (one electrode of one sample), F = T / 2 + 1 bins (integer division):
  *   Transform:  X_f = sum_t x_t (cos th - i sin th),  th = 2 pi ((f t) mod T) / T,  f = 0..F-1.

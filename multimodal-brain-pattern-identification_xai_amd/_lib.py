@@ -22,6 +22,7 @@ BX_CAM_GRADCAM, BX_CAM_GRADCAM_PP, BX_CAM_LAYERCAM = 0, 1, 2
 BX_SCORECAM_PROB, BX_SCORECAM_INCREASE = 0, 1
 BX_BLUR_AXES_HW, BX_BLUR_AXES_H, BX_BLUR_AXES_W = 0, 1, 2
 BX_BLUR_MAX_RADIUS = 16384
+BX_GUIDED_OK, BX_GUIDED_CAP, BX_GUIDED_NAN = 0, 1, 2
 BX_SPECTRAL_AMPLITUDE_GRADIENT, BX_SPECTRAL_GRADIENT_X_AMPLITUDE = 0, 1
 BX_SPECTRAL_CELLS_BAND, BX_SPECTRAL_CELLS_ELECTRODE_BAND = 0, 1
 BX_SPECTRAL_MAX_T = 8192
@@ -221,6 +222,8 @@ SIGNATURES = {
     "bx_blur_rows": (i32, [vp] * 5 + [i32] * 10 + [vp]),
     "bx_blurig_accumulate": (i32, [vp] * 4 + [i32] * 7 + [vp]),
     "bx_blurig_sum_rows": (i32, [vp, vp, i32, i32, vp]),
+    "bx_guided_ig_init": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "bx_guided_ig_step": (i32, [vp] * 8 + [i32] * 6 + [C.c_double, i32, i32, i32, vp]),
     "bx_rdft_rows": (i32, [vp] * 4 + [i32, i32, vp]),
     "bx_spectral_accumulate": (i32, [vp] * 3 + [i32] * 7 + [vp]),
     "bx_spectral_values": (i32, [vp] * 5 + [i32] * 5 + [vp]),

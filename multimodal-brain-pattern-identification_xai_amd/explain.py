@@ -51,6 +51,11 @@
                                  (bx_blur_rows), an fp64 running sum of w * gradient * derivative in fixed step order
                                  (bx_blurig_accumulate), the completeness error from fp64 row sums (bx_blurig_sum_rows).
                                  ``blur_path`` returns the rows, ``gaussian_blur`` is the same kernel as a plain blur.
+* ``guided_ig``               -- Guided Integrated Gradients (Kapishnikov et al., CVPR 2021; saliency.GuidedIG; not in the reference):
+                                 the adaptive path from a baseline to the input on which, at every step, only the cells with the
+                                 smallest |gradient| move; every (sample, class) pair walks its own path, and a step's whole inner
+                                 loop -- clamp, fp64 sums, the exact k-th smallest |gradient| by a radix select, move, fp64
+                                 attribution -- is one launch (bx_guided_ig_init, bx_guided_ig_step) between the model's passes.
 * ``spectral_gradients`` / ``spectral_occlusion`` -- the EEG input explained by frequency (Schirrmeister et al. 2017; braindecode's
                                  compute_amplitude_gradients; not in the reference): a real DFT of any length as a direct fp64 sum over a
                                  host-made twiddle table (bx_rdft_rows), the path-weighted gradient summed in fp64 in fixed step order
@@ -2847,6 +2852,156 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
                 endpoint = _fuse(model, multimodal, gp.input_is_spec, net(last), gp.fixed).float().contiguous()
             delta = gp.completeness(values, per, endpoint)
     return gp.result(return_parts, BlurIGResult, amap, values, endpoint, delta, sigmas, n, max_sigma, sqrt, eps, axes)
+
+
+# ------------------------------------------------------------------------------------------------
+# Guided Integrated Gradients (Kapishnikov et al., CVPR 2021; PAIR's saliency.GuidedIG).  The definition is pinned in include/brainxai.h;
+# tests/guided_ig_ref.py restates it.
+GuidedIGResult = collections.namedtuple("GuidedIGResult", "map values classes out endpoint delta iterations path gradients steps fraction max_dist baseline")
+GuidedIGResult.__doc__ = """What ``guided_ig(..., return_parts=True)`` returns: ``map`` fp32 [B,H,W] / [B,Chans,T], with a class axis for class_idx='all'
+(what the plain call returns), ``values`` fp32 [B(,K),*x.shape[1:]] (the attribution element by element), ``classes`` int64 [B] (None
+for class_idx='all'), ``out`` fp32 [B,K] (the log-probabilities of the clean input), ``endpoint`` fp32 [B,K] (those of the baseline),
+``delta`` fp64 [B] or [B,K] (sum of the values - (F_c(x) - endpoint_c): the completeness error), ``iterations`` int32 [B(,K),steps] (the
+passes every step took), ``path`` and ``gradients`` fp32 [B(,K),steps,*x.shape[1:]] (the point and the gradient at the top of every step;
+None without keep_path), all on the device; the other fields as given."""
+
+_GUIDED_MAX_CELLS = (1 << 20) - 1                                                 # a row of bx_guided_ig_step (include/brainxai.h)
+_GUIDED_MAX_PASSES = 1024
+
+
+def guided_ig_passes(cells, fraction):
+    """(k, cap): the rank k = floor((cells - 1) * fraction) of the threshold among a row's |gradients| (numpy's quantile(.., 'lower') index)
+    and the most passes a step of ``guided_ig`` can take, ceil(cells / (k + 1)) + 2."""
+    k = int(math.floor((int(cells) - 1) * float(fraction)))
+    return k, -(-int(cells) // (k + 1)) + 2
+
+
+def _guided_steps(who, steps, fraction, max_dist):
+    if isinstance(steps, bool) or not isinstance(steps, numbers.Integral):
+        raise ValueError(f"{who}: steps must be an int, got {steps!r}")
+    if int(steps) < 1:
+        raise ValueError(f"{who}: steps = {int(steps)} < 1")
+    if isinstance(fraction, bool) or not isinstance(fraction, numbers.Real) or not 0 < fraction <= 1:
+        raise ValueError(f"{who}: fraction must be a number in (0, 1], got {fraction!r}")
+    if isinstance(max_dist, bool) or not isinstance(max_dist, numbers.Real) or not 0 <= max_dist <= 1:
+        raise ValueError(f"{who}: max_dist must be a number in [0, 1], got {max_dist!r}")
+    return int(steps), float(fraction), float(max_dist)
+
+
+def guided_ig(model, eeg, spec, *, input="spec", steps=200, fraction=0.25, max_dist=0.02, baseline=0.0, class_idx=None, max_batch=256,
+              keep_path=False, return_parts=False):
+    """Guided Integrated Gradients (Kapishnikov et al., CVPR 2021; saliency.GuidedIG): integrated gradients along a path from the
+    baseline to the input that is chosen while it is walked -- at every step only the ``fraction`` of the cells with the smallest
+    |gradient| move, and no cell strays further than ``max_dist`` from the straight line -- so that cells whose large gradients have
+    nothing to do with the prediction do not collect attribution on the way.  For either input of the multimodal model or a
+    stand-alone branch, batched over samples and classes; F_c is the model's output log-probability of class c.
+
+    input:       'spec': x = spec [B,C,H,W], map [B,H,W] (the values summed over the channels); 'eeg': x = eeg [B,1,Chans,T], map
+                 [B,Chans,T] (the values themselves).
+    model:       a MultimodalModel (the other input stays the sample's own); a stand-alone Spectrogram_Model (eeg=None, input='spec');
+                 a stand-alone EEGNet / EEGNetAttentionDeep (spec=None, input='eeg').
+    steps, fraction, max_dist: saliency's x_steps, fraction and max_dist; max_dist = 0 walks the straight line (the left Riemann sum of
+                 integrated gradients).  A fraction so small that a step could take more than 1024 passes is refused.
+    baseline:    a number, one value per channel / electrode, or a tensor of the input's shape (``gaussian_blur``'s result fits).
+    class_idx:   None = each sample's arg-max class on the clean input; an int; one class per sample (sequence / tensor [B]); 'all' =
+                 every class, the map gains a class axis [B,K,...] (K <= 32).  Every (sample, class) pair walks a path of its own.
+    max_batch:   rows ((sample, class) points) per forward and backward pass.  No bit of the result depends on it.
+    keep_path:   keep the point and the gradient at the top of every step (``path``, ``gradients`` of the result).
+    Per step and per pass of at most max_batch rows: one forward pass, one backward pass whose one-hot seed names each row's own class
+    (bx_expgrad_seed), and one bx_guided_ig_step, which runs every pass of the step's inner loop for those rows on the device -- the
+    clamp to the window, the fp64 sums, the exact k-th smallest |gradient| by a radix select, the move and the fp64 attribution -- so
+    the host is not asked anything inside a step; the rows' status is read once, after the last step.  bx_expgrad_finish rounds the
+    values and sums the channels; ``delta`` is the completeness error sum(values) - (F_c(x) - F_c(baseline)) (bx_blurig_sum_rows), reported,
+    not minimised.  In a MultimodalModel the branch whose input does not change runs once per sample.  The training flag and every
+    requires_grad are restored on return.  Returns the map (device, fp32), or ``GuidedIGResult`` with return_parts."""
+    return _guided_ig(model, eeg, spec, input, steps, fraction, max_dist, baseline, class_idx, max_batch, keep_path, return_parts)
+
+
+def _guided_ig(model, eeg, spec, input, steps, fraction, max_dist, baseline, class_idx, max_batch, keep_path, return_parts, profile=None):
+    """``guided_ig`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'forward', 'backward',
+    'step', 'finish' -- device events around every phase of the pass (tools/guided_ig_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "guided_ig"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    n, fraction, max_dist = _guided_steps(who, steps, fraction, max_dist)
+    max_batch = _max_batch(who, max_batch)
+    x = _input_tensor(who, input, eeg, spec)
+    B = _nonempty(who, x)
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    Kc = K if all_classes else 1
+    per, R = x.numel() // B, B * Kc
+    if per > _GUIDED_MAX_CELLS:
+        raise ValueError(f"{who}: {per} cells per sample, supported 1..{_GUIDED_MAX_CELLS}")
+    if R * n >= 1 << 31 or R * per >= 1 << 31 or R > 65535:
+        raise ValueError(f"{who}: B * Kc * steps = {R * n} or B * Kc * per = {R * per} beyond 32-bit offsets, or B * Kc = {R} > 65535; use fewer samples per call")
+    per_len, what = _per_cell(who, x, input == "spec")
+    kind, base = _baseline_for(who, baseline, x, per_len, what)
+    k, cap = guided_ig_passes(per, fraction)
+    if cap > _GUIDED_MAX_PASSES:
+        raise ValueError(f"{who}: fraction = {fraction!r} is too small for an input of {per} cells: a step could take {cap} passes, "
+                         f"supported up to {_GUIDED_MAX_PASSES}")
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+
+    lib = L.load()
+    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", 1, cls_h, all_classes, max_batch, profile)
+    with gp.open():
+        xs, dev, trail = gp.xs, gp.dev, tuple(gp.xs.shape[1:])
+        base = base.to(dev, torch.float32)
+        if kind == 1:
+            base = base.reshape((1, -1, 1, 1) if gp.input_is_spec else (1, 1, -1, 1))
+        xb = (base.reshape(xs.shape) if kind == 2 else base.expand_as(xs)).contiguous()
+        gp.clean()
+        row_cls = (torch.arange(K, dtype=torch.int32, device=dev).repeat(B) if all_classes else gp.classes).contiguous()
+        xr = torch.empty(R, *trail, dtype=torch.float32, device=dev)             # the moving points, one row per (sample, class)
+        attr = torch.empty(R, per, dtype=torch.float64, device=dev)
+        l_total = torch.empty(R, dtype=torch.float64, device=dev)
+        status = torch.empty(R, dtype=torch.int32, device=dev)
+        iters = torch.zeros(R, n, dtype=torch.int32, device=dev)
+        path = torch.empty(R, n, *trail, dtype=torch.float32, device=dev) if keep_path else None
+        grads = torch.empty(R, n, *trail, dtype=torch.float32, device=dev) if keep_path else None
+        with gp.lap("step"):
+            L.check(lib.bx_guided_ig_init(_p(xs), _p(xb), 1, _p(xr), _p(attr), _p(l_total), _p(status), B, Kc, per, _stream()), "bx_guided_ig_init")
+        with torch.no_grad(), gp.lap("forward"):
+            endpoint = _fuse(model, multimodal, gp.input_is_spec, net(xb), gp.fixed).float().contiguous()
+        seed_rows = torch.empty(min(gp.max_rows, R), K, dtype=torch.float32, device=dev)
+        for i in range(n):
+            if keep_path:
+                path[:, i] = xr
+            for row0, rows in _sample_chunks(R, gp.max_rows):
+                with gp.lap("forward"):
+                    r = xr[row0:row0 + rows].detach().requires_grad_(True)      # the kernel's own rows: no copy
+                    rep = gp.fixed.index_select(0, _sample_of(row0, rows, Kc, dev)) if multimodal else None
+                    y = _fuse(model, multimodal, gp.input_is_spec, net(r), rep).float()
+                with gp.lap("backward"):
+                    L.check(lib.bx_expgrad_seed(_p(row_cls), -1, _p(seed_rows), R, 1, K, row0, rows, _stream()), "bx_expgrad_seed")
+                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows[:rows])
+                    g = g.to(torch.float32).contiguous()
+                del y, r
+                if keep_path:
+                    grads[row0:row0 + rows, i] = g
+                with gp.lap("step"):
+                    L.check(lib.bx_guided_ig_step(_p(xs), _p(xb), _p(xr), _p(g), _p(attr), _p(l_total), _p(status), _p(iters), B, Kc, per, i, n, k,
+                                                  max_dist, cap, row0, rows, _stream()), "bx_guided_ig_step")
+        with gp.lap("finish"):
+            values = gp.empty(*trail)
+            amap = gp.empty(*trail[1:]) if gp.input_is_spec else None
+            L.check(lib.bx_expgrad_finish(_p(attr), _p(values), _p(amap), R, gp.Cc, gp.HW, 1, _stream()), "bx_expgrad_finish")
+            if amap is None:                                        # an EEG input has one channel: the map is the values
+                amap = values[:, :, 0]
+            delta = gp.completeness(values, per, endpoint)
+        st = status.cpu()                                           # the one read of the rows' status
+        if bool((st != L.BX_GUIDED_OK).any()):
+            bad = int((st != L.BX_GUIDED_OK).nonzero()[0])
+            why = ("a NaN among the gradients" if int(st[bad]) == L.BX_GUIDED_NAN else f"a step that did not end within {cap} passes")
+            raise RuntimeError(f"brainxai.{who}: sample {bad // Kc}, class slot {bad % Kc} stopped: {why}")
+    shape = (lambda t: t.reshape(B, Kc, *t.shape[1:]) if all_classes else t)
+    return gp.result(return_parts, GuidedIGResult, amap, values, endpoint, delta, shape(iters), None if path is None else shape(path),
+                     None if grads is None else shape(grads), n, fraction, max_dist, baseline)
 
 
 # ------------------------------------------------------------------------------------------------
