@@ -1102,6 +1102,48 @@ int bx_ssim_rows(const float* a, const float* b, const double* taps, const float
 /* p fp32 [n] on the device, 1 <= n < 2^31: the re-initialisation above.  One Philox block serves four elements; 16-byte stores when p is
  * 16-byte aligned, the partial last block element by element. */
 int bx_param_uniform(float* p, size_t n, float bound, uint64_t seed, uint32_t j, uint32_t s, bxStream stream);
+/* ---- Fusion SHAP: the exact Shapley values of the votes the two branches hand to the fusion head (Shapley 1953; Lundberg & Lee,
+ * NeurIPS 2017, the interventional value function of Janzing et al., AISTATS 2020).  The model is a late fusion: each branch emits K
+ * log-probabilities (its votes), the head F is cat -> Linear(2K,Hd) -> ReLU -> Linear(Hd,K) -> LogSoftmax (bx_fusion_head_fwd).  For
+ * sample b the fused input is z = (e_0..e_K-1, s_0..s_K-1); vote i < K is the EEG branch's, vote K + i the spectrogram branch's.  A
+ * player is a group of votes; the M <= 16 players partition the 2K votes.  For a coalition S of players, a class c and the background
+ * rows z(j), j < Nb (a row supplies both branches' votes of the same background sample: a joint background):
+ *     v_c(S) = (1/Nb) sum_j score_c( F( z on the votes of S, z(j) on the others ) )
+ *     phi_i  = sum over S without i of |S|! (M - |S| - 1)! / M! * ( v(S + i) - v(S) )           over all 2^M coalitions
+ * so that sum_i phi_i = v(all) - v(none) = score(sample) - mean score(background).  The modality game is the M = 2 game of {all EEG
+ * votes}, {all spectrogram votes}; it is not the sum of its members' values in a finer game.  interaction = v(all) - v(EEG) - v(spec)
+ * + v(none) of that game: positive when the two modalities reinforce each other for the class.
+ * Every entry point refuses its limits with BX_EINVAL before any pointer is touched. */
+#define BX_FUSION_SCORE_PROB 0
+#define BX_FUSION_SCORE_LOGPROB 1
+/* The values of a list of coalitions.  e_x, s_x fp32 [B,K] (the samples' votes), e_bg, s_bg fp32 [Nb,K] (the background rows'), masks
+ * u32 [NS] on the device: bit i set = vote i comes from the sample, clear = from the background row; bits 2K.. are ignored.  The
+ * players are expanded to vote masks by the caller, and the four masks of the modality game are ordinary entries of the list.  w1
+ * [Hd,2K], b1 [Hd], w2 [K,Hd], b2 [K]: the head.  v fp64 [B,NS,K], every element written.
+ * Arithmetic, the same for every mask.  fp32 with the clean head's operations.  The 2K votes are cut into groups of at most 8: for
+ * K <= 8 the EEG half and the spectrogram half, for K > 8 votes 0..7, 8..K-1, K..K+7, K+8..2K-1.  The partial sum of a group is one fmaf
+ * chain over its votes in ascending order, the first group's starting from b1[h] and the others' from 0; the pre-activation is the
+ * groups' partial sums added in group order, ((g0 + g1) + g2) + g3.  (The clean head runs one chain over all 2K votes: the two differ
+ * by the rounding of the joins.)  Then max(., 0); logit_k = one fmaf chain over h = 0..Hd-1 starting from b2[k], the clean head's order;
+ * the max-shifted log-sum-exp in class order.  BX_FUSION_SCORE_LOGPROB scores the log-probability, BX_FUSION_SCORE_PROB
+ * exp(lp_k - max lp) / sum_k exp(lp_k - max lp), which is bx_softmax_rows of it.  The mean over the background is an fp64 running sum
+ * of the fp32 scores in the order j = 0..Nb-1, divided by Nb once.  No atomics; a thread owns a coalition from its first table read to
+ * its store, so no bit of v depends on NS, on the position of a mask in the list, on how a list is cut into calls or on the grid.
+ * A workgroup holds the groups' partial sums for every setting of a group's bits in LDS, per (sample, background row) pair and tile of
+ * hidden units -- sum_g 2^bits(g) floats per hidden unit beside the second layer's tile, 64 KB at the most -- so a coalition costs one
+ * LDS read per group, the adds, the ReLU and K multiply-adds per hidden unit.
+ * 1 <= K <= 16 (a mask has 32 bits), 2K <= Hd <= 1024, B <= 65535, B * NS * K < 2^31. */
+int bx_fusion_values(const float* e_x, const float* s_x, const float* e_bg, const float* s_bg, const uint32_t* masks, const float* w1,
+                     const float* b1, const float* w2, const float* b2, int score_kind, double* v, int B, int Nb, int NS, int K, int Hd,
+                     bxStream stream);
+/* The Shapley sum.  v fp64 [R, 2^M]: row r holds one (sample, class) pair's values indexed by the coalition's integer (bit i = player
+ * i); weights fp64 [M]: weights[s] = s! (M - s - 1)! / M!, the host's table; phi fp64 [R,M].  phi[r,i] is the sum over the coalitions
+ * without player i, in ascending order of their integer, of weights[|S|] * (v[S + i] - v[S]); the difference, the product and the sum
+ * are rounded one by one.  One thread per (row, player), no atomics.  1 <= M <= 16, R * 2^M < 2^31.  M = 2 on the rows (none, EEG, spec,
+ * all) is the modality game. */
+int bx_shapley_exact(const double* v, const double* weights, double* phi, int R, int M, bxStream stream);
+/* out[r] = ((v[r,3] - v[r,1]) - v[r,2]) + v[r,0] of the modality game's rows v fp64 [R,4] = (none, EEG, spec, all).  R < 2^29. */
+int bx_fusion_interaction(const double* v, double* out, int R, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

@@ -27,6 +27,7 @@ BX_SPECTRAL_AMPLITUDE_GRADIENT, BX_SPECTRAL_GRADIENT_X_AMPLITUDE = 0, 1
 BX_SPECTRAL_CELLS_BAND, BX_SPECTRAL_CELLS_ELECTRODE_BAND = 0, 1
 BX_SPECTRAL_MAX_T = 8192
 BX_SSIM_MAX_WIN = 63
+BX_FUSION_SCORE_PROB, BX_FUSION_SCORE_LOGPROB = 0, 1
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -237,6 +238,9 @@ SIGNATURES = {
     "bx_ssim_strip": (i32, [i32, i32, i32]),
     "bx_ssim_rows_workspace": (sz, [i32] * 4),
     "bx_ssim_rows": (i32, [vp] * 7 + [C.c_double, C.c_double, vp] + [i32] * 5 + [vp, sz, vp]),
+    "bx_fusion_values": (i32, [vp] * 9 + [i32, vp] + [i32] * 5 + [vp]),
+    "bx_shapley_exact": (i32, [vp, vp, vp, i32, i32, vp]),
+    "bx_fusion_interaction": (i32, [vp, vp, i32, vp]),
     "bx_param_uniform": (i32, [vp, sz, f32, C.c_uint64, u32, u32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbrainxai.so")
-SOURCES = ["core.hip", "conv3x3.hip", "conv3x3_mfma.hip", "conv3x3_split.hip", "tail.hip", "heads.hip", "eeg.hip", "eeg_generic.hip", "eeg_mfma.hip", "eeg_collapse.hip", "eeg_deep.hip", "eeg_cam.hip", "attrib.hip", "montage.hip", "specprep.hip", "lime.hip", "faith.hip", "rise.hip", "scorecam.hip", "occlusion.hip", "shap.hip", "expgrad.hip", "smoothgrad.hip", "infidelity.hip", "blurig.hip", "spectral.hip", "similarity.hip", "guided_ig.hip"]
+SOURCES = ["core.hip", "conv3x3.hip", "conv3x3_mfma.hip", "conv3x3_split.hip", "tail.hip", "heads.hip", "eeg.hip", "eeg_generic.hip", "eeg_mfma.hip", "eeg_collapse.hip", "eeg_deep.hip", "eeg_cam.hip", "attrib.hip", "montage.hip", "specprep.hip", "lime.hip", "faith.hip", "rise.hip", "scorecam.hip", "occlusion.hip", "shap.hip", "expgrad.hip", "smoothgrad.hip", "infidelity.hip", "blurig.hip", "spectral.hip", "similarity.hip", "guided_ig.hip", "fusion_shap.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # No packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32), round 3.  Found with the EEG branch running beside the
@@ -26,8 +26,10 @@ if os.environ.get("BX_PACKED_FP32", "0") != "1":
 # operations of beta * d - drop likewise; Blur IG's filters are explicit fmaf chains and its accumulate's g * D, w * (g * D) and sum three
 # separate fp64 roundings; the spectral accumulate's w * g and sum likewise (its transforms name their fma); the randomization test's
 # draws bound * u and the fp64 sums of the map correlations and of SSIM likewise; Guided IG's points base + alpha * (x - base), its moves
-# x + gamma * (X_max - x) and its attr += (x - x_old) * g likewise
-EXTRA_FLAGS = {"montage.hip": ["-ffp-contract=off"], "specprep.hip": ["-ffp-contract=off"], "rise.hip": ["-ffp-contract=off"],
+# x + gamma * (X_max - x) and its attr += (x - x_old) * g likewise; Fusion SHAP names every fmaf of the head, and the Shapley sum's
+# w * (v(S + i) - v(S)) and its running sum are separate fp64 roundings
+EXTRA_FLAGS = {"fusion_shap.hip": ["-ffp-contract=off"],
+"montage.hip": ["-ffp-contract=off"], "specprep.hip": ["-ffp-contract=off"], "rise.hip": ["-ffp-contract=off"],
                "scorecam.hip": ["-ffp-contract=off"], "expgrad.hip": ["-ffp-contract=off"], "smoothgrad.hip": ["-ffp-contract=off"],
                "infidelity.hip": ["-ffp-contract=off"], "blurig.hip": ["-ffp-contract=off"], "spectral.hip": ["-ffp-contract=off"],
                "similarity.hip": ["-ffp-contract=off"], "guided_ig.hip": ["-ffp-contract=off"]}

@@ -75,6 +75,13 @@
                                  (bx_row_minmax, bx_ssim_rows) of two maps; the model parameter randomization test re-initialises
                                  the layers from the output towards the input with counter-based draws (bx_param_uniform), compares
                                  every stage's map with the trained model's and restores the parameters bit for bit.
+* ``fusion_shap``             -- the exact Shapley values of the two modalities (Lundberg & Lee, NeurIPS 2017; not in the reference): the
+                                 players are the votes -- log-probabilities -- the two branches hand to the fusion head, alone, by
+                                 modality, by class or in any partition; all 2^M coalitions are enumerated against a joint background,
+                                 the head evaluated on every (sample, background row, coalition) in one launch that shares the first
+                                 layer between coalitions through LDS tables and averages in fp64 (bx_fusion_values); fixed-order fp64
+                                 Shapley sums, the modality game and its interaction (bx_shapley_exact, bx_fusion_interaction).
+                                 ``fusion_votes`` returns the votes, ``modality_importance`` the mean |value| per player.
 """
 from __future__ import annotations
 
@@ -3954,3 +3961,249 @@ def randomization_test(model, explain, eeg, spec, *, input="spec", layers=None, 
         finally:
             _rand_restore([pair for group in saved for pair in group])
     return RandomizationResult(layers, {m: torch.stack(v, dim=-1) for m, v in sims.items()}, phi0, maps, order, seed)
+
+
+# ------------------------------------------------------------------------------------------------
+# Fusion SHAP: the exact Shapley values of the votes (log-probabilities) the two branches hand to the fusion head.  The definition is
+# pinned in include/brainxai.h; tests/fusion_shap_ref.py restates it.
+_FUSION_MAX_M = 16
+_FUSION_SCORES = {"prob": L.BX_FUSION_SCORE_PROB, "logprob": L.BX_FUSION_SCORE_LOGPROB}
+FusionVotes = collections.namedtuple("FusionVotes", "e s")
+FusionVotes.__doc__ = """The two branches' votes of N samples: ``e`` (EEG) and ``s`` (spectrogram), fp32 [N,K] log-probabilities each, on the device.
+``fusion_votes`` returns one; ``fusion_shap`` takes one as its background, so a background set runs through the branches once."""
+FusionShapResult = collections.namedtuple("FusionShapResult", "values modality interaction v classes clean empty votes background players masks score")
+FusionShapResult.__doc__ = """What ``fusion_shap(..., return_parts=True)`` returns: ``values`` fp64 [B,M] or [B,K,M] (what the plain call returns), ``modality`` fp64
+[B(,K),2] (the M = 2 game of the EEG votes against the spectrogram votes, (EEG, spec); not the sum of the members' values of a finer game),
+``interaction`` fp64 [B(,K)] = v(all) - v(EEG) - v(spec) + v(none), ``v`` fp64 [B,2^M,K] (the value of every class under every coalition
+of the players, coalition = the integer whose bit i is player i), ``classes`` int64 [B] (None for class_idx='all'), ``clean`` / ``empty`` fp64
+[B,K] = v(all) / v(none) (the scores of the samples and the mean scores of the background rows), ``votes`` and ``background`` (the
+samples' and the background's ``FusionVotes``), all on the device; ``players`` (a list of M lists of votes, vote i < K = the EEG branch's
+i-th, vote K + i = the spectrogram branch's), ``masks`` uint32 [2^M] (bit i = vote i comes from the sample) on the host; ``score`` as given."""
+
+
+def shapley_weights(M):
+    """fp64 [M] on the host: weights[s] = s! (M - s - 1)! / M!, the weight of a coalition of size s in a game of M players (each exact
+    integer quotient rounded once).  Summed over the 2^(M-1) coalitions without a player they give 1."""
+    if isinstance(M, bool) or not isinstance(M, numbers.Integral) or not 1 <= int(M) <= _FUSION_MAX_M:
+        raise ValueError(f"shapley_weights: M must be an int in 1..{_FUSION_MAX_M}, got {M!r}")
+    M = int(M)
+    return np.array([math.factorial(s) * math.factorial(M - s - 1) / math.factorial(M) for s in range(M)], dtype=np.float64)
+
+
+def _fusion_players(who, players, K):
+    """-> the players as a list of M lists of votes (vote i < K: the EEG branch's i-th, vote K + i: the spectrogram branch's)."""
+    if isinstance(players, str):
+        if players == "modality":
+            return [list(range(K)), list(range(K, 2 * K))]
+        if players == "class":
+            if K > _FUSION_MAX_M:
+                raise ValueError(f"{who}: players='class' has {K} players, more than {_FUSION_MAX_M}; use 'modality' or an explicit partition")
+            return [[c, K + c] for c in range(K)]
+        if players == "votes":
+            if 2 * K > _FUSION_MAX_M:
+                raise ValueError(f"{who}: players='votes' has 2K = {2 * K} players, more than {_FUSION_MAX_M}; use 'modality' or 'class'")
+            return [[i] for i in range(2 * K)]
+        raise ValueError(f"{who}: unknown players {players!r}; use 'votes', 'modality', 'class' or a partition of range({2 * K})")
+    try:
+        groups = [[v for v in grp] for grp in players]
+    except TypeError:
+        raise ValueError(f"{who}: players must be 'votes', 'modality', 'class' or a list of lists of votes") from None
+    if not 1 <= len(groups) <= _FUSION_MAX_M:
+        raise ValueError(f"{who}: {len(groups)} players, supported 1..{_FUSION_MAX_M}")
+    seen = set()
+    for grp in groups:
+        if not grp:
+            raise ValueError(f"{who}: an empty player")
+        for vt in grp:
+            if isinstance(vt, bool) or not isinstance(vt, numbers.Integral) or not 0 <= int(vt) < 2 * K:
+                raise ValueError(f"{who}: vote {vt!r} outside range({2 * K})")
+            if int(vt) in seen:
+                raise ValueError(f"{who}: vote {int(vt)} belongs to two players")
+            seen.add(int(vt))
+    if len(seen) != 2 * K:
+        raise ValueError(f"{who}: the players leave out the votes {sorted(set(range(2 * K)) - seen)}")
+    return [[int(vt) for vt in grp] for grp in groups]
+
+
+def _fusion_masks(groups, K):
+    """uint32 [2^M + 4] on the host: the vote mask of every coalition of the M players, coalition = the integer whose bit i is player
+    i, then the four masks of the modality game (none, EEG, spec, all) -- ordinary entries of the one list the kernel walks."""
+    M = len(groups)
+    gm = [sum(1 << vt for vt in grp) for grp in groups]
+    S = np.arange(1 << M, dtype=np.uint64)
+    masks = np.zeros(1 << M, dtype=np.uint64)
+    for i in range(M):
+        masks |= ((S >> np.uint64(i)) & np.uint64(1)) * np.uint64(gm[i])
+    e_half = (1 << K) - 1
+    return np.concatenate([masks, np.array([0, e_half, e_half << K, e_half | e_half << K], dtype=np.uint64)]).astype(np.uint32)
+
+
+def _fusion_head(who, model):
+    """-> (K, Hd) of a MultimodalModel with the reference's head, cat -> Linear(2K,Hd) -> ReLU -> Linear(Hd,K) -> LogSoftmax; anything
+    else is refused."""
+    lin = torch.nn.Linear
+    if not (hasattr(model, "eeg_model") and hasattr(model, "spectrogram_model") and isinstance(getattr(model, "fc1", None), lin)
+            and isinstance(getattr(model, "fc2", None), lin)):
+        raise ValueError(f"{who}: needs a MultimodalModel (two branches and the fusion head fc1 -> ReLU -> fc2); a stand-alone branch has no modalities to weigh")
+    K, Hd = int(model.fc2.out_features), int(model.fc1.out_features)
+    if int(model.fc1.in_features) != 2 * K or int(model.fc2.in_features) != Hd or model.fc1.bias is None or model.fc2.bias is None:
+        raise ValueError(f"{who}: the head must be Linear(2K,Hd) -> ReLU -> Linear(Hd,K) with biases; got fc1 {tuple(model.fc1.weight.shape)}, fc2 {tuple(model.fc2.weight.shape)}")
+    if not (1 <= K <= 16 and 2 * K <= Hd <= 1024):
+        raise ValueError(f"{who}: K = {K} classes and Hd = {Hd} hidden units; supported 1 <= K <= 16, 2K <= Hd <= 1024")
+    return K, Hd
+
+
+def _fusion_inputs(who, eeg, spec, what="the inputs"):
+    """-> N: ``eeg`` [N,1,Chans,T] and ``spec`` [N,C,H,W] with the same N >= 1."""
+    if not (isinstance(eeg, torch.Tensor) and eeg.dim() == 4 and eeg.shape[1] == 1 and isinstance(spec, torch.Tensor) and spec.dim() == 4):
+        raise ValueError(f"{who}: {what} must be the tensors eeg [N,1,Chans,T] and spec [N,C,H,W]")
+    if eeg.shape[0] != spec.shape[0]:
+        raise ValueError(f"{who}: {what} have {int(eeg.shape[0])} EEG and {int(spec.shape[0])} spectrogram samples; both branches vote on the same samples")
+    if eeg.shape[0] < 1 or eeg.numel() == 0 or spec.numel() == 0:
+        raise ValueError(f"{who}: {what} are empty")
+    return int(eeg.shape[0])
+
+
+def _fusion_branches(model, eeg, spec, max_batch):
+    """``FusionVotes`` of the samples: both branches in passes of at most max_batch rows (inside eval mode, without autograd)."""
+    sm = model.spectrogram_model
+    cap = min(_row_cap(spec, "spec", getattr(sm, "compute_dtype", torch.float32), max_batch), _row_cap(eeg, "eeg", torch.float32, max_batch))
+    xe, xs = eeg.detach().to(torch.float32).contiguous(), spec.detach().to(torch.float32).contiguous()
+    N = int(xe.shape[0])
+    e = torch.cat([model.eeg_model(xe[i:i + cap]).float() for i in range(0, N, cap)]).contiguous()
+    s = torch.cat([sm(xs[i:i + cap]).float() for i in range(0, N, cap)]).contiguous()
+    return FusionVotes(e, s)
+
+
+def fusion_votes(model, eeg, spec, max_batch=256):
+    """The votes of both branches of a MultimodalModel on N samples: ``FusionVotes(e, s)``, fp32 [N,K] log-probabilities each -- what
+    ``fusion_shap`` explains and what it takes as a background, so that a background set runs through the branches once for many
+    calls.  Eval mode without autograd, passes of at most max_batch rows; no bit depends on max_batch.  The training flag and every
+    requires_grad are restored on return."""
+    who = "fusion_votes"
+    max_batch = _max_batch(who, max_batch)
+    _fusion_head(who, model)
+    _fusion_inputs(who, eeg, spec)
+    _need_gpu(who, "the model and its inputs", model, eeg, spec)
+    with torch.cuda.device(eeg.device), _eval_frozen(model), torch.no_grad():
+        return _fusion_branches(model, eeg, spec, max_batch)
+
+
+def fusion_shap(model, eeg, spec, background, *, players="votes", class_idx=None, score="prob", max_batch=256, return_parts=False):
+    """How much of a decision came from the EEG branch and how much from the spectrogram branch: the exact Shapley values of the votes
+    the two branches hand to the fusion head.  Every other attribution here explains one input while the other is held; this one
+    explains the fusion.  The model is a late fusion: each branch emits K log-probabilities (its votes) and the head is
+    cat -> Linear(2K,Hd) -> ReLU -> Linear(Hd,K) -> LogSoftmax, so the game has at most 2K players, every coalition is enumerated -- no
+    sampling, no surrogate fit -- and both branches run once per sample and once per background sample.
+        v_c(S) = mean over the background rows j of score_c( head( the sample's votes on S, row j's votes elsewhere ) )
+        phi_i  = sum over S without i of |S|! (M - |S| - 1)! / M! (v(S + i) - v(S))
+    and the values of a sample add up to score(sample) - mean score(background).
+
+    model:       a MultimodalModel with the reference's head; anything else is refused.
+    background:  (eeg_bg, spec_bg) with Nb samples each, run through the branches in passes of at most max_batch; 'uniform': one row with
+                 every vote -log K, the vote of a branch that knows nothing (no data needed); a ``FusionVotes`` (``fusion_votes``): votes
+                 already computed.  A background row supplies both branches' votes of the same sample (a joint, interventional background).
+    players:     'votes': every vote alone, M = 2K <= 16; 'modality': M = 2, all EEG votes against all spectrogram votes; 'class': M = K,
+                 {e_c, s_c} per class -- which class's evidence, from both branches together, moved the explained class; or a partition
+                 of range(2K) into lists (vote i < K = the EEG branch's i-th, vote K + i = the spectrogram branch's), M <= 16.
+    class_idx:   None = each sample's arg-max class; an int; one class per sample (sequence / tensor [B]); 'all' = every class, the
+                 result gains a class axis.
+    score:       'prob': the softmax probability; 'logprob': the log-probability.
+    max_batch:   rows per pass through the branches; no bit of the result depends on it.
+    One launch evaluates the head on every (sample, background row, coalition) in fp32 and averages in fp64 in the rows' order
+    (bx_fusion_values); the Shapley sums are fp64 in a fixed order with the host's weights (bx_shapley_exact, ``shapley_weights``).  The
+    modality game and the interaction come from the same launch and the same code path for every ``players``.  The training flag and
+    every requires_grad are restored on return.  Returns the values fp64 [B,M] ([B,K,M] for 'all') on the device, or ``FusionShapResult``
+    with return_parts."""
+    return _fusion_shap(model, eeg, spec, background, players, class_idx, score, max_batch, return_parts)
+
+
+def _fusion_shap(model, eeg, spec, background, players, class_idx, score, max_batch, return_parts, profile=None):
+    """``fusion_shap`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'branches', 'values',
+    'shapley' -- device events around every phase (tools/fusion_shap_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "fusion_shap"
+    if score not in _FUSION_SCORES:
+        raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
+    max_batch = _max_batch(who, max_batch)
+    K, Hd = _fusion_head(who, model)
+    B = _fusion_inputs(who, eeg, spec)
+    groups = _fusion_players(who, players, K)
+    M = len(groups)
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    bg_votes, bg_inputs = None, ()
+    if isinstance(background, str):
+        if background != "uniform":
+            raise ValueError(f"{who}: unknown background {background!r}; use 'uniform', (eeg_bg, spec_bg) or a FusionVotes")
+        Nb = 1
+    elif isinstance(background, FusionVotes):
+        e_b, s_b = background
+        if not all(isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == K and t.dtype == torch.float32 for t in (e_b, s_b)):
+            raise ValueError(f"{who}: a FusionVotes background holds two fp32 tensors [Nb, {K}]")
+        if e_b.shape[0] != s_b.shape[0] or e_b.shape[0] < 1:
+            raise ValueError(f"{who}: the background holds {int(e_b.shape[0])} EEG and {int(s_b.shape[0])} spectrogram rows; a row is one sample's two votes")
+        bg_votes, Nb = background, int(e_b.shape[0])
+    elif isinstance(background, (tuple, list)) and len(background) == 2:
+        Nb = _fusion_inputs(who, background[0], background[1], "the background (eeg_bg, spec_bg)")
+        if tuple(background[0].shape[1:]) != tuple(eeg.shape[1:]) or tuple(background[1].shape[1:]) != tuple(spec.shape[1:]):
+            raise ValueError(f"{who}: the background samples are shaped {tuple(background[0].shape[1:])} / {tuple(background[1].shape[1:])}, "
+                             f"the inputs {tuple(eeg.shape[1:])} / {tuple(spec.shape[1:])}")
+        bg_inputs = tuple(background)
+    else:
+        raise ValueError(f"{who}: background must be 'uniform', (eeg_bg, spec_bg) or a FusionVotes, got {type(background).__name__}")
+    masks = _fusion_masks(groups, K)
+    NS, n = int(masks.shape[0]), 1 << M
+    if B > 65535 or B * NS * K >= 1 << 31:
+        raise ValueError(f"{who}: B = {B} samples (limit 65535) or B * (2^M + 4) * K = {B * NS * K} beyond 32-bit offsets; use fewer samples per call")
+    _need_gpu(who, "the model, its inputs and the background", model, eeg, spec, *bg_inputs, *(bg_votes or ()))
+
+    lib = L.load()
+    dev = eeg.device
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad():
+        with _lap(profile, "branches"):
+            votes = _fusion_branches(model, eeg, spec, max_batch)
+            if bg_inputs:
+                bg_votes = _fusion_branches(model, bg_inputs[0].to(dev), bg_inputs[1].to(dev), max_batch)
+            elif bg_votes is None:
+                row = torch.full((1, K), float(np.float32(-math.log(K))), dtype=torch.float32, device=dev)
+                bg_votes = FusionVotes(row, row.clone())
+            else:
+                bg_votes = FusionVotes(*(t.detach().to(dev).contiguous() for t in bg_votes))
+        w1, b1, w2, b2 = (t.detach().to(torch.float32).contiguous() for t in (model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias))
+        masks_d = torch.from_numpy(masks.view(np.int32)).to(dev)
+        with _lap(profile, "values"):
+            v = torch.empty(B, NS, K, dtype=torch.float64, device=dev)
+            L.check(lib.bx_fusion_values(_p(votes.e), _p(votes.s), _p(bg_votes.e), _p(bg_votes.s), _p(masks_d), _p(w1), _p(b1), _p(w2), _p(b2),
+                                         _FUSION_SCORES[score], _p(v), B, Nb, NS, K, Hd, _stream()), "bx_fusion_values")
+        with _lap(profile, "shapley"):
+            empty, clean = v[:, n].contiguous(), v[:, n + 3].contiguous()            # the modality game's none and all
+            classes = _class_tensor(cls_h, all_classes, clean, dev)
+            # one row per (sample, class): the explained class's column of every coalition (a gather; the arithmetic is the library's)
+            rows = v.permute(0, 2, 1) if all_classes else v.gather(2, classes.long()[:, None, None].expand(B, NS, 1)).permute(0, 2, 1)
+            R = B * (K if all_classes else 1)
+            game, duo = rows[..., :n].reshape(R, n).contiguous(), rows[..., n:].reshape(R, 4).contiguous()
+            values, modality, interaction = (torch.empty(R, m, dtype=torch.float64, device=dev) for m in (M, 2, 1))
+            for vr, m, out in ((game, M, values), (duo, 2, modality)):
+                w_d = torch.from_numpy(shapley_weights(m)).to(dev)
+                L.check(lib.bx_shapley_exact(_p(vr), _p(w_d), _p(out), R, m, _stream()), "bx_shapley_exact")
+            L.check(lib.bx_fusion_interaction(_p(duo), _p(interaction), R, _stream()), "bx_fusion_interaction")
+    lead = (B, K) if all_classes else (B,)
+    values, modality, interaction = values.reshape(*lead, M), modality.reshape(*lead, 2), interaction.reshape(*lead)
+    if not return_parts:
+        return values
+    return FusionShapResult(values, modality, interaction, v[:, :n].contiguous(), None if classes is None else classes.long(), clean, empty, votes,
+                            bg_votes, groups, masks[:n].copy(), score)
+
+
+def modality_importance(values):
+    """The dataset-level figure: the mean |phi| of every player over the samples.  values: ``fusion_shap``'s values fp64 [B,M] or [B,K,M],
+    or its ``FusionShapResult`` -> fp32 [M] or [K,M] (bx_mean_abs_rows: an fp64 sum over the samples in a fixed order, one rounding).
+    On ``FusionShapResult.modality`` it is the share of the two modalities."""
+    who = "modality_importance"
+    if isinstance(values, FusionShapResult):
+        values = values.values
+    if not isinstance(values, torch.Tensor) or values.dim() not in (2, 3) or values.numel() == 0:
+        raise ValueError(f"{who}: values must be fusion_shap's values [B,M] or [B,K,M] or its FusionShapResult")
+    if not values.is_cuda:
+        raise RuntimeError(f"brainxai.{who}: the values must live on the GPU; there is no CPU path")
+    return channel_importance(values.movedim(0, -1))
