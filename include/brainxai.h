@@ -324,6 +324,12 @@ typedef struct {
                          * through it -- a captured graph is replayed on the caller's batch without a copy.  Collapsed evaluation-mode
                          * path only (collapse = 1, training = 0), where one kernel reads x and nothing is kept for a backward;
                          * the `x` argument must still be a valid pointer of the same shape (it is what an eager run reads). */
+  int grad;             /* 1: bx_eeg_features_bwd will follow this forward (training = 1 implies it).  The register-tiled backward holds
+                         * rows up to T = 4096 (its LDS tiles and per-thread dx registers); with a backward announced, longer rows run
+                         * on the general kernel set in BOTH directions, so that a pass whose forward was accepted is computed by its
+                         * backward.  0 with training = 0 (inference, Grad-CAM, attribution sweeps under no-grad): the register-tiled
+                         * forward up to T = 15000, whose arena bx_eeg_saved_layout / bx_eeg_cam read.  Forward, backward, saved_bytes
+                         * and workspace must see the same value. */
 } bxEegDesc;
 /* Parameter block: pointers to the fp32 tensors of the module, reference names in comments. */
 typedef struct {
@@ -348,7 +354,8 @@ int bx_eeg_features_fwd(const bxEegDesc* d, const bxEegParams* p, const float* x
 int bx_eeg_features_bwd(const bxEegDesc* d, const bxEegParams* p, const float* x, const float* dfeat,
                         const uint64_t* seed, const void* saved, const bxEegGrads* g, float* dx,
                         void* workspace, size_t workspace_bytes, bxStream stream);
-/* Byte offsets, inside the saved arena of the tuned family (F1=8, D=2, F2=16, K2=16, K1 <= 64, Chans <= 64, T <= 15000), of the
+/* Byte offsets, inside the saved arena of the tuned family (F1=8, D=2, F2=16, K2=16, K1 <= 64, Chans <= 64, T <= 15000; with
+ * training = 1 or grad = 1 in the descriptor T <= 4096, what the register-tiled backward holds), of the
  * depthwise output dmap fp32 [B,F1*D,T] and the separable output smap fp32 [B,F2,T/P1] (both before their BatchNorm).
  * BX_EUNSUPPORTED for any other geometry. */
 int bx_eeg_saved_layout(const bxEegDesc* d, size_t* off_dmap, size_t* off_smap);

@@ -595,8 +595,7 @@ __global__ __launch_bounds__(256) void k_eeg_bn_bwd_apply16(const float* __restr
 //     float4s for 128 FMAs.
 // (b) partial dws[o][fd][k] = sum_t ds[o][t] p1[fd][t+k-padl] over the quarter's time range: thread = (o, fd), 16 tap
 //     accumulators, sliding p1 window: 2 float4 reads per 64 FMAs.
-// Row pitch TP: multiple of 4 with TP/4 odd (the 16 fd rows a wave reads then fall on different bank groups).
-__host__ __device__ inline int eeg_sepb_pitch(int T1) { int tp = ((T1 + 7) & ~7) + 24; if (((tp >> 2) & 1) == 0) tp += 4; return tp; }
+// Row pitch TP = eeg_sepb_pitch(T1) (eeg_internal.h): multiple of 4 with TP/4 odd.
 // The BatchNorm3 backward apply (k_eeg_bn_bwd_apply: ds = a (du - k1 - xhat k2), elementwise) rides in the staging of ds when `pre`
 // is given: same expression, evaluated on the way into LDS -- one launch and one pass over du3 fewer.
 __global__ __launch_bounds__(256) void k_eeg_sep_bwd(const float* __restrict__ ds, const float* __restrict__ p1, const float* __restrict__ ws,
@@ -823,7 +822,7 @@ __global__ void k_eeg_dw_bwd_finalize(const float* __restrict__ rpart, int B, Ee
 // fit a CU -- then the temporal-conv weight gradient partial dW1[f][k] = sum_t dc1[f][t] x[t+k-padl] (thread = filter x
 // 4 consecutive taps x one time quarter, sliding x window: 1 dc1 + 1 x LDS read per 4 FMAs) and, optionally,
 // dx[t] = sum_{f,k} w1[f][k] dc1[f][t-k+padl].
-#define EEG_DX_MAX 16          // dx values a thread can own: T <= 256*16
+// (EEG_DX_MAX, eeg_internal.h: dx values a thread can own, T <= 256 * EEG_DX_MAX)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <typename T>
 __global__ __launch_bounds__(256) void k_eeg_conv1_bwd(const T* __restrict__ c1, const float* __restrict__ dd, const float* __restrict__ x,
@@ -1039,10 +1038,11 @@ extern "C" int bx_eeg_features_bwd(const bxEegDesc* d, const bxEegParams* p, con
   // separable conv (the BatchNorm3 backward apply rides in its staging)
   {
     // the two halves of the kernel in separate workgroups while that is what gives every CU two; B = 64: 27.0 -> 24.0 us
-    const bool split = g.B * 4 < 1024;
-    const size_t tile = (size_t)16 * eeg_sepb_pitch(g.T1);
-    const size_t lds = (split ? (tile + (tile > 4096 ? tile : 4096)) : (2 * tile + 4096)) * sizeof(float);
-    BX_REQUIRE(lds <= 160 * 1024, "bx_eeg_features_bwd: T/P1 too long for the LDS tile (%zu bytes)", lds);
+    const bool split = eeg_sepb_split(g.B);
+    const size_t lds = eeg_sepb_lds(g.B, g.T1);
+    // (eeg_tuned() sends such rows to the general kernels when the descriptor announces a backward: training mode or bxEegDesc.grad)
+    BX_REQUIRE(lds <= EEG_LDS_MAX, "bx_eeg_features_bwd: T/P1 too long for the LDS tile (%zu bytes); set bxEegDesc.grad for the forward of an "
+                                   "evaluation-mode pass that a backward follows", lds);
     if (hipFuncSetAttribute((const void*)k_eeg_sep_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       BX_FAIL(BX_EHIP, "bx_eeg_features_bwd: cannot reserve %zu bytes of LDS", lds);
     hipLaunchKernelGGL(k_eeg_sep_bwd, dim3(g.B, split ? 8 : 4), dim3(256), lds, s, du3, p1, p->sep_w, dp1, sepp, g, smap, st.mean3, st.inv3, (const float*)coef3);
@@ -1116,8 +1116,9 @@ extern "C" int bx_eeg_features_bwd(const bxEegDesc* d, const bxEegParams* p, con
     BX_SUM_PARTIALS(w1part, gr->conv1_w, g.B * g.Ch, 8 * g.K1, s);
     BX_CHECK_LAUNCH("eeg conv1 wgrad reduce");
   } else if (gr->conv1_w || dx) {
-    const size_t lds = ((size_t)5 * ((g.T + 2 * EEG_MAXK + 3) & ~3) + 4096) * sizeof(float);
-    BX_REQUIRE(lds <= 160 * 1024 && g.T <= 256 * EEG_DX_MAX, "bx_eeg_features_bwd: T too long (LDS tile %zu bytes, T <= %d)", lds, 256 * EEG_DX_MAX);
+    const size_t lds = eeg_conv1_bwd_lds(g.T);
+    BX_REQUIRE(lds <= EEG_LDS_MAX && g.T <= 256 * EEG_DX_MAX, "bx_eeg_features_bwd: T too long (LDS tile %zu bytes, T <= %d); set bxEegDesc.grad "
+               "for the forward of an evaluation-mode pass that a backward follows", lds, 256 * EEG_DX_MAX);
     BX_DISPATCH_DTYPE(d->dtype, T,
       if (hipFuncSetAttribute((const void*)k_eeg_conv1_bwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         BX_FAIL(BX_EHIP, "bx_eeg_features_bwd: cannot reserve %zu bytes of LDS", lds);

@@ -7,7 +7,10 @@
 #define EEG_MAXK 64
 #define EEG_MAXF 16          // F1*D and F2 upper bound
 #define EEG_MAXCH 64
-#define EEG_MAXT 15000       // longest row the tuned kernels' one-row LDS tile holds
+#define EEG_MAXT 15000       // longest row the tuned FORWARD's one-row LDS tile holds (evaluation-mode passes nothing differentiates: inference,
+                             // Grad-CAM); a pass that a backward can follow is tuned only while eeg_tuned_bwd_holds(), see eeg_tuned()
+#define EEG_DX_MAX 16        // dx values a thread of k_eeg_conv1_bwd can own: T <= 256 * EEG_DX_MAX
+#define EEG_LDS_MAX ((size_t)160 * 1024)      // dynamic LDS a tuned backward kernel may ask for
 #define EEGC_RS_BYTES ((size_t)(64 * 64 + 64) * sizeof(double))
 
 struct EegGeom {
@@ -47,5 +50,29 @@ static EegStats eeg_stats(const EegGeom& g, void* saved) {
   s.mean3 = p; s.inv3 = p + g.F2; s.sc3 = p + 2 * g.F2; s.sh3 = p + 3 * g.F2;
   return s;
 }
-// the tuned path needs the reference's default family AND rows that fit its one-row LDS tile; everything else: general kernels
-static bool eeg_tuned(const bxEegDesc* d, EegGeom* g) { return eeg_geom(d, g) == 0 && d->T <= EEG_MAXT; }
+// ---- what the tuned backward holds: the expressions its launchers (bx_eeg_features_bwd, eeg.hip) check, in one place ----
+// k_eeg_sep_bwd: row pitch of its LDS tiles, multiple of 4 with pitch/4 odd (the 16 fd rows a wave reads then fall on different bank groups)
+__host__ __device__ inline int eeg_sepb_pitch(int T1) { int tp = ((T1 + 7) & ~7) + 24; if (((tp >> 2) & 1) == 0) tp += 4; return tp; }
+// ... its two halves run in separate workgroups while that is what gives every CU two
+static inline bool eeg_sepb_split(int B) { return B * 4 < 1024; }
+static inline size_t eeg_sepb_lds(int B, int T1) {
+  const size_t tile = (size_t)16 * eeg_sepb_pitch(T1);
+  return (eeg_sepb_split(B) ? (tile + (tile > 4096 ? tile : 4096)) : (2 * tile + 4096)) * sizeof(float);
+}
+// k_eeg_conv1_bwd: four dc1 rows and the x row with 64-sample halos, plus the [256][16] combine buffer
+static inline size_t eeg_conv1_bwd_lds(int T) { return ((size_t)5 * ((T + 2 * EEG_MAXK + 3) & ~3) + 4096) * sizeof(float); }
+// Every backward goes through k_eeg_sep_bwd.  k_eeg_conv1_bwd is the fp32 path and what every other route falls back to: the matrix-core
+// weight gradient (eeg_mfma.hip) is taken only while its own LDS fits and BX_EEG_NO_MFMA is unset, the collapsed forms only at
+// kernLength 64 -- neither can be read off the descriptor, so its limits decide.  (bx_eegc_dx_launch's own limit is Chans <= EEG_MAXCH,
+// which eeg_geom already enforces.)
+static bool eeg_tuned_bwd_holds(const EegGeom& g) {
+  return eeg_sepb_lds(g.B, g.T1) <= EEG_LDS_MAX && eeg_conv1_bwd_lds(g.T) <= EEG_LDS_MAX && g.T <= 256 * EEG_DX_MAX;
+}
+// The route is a function of the descriptor alone: bx_eeg_saved_bytes, bx_eeg_workspace, bx_eeg_saved_layout, the forward, the backward and
+// the class-activation kernels all ask here and cannot disagree.  Tuned: the reference's default family AND rows that fit the forward's
+// one-row LDS tile AND -- when a backward can follow (training mode, or bxEegDesc.grad) -- rows that the tuned backward holds.
+// Everything else: the general kernels (eeg_generic.hip).
+static bool eeg_tuned(const bxEegDesc* d, EegGeom* g) {
+  if (eeg_geom(d, g) != 0 || d->T > EEG_MAXT) return false;
+  return !(d->training || d->grad) || eeg_tuned_bwd_holds(*g);
+}

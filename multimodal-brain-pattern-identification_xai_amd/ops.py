@@ -1007,6 +1007,8 @@ def _eeg_forward(x, c1w, bn1w, bn1b, dww, bn2w, bn2b, sepw, bn3w, bn3b, bufs, cf
                                       (not cfg.training and not params_need_grad)) else 0
     desc = L.EegDesc(B, Ch, T, cfg.F1, cfg.D, cfg.F2, cfg.K1, cfg.K2, cfg.P1, cfg.P2, 1 if cfg.training else 0, cfg.eps, cfg.momentum,
                      float(cfg.dropout_p), cfg.salt, bx_dtype(cfg.dtype), collapse, float(getattr(cfg, "dropout_p2", -1.0)))
+    # a backward follows: rows longer than the register-tiled backward holds then run on the general kernels in both directions
+    desc.grad = 1 if getattr(cfg, "grad_mode", True) and any(needs_input_grad[0:10]) else 0
     if INPUT_SLOTS and collapse and not cfg.training and not torch.is_grad_enabled() and cfg.K1 == 64:
         desc.x_slot = _take_slot(x)                      # a graph input read through its device slot (GradCamSweep)
     nsaved = lib.bx_eeg_saved_bytes(C.byref(desc))
