@@ -1151,6 +1151,78 @@ int bx_fusion_values(const float* e_x, const float* s_x, const float* e_bg, cons
 int bx_shapley_exact(const double* v, const double* weights, double* phi, int R, int M, bxStream stream);
 /* out[r] = ((v[r,3] - v[r,1]) - v[r,2]) + v[r,0] of the modality game's rows v fp64 [R,4] = (none, EEG, spec, all).  R < 2^29. */
 int bx_fusion_interaction(const double* v, double* out, int R, bxStream stream);
+/* ---- Optimised perturbation masks (Fong & Vedaldi, ICCV 2017, "meaningful perturbations"; the basis of TorchRay's extremal
+ * perturbations): per (sample, class) row the smallest smooth mask whose removal (deletion) or whose preservation alone changes the
+ * class score is learned by Adam; the model's forward and backward passes between the launches are its own kernels.
+ * Mask domain [Hm,Wm], as for RISE: [H,W] of a spectrogram (one value for all C channels of a pixel), [Chans,T] of an EEG input, or [1,T]
+ * (a time column across electrodes); Hm * Wm < 2^20.  Grid gh x gw, 1 <= gh <= min(32, Hm), 1 <= gw <= min(32, Wm).
+ * Row r = b * Kc + slot owns a parameter grid m_r fp32 [gh,gw] in [0, 1] (1.0 at the start) and the Adam moments mu_r, nu_r fp64 [gh,gw]
+ * (0 at the start).
+ * Up-sampling M = U(m): bilinear, align_corners=False, to Hm x Wm, in fp32 without fused multiply-adds (bx_resize_bilinear's
+ * convention).  Per axis, for pixel u of an axis of n pixels and g cells:
+ *     s = max(0, (u + 0.5) * (g / n) - 0.5),  i0 = min(int(s), g - 1),  i1 = min(i0 + 1, g - 1),  l = s - i0,
+ *     M = (1 - ly) * ((1 - lx) * m[y0][x0] + lx * m[y0][x1]) + ly * ((1 - lx) * m[y1][x0] + lx * m[y1][x1])
+ * (horizontal blend first, then vertical).  An all-ones grid gives exactly 1.0.
+ * Rows: X = base + M * (x - base) in fp32 as written (three roundings), fp32 in the input's own layout ([rows,C,H,W] or [rows,1,Chans,T]:
+ * they go through the model with requires_grad).  baseline_kind as in bx_rise_perturb_*: 0 one value, 1 one value per channel /
+ * electrode, 2 a tensor of x's shape.
+ * Objective, minimised per row, with s_c(X) the class probability (score BX_MASKOPT_PROB) or log-probability (BX_MASKOPT_LOGPROB):
+ *     deletion      L = l1 mean(1 - m) + tv TV_beta(m) + s_c(X)          preservation  L = l1 mean(m) + tv TV_beta(m) - s_c(X)
+ * TV_beta(m) = the sum of |d|^beta over every horizontal and vertical neighbour difference d, beta in {1, 2, 3}: |d|, |d| |d|,
+ * (|d| |d|) |d|; its derivative by d is sign(d) (0 at d = 0), 2 d, (3 d) |d|.
+ * Gradient, all in fp64, with g = dF_c/dX fp32 from the backward pass (F_c the output log-probability, one-hot seed: bx_expgrad_seed):
+ *   1. t(p) = SUM_c (double)g[c,p] * (double)fl32(x[c,p] - base[c,p]), from 0.0 in channel order.  An EEG input with a [Chans,T] domain
+ *      has one channel; under a [1,T] domain the electrodes are the channels of a column, in electrode order.
+ *   2. G_data[i,j] = sign * w_r * SUM_y wy(y,i) * ( SUM_x wx(x,j) * t(y,x) ),  wx(x,j) = (j == i0 ? (double)fl32(1 - l) : 0) +
+ *      (j == i1 ? (double)l : 0) (the forward's fp32 weights, widened exactly; an add of two doubles) and wy alike.  The inner sum first,
+ *      from 0.0 over cell j's footprint in ascending x; then the outer one, from 0.0 over cell i's footprint in ascending y.  The
+ *      footprint of cell j is every pixel whose i0 is j - 1 or j (a contiguous range; a pixel of it whose weight is 0 adds its exact
+ *      zero product).  w_r = 1 for the log-probability and (double)expf(y_r[c]) for the probability, y_r the row's fp32 output: the
+ *      chain rule of the probability; expf is the correctly rounded fp32 exponential, fl32(exp((double)y)).  sign = + for deletion,
+ *      - for preservation.
+ *   3. G = (G_data -+ l1 / (gh gw)) + tv * dTV, - for deletion and + for preservation; l1 / (gh gw) is one fp64 division;
+ *      dTV[i,j] = from 0.0: + TV'(m[i][j] - m[i][j-1]) - TV'(m[i][j+1] - m[i][j]) + TV'(m[i][j] - m[i-1][j]) - TV'(m[i+1][j] - m[i][j]),
+ *      each term only where the neighbour exists; the differences of the fp32 values are exact in fp64.
+ *   Every product and every sum is rounded on its own (the file is built with -ffp-contract=off).
+ * Adam, fp64, `it` counted from 0, c1 = 1 - b1^(it+1) and c2 = 1 - b2^(it+1) computed by the host in fp64:
+ *     mu = b1 * mu + (1 - b1) * G;   nu = b2 * nu + ((1 - b2) * G) * G;
+ *     m = clamp( fl32( (double)m - (lr * (mu / c1)) / (sqrt(nu / c2) + eps) ), 0, 1 ),   clamp(v) = v < 0 ? 0 : (v > 1 ? 1 : v).
+ * History, recorded before the update: history[r,it] = ( s_c = (double)expf(y) or (double)y,  mean m = SUM m / (gh gw),  TV_beta(m) ).
+ * The two sums over the grid run over the cells e = i gw + j in the order of bx_blurig_sum_rows: 64 partial sums over e = l, l + 64, ...
+ * (ascending), added by the xor butterfly (offsets 32, 16, .., 1); cell e's TV term is, from 0.0, |m[i][j+1] - m[i][j]|^beta then
+ * |m[i+1][j] - m[i][j]|^beta, each where the neighbour exists.
+ * Status: a row whose y_r[c] is NaN or whose G_data holds a NaN -- every pixel lies in a footprint, so a NaN in g always does -- gets
+ * BX_MASKOPT_NAN before anything of the step is written; m, the moments and the later history entries of a row whose status is not
+ * BX_MASKOPT_OK are left alone by every later step.  Other rows are not affected.
+ * The sums depend on the shapes alone: a thread owns its outputs and adds in ascending order, no atomics.  R = B * Kc <= 65535; every
+ * offset stays below 2^31.  Limits are refused with BX_EINVAL / BX_EUNSUPPORTED before any pointer is touched.  Each entry point handles
+ * the row window [row0, row0 + rows), which may begin and end inside a sample. */
+enum { BX_MASKOPT_OK = 0, BX_MASKOPT_NAN = 1 };
+enum { BX_MASKOPT_DELETION = 0, BX_MASKOPT_PRESERVATION = 1 };
+enum { BX_MASKOPT_PROB = 0, BX_MASKOPT_LOGPROB = 1 };
+/* m fp32 [R,gh,gw] = 1, mu and nu fp64 [R,gh,gw] = 0, status i32 [R] = BX_MASKOPT_OK, for the window's rows (the whole arrays are passed). */
+int bx_maskopt_init(float* m, double* mu, double* nu, int* status, int B, int Kc, int gh, int gw, int row0, int rows, bxStream stream);
+/* out fp32 [rows,Hm,Wm] = U(m_r) of the window's rows (for the result, plots and tests); m is the whole array.  rows * Hm * Wm < 2^31. */
+int bx_maskopt_masks(const float* m, float* out, int B, int Kc, int gh, int gw, int Hm, int Wm, int row0, int rows, bxStream stream);
+/* The rows of the window.  x fp32 [B,C,H,W] -> out fp32 [rows,C,H,W]; m the whole array; a kind-1 baseline holds C values. */
+int bx_maskopt_rows_spec(const float* x, const float* m, const float* baseline, int baseline_kind, float* out, int B, int Kc, int C, int H, int W,
+                         int gh, int gw, int row0, int rows, bxStream stream);
+/* x fp32 [B,1,Chans,T] -> out fp32 [rows,1,Chans,T].  map_rows = Chans: the domain is [Chans,T]; map_rows = 1: it is [1,T] and a
+ * column's value applies to every electrode.  A kind-1 baseline holds Chans values. */
+int bx_maskopt_rows_eeg(const float* x, const float* m, int map_rows, const float* baseline, int baseline_kind, float* out, int B, int Kc, int Chans,
+                        int T, int gh, int gw, int row0, int rows, bxStream stream);
+/* One iteration for the window's rows: gradient, regularisers, Adam, clamp, history and status; the host is asked nothing.  x fp32
+ * [B,C,H,W] with map_rows = 0 for a spectrogram, or [B,1,Chans,T] given as C = 1, H = Chans, W = T with map_rows = Chans or 1.  g fp32
+ * [rows,C,H,W] and y fp32 [rows,K] belong to the window's rows; classes i32 [R] (the class of every row), m, mu, nu, status and history
+ * fp64 [R,iterations,3] are the whole arrays.  G_out: NULL, or fp64 [R,gh,gw] that receives G of the rows that took the step.  scratch:
+ * fp64 [rows,Hm,gw], the horizontal sums between the step's two launches (the first runs one workgroup per line (row, y): t of a tile of
+ * the line into LDS with coalesced loads, then thread j adds cell j's footprint from there; the second runs one workgroup per row, one
+ * thread per grid cell).  mode BX_MASKOPT_DELETION / _PRESERVATION,
+ * score BX_MASKOPT_PROB / _LOGPROB, tv_beta 1..3; lr, l1, tv, eps >= 0; b1, b2 in [0, 1); c1, c2 in (0, 1]. */
+int bx_maskopt_step(const float* x, const float* baseline, int baseline_kind, const float* g, const float* y, const int* classes, float* m, double* mu,
+                    double* nu, int* status, double* history, double* G_out, double* scratch, int B, int Kc, int C, int H, int W, int map_rows, int K,
+                    int gh, int gw, int mode, int score, int tv_beta, double lr, double l1, double tv, double b1, double b2, double eps, double c1,
+                    double c2, int it, int iterations, int row0, int rows, bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

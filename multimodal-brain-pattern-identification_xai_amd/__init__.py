@@ -13,7 +13,7 @@ from .explain import (GradCamSweep, expected_gradients, generate_saliency_maps, 
                       GradientShapResult, gradient_shap, channel_importance, GradientExplainer,
                       SmoothGradResult, smooth_grad, smooth_grad_noise,
                       BlurIGResult, blur_ig, blur_path, gaussian_blur,
-                      GuidedIGResult, guided_ig, guided_ig_passes,
+                      GuidedIGResult, guided_ig, guided_ig_passes, MaskExplainResult, mask_explain,
                       SpectralGradientsResult, spectral_gradients, SpectralOcclusionResult, spectral_occlusion, eeg_spectrum, band_sums,
                       spectral_band_bins, spectral_twiddles, CLINICAL_BANDS,
                       InfidelityResult, infidelity, SensitivityResult, sensitivity_max,

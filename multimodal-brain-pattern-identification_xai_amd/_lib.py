@@ -28,6 +28,9 @@ BX_SPECTRAL_CELLS_BAND, BX_SPECTRAL_CELLS_ELECTRODE_BAND = 0, 1
 BX_SPECTRAL_MAX_T = 8192
 BX_SSIM_MAX_WIN = 63
 BX_FUSION_SCORE_PROB, BX_FUSION_SCORE_LOGPROB = 0, 1
+BX_MASKOPT_OK, BX_MASKOPT_NAN = 0, 1
+BX_MASKOPT_DELETION, BX_MASKOPT_PRESERVATION = 0, 1
+BX_MASKOPT_PROB, BX_MASKOPT_LOGPROB = 0, 1
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -242,6 +245,11 @@ SIGNATURES = {
     "bx_fusion_values": (i32, [vp] * 9 + [i32, vp] + [i32] * 5 + [vp]),
     "bx_shapley_exact": (i32, [vp, vp, vp, i32, i32, vp]),
     "bx_fusion_interaction": (i32, [vp, vp, i32, vp]),
+    "bx_maskopt_init": (i32, [vp] * 4 + [i32] * 6 + [vp]),
+    "bx_maskopt_masks": (i32, [vp, vp] + [i32] * 8 + [vp]),
+    "bx_maskopt_rows_spec": (i32, [vp, vp, vp, i32, vp] + [i32] * 9 + [vp]),
+    "bx_maskopt_rows_eeg": (i32, [vp, vp, i32, vp, i32, vp] + [i32] * 8 + [vp]),
+    "bx_maskopt_step": (i32, [vp, vp, i32] + [vp] * 10 + [i32] * 12 + [C.c_double] * 8 + [i32] * 4 + [vp]),
     "bx_param_uniform": (i32, [vp, sz, f32, C.c_uint64, u32, u32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),

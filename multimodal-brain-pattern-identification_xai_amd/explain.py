@@ -82,6 +82,13 @@
                                  layer between coalitions through LDS tables and averages in fp64 (bx_fusion_values); fixed-order fp64
                                  Shapley sums, the modality game and its interaction (bx_shapley_exact, bx_fusion_interaction).
                                  ``fusion_votes`` returns the votes, ``modality_importance`` the mean |value| per player.
+* ``mask_explain``            -- optimised perturbation masks (Fong & Vedaldi, ICCV 2017; the basis of TorchRay's extremal perturbations;
+                                 not in the reference): per (sample, class) a gh x gw grid, up-sampled bilinearly, is learned by Adam so
+                                 that deleting (or preserving only) the smallest smooth region changes the class score; the rows
+                                 (bx_maskopt_rows_*) and one step per iteration -- the fold of dF/dX through the blend and the
+                                 up-sampling onto the grid in fp64 in a fixed order, the L1 and TV regularisers, Adam, the clamp, the
+                                 history and the status (bx_maskopt_init, bx_maskopt_step) -- between the model's passes;
+                                 bx_maskopt_masks up-samples the grids for the result.
 """
 from __future__ import annotations
 
@@ -3009,6 +3016,221 @@ def _guided_ig(model, eeg, spec, input, steps, fraction, max_dist, baseline, cla
     shape = (lambda t: t.reshape(B, Kc, *t.shape[1:]) if all_classes else t)
     return gp.result(return_parts, GuidedIGResult, amap, values, endpoint, delta, shape(iters), None if path is None else shape(path),
                      None if grads is None else shape(grads), n, fraction, max_dist, baseline)
+
+
+# ------------------------------------------------------------------------------------------------
+# Optimised perturbation masks (Fong & Vedaldi, ICCV 2017, "meaningful perturbations"; the basis of TorchRay's extremal perturbations).
+# The definition is pinned in include/brainxai.h; tests/maskopt_ref.py restates it.
+MaskExplainResult = collections.namedtuple("MaskExplainResult", "map mask upsampled history final clean reference classes out path gradients outputs input mode "
+                                           "grid iterations lr l1 tv tv_beta betas eps baseline cells score")
+MaskExplainResult.__doc__ = """What ``mask_explain(..., return_parts=True)`` returns: ``map`` fp32 [B,Hm,Wm], with a class axis for class_idx='all' (what
+the plain call returns: 1 - upsampled for deletion, upsampled for preservation), ``mask`` fp32 [B(,K),gh,gw] (the learned grids),
+``upsampled`` fp32 [B(,K),Hm,Wm] (U(mask)), ``history`` fp64 [B(,K),iterations,3] = (score, mean of the grid, TV_beta of the grid) before
+every update, ``final`` fp32 [B(,K)] (the score of the input seen through the final mask, from one more forward pass), ``clean`` and
+``reference`` fp32 [B(,K)] (the score of the input itself and of the all-baseline input), ``classes`` int64 [B] (None for
+class_idx='all'), ``out`` fp32 [B,K] (the log-probabilities of the clean input), ``path`` fp32 [B(,K),iterations,gh,gw], ``gradients`` fp32
+[B(,K),iterations,*x.shape[1:]] and ``outputs`` fp32 [B(,K),iterations,K] (the grid, the gradient and the model's output at the top of every
+iteration; None without keep_path), all on the device; the other fields as given (``grid`` as the pair used)."""
+
+_MASKOPT_MODES = {"deletion": L.BX_MASKOPT_DELETION, "preservation": L.BX_MASKOPT_PRESERVATION}
+_MASKOPT_SCORES = {"prob": L.BX_MASKOPT_PROB, "logprob": L.BX_MASKOPT_LOGPROB}
+_MASKOPT_MAX_ROWS = 65535
+
+
+def _maskopt_grid(who, grid, Hm, Wm):
+    """-> (gh, gw): a pair as given, an int clipped per axis to min(grid, Hm / Wm, 32); checked against the domain."""
+    if isinstance(grid, numbers.Integral) and not isinstance(grid, bool):
+        if int(grid) < 1:
+            raise ValueError(f"{who}: grid = {int(grid)} < 1")
+        gh, gw = min(int(grid), Hm, _RISE_MAX_G), min(int(grid), Wm, _RISE_MAX_G)
+    else:
+        try:
+            gh, gw = (int(v) for v in grid)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: grid must be an int or a pair (gh, gw), got {grid!r}") from None
+    if not (1 <= gh <= min(_RISE_MAX_G, Hm) and 1 <= gw <= min(_RISE_MAX_G, Wm)):
+        raise ValueError(f"{who}: grid {gh} x {gw} outside 1..min({_RISE_MAX_G}, {Hm}) x 1..min({_RISE_MAX_G}, {Wm})")
+    return gh, gw
+
+
+def _maskopt_settings(who, iterations, lr, l1, tv, tv_beta, betas, eps):
+    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral):
+        raise ValueError(f"{who}: iterations must be an int, got {iterations!r}")
+    if int(iterations) < 1:
+        raise ValueError(f"{who}: iterations = {int(iterations)} < 1")
+    for name, v in (("lr", lr), ("l1", l1), ("tv", tv), ("eps", eps)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{who}: {name} must be a finite number >= 0, got {v!r}")
+    if isinstance(tv_beta, bool) or not isinstance(tv_beta, numbers.Integral) or int(tv_beta) not in (1, 2, 3):
+        raise ValueError(f"{who}: tv_beta must be 1, 2 or 3, got {tv_beta!r}")
+    try:
+        b1, b2 = (float(v) for v in betas)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: betas must be a pair (b1, b2), got {betas!r}") from None
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"{who}: betas ({b1}, {b2}) outside [0, 1)")
+    return int(iterations), float(lr), float(l1), float(tv), int(tv_beta), b1, b2, float(eps)
+
+
+def mask_explain(model, eeg, spec, *, input="spec", mode="deletion", grid=16, iterations=300, lr=0.1, l1=0.01, tv=0.2, tv_beta=3, betas=(0.9, 0.999),
+                 eps=1e-8, baseline=0.0, cells="electrode_time", class_idx=None, score="prob", max_batch=256, keep_path=False, return_parts=False):
+    """Optimised perturbation masks (Fong & Vedaldi, ICCV 2017, "meaningful perturbations"; the basis of TorchRay's extremal
+    perturbations): per (sample, class) the smallest smooth region whose removal (mode='deletion') or whose preservation alone
+    ('preservation') changes the class score is learned by Adam -- the objective behind ``deletion_insertion``, optimised directly.
+    The mask is a gh x gw grid m in [0, 1], up-sampled bilinearly (align_corners=False) to the mask domain, M = U(m); the model sees
+    X = base + M (x - base), and per row
+        deletion      L = l1 mean(1 - m) + tv TV_beta(m) + s_c(X)          preservation  L = l1 mean(m) + tv TV_beta(m) - s_c(X)
+    with TV_beta the sum of |d|^beta over the neighbour differences of the grid.
+
+    input:       'spec': masks over [H,W], one value for all channels of a pixel, map [B,H,W]; 'eeg': masks over [Chans,T], map
+                 [B,Chans,T], or with cells='time' over [1,T] (a column's value applies to every electrode), map [B,1,T].
+    model:       a MultimodalModel (the other input stays the sample's own); a stand-alone Spectrogram_Model (eeg=None, input='spec');
+                 a stand-alone EEGNet / EEGNetAttentionDeep (spec=None, input='eeg').
+    grid:        a pair (gh, gw) in 1..min(32, Hm) x 1..min(32, Wm), or an int, clipped per axis to min(grid, Hm or Wm, 32).
+    iterations, lr, betas, eps: Adam's, from a grid of ones; l1, tv, tv_beta (1, 2 or 3): the regularisers.
+    baseline:    what a masked-out cell shows: a number, one value per channel / electrode, or a tensor of the input's shape
+                 (``gaussian_blur``'s result is Fong & Vedaldi's blurred reference).
+    class_idx:   None = each sample's arg-max class on the clean input; an int; one class per sample (sequence / tensor [B]); 'all' =
+                 every class, the map gains a class axis [B,K,...] (K <= 32).  Every (sample, class) pair learns a mask of its own.
+    score:       'prob' or 'logprob': s_c, the class probability or the log-probability.
+    max_batch:   rows ((sample, class) pairs) per forward and backward pass.  No bit of the result depends on it.
+    keep_path:   keep the grid, the gradient and the output at the top of every iteration (``path``, ``gradients``, ``outputs``).
+    The map is 1 - U(m) for deletion and U(m) for preservation: high means important, and it fits ``deletion_insertion``,
+    ``attribution_ranks``, ``map_similarity`` and ``infidelity`` as it is.  Per iteration and per pass of at most max_batch rows: the rows
+    (bx_maskopt_rows_*), one forward pass, one backward pass whose one-hot seed names each row's own class (bx_expgrad_seed), and one
+    bx_maskopt_step, which folds dF/dX back through the blend and the up-sampling onto the grid in fp64 in a fixed order, adds the
+    regularisers, takes the Adam step, clamps, and records the history -- the host is asked nothing; the rows' status is read once,
+    after the last iteration.  In a MultimodalModel the branch whose input does not change runs once per sample.  The training flag and
+    every requires_grad are restored on return.  Returns the map (device, fp32), or ``MaskExplainResult`` with return_parts."""
+    return _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, tv_beta, betas, eps, baseline, cells, class_idx, score, max_batch,
+                         keep_path, return_parts)
+
+
+def _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, tv_beta, betas, eps, baseline, cells, class_idx, score, max_batch, keep_path,
+                  return_parts, profile=None):
+    """``mask_explain`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'rows', 'forward',
+    'backward', 'step', 'finish' -- device events around every phase of the pass (tools/mask_explain_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "mask_explain"
+    if input not in _FAITH_INPUTS:
+        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    if mode not in _MASKOPT_MODES:
+        raise ValueError(f"{who}: unknown mode {mode!r}; use 'deletion' or 'preservation'")
+    if score not in _MASKOPT_SCORES:
+        raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
+    if cells not in _RISE_CELLS:
+        raise ValueError(f"{who}: unknown cells {cells!r}; use 'electrode_time' or 'time'")
+    if cells == "time" and input != "eeg":
+        raise ValueError(f"{who}: cells='time' masks time columns of the EEG input; input='spec' has no such map")
+    n, lr, l1, tv, tv_beta, b1, b2, eps = _maskopt_settings(who, iterations, lr, l1, tv, tv_beta, betas, eps)
+    max_batch = _max_batch(who, max_batch)
+    x = _input_tensor(who, input, eeg, spec)
+    B = _nonempty(who, x)
+    per_len, what = _per_cell(who, x, input == "spec")
+    if input == "spec":
+        map_rows, Hm, Wm = 0, int(x.shape[2]), int(x.shape[3])
+    else:
+        map_rows = 1 if cells == "time" else int(x.shape[2])
+        Hm, Wm = map_rows, int(x.shape[3])
+    if not 1 <= Hm * Wm <= _FAITH_MAX_N:
+        raise ValueError(f"{who}: {Hm * Wm} cells per mask, supported 1..{_FAITH_MAX_N}")
+    gh, gw = _maskopt_grid(who, grid, Hm, Wm)
+    other = eeg if input == "spec" else spec
+    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    Kc = K if all_classes else 1
+    per, R = x.numel() // B, B * Kc
+    if R * per >= 1 << 31 or R * n * 3 >= 1 << 31 or R * Hm * Wm >= 1 << 31 or (keep_path and R * n * per >= 1 << 31) or R > _MASKOPT_MAX_ROWS:
+        raise ValueError(f"{who}: B * Kc * per = {R * per}, B * Kc * iterations * 3 = {R * n * 3}" + (f", B * Kc * iterations * per = {R * n * per} (keep_path)" if keep_path else "")
+                         + f" beyond 32-bit offsets, or B * Kc = {R} > {_MASKOPT_MAX_ROWS}; use fewer samples per call")
+    kind, base = _baseline_for(who, baseline, x, per_len, what)
+    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+
+    lib = L.load()
+    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", 1, cls_h, all_classes, max_batch, profile)
+    code_mode, code_score = _MASKOPT_MODES[mode], _MASKOPT_SCORES[score]
+    Cc, Hh, Ww = (int(v) for v in x.shape[1:])
+    with gp.open():
+        xs, dev, trail = gp.xs, gp.dev, tuple(gp.xs.shape[1:])
+        base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
+        gp.clean()
+        row_cls = (torch.arange(K, dtype=torch.int32, device=dev).repeat(B) if all_classes else gp.classes).contiguous()
+        m = torch.empty(R, gh, gw, dtype=torch.float32, device=dev)              # the grids, one row per (sample, class)
+        mu = torch.empty(R, gh, gw, dtype=torch.float64, device=dev)
+        nu = torch.empty(R, gh, gw, dtype=torch.float64, device=dev)
+        status = torch.empty(R, dtype=torch.int32, device=dev)
+        history = torch.zeros(R, n, 3, dtype=torch.float64, device=dev)
+        chunk = min(gp.max_rows, R)
+        scratch = torch.empty(chunk, Hm, gw, dtype=torch.float64, device=dev)
+        seed_rows = torch.empty(chunk, K, dtype=torch.float32, device=dev)
+        path = torch.empty(R, n, gh, gw, dtype=torch.float32, device=dev) if keep_path else None
+        grads = torch.empty(R, n, *trail, dtype=torch.float32, device=dev) if keep_path else None
+        outs = torch.empty(R, n, K, dtype=torch.float32, device=dev) if keep_path else None
+
+        def write(row0, rows):
+            r = torch.empty(rows, *trail, dtype=torch.float32, device=dev)
+            if gp.input_is_spec:
+                L.check(lib.bx_maskopt_rows_spec(_p(xs), _p(m), _p(base), kind, _p(r), B, Kc, Cc, Hh, Ww, gh, gw, row0, rows, _stream()), "bx_maskopt_rows_spec")
+            else:
+                L.check(lib.bx_maskopt_rows_eeg(_p(xs), _p(m), map_rows, _p(base), kind, _p(r), B, Kc, Hh, Ww, gh, gw, row0, rows, _stream()), "bx_maskopt_rows_eeg")
+            return r
+
+        def forward(r, row0, rows):
+            rep = gp.fixed.index_select(0, _sample_of(row0, rows, Kc, dev)) if multimodal else None
+            return _fuse(model, multimodal, gp.input_is_spec, net(r), rep).float().contiguous()
+
+        def scores(logp):
+            """fp32 [B(,K)] scores of log-probabilities [R,K], row r's own class (every class for class_idx='all')"""
+            s = logp if score == "logprob" else _softmax_rows(logp)
+            return s.gather(1, row_cls.long()[:, None])[:, 0]
+
+        with gp.lap("step"):
+            L.check(lib.bx_maskopt_init(_p(m), _p(mu), _p(nu), _p(status), B, Kc, gh, gw, 0, R, _stream()), "bx_maskopt_init")
+        with torch.no_grad(), gp.lap("forward"):
+            xb = (base if kind == 2 else base.reshape((1, -1, 1, 1) if gp.input_is_spec or kind == 0 else (1, 1, -1, 1)).expand_as(xs)).contiguous()
+            endpoint = _fuse(model, multimodal, gp.input_is_spec, net(xb), gp.fixed).float().contiguous()
+        for it in range(n):
+            c1, c2 = 1.0 - b1 ** (it + 1), 1.0 - b2 ** (it + 1)
+            if keep_path:
+                path[:, it] = m
+            for row0, rows in _sample_chunks(R, gp.max_rows):
+                with gp.lap("rows"):
+                    r = write(row0, rows)
+                with gp.lap("forward"):
+                    r.requires_grad_(True)
+                    y = forward(r, row0, rows)
+                with gp.lap("backward"):
+                    L.check(lib.bx_expgrad_seed(_p(row_cls), -1, _p(seed_rows), R, 1, K, row0, rows, _stream()), "bx_expgrad_seed")
+                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows[:rows])
+                    g = g.to(torch.float32).contiguous()
+                    yd = y.detach()
+                del y, r
+                if keep_path:
+                    grads[row0:row0 + rows, it] = g
+                    outs[row0:row0 + rows, it] = yd
+                with gp.lap("step"):
+                    L.check(lib.bx_maskopt_step(_p(xs), _p(base), kind, _p(g), _p(yd), _p(row_cls), _p(m), _p(mu), _p(nu), _p(status), _p(history), None,
+                                                _p(scratch), B, Kc, Cc, Hh, Ww, map_rows, K, gh, gw, code_mode, code_score, tv_beta, lr, l1, tv, b1, b2, eps,
+                                                c1, c2, it, n, row0, rows, _stream()), "bx_maskopt_step")
+        with gp.lap("finish"), torch.no_grad():
+            up = torch.empty(R, Hm, Wm, dtype=torch.float32, device=dev)
+            L.check(lib.bx_maskopt_masks(_p(m), _p(up), B, Kc, gh, gw, Hm, Wm, 0, R, _stream()), "bx_maskopt_masks")
+            amap = 1.0 - up if mode == "deletion" else up
+            last = torch.empty(R, K, dtype=torch.float32, device=dev)
+            for row0, rows in _sample_chunks(R, gp.max_rows):
+                last[row0:row0 + rows] = forward(write(row0, rows), row0, rows)
+            rep = (lambda t: t.repeat_interleave(Kc, dim=0) if all_classes else t)
+            final, clean, reference = scores(last), scores(rep(gp.out)), scores(rep(endpoint))
+        st = status.cpu()                                           # the one read of the rows' status
+        if bool((st != L.BX_MASKOPT_OK).any()):
+            bad = int((st != L.BX_MASKOPT_OK).nonzero()[0])
+            raise RuntimeError(f"brainxai.{who}: sample {bad // Kc}, class slot {bad % Kc} stopped: a NaN among the gradients or the outputs")
+    shape = (lambda t: None if t is None else (t.reshape(B, Kc, *t.shape[1:]) if all_classes else t))
+    parts = (lambda amap, mask, classes, out, *rest: MaskExplainResult(amap, mask, *rest[:5], classes, out, *rest[5:]))
+    return gp.result(return_parts, parts, amap.reshape(B, Kc, Hm, Wm), m.reshape(B, Kc, gh, gw), shape(up), shape(history), shape(final), shape(clean),
+                     shape(reference), shape(path), shape(grads), shape(outs), input, mode, (gh, gw), n, lr, l1, tv, tv_beta, (b1, b2), eps, baseline, cells, score)
 
 
 # ------------------------------------------------------------------------------------------------
