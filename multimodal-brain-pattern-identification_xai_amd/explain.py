@@ -1104,8 +1104,10 @@ def _faith_baseline(baseline, x, per_len, what):
     return _baseline_for("deletion_insertion", baseline, x, per_len, what)
 
 
-# ---- what the perturb-and-predict drivers (deletion_insertion, rise, occlusion, kernel_shap, score_cam) share: each driver keeps its
-# own order of checks, built from the pieces below, and its own clean pass; the rows all go through one _RowPass ----
+# ---- what the drivers that run rows through the model share: each driver keeps its own order of checks, built from the pieces below.
+# The perturb-and-predict drivers (deletion_insertion, rise, occlusion, kernel_shap, score_cam, spectral_occlusion, infidelity) keep
+# their own clean pass and send their rows through one _RowPass; the gradient drivers (gradient_shap, smooth_grad, blur_ig,
+# spectral_gradients by its sampled route; guided_ig, mask_explain by its per-row route) go through one _GradPass ----
 @contextlib.contextmanager
 def _lap(profile, name):
     """Device events around a phase, appended to ``profile`` as (name, start, end); nothing when profile is None."""
@@ -1252,6 +1254,15 @@ def _explained_classes(who, class_idx, B, K, allow_all):
     return cls_h, False
 
 
+def _explained_model(who, model, x, other, input_is_spec, class_idx):
+    """-> (multimodal, K, net, cls_h, all_classes): ``_target_model``, the refusal of more than 32 classes, and ``_explained_classes``
+    with 'all' allowed -- the three checks most drivers make one after the other."""
+    multimodal, K, net = _target_model(who, model, x, other, input_is_spec)
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    return (multimodal, K, net) + _explained_classes(who, class_idx, int(x.shape[0]), K, allow_all=True)
+
+
 def _row_cap(x, input, dt, max_batch, beside=0):
     """Rows per forward pass: max_batch, capped so that a pass addresses its largest activation with 32-bit byte offsets -- stage 1's
     H x W x 16 channels in dt for a spectrogram [B,C,H,W], EEGNet's F1 x Chans x T in fp32 for an EEG input [B,1,Chans,T].  beside: the
@@ -1374,12 +1385,19 @@ def _sample_of(row0, rows, n, dev):
 
 
 class _GradPass:
-    """What the sampled-gradient drivers (gradient_shap, smooth_grad, blur_ig) do alike once their arguments are checked: n sampled rows per
-    sample, sample-major, run through the branch that reads them with the other branch's per-sample output gathered into the fusion
-    head, and one backward pass per explained class from a one-hot seed (bx_expgrad_seed).  A driver brings its row writer, its
-    accumulate and its finish; the chunking by max_batch, the clean pass, the fp64 sums and the 'forward' / 'rows' / 'backward' /
-    'accumulate' laps of ``profile`` are here.  Inside ``open()``, ``xs`` is the explained input (fp32, contiguous); ``clean`` sets
-    ``out``, ``classes`` and ``fixed`` (None for a stand-alone model).  Cc, HW: the channels and pixels a finish launch reduces over."""
+    """What the gradient drivers do alike once their arguments are checked: rows run through the branch that reads them with the other
+    branch's per-sample output gathered into the fusion head, and backward passes from one-hot seeds (bx_expgrad_seed), in chunks of at
+    most max_batch rows.  Two routes, one pass object:
+      sampled  (gradient_shap, smooth_grad, blur_ig, spectral_gradients): n sampled rows per sample, sample-major; ``sweep`` runs every
+               chunk forward once and backward once per explained class slot.  The driver brings its row writer and its accumulate;
+               ``sums`` are the fp64 sums carried between chunks.
+      per row  (guided_ig, mask_explain; built with n = 1): R = B * Kc rows, one per (sample, class), iterated; ``row_steps`` runs every
+               chunk of every iteration forward and backward once, the seed naming each row's own class (``row_classes``).  The driver
+               brings its row writer and its step; ``baseline_rows`` / ``endpoint`` are the path's other end, ``stopped`` the one read of
+               the rows' status, ``per_row`` the class axis of what the driver kept per row.
+    The clean pass, the 'forward' / 'rows' / 'backward' / 'accumulate' / 'step' laps of ``profile``, ``finish_values``, ``completeness``
+    and ``result`` serve both.  Inside ``open()``, ``xs`` is the explained input (fp32, contiguous); ``clean`` sets ``out``, ``classes``
+    and ``fixed`` (None for a stand-alone model).  Cc, HW: the channels and pixels a finish launch reduces over."""
 
     def __init__(self, model, net, multimodal, K, x, other, input_is_spec, n, cls_h, all_classes, max_batch, profile, beside=0):
         self.model, self.net, self.multimodal, self.K, self.other, self.input_is_spec = model, net, multimodal, K, other, input_is_spec
@@ -1412,6 +1430,12 @@ class _GradPass:
         """``count`` fp64 zero sums [B,Kc,per]: what is carried between chunks, so that no bit depends on max_batch."""
         return [torch.zeros(self.B, self.Kc, self.per, dtype=torch.float64, device=self.dev) for _ in range(count)]
 
+    def forward(self, r, row0, rows, per_sample):
+        """fp32 [rows, K]: the model's output of rows row0..row0+rows-1, ``per_sample`` consecutive ones per sample, with the other
+        branch's output of the sample each row belongs to."""
+        rep = self.fixed.index_select(0, _sample_of(row0, rows, per_sample, self.dev)) if self.multimodal else None
+        return _fuse(self.model, self.multimodal, self.input_is_spec, self.net(r), rep).float()
+
     def sweep(self, write, accumulate):
         """For every chunk: ``write(row0, rows)`` returns the fp32 rows in the input's own layout; one forward pass; then per class slot
         one backward pass and ``accumulate(g, slot, row0, rows)``, g fp32 contiguous: the gradient of the slot's class by the rows."""
@@ -1421,10 +1445,7 @@ class _GradPass:
                 r = write(row0, rows)
             with self.lap("forward"):
                 r.requires_grad_(True)
-                rep = None
-                if self.multimodal:                                 # the other branch's output of the sample each row belongs to
-                    rep = self.fixed.index_select(0, _sample_of(row0, rows, self.n, self.dev))
-                y = _fuse(self.model, self.multimodal, self.input_is_spec, self.net(r), rep).float()
+                y = self.forward(r, row0, rows, self.n)
             seed_rows = torch.empty(rows, self.K, dtype=torch.float32, device=self.dev)
             for slot in range(self.Kc):
                 with self.lap("backward"):
@@ -1435,6 +1456,67 @@ class _GradPass:
                 with self.lap("accumulate"):
                     accumulate(g, slot, row0, rows)
             del y, r
+
+    def row_classes(self):
+        """int32 [R], contiguous: the class of every (sample, class) row."""
+        if not self.all_classes:
+            return self.classes.contiguous()
+        return torch.arange(self.K, dtype=torch.int32, device=self.dev).repeat(self.B).contiguous()
+
+    def baseline_rows(self, kind, base):
+        """The baseline of ``_baseline_for`` as a contiguous fp32 tensor of the input's shape, on the device."""
+        base = base.to(self.dev, torch.float32)
+        if kind == 2:
+            return base.reshape(self.xs.shape).contiguous()
+        return base.reshape((1, -1, 1, 1) if self.input_is_spec or kind == 0 else (1, 1, -1, 1)).expand_as(self.xs).contiguous()
+
+    def endpoint(self, xb):
+        """fp32 [B,K]: the model's output at ``xb`` (the input's shape), the other branch's output as in the clean pass."""
+        with torch.no_grad(), self.lap("forward"):
+            return _fuse(self.model, self.multimodal, self.input_is_spec, self.net(xb), self.fixed).float().contiguous()
+
+    def row_steps(self, iterations, write, step, rows_lap=False):
+        """For every iteration i and every chunk of the R = B * Kc rows: ``write(row0, rows)`` returns the fp32 rows in the input's own
+        layout (under the 'rows' lap with rows_lap; a writer that returns a view of rows the driver keeps has nothing to time); one
+        forward pass; one backward pass from the seed of each row's own class; then ``step(i, g, y, row0, rows)``, g the gradient by the
+        rows and y the model's output of them, both fp32, contiguous and detached."""
+        lib, R = L.load(), self.B * self.Kc
+        row_cls = self.row_classes()
+        seed_rows = torch.empty(min(self.max_rows, R), self.K, dtype=torch.float32, device=self.dev)
+        for i in range(iterations):
+            for row0, rows in _sample_chunks(R, self.max_rows):
+                with self.lap("rows") if rows_lap else contextlib.nullcontext():
+                    r = write(row0, rows)
+                with self.lap("forward"):
+                    r.requires_grad_(True)
+                    y = self.forward(r, row0, rows, self.Kc)
+                with self.lap("backward"):
+                    L.check(lib.bx_expgrad_seed(_p(row_cls), -1, _p(seed_rows), R, 1, self.K, row0, rows, _stream()), "bx_expgrad_seed")
+                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows[:rows])
+                    g, yd = g.to(torch.float32).contiguous(), y.detach().contiguous()
+                del y, r
+                with self.lap("step"):
+                    step(i, g, yd, row0, rows)
+
+    def stopped(self, who, status, ok, why):
+        """The one read of the rows' status words (int32 [R]): the first row that is not ``ok`` is reported as its (sample, class slot),
+        with ``why(code)`` as the reason."""
+        st = status.cpu()
+        if bool((st != ok).any()):
+            bad = int((st != ok).nonzero()[0])
+            raise RuntimeError(f"brainxai.{who}: sample {bad // self.Kc}, class slot {bad % self.Kc} stopped: {why(int(st[bad]))}")
+
+    def per_row(self, t):
+        """What a driver kept per row, [R,...], with the class axis [B,Kc,...] for class_idx='all'; None stays None."""
+        return t.reshape(self.B, self.Kc, *t.shape[1:]) if t is not None and self.all_classes else t
+
+    def finish_values(self, acc, n):
+        """-> (values fp32 [B,Kc,*x.shape[1:]], map fp32 [B,Kc,*x.shape[2:]]): the fp64 sums [B*Kc, per] divided by n and rounded, and
+        summed over the channels (bx_expgrad_finish); the lap is the driver's."""
+        values = self.empty(*self.xs.shape[1:])
+        amap = self.empty(*self.xs.shape[2:]) if self.input_is_spec else None
+        L.check(L.load().bx_expgrad_finish(_p(acc), _p(values), _p(amap), self.B * self.Kc, self.Cc, self.HW, n, _stream()), "bx_expgrad_finish")
+        return values, values[:, :, 0] if amap is None else amap                  # an EEG input has one channel: the map is the values
 
     def empty(self, *trail):
         """fp32 [B,Kc,*trail], empty: ``empty(*xs.shape[1:])`` is the estimator element by element, for the driver's finish launch."""
@@ -1719,10 +1801,7 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     geom = _rise_geometry(who, grid, Hm, Wm)
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     bits, shifts = _rise_mask_set(who, num_masks, geom, p1, seed, masks)
     N = int(bits.shape[0])
@@ -1851,10 +1930,7 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
     ny, nx = geom[4:]
     N = ny * nx
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
@@ -2085,10 +2161,7 @@ def _kernel_shap(model, eeg, spec, input, segments, num_samples, baseline, class
     Hm, Wm = seg.shape
     map_rows = None if input == "spec" else Hm
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     Z, weights, exact = _shap_coalitions(who, M, 2 * M + 2048 if num_samples is None else num_samples, seed, coalitions)
     N = int(Z.shape[0])
@@ -2402,10 +2475,7 @@ def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, see
     if Nb < 1:
         raise ValueError(f"{who}: empty background (Nb = 0)")
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     Kc = K if all_classes else 1
     per = x.numel() // B
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or Nb * per >= 1 << 31:
@@ -2431,11 +2501,7 @@ def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, see
         gp.sweep(write, lambda g, slot, row0, rows: L.check(lib.bx_expgrad_accumulate(
             _p(xs), _p(bgs), _p(idx_d), _p(g), _p(acc), B, Nb, n, per, Kc, slot, row0, rows, _stream()), "bx_expgrad_accumulate"))
         with gp.lap("finish"):
-            values = gp.empty(*xs.shape[1:])
-            amap = gp.empty(*xs.shape[2:]) if gp.input_is_spec else None
-            L.check(lib.bx_expgrad_finish(_p(acc), _p(values), _p(amap), B * Kc, gp.Cc, gp.HW, n, _stream()), "bx_expgrad_finish")
-            if amap is None:                                        # an EEG input has one channel: the map is the values
-                amap = values[:, :, 0]
+            values, amap = gp.finish_values(acc, n)
     return gp.result(return_parts, GradientShapResult, amap, values, idx, alpha, n)
 
 
@@ -2571,10 +2637,7 @@ def _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, cl
     B = _nonempty(who, x)
     level, sd = _level_or_absolute(who, B, "noise_level", noise_level, "stdev", stdev, 0.15, True)
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     Kc = K if all_classes else 1
     per = x.numel() // B
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or B * Kc > 65535:
@@ -2821,10 +2884,7 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
     x = _input_tensor(who, input, eeg, spec)
     B = _nonempty(who, x)
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     Kc = K if all_classes else 1
     per = x.numel() // B
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or B * Kc > 65535:
@@ -2855,11 +2915,7 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
         gp.sweep(write, lambda g, slot, row0, rows: L.check(lib.bx_blurig_accumulate(
             _p(g), _p(kept["D"]), _p(w_d), _p(acc), B, n, per, Kc, slot, row0, rows, _stream()), "bx_blurig_accumulate"))
         with gp.lap("finish"):
-            values = gp.empty(*xs.shape[1:])
-            amap = gp.empty(*xs.shape[2:]) if gp.input_is_spec else None
-            L.check(lib.bx_expgrad_finish(_p(acc), _p(values), _p(amap), B * Kc, gp.Cc, gp.HW, 1, _stream()), "bx_expgrad_finish")
-            if amap is None:                                        # an EEG input has one channel: the map is the values
-                amap = values[:, :, 0]
+            values, amap = gp.finish_values(acc, 1)
             last = torch.empty_like(xs)                             # the end of the path: x blurred with sigma_n
             _blur_rows(lib, xs, torch.from_numpy(end_taps).to(gp.dev), torch.from_numpy(end_radius).to(gp.dev), end_taps.shape[2], last, None, 1, axes, 0, 0, B)
             with torch.no_grad():
@@ -2943,10 +2999,7 @@ def _guided_ig(model, eeg, spec, input, steps, fraction, max_dist, baseline, cla
     x = _input_tensor(who, input, eeg, spec)
     B = _nonempty(who, x)
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     Kc = K if all_classes else 1
     per, R = x.numel() // B, B * Kc
     if per > _GUIDED_MAX_CELLS:
@@ -2965,12 +3018,8 @@ def _guided_ig(model, eeg, spec, input, steps, fraction, max_dist, baseline, cla
     gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", 1, cls_h, all_classes, max_batch, profile)
     with gp.open():
         xs, dev, trail = gp.xs, gp.dev, tuple(gp.xs.shape[1:])
-        base = base.to(dev, torch.float32)
-        if kind == 1:
-            base = base.reshape((1, -1, 1, 1) if gp.input_is_spec else (1, 1, -1, 1))
-        xb = (base.reshape(xs.shape) if kind == 2 else base.expand_as(xs)).contiguous()
+        xb = gp.baseline_rows(kind, base)
         gp.clean()
-        row_cls = (torch.arange(K, dtype=torch.int32, device=dev).repeat(B) if all_classes else gp.classes).contiguous()
         xr = torch.empty(R, *trail, dtype=torch.float32, device=dev)             # the moving points, one row per (sample, class)
         attr = torch.empty(R, per, dtype=torch.float64, device=dev)
         l_total = torch.empty(R, dtype=torch.float64, device=dev)
@@ -2980,42 +3029,23 @@ def _guided_ig(model, eeg, spec, input, steps, fraction, max_dist, baseline, cla
         grads = torch.empty(R, n, *trail, dtype=torch.float32, device=dev) if keep_path else None
         with gp.lap("step"):
             L.check(lib.bx_guided_ig_init(_p(xs), _p(xb), 1, _p(xr), _p(attr), _p(l_total), _p(status), B, Kc, per, _stream()), "bx_guided_ig_init")
-        with torch.no_grad(), gp.lap("forward"):
-            endpoint = _fuse(model, multimodal, gp.input_is_spec, net(xb), gp.fixed).float().contiguous()
-        seed_rows = torch.empty(min(gp.max_rows, R), K, dtype=torch.float32, device=dev)
-        for i in range(n):
-            if keep_path:
-                path[:, i] = xr
-            for row0, rows in _sample_chunks(R, gp.max_rows):
-                with gp.lap("forward"):
-                    r = xr[row0:row0 + rows].detach().requires_grad_(True)      # the kernel's own rows: no copy
-                    rep = gp.fixed.index_select(0, _sample_of(row0, rows, Kc, dev)) if multimodal else None
-                    y = _fuse(model, multimodal, gp.input_is_spec, net(r), rep).float()
-                with gp.lap("backward"):
-                    L.check(lib.bx_expgrad_seed(_p(row_cls), -1, _p(seed_rows), R, 1, K, row0, rows, _stream()), "bx_expgrad_seed")
-                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows[:rows])
-                    g = g.to(torch.float32).contiguous()
-                del y, r
-                if keep_path:
-                    grads[row0:row0 + rows, i] = g
-                with gp.lap("step"):
-                    L.check(lib.bx_guided_ig_step(_p(xs), _p(xb), _p(xr), _p(g), _p(attr), _p(l_total), _p(status), _p(iters), B, Kc, per, i, n, k,
-                                                  max_dist, cap, row0, rows, _stream()), "bx_guided_ig_step")
+        endpoint = gp.endpoint(xb)
+
+        def step(i, g, y, row0, rows):
+            if keep_path:                                           # the point and the gradient at the top of the step
+                path[row0:row0 + rows, i] = xr[row0:row0 + rows]
+                grads[row0:row0 + rows, i] = g
+            L.check(lib.bx_guided_ig_step(_p(xs), _p(xb), _p(xr), _p(g), _p(attr), _p(l_total), _p(status), _p(iters), B, Kc, per, i, n, k,
+                                          max_dist, cap, row0, rows, _stream()), "bx_guided_ig_step")
+
+        gp.row_steps(n, lambda row0, rows: xr[row0:row0 + rows].detach(), step)    # the kernel's own rows: no copy
         with gp.lap("finish"):
-            values = gp.empty(*trail)
-            amap = gp.empty(*trail[1:]) if gp.input_is_spec else None
-            L.check(lib.bx_expgrad_finish(_p(attr), _p(values), _p(amap), R, gp.Cc, gp.HW, 1, _stream()), "bx_expgrad_finish")
-            if amap is None:                                        # an EEG input has one channel: the map is the values
-                amap = values[:, :, 0]
+            values, amap = gp.finish_values(attr, 1)
             delta = gp.completeness(values, per, endpoint)
-        st = status.cpu()                                           # the one read of the rows' status
-        if bool((st != L.BX_GUIDED_OK).any()):
-            bad = int((st != L.BX_GUIDED_OK).nonzero()[0])
-            why = ("a NaN among the gradients" if int(st[bad]) == L.BX_GUIDED_NAN else f"a step that did not end within {cap} passes")
-            raise RuntimeError(f"brainxai.{who}: sample {bad // Kc}, class slot {bad % Kc} stopped: {why}")
-    shape = (lambda t: t.reshape(B, Kc, *t.shape[1:]) if all_classes else t)
-    return gp.result(return_parts, GuidedIGResult, amap, values, endpoint, delta, shape(iters), None if path is None else shape(path),
-                     None if grads is None else shape(grads), n, fraction, max_dist, baseline)
+        gp.stopped(who, status, L.BX_GUIDED_OK,
+                   lambda code: "a NaN among the gradients" if code == L.BX_GUIDED_NAN else f"a step that did not end within {cap} passes")
+    return gp.result(return_parts, GuidedIGResult, amap, values, endpoint, delta, gp.per_row(iters), gp.per_row(path), gp.per_row(grads), n, fraction,
+                     max_dist, baseline)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -3136,10 +3166,7 @@ def _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, t
         raise ValueError(f"{who}: {Hm * Wm} cells per mask, supported 1..{_FAITH_MAX_N}")
     gh, gw = _maskopt_grid(who, grid, Hm, Wm)
     other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
     Kc = K if all_classes else 1
     per, R = x.numel() // B, B * Kc
     if R * per >= 1 << 31 or R * n * 3 >= 1 << 31 or R * Hm * Wm >= 1 << 31 or (keep_path and R * n * per >= 1 << 31) or R > _MASKOPT_MAX_ROWS:
@@ -3156,15 +3183,13 @@ def _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, t
         xs, dev, trail = gp.xs, gp.dev, tuple(gp.xs.shape[1:])
         base = base.to(dev, torch.float32).reshape(xs.shape if kind == 2 else (-1,)).contiguous()
         gp.clean()
-        row_cls = (torch.arange(K, dtype=torch.int32, device=dev).repeat(B) if all_classes else gp.classes).contiguous()
+        row_cls = gp.row_classes()
         m = torch.empty(R, gh, gw, dtype=torch.float32, device=dev)              # the grids, one row per (sample, class)
         mu = torch.empty(R, gh, gw, dtype=torch.float64, device=dev)
         nu = torch.empty(R, gh, gw, dtype=torch.float64, device=dev)
         status = torch.empty(R, dtype=torch.int32, device=dev)
         history = torch.zeros(R, n, 3, dtype=torch.float64, device=dev)
-        chunk = min(gp.max_rows, R)
-        scratch = torch.empty(chunk, Hm, gw, dtype=torch.float64, device=dev)
-        seed_rows = torch.empty(chunk, K, dtype=torch.float32, device=dev)
+        scratch = torch.empty(min(gp.max_rows, R), Hm, gw, dtype=torch.float64, device=dev)
         path = torch.empty(R, n, gh, gw, dtype=torch.float32, device=dev) if keep_path else None
         grads = torch.empty(R, n, *trail, dtype=torch.float32, device=dev) if keep_path else None
         outs = torch.empty(R, n, K, dtype=torch.float32, device=dev) if keep_path else None
@@ -3177,57 +3202,35 @@ def _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, t
                 L.check(lib.bx_maskopt_rows_eeg(_p(xs), _p(m), map_rows, _p(base), kind, _p(r), B, Kc, Hh, Ww, gh, gw, row0, rows, _stream()), "bx_maskopt_rows_eeg")
             return r
 
-        def forward(r, row0, rows):
-            rep = gp.fixed.index_select(0, _sample_of(row0, rows, Kc, dev)) if multimodal else None
-            return _fuse(model, multimodal, gp.input_is_spec, net(r), rep).float().contiguous()
-
         def scores(logp):
             """fp32 [B(,K)] scores of log-probabilities [R,K], row r's own class (every class for class_idx='all')"""
             s = logp if score == "logprob" else _softmax_rows(logp)
             return s.gather(1, row_cls.long()[:, None])[:, 0]
 
+        def step(it, g, y, row0, rows):
+            if keep_path:                                           # the grid, the gradient and the output at the top of the iteration
+                path[row0:row0 + rows, it] = m[row0:row0 + rows]
+                grads[row0:row0 + rows, it] = g
+                outs[row0:row0 + rows, it] = y
+            L.check(lib.bx_maskopt_step(_p(xs), _p(base), kind, _p(g), _p(y), _p(row_cls), _p(m), _p(mu), _p(nu), _p(status), _p(history), None,
+                                        _p(scratch), B, Kc, Cc, Hh, Ww, map_rows, K, gh, gw, code_mode, code_score, tv_beta, lr, l1, tv, b1, b2, eps,
+                                        1.0 - b1 ** (it + 1), 1.0 - b2 ** (it + 1), it, n, row0, rows, _stream()), "bx_maskopt_step")
+
         with gp.lap("step"):
             L.check(lib.bx_maskopt_init(_p(m), _p(mu), _p(nu), _p(status), B, Kc, gh, gw, 0, R, _stream()), "bx_maskopt_init")
-        with torch.no_grad(), gp.lap("forward"):
-            xb = (base if kind == 2 else base.reshape((1, -1, 1, 1) if gp.input_is_spec or kind == 0 else (1, 1, -1, 1)).expand_as(xs)).contiguous()
-            endpoint = _fuse(model, multimodal, gp.input_is_spec, net(xb), gp.fixed).float().contiguous()
-        for it in range(n):
-            c1, c2 = 1.0 - b1 ** (it + 1), 1.0 - b2 ** (it + 1)
-            if keep_path:
-                path[:, it] = m
-            for row0, rows in _sample_chunks(R, gp.max_rows):
-                with gp.lap("rows"):
-                    r = write(row0, rows)
-                with gp.lap("forward"):
-                    r.requires_grad_(True)
-                    y = forward(r, row0, rows)
-                with gp.lap("backward"):
-                    L.check(lib.bx_expgrad_seed(_p(row_cls), -1, _p(seed_rows), R, 1, K, row0, rows, _stream()), "bx_expgrad_seed")
-                    (g,) = torch.autograd.grad(y, r, grad_outputs=seed_rows[:rows])
-                    g = g.to(torch.float32).contiguous()
-                    yd = y.detach()
-                del y, r
-                if keep_path:
-                    grads[row0:row0 + rows, it] = g
-                    outs[row0:row0 + rows, it] = yd
-                with gp.lap("step"):
-                    L.check(lib.bx_maskopt_step(_p(xs), _p(base), kind, _p(g), _p(yd), _p(row_cls), _p(m), _p(mu), _p(nu), _p(status), _p(history), None,
-                                                _p(scratch), B, Kc, Cc, Hh, Ww, map_rows, K, gh, gw, code_mode, code_score, tv_beta, lr, l1, tv, b1, b2, eps,
-                                                c1, c2, it, n, row0, rows, _stream()), "bx_maskopt_step")
+        endpoint = gp.endpoint(gp.baseline_rows(kind, base))
+        gp.row_steps(n, write, step, rows_lap=True)
         with gp.lap("finish"), torch.no_grad():
             up = torch.empty(R, Hm, Wm, dtype=torch.float32, device=dev)
             L.check(lib.bx_maskopt_masks(_p(m), _p(up), B, Kc, gh, gw, Hm, Wm, 0, R, _stream()), "bx_maskopt_masks")
             amap = 1.0 - up if mode == "deletion" else up
             last = torch.empty(R, K, dtype=torch.float32, device=dev)
             for row0, rows in _sample_chunks(R, gp.max_rows):
-                last[row0:row0 + rows] = forward(write(row0, rows), row0, rows)
+                last[row0:row0 + rows] = gp.forward(write(row0, rows), row0, rows, Kc)
             rep = (lambda t: t.repeat_interleave(Kc, dim=0) if all_classes else t)
             final, clean, reference = scores(last), scores(rep(gp.out)), scores(rep(endpoint))
-        st = status.cpu()                                           # the one read of the rows' status
-        if bool((st != L.BX_MASKOPT_OK).any()):
-            bad = int((st != L.BX_MASKOPT_OK).nonzero()[0])
-            raise RuntimeError(f"brainxai.{who}: sample {bad // Kc}, class slot {bad % Kc} stopped: a NaN among the gradients or the outputs")
-    shape = (lambda t: None if t is None else (t.reshape(B, Kc, *t.shape[1:]) if all_classes else t))
+        gp.stopped(who, status, L.BX_MASKOPT_OK, lambda code: "a NaN among the gradients or the outputs")
+    shape = gp.per_row
     parts = (lambda amap, mask, classes, out, *rest: MaskExplainResult(amap, mask, *rest[:5], classes, out, *rest[5:]))
     return gp.result(return_parts, parts, amap.reshape(B, Kc, Hm, Wm), m.reshape(B, Kc, gh, gw), shape(up), shape(history), shape(final), shape(clean),
                      shape(reference), shape(path), shape(grads), shape(outs), input, mode, (gh, gw), n, lr, l1, tv, tv_beta, (b1, b2), eps, baseline, cells, score)
@@ -3416,10 +3419,7 @@ def _spectral_gradients(model, eeg, spec, kind, steps, fs, bands, class_idx, max
     B, Chans, T, F = _spectral_shape(who, x)
     fs = _spectral_fs(who, fs)
     band_bins = None if bands is None else spectral_band_bins(bands, T, fs, who)
-    multimodal, K, net = _target_model(who, model, x, spec, False)
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, spec, False, class_idx)
     Kc = K if all_classes else 1
     per = Chans * T
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31:
@@ -3455,8 +3455,7 @@ def _spectral_gradients(model, eeg, spec, kind, steps, fs, bands, class_idx, max
                     "bx_spectral_values")
         if not return_parts:
             return amap if all_classes else amap[:, 0]
-        gradient = gp.empty(*xs.shape[1:])
-        L.check(lib.bx_expgrad_finish(_p(acc), _p(gradient), None, B * Kc, 1, per, 1, _stream()), "bx_expgrad_finish")
+        gradient, _ = gp.finish_values(acc, 1)
         band_vals = None if band_bins is None else _band_sum(lib, amap, torch.tensor(band_bins, dtype=torch.int32, device=dev), len(band_bins))
         delta = None
         if n > 1 and kind == "gradient_x_amplitude":
@@ -3504,10 +3503,7 @@ def _spectral_occlusion(model, eeg, spec, bands, fs, cells, class_idx, score, ma
     band_bins = spectral_band_bins(bands, T, fs, who)
     nb = len(band_bins)
     N = nb if cells == "band" else nb * Chans
-    multimodal, K, net = _target_model(who, model, x, spec, False)
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, spec, False, class_idx)
     if B * N * K >= 1 << 31 or B * Chans * T >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * Chans * T = {B * Chans * T} beyond 32-bit offsets; use fewer samples per call")
     _need_gpu(who, "the model and its inputs", model, x, spec if multimodal else None)
@@ -3647,10 +3643,7 @@ def _infidelity(model, eeg, spec, attribution, input, nsamples, noise_level, std
     _per_cell(who, x, is_spec)
     level, sd = _level_or_absolute(who, B, "noise_level", noise_level, "stdev", stdev, 0.15, True)
     other = eeg if is_spec else spec
-    multimodal, K, net = _target_model(who, model, x, other, is_spec)
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, is_spec, class_idx)
     grouped, cells = _infidelity_cells(who, attribution, x, is_spec, all_classes, K)
     Kc = K if all_classes else 1
     per = x.numel() // B

@@ -1,12 +1,18 @@
-"""GPU: the pass that gradient_shap and smooth_grad share (explain._GradPass), at its seam: the chunking by max_batch, the gradient
-seeds read at the rows of a chunk, and the model's state when a driver's own step fails.
+"""GPU: the pass behind the gradient drivers (explain._GradPass), at its seam: the chunking by max_batch, the gradient seeds read at
+the rows of a chunk, and the model's state when a driver's own step fails.  Its sampled route serves gradient_shap, smooth_grad and
+blur_ig (n rows per sample, one backward pass per class slot), its per-row route guided_ig and mask_explain (one row per (sample,
+class), iterated).
 
-Shapes: the interface model of tests/grad_gpu.py, B = 2, EEG 19x2000 and spectrogram 4x32x64, n = 6 draws (Nb = 3 backgrounds): 12 rows.
-max_batch 256 is one chunk, 1 a chunk per row; at 5 and 7 the chunks begin and end inside a sample and the last one is short.
+Shapes: the interface model of tests/grad_gpu.py, B = 2, EEG 19x2000 and spectrogram 4x32x64.  Sampled route: n = 6 draws (Nb = 3
+backgrounds) or 6 blur steps: 12 rows.  max_batch 256 is one chunk, 1 a chunk per row; at 5 and 7 the chunks begin and end inside a
+sample and the last one is short.  Per-row route: class_idx='all', 2 x 6 = 12 rows, 3 steps / iterations, max_batch 5: three chunks
+per iteration (that no bit of these two drivers' results depends on max_batch is asserted by test_class_forms_and_max_batch of
+tests/test_gpu_guided_ig.py and tests/test_gpu_maskopt.py).
 Bound: against the one-chunk call the values stay within TOL = 1e-3 of the per-(sample, class) maximum, the project's fp32 gradient
 bound (TOL of tests/test_gpu_parity.py) -- gradients of batches composed differently need not be bit-equal; what does not pass through
-a chunk (the classes, the clean output, sigma, the draws) is equal bit for bit.  The guard, on the one-chunk side alone: explaining
-classes [1, 4] instead of [4, 1] moves the values by more than 100 x TOL for every sample, so a seed read at the wrong row cannot pass.
+a chunk (the classes, the clean output, sigma, the draws, blur_ig's endpoint and schedule) is equal bit for bit.  The guard, on the
+one-chunk side alone: explaining classes [1, 4] instead of [4, 1] moves the values by more than 100 x TOL for every sample, so a seed
+read at the wrong row cannot pass.
 Observed figures are printed by each test (run with -s)."""
 import functools
 
@@ -22,17 +28,28 @@ from tests import perturb_gpu as PG
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
 N = 6
-DRIVERS = {"gradient_shap": "bx_expgrad_rows", "smooth_grad": "bx_smoothgrad_rows"}          # the driver's own row launch
+STEPS = 3
+BLUR_MAX_SIGMA = {"eeg": 8.0, "spec": 3.0}                    # those of tests/test_gpu_blur_ig.py: the filters fit both inputs
+# the driver's own per-chunk launch, the one that is made to fail: the row writers of the sampled route, the step / the rows of the per-row one
+SAMPLED = {"gradient_shap": "bx_expgrad_rows", "smooth_grad": "bx_smoothgrad_rows", "blur_ig": "bx_blur_rows"}
+PER_ROW = {"guided_ig": "bx_guided_ig_step", "mask_explain": "bx_maskopt_rows_{input}"}
 CLASS_FORMS = {"top": None, "pair": [4, 1], "swapped": [1, 4], "all": "all"}
-drivers_and_inputs = pytest.mark.parametrize("driver,input", [(d, i) for d in DRIVERS for i in ("eeg", "spec")])
+sampled_and_inputs = pytest.mark.parametrize("driver,input", [(d, i) for d in SAMPLED for i in ("eeg", "spec")])
+drivers_and_inputs = pytest.mark.parametrize("driver,input", [(d, i) for d in (*SAMPLED, *PER_ROW) for i in ("eeg", "spec")])
 
 
 def _call(driver, input, form, max_batch):
     mine, eeg, spec = GG.iface()
-    kw = dict(input=input, nsamples=N, class_idx=CLASS_FORMS[form], seed=3, max_batch=max_batch, return_parts=True)
+    kw = dict(input=input, class_idx=CLASS_FORMS[form], max_batch=max_batch, return_parts=True)
     if driver == "gradient_shap":
-        return brainxai.gradient_shap(mine, eeg, spec, GG.backgrounds()[input == "spec"], **kw)
-    return brainxai.smooth_grad(mine, eeg, spec, **kw)
+        return brainxai.gradient_shap(mine, eeg, spec, GG.backgrounds()[input == "spec"], nsamples=N, seed=3, **kw)
+    if driver == "smooth_grad":
+        return brainxai.smooth_grad(mine, eeg, spec, nsamples=N, seed=3, **kw)
+    if driver == "blur_ig":
+        return brainxai.blur_ig(mine, eeg, spec, steps=N, max_sigma=BLUR_MAX_SIGMA[input], **kw)
+    if driver == "guided_ig":
+        return brainxai.guided_ig(mine, eeg, spec, steps=STEPS, keep_path=True, **kw)
+    return brainxai.mask_explain(mine, eeg, spec, iterations=STEPS, grid=6, keep_path=True, **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -53,10 +70,11 @@ def _same(a, b):
 
 
 @pytest.mark.parametrize("form", ["top", "pair", "all"])
-@drivers_and_inputs
+@sampled_and_inputs
 def test_chunks_against_one_chunk(driver, input, form):
     one = _one_chunk(driver, input, form)
-    fixed = [f for f in one._fields if f not in ("attribution", "values")]           # classes, out, sigma / idx, alpha, and what was given
+    # classes, out, sigma / idx, alpha / endpoint, sigmas, and what was given; blur_ig's map and delta are sums of its values
+    fixed = [f for f in one._fields if f not in ("attribution", "map", "values", "delta")]
     line = []
     for max_batch in (1, 5, 7):
         res = _call(driver, input, form, max_batch)
@@ -68,7 +86,7 @@ def test_chunks_against_one_chunk(driver, input, form):
     print(f"{driver} {input} input, classes {form}: of the per-(sample, class) maximum, " + "; ".join(line))
 
 
-@drivers_and_inputs
+@sampled_and_inputs
 def test_swapped_classes_move_the_one_chunk_result(driver, input):
     pair, swapped = _one_chunk(driver, input, "pair"), _one_chunk(driver, input, "swapped")
     assert pair.classes.tolist() == [4, 1] and swapped.classes.tolist() == [1, 4]
@@ -83,11 +101,13 @@ class _RowWriterFailed(Exception):
 
 @drivers_and_inputs
 def test_state_after_a_failing_row_writer(driver, input, monkeypatch):
-    """A Python exception out of the driver's write step, in the second chunk: the training flag and every requires_grad come back, and
-    the next call returns the bits of a call made before."""
+    """A Python exception out of the driver's own per-chunk launch, in the second chunk: the training flag and every requires_grad come
+    back, and the next call returns the bits of a call made before."""
     mine, _, _ = GG.iface()
-    fresh = _call(driver, input, "pair", 5)
-    lib, launch, calls = L.load(), getattr(L.load(), DRIVERS[driver]), []
+    form = "all" if driver in PER_ROW else "pair"                                    # 12 rows either way: three chunks of at most 5
+    name = {**SAMPLED, **PER_ROW}[driver].format(input=input)
+    fresh = _call(driver, input, form, 5)
+    lib, launch, calls = L.load(), getattr(L.load(), name), []
 
     def failing(*args):
         calls.append(len(args))
@@ -101,14 +121,14 @@ def test_state_after_a_failing_row_writer(driver, input, monkeypatch):
     try:
         before = PG.model_state(mine)
         with monkeypatch.context() as patch:
-            patch.setattr(lib, DRIVERS[driver], failing)
+            patch.setattr(lib, name, failing)
             with pytest.raises(_RowWriterFailed):
-                _call(driver, input, "pair", 5)
-        assert len(calls) == 2 and getattr(lib, DRIVERS[driver]) is launch
+                _call(driver, input, form, 5)
+        assert len(calls) == 2 and getattr(lib, name) is launch
         assert PG.model_state(mine) == before and mine.training and not frozen.requires_grad
     finally:
         frozen.requires_grad_(True)
         mine.eval()
-    again = _call(driver, input, "pair", 5)
+    again = _call(driver, input, form, 5)
     for f in fresh._fields:
         assert _same(getattr(again, f), getattr(fresh, f)), f"{driver} {input}: {f} after the failed call differs from the call before it"
