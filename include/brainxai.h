@@ -1223,6 +1223,66 @@ int bx_maskopt_step(const float* x, const float* baseline, int baseline_kind, co
                     double* nu, int* status, double* history, double* G_out, double* scratch, int B, int Kc, int C, int H, int W, int map_rows, int K,
                     int gh, int gw, int mode, int score, int tv_beta, double lr, double l1, double tv, double b1, double b2, double eps, double c1,
                     double c2, int it, int iterations, int row0, int rows, bxStream stream);
+/* ---- TCAV: Testing with Concept Activation Vectors (Kim et al., ICML 2018; Captum's concept.TCAV; the mean-difference "pattern" CAV of
+ * Pahde et al. 2022).  a(x) in R^D is the activation of the target layer for one example, flattened in the order the capture returns
+ * it (NHWC for a spectrogram target, the feature order for the EEG branch's features).  Concept sets P_1..P_Q and random sets N_1..N_R
+ * of n examples each are stacked, set after set, into A [M,D], M = (Q + R) n.
+ *     mean = column mean of A;   G0 = (A - 1 mean^T)(A - 1 mean^T)^T, fp64 [M,M], computed once.
+ * The global centring removes the common offset of post-ReLU activations; every quantity below is a function of G0 alone.
+ * A problem is a list of rows I of A (positives first, then negatives; at most 512), labels y = +1 / -1 and fit marks; the rows without a
+ * fit mark are held out.  With F the nf fit rows, H = I - 11^T/nf and ybar the mean label of F:
+ *     BX_TCAV_RIDGE            min (w a_i + b - y_i)^2 + lambda |w|^2 over F:  K = H G0[F,F] H,  lambda = ridge tr(K) / nf (relative, so the
+ *                              scale of a layer or of bf16 storage does not matter),  (K + lambda I) alpha = H y by Cholesky,
+ *                              beta = H alpha;  cond(K + lambda I) <= nf / ridge + 1 by construction
+ *     BX_TCAV_MEAN_DIFFERENCE  beta_i = +1 / n+ on the positive fit rows, -1 / n- on the negative ones;  lambda = 0
+ * Both have sum beta = 0, and from there one path:  w = sum_i beta_i (a_i - mean),  |w|^2 = beta^T G0[F,F] beta,  the CAV v = w / |w|
+ * points towards the concept.  s_j = sum_i beta_i G0[F_i, j] for any stacked row j; the decision value of row j of I is
+ * s_j - mean_F(s) + ybar (ridge) or s_j - (mean of s over the positive fit rows + mean over the negative ones) / 2 (mean difference);
+ * a row is classified +1 when its decision value is > 0.
+ * Status, per problem: 0 fitted; 1 tr(K) <= nf 2^-52 tr(G0[F,F]) -- no scatter inside the problem beyond the rounding of the centring
+ * (ridge only); 2 |w|^2 <= nf 2^-52 (sum_i |beta_i| sqrt(G0[F_i,F_i]))^2 -- w = 0 up to the rounding of its own sum; 3 a Cholesky pivot
+ * that is not above nf 2^-52 times its entry of K + lambda I (bx_shap_fit's criterion); 4 a malformed problem (a row outside 0..M-1, a
+ * label other than +-1, a class without a fit row, more fit rows than nfmax).  A problem with a status writes its status and nothing
+ * else.
+ * Sensitivity S_k(x; v) = grad_a F_k(x) . v, F_k the output log-probability of class k; the TCAV score of (problem, class k) is the share
+ * of the rows explained for class k whose S is > 0.
+ * fp32 or bf16 activations and gradients (dtype as in bx_cam_reduce); no atomics; every sum is taken in an order that depends on the
+ * shapes alone; the file is built with -ffp-contract=off and names its fused multiply-adds.  Limits: M <= 8192, D <= 2^24, at most 512
+ * rows per problem, 65535 problems, 32 classes; beyond them BX_EUNSUPPORTED before any pointer is touched. */
+enum { BX_TCAV_RIDGE = 0, BX_TCAV_MEAN_DIFFERENCE = 1 };
+/* mean fp64 [D]: mean[d] = (sum_i (double)A[i,d], i ascending from 0.0) / M. */
+int bx_tcav_mean(const void* A, double* mean, int M, int D, int dtype, bxStream stream);
+/* G0 fp64 [M,M].  An entry is the sum over d of fma((double)A[i,d] - mean[d], (double)A[j,d] - mean[d], .): the features are cut into
+ * S = ceil(D / len) splits of len = max(512, ceil(D / 32) rounded up to a multiple of 32) features, a split is summed in ascending d from
+ * 0.0 by one workgroup per 64 x 64 tile of row pairs (features streamed through LDS 32 at a time), and the S partial sums, kept in the
+ * workspace, are added in split order.  Only the tiles of the lower triangle are computed; (i, j) and (j, i) receive the same value,
+ * so G0 is symmetric bit for bit.  Plain fp64 FMAs, not the f64 MFMA (TCAV).  workspace: 16-byte aligned. */
+size_t bx_tcav_gram_workspace(int M, int D);
+int bx_tcav_gram(const void* A, const double* mean, double* G0, int M, int D, int dtype, void* workspace, size_t workspace_bytes, bxStream stream);
+/* P problems, one workgroup each.  rows, labels, fit i32 [P,NI] (row of A, +1 / -1, 1 = fit row / 0 = held out) and counts i32 [P] (the
+ * rows of problem p are its first counts[p] entries); nfmax >= the largest number of fit rows.  workspace: P slabs of nfmax^2 doubles
+ * (bx_tcav_fit_workspace), in which a problem gathers G0[F,F], centres it, adds lambda and factorises.  Outputs of a fitted problem:
+ * beta fp64 [P,M] (the dual coefficients at the fit rows' columns, 0.0 elsewhere), norm fp64 [P] = |w|, lam fp64 [P], decision fp64
+ * [P,NI] (its first counts[p] entries), accuracy fp64 [P,2] = the share of correctly classified fit rows and of held-out rows (NaN
+ * without held-out rows); status i32 [P] is written for every problem.  ridge > 0 (ridge only). */
+size_t bx_tcav_fit_workspace(int P, int nfmax);
+int bx_tcav_fit(const double* G0, int M, const int* rows, const int* labels, const int* fit, const int* counts, int P, int NI, int nfmax,
+                int classifier, double ridge, void* workspace, size_t workspace_bytes, double* beta, double* norm, double* lam, int* status,
+                double* decision, double* accuracy, bxStream stream);
+/* V fp32 [P,D]: V[p,d] = fl32( (sum_i beta[p,i] * ((double)A[i,d] - mean[d]), i ascending from 0.0, product and sum rounded one by one;
+ * rows whose beta is 0.0 add nothing) / norm[p] ).  The row of a problem whose status is not 0 is left as it was. */
+int bx_tcav_vectors(const void* A, const double* mean, const double* beta, const double* norm, const int* status, float* V, int M, int D, int P,
+                    int dtype, bxStream stream);
+/* S fp64 [rows_total,P]: S[row0 + r, p] = sum_d (double)G[r,d] * (double)V[p,d] for the rows r < rows of the gradient chunk G [rows,D]
+ * (the product of two fp32 values is exact).  256 partial sums over d = t, t + 256, ... (ascending), added 16 by 16 in ascending t and
+ * then in ascending group: the order depends on D alone, so no bit depends on how the rows are cut into chunks.  The other rows of S
+ * are not touched. */
+int bx_tcav_sensitivity(const void* G, const float* V, double* S, int rows, int D, int P, int row0, int rows_total, int dtype, bxStream stream);
+/* score, mean, mean_abs fp64 [P,K] and counts i32 [K]: over the rows r (ascending) explained for class k -- classes i32 [rows], or
+ * r % K when classes is NULL (every sample for every class, class fastest) -- the share with S[r,p] > 0, the mean of S[r,p] and the mean
+ * of |S[r,p]|; NaN for a class without rows.  counts[k] = the number of rows of class k. */
+int bx_tcav_score(const double* S, const int* classes, int rows, int P, int K, double* score, double* mean, double* mean_abs, int* counts,
+                  bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

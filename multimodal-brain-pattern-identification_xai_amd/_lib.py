@@ -31,6 +31,8 @@ BX_FUSION_SCORE_PROB, BX_FUSION_SCORE_LOGPROB = 0, 1
 BX_MASKOPT_OK, BX_MASKOPT_NAN = 0, 1
 BX_MASKOPT_DELETION, BX_MASKOPT_PRESERVATION = 0, 1
 BX_MASKOPT_PROB, BX_MASKOPT_LOGPROB = 0, 1
+BX_TCAV_RIDGE, BX_TCAV_MEAN_DIFFERENCE = 0, 1
+BX_TCAV_MAX_M = 8192
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -250,6 +252,14 @@ SIGNATURES = {
     "bx_maskopt_rows_spec": (i32, [vp, vp, vp, i32, vp] + [i32] * 9 + [vp]),
     "bx_maskopt_rows_eeg": (i32, [vp, vp, i32, vp, i32, vp] + [i32] * 8 + [vp]),
     "bx_maskopt_step": (i32, [vp, vp, i32] + [vp] * 10 + [i32] * 12 + [C.c_double] * 8 + [i32] * 4 + [vp]),
+    "bx_tcav_mean": (i32, [vp, vp, i32, i32, i32, vp]),
+    "bx_tcav_gram_workspace": (sz, [i32, i32]),
+    "bx_tcav_gram": (i32, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "bx_tcav_fit_workspace": (sz, [i32, i32]),
+    "bx_tcav_fit": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, C.c_double, vp, sz] + [vp] * 6 + [vp]),
+    "bx_tcav_vectors": (i32, [vp] * 6 + [i32] * 4 + [vp]),
+    "bx_tcav_sensitivity": (i32, [vp, vp, vp] + [i32] * 6 + [vp]),
+    "bx_tcav_score": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "bx_param_uniform": (i32, [vp, sz, f32, C.c_uint64, u32, u32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),

@@ -89,6 +89,13 @@
                                  up-sampling onto the grid in fp64 in a fixed order, the L1 and TV regularisers, Adam, the clamp, the
                                  history and the status (bx_maskopt_init, bx_maskopt_step) -- between the model's passes;
                                  bx_maskopt_masks up-samples the grids for the result.
+* ``tcav`` / ``train_cavs``   -- Testing with Concept Activation Vectors (Kim et al., ICML 2018; Captum's concept.TCAV; not in the
+                                 reference): whether a concept, given as example inputs, moves a class at a layer.  The activations of
+                                 every concept and random example are stacked once; their centred fp64 Gram matrix (bx_tcav_mean,
+                                 bx_tcav_gram) serves every linear classifier -- dual ridge by Cholesky or the mean difference, one
+                                 workgroup per problem (bx_tcav_fit) -- the CAVs (bx_tcav_vectors), fp64 directional derivatives
+                                 against all of them in a fixed order (bx_tcav_sensitivity) and the scores (bx_tcav_score);
+                                 ``welch_t_test`` is the host's significance test against the null problems.
 """
 from __future__ import annotations
 
@@ -4422,3 +4429,447 @@ def modality_importance(values):
     if not values.is_cuda:
         raise RuntimeError(f"brainxai.{who}: the values must live on the GPU; there is no CPU path")
     return channel_importance(values.movedim(0, -1))
+
+
+# ---- TCAV: concept activation vectors and TCAV scores (include/brainxai.h, "TCAV") ----
+_TCAV_CLASSIFIERS = {"ridge": L.BX_TCAV_RIDGE, "mean_difference": L.BX_TCAV_MEAN_DIFFERENCE}
+_TCAV_EEG_TARGET = re.compile(r"^(?:eeg_model\.)?features$")
+_TCAV_MAX_N = 256
+_TCAV_STATUS = {1: "its examples do not differ in this layer (tr K = 0)", 2: "the two sets have the same mean in this layer (w = 0)",
+                3: "the Cholesky factorisation met a non-positive pivot", 4: "the problem is malformed"}
+
+
+class CavSet(collections.namedtuple("CavSet", "vectors problems names accuracy holdout_accuracy norms lam decision gram target_layer input shape "
+                                              "classifier ridge holdout n")):
+    """What ``train_cavs`` returns: ``vectors`` fp32 [P,D] on the device (unit CAVs, oriented towards the concept), ``problems`` int64
+    host [P,2] -- row p of ``vectors`` separates concept problems[p,0] from random set problems[p,1]; the null problems come last with
+    problems[p,0] = -1: random set problems[p,1] against random set (problems[p,1] + 1) % R -- ``names`` (the concepts in order),
+    ``accuracy`` and ``holdout_accuracy`` fp64 [P] (NaN without held-out rows), ``norms`` fp64 [P] = |w|, ``lam`` fp64 [P], ``decision``
+    fp64 [P,2n] (positives first, then negatives, held-out rows included), ``gram`` fp64 [M,M] (keep_gram=True, else None),
+    ``target_layer`` and ``input`` (normalised), ``shape`` (the unflattened activation shape) and the arguments ``classifier``,
+    ``ridge``, ``holdout`` and the set size ``n``."""
+    __slots__ = ()
+
+    @property
+    def Q(self):
+        return len(self.names)
+
+    @property
+    def R(self):
+        return int((self.problems[:, 0] == 0).sum()) if self.Q else int((self.problems[:, 0] < 0).sum())
+
+    def index(self, name, r):
+        """The row of ``vectors`` for concept ``name`` against random set r."""
+        if name not in self.names:
+            raise KeyError(f"CavSet: no concept {name!r}; it holds " + ", ".join(repr(s) for s in self.names))
+        if not 0 <= int(r) < self.R:
+            raise IndexError(f"CavSet: random set {r} outside 0..{self.R - 1}")
+        return self.names.index(name) * self.R + int(r)
+
+    def vector(self, name, r=0):
+        """The CAV of concept ``name`` against random set r, reshaped to the activation's shape."""
+        return self.vectors[self.index(name, r)].reshape(self.shape)
+
+
+TcavResult = collections.namedtuple("TcavResult", "scores scores_per_random null_scores p_value t dof mean_sensitivity mean_abs_sensitivity sensitivity "
+                                                  "classes out counts cavs")
+TcavResult.__doc__ = """What ``tcav(..., return_parts=True)`` returns: ``scores`` fp64 [Q,K] (what the plain call returns: the mean over the random sets),
+``scores_per_random`` fp64 [Q,R,K], ``null_scores`` fp64 [R,K] (random set against random set; [0,K] when R < 2), ``p_value``, ``t``, ``dof`` fp64
+[Q,K] (Welch's two-sided test of the R concept scores against the R null scores; NaN when R < 2 or a variance is 0),
+``mean_sensitivity`` and ``mean_abs_sensitivity`` fp64 [Q,R,K], ``sensitivity`` fp64 [B,P] ([B,K,P] for class_idx='all'; P counts the null
+problems too, in ``cavs.problems``' order), ``classes`` int64 [B] (None for 'all'), ``out`` fp32 [B,K], ``counts`` int64 [K] (the samples
+behind each class's score) and ``cavs``, the ``CavSet``.  A class without samples has NaN scores."""
+
+
+def _betacf(a, b, x):
+    """The continued fraction of the incomplete beta function by the modified Lentz method (Numerical Recipes 6.4)."""
+    tiny, qab, qap, qam = 1e-300, a + b, a + 1.0, a - 1.0
+    c, d = 1.0, 1.0 - qab * x / qap
+    d = 1.0 / (tiny if abs(d) < tiny else d)
+    h = d
+    for m in range(1, 10000):
+        m2 = 2 * m
+        for aa in (m * (b - m) * x / ((qam + m2) * (a + m2)), -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))):
+            d = 1.0 + aa * d
+            d = 1.0 / (tiny if abs(d) < tiny else d)
+            c = 1.0 + aa / c
+            c = tiny if abs(c) < tiny else c
+            de = d * c
+            h *= de
+        if abs(de - 1.0) < 1e-16:
+            break
+    return h
+
+
+def regularized_incomplete_beta(a, b, x):
+    """I_x(a, b) in fp64 on the host: the continued fraction, on the side of the symmetry point where it converges fast."""
+    if not (a > 0 and b > 0) or math.isnan(x):
+        return float("nan")
+    if x <= 0.0:
+        return 0.0
+    if x >= 1.0:
+        return 1.0
+    front = math.exp(math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b) + a * math.log(x) + b * math.log1p(-x))
+    if x < (a + 1.0) / (a + b + 2.0):
+        return front * _betacf(a, b, x) / a
+    return 1.0 - front * _betacf(b, a, 1.0 - x) / b
+
+
+def welch_t_test(a, b):
+    """Welch's two-sided t-test of two samples along the last axis (scipy.stats.ttest_ind(a, b, axis=-1, equal_var=False), without
+    scipy) -> (t, dof, p), fp64 numpy arrays of the leading shape.  NaN where a sample has fewer than 2 values, a variance is 0 or a
+    value is NaN.  The Student t distribution comes from the regularised incomplete beta function, p = I_{dof / (dof + t^2)}(dof / 2, 1 / 2)."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    lead = np.broadcast_shapes(a.shape[:-1], b.shape[:-1])
+    na, nb = a.shape[-1], b.shape[-1]
+    t, dof, p = (np.full(lead, np.nan) for _ in range(3))
+    if na < 2 or nb < 2:
+        return t, dof, p
+    a, b = np.broadcast_to(a, lead + (na,)), np.broadcast_to(b, lead + (nb,))
+    for ix in np.ndindex(*lead):
+        u, v = a[ix], b[ix]
+        va, vb = float(u.var(ddof=1)) / na, float(v.var(ddof=1)) / nb
+        if not (va > 0.0 and vb > 0.0):                              # a zero variance, or a NaN
+            continue
+        t[ix] = (float(u.mean()) - float(v.mean())) / math.sqrt(va + vb)
+        dof[ix] = (va + vb) ** 2 / (va * va / (na - 1) + vb * vb / (nb - 1))
+        p[ix] = regularized_incomplete_beta(0.5 * dof[ix], 0.5, dof[ix] / (dof[ix] + t[ix] * t[ix]))
+    return t, dof, p
+
+
+def _tcav_target(who, model, input, target_layer):
+    """-> (input_is_spec, multimodal, net, target name, (stage, conv_k) or None): the explained branch and the normalised target."""
+    if input not in ("spec", "eeg"):
+        raise ValueError(f"{who}: input must be 'spec' or 'eeg', got {input!r}")
+    input_is_spec = input == "spec"
+    if target_layer is None:
+        target_layer = "spectrogram_model.block5" if input_is_spec else "eeg_model.features"
+    ms = _TARGET.match(target_layer) if isinstance(target_layer, str) else None
+    me = _TCAV_EEG_TARGET.match(target_layer) if isinstance(target_layer, str) else None
+    if not ms and not me:
+        raise ValueError(f"{who}: unknown target_layer {target_layer!r}; use 'spectrogram_model.blockN[.convK]' (input='spec') or "
+                         "'eeg_model.features' (input='eeg')")
+    if bool(ms) != input_is_spec:
+        raise ValueError(f"{who}: target_layer {target_layer!r} belongs to the {'spectrogram' if ms else 'EEG'} branch but input={input!r}; "
+                         "a branch's activation depends on its own input only")
+    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
+    net = (model.spectrogram_model if input_is_spec else model.eeg_model) if multimodal else model
+    if input_is_spec:
+        if not (hasattr(net, "block1") and hasattr(net, "fc")):
+            raise ValueError(f"{who}: input='spec' needs a MultimodalModel or a Spectrogram_Model")
+        stage, conv_k = int(ms.group(1)), int(ms.group(2)) if ms.group(2) else 0
+        return True, multimodal, net, f"spectrogram_model.block{stage}" + (f".conv{conv_k}" if conv_k else ""), (stage, conv_k)
+    from .models import EEGNet, EEGNetAttentionDeep
+    if not isinstance(net, (EEGNet, EEGNetAttentionDeep)):
+        raise ValueError(f"{who}: input='eeg' needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
+    return False, multimodal, net, "eeg_model.features", None
+
+
+def _tcav_shape(who, net, where, tail):
+    """The unflattened activation shape of one example whose input is shaped ``tail`` (C,H,W or 1,Chans,T), from the geometry alone."""
+    if where is None:
+        g = net._geom
+        feats = g.F2 * (int(tail[2]) // (g.P1 * g.P2))
+        if feats < 1:
+            raise ValueError(f"{who}: {int(tail[2])} time samples leave no EEG features")
+        return (feats,)
+    H, W = int(tail[1]), int(tail[2])
+    for i in range(1, where[0] + 1):
+        blk = getattr(net, f"block{i}")
+        if i == where[0] and where[1]:
+            break
+        H, W = H // blk.pool_window[0], W // blk.pool_window[1]
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: a spectrogram of {int(tail[1])} x {int(tail[2])} does not reach block{where[0]}")
+    return (H, W, int(getattr(net, f"block{where[0]}").out_channels))
+
+
+def _tcav_options(who, classifier, ridge, holdout):
+    if classifier not in _TCAV_CLASSIFIERS:
+        raise ValueError(f"{who}: unknown classifier {classifier!r}; use " + " or ".join(f"'{k}'" for k in _TCAV_CLASSIFIERS))
+    if isinstance(ridge, bool) or not isinstance(ridge, numbers.Real) or not math.isfinite(ridge) or not ridge > 0:
+        raise ValueError(f"{who}: ridge must be a finite number > 0, got {ridge!r}")
+    if isinstance(holdout, bool) or not isinstance(holdout, numbers.Real) or not 0 <= holdout < 0.5:
+        raise ValueError(f"{who}: holdout must be a fraction in [0, 0.5), got {holdout!r}")
+    return float(ridge), float(holdout)
+
+
+def _tcav_sets(who, concepts, randoms, input_is_spec, tail, holdout):
+    """-> (names, the Q + R example tensors in stacking order, n, held-out rows per set, the examples' shape).  ``tail``: the explained input's shape without
+    its batch axis, or None (``train_cavs``: the first set's)."""
+    if not isinstance(concepts, dict) or not concepts or not all(isinstance(k, str) for k in concepts):
+        raise ValueError(f"{who}: concepts must be a non-empty dict of name -> example tensor")
+    if not isinstance(randoms, (list, tuple)) or len(randoms) < 1:
+        raise ValueError(f"{who}: randoms must be a list of at least one example tensor")
+    form = "[n,C,H,W]" if input_is_spec else "[n,1,Chans,T]"
+    sets = [(f"concepts[{k!r}]", t) for k, t in concepts.items()] + [(f"randoms[{r}]", t) for r, t in enumerate(randoms)]
+    n = None
+    for what, t in sets:
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or (not input_is_spec and t.shape[1] != 1) or t.numel() == 0:
+            raise ValueError(f"{who}: {what} must be a tensor {form}")
+        if tail is None:
+            tail = tuple(t.shape[1:])
+        if tuple(t.shape[1:]) != tuple(tail):
+            raise ValueError(f"{who}: {what} holds examples shaped {tuple(t.shape[1:])}, the explained input's are {tuple(tail)}")
+        if n is None:
+            n = int(t.shape[0])
+        if int(t.shape[0]) != n:
+            raise ValueError(f"{who}: {what} holds {int(t.shape[0])} examples, {sets[0][0]} {n}; every set must have the same size")
+    if not 2 <= n <= _TCAV_MAX_N:
+        raise ValueError(f"{who}: {n} examples per set, supported 2..{_TCAV_MAX_N}")
+    nh = int(math.ceil(holdout * n - 1e-12))
+    if n - nh < 2:
+        raise ValueError(f"{who}: holdout = {holdout} leaves {n - nh} of {n} examples per set for the fit; at least 2 are needed")
+    if len(sets) * n > L.BX_TCAV_MAX_M:
+        raise ValueError(f"{who}: {len(sets)} sets of {n} examples stack to {len(sets) * n} rows, supported up to {L.BX_TCAV_MAX_M}")
+    return list(concepts), [t for _, t in sets], n, nh, tuple(tail)
+
+
+def _tcav_free_bytes(dev):
+    """The free memory of a GPU in bytes; None for any other device (the closing refusal then speaks)."""
+    return int(torch.cuda.mem_get_info(dev)[0]) if dev.type == "cuda" else None
+
+
+def _tcav_fits_memory(who, model, net, where, sets, shape):
+    """The refusal of a stack of activations [M,D], in the branch's storage dtype, beyond the free memory of the model's device."""
+    M, D, dev = len(sets) * int(sets[0].shape[0]), int(np.prod(shape)), next(model.parameters()).device
+    esize = 2 if where is not None and getattr(net, "compute_dtype", torch.float32) == torch.bfloat16 else 4
+    need, free = M * D * esize, _tcav_free_bytes(dev)
+    if free is not None and need > free:
+        raise ValueError(f"{who}: the stacked activations, {M} rows of {D} features, take {need} bytes; {free} bytes of device memory are free -- "
+                         "use fewer or smaller sets, or a deeper target_layer")
+
+
+def _tcav_problems(Q, R, n, nh):
+    """The problems' tables: (problems int64 [P,2], rows, labels, fit int32 [P,2n]).  Set s occupies the stacked rows s n .. s n + n - 1."""
+    pairs = [(q, r, q, Q + r) for q in range(Q) for r in range(R)] + ([(-1, r, Q + r, Q + (r + 1) % R) for r in range(R)] if R >= 2 else [])
+    ar = np.arange(n)
+    rows = np.array([np.concatenate([sp * n + ar, sn * n + ar]) for _, _, sp, sn in pairs], dtype=np.int32)
+    labels = np.tile(np.concatenate([np.ones(n), -np.ones(n)]).astype(np.int32), (len(pairs), 1))
+    fit = np.tile(np.concatenate([ar < n - nh, ar < n - nh]).astype(np.int32), (len(pairs), 1))
+    return np.array([(q, r) for q, r, _, _ in pairs], dtype=np.int64).reshape(len(pairs), 2), rows, labels, fit
+
+
+def _tcav_pair_name(names, problems, p, R):
+    q, r = int(problems[p, 0]), int(problems[p, 1])
+    return f"concept {names[q]!r} against random set {r}" if q >= 0 else f"random set {r} against random set {(r + 1) % R} (a null problem)"
+
+
+def _tcav_activations(net, where, sets, D, dt, cap, dev):
+    """The stacked activations [M,D] in the branch's storage dtype: every example once through the explained branch, without autograd."""
+    n = int(sets[0].shape[0])
+    A = torch.empty(len(sets) * n, D, dtype=dt, device=dev)
+    ctx = _SpecTarget(getattr(net, f"block{where[0]}"), where[1]) if where is not None else contextlib.nullcontext()
+    with torch.no_grad(), ctx as tgt:
+        for s, t in enumerate(sets):
+            xs = t.detach().to(dev, torch.float32).contiguous()
+            for i in range(0, n, cap):
+                if where is None:
+                    a = ops.eeg_features_keep(net, xs[i:i + cap])[0]
+                else:
+                    net(xs[i:i + cap])
+                    a = tgt.act()
+                A[s * n + i:s * n + i + a.shape[0]] = a.reshape(a.shape[0], D)
+    return A
+
+
+def train_cavs(model, concepts, randoms, *, input="spec", target_layer=None, classifier="ridge", ridge=1e-2, holdout=0.0, max_batch=256,
+               keep_gram=False):
+    """Concept activation vectors of a layer (Kim et al., ICML 2018): for every (concept, random set) pair a linear classifier between the
+    layer's activations of the concept's examples and of the random set's, whose unit normal, oriented towards the concept, is the CAV;
+    with two random sets or more also the null problems, random set r against random set r + 1.
+
+    concepts:     dict name -> examples; randoms: list of example tensors.  Examples are inputs of the explained branch alone, [n,C,H,W]
+                  (input='spec') or [n,1,Chans,T] ('eeg'): a branch's activation depends on its own input only.  Every set has the same
+                  2 <= n <= 256 examples.  Building the sets is the caller's job (``gaussian_blur``, ``eeg_spectrum`` / ``band_sums`` and the
+                  stackers of ``brainxai.data`` help).
+    target_layer: 'spectrogram_model.blockN' or '.blockN.convK' (what ``grad_cam`` captures there, flattened NHWC) or
+                  'eeg_model.features' (the flattened block-2 features of an EEGNet / EEGNetAttentionDeep); the prefix is optional and a
+                  stand-alone branch is accepted.  Default: block5 / features.
+    classifier:   'ridge': least squares with lambda = ridge * tr(K) / rows, solved in the dual by an fp64 Cholesky factorisation;
+                  'mean_difference': the difference of the two sets' mean activations (Pattern-CAV, Pahde et al. 2022).
+    holdout:      0 <= h < 0.5: the last ceil(h n) examples of every set are kept out of the fit; ``holdout_accuracy`` is theirs.
+    The examples run through the branch once, in passes of at most max_batch, in evaluation mode without autograd; the Gram matrix of
+    the stacked, centred activations is computed once (bx_tcav_mean, bx_tcav_gram) and every classifier is a function of it
+    (bx_tcav_fit); bx_tcav_vectors forms the CAVs.  A pair that cannot be separated -- identical examples -- raises, naming the pair.
+    The training flag and every requires_grad are restored on return.  Returns a ``CavSet``."""
+    who = "train_cavs"
+    max_batch = _max_batch(who, max_batch)
+    input_is_spec, _, net, target, where = _tcav_target(who, model, input, target_layer)
+    ridge, holdout = _tcav_options(who, classifier, ridge, holdout)
+    names, sets, n, nh, tail = _tcav_sets(who, concepts, randoms, input_is_spec, None, holdout)
+    shape = _tcav_shape(who, net, where, tail)
+    _tcav_fits_memory(who, model, net, where, sets, shape)
+    return _train_cavs(who, model, net, input, target, where, names, sets, n, nh, shape, classifier, ridge, holdout, max_batch, keep_gram, None)
+
+
+def _train_cavs(who, model, net, input, target, where, names, sets, n, nh, shape, classifier, ridge, holdout, max_batch, keep_gram, profile):
+    """``train_cavs`` once its arguments are checked.  profile: phases 'activations', 'gram', 'fit', 'vectors'."""
+    Q, R, D = len(names), len(sets) - len(names), int(np.prod(shape))
+    M = (Q + R) * n
+    dev = next(model.parameters()).device
+    dt = getattr(net, "compute_dtype", torch.float32) if where is not None else torch.float32
+    _need_gpu(who, "the model and the example sets", model, *sets)
+    lib = L.load()
+    problems, rows, labels, fit = _tcav_problems(Q, R, n, nh)
+    P, NI, nf = int(rows.shape[0]), 2 * n, 2 * (n - nh)
+    with torch.cuda.device(dev), _eval_frozen(model):
+        with _lap(profile, "activations"):
+            cap = _row_cap(sets[0], input, dt, max_batch)
+            A = _tcav_activations(net, where, sets, D, dt, cap, dev)
+        code = ops.bx_dtype(A.dtype)
+        with _lap(profile, "gram"):
+            mean = torch.empty(D, dtype=torch.float64, device=dev)
+            gram = torch.empty(M, M, dtype=torch.float64, device=dev)
+            L.check(lib.bx_tcav_mean(_p(A), _p(mean), M, D, code, _stream()), "bx_tcav_mean")
+            ws = ops.workspace(lib.bx_tcav_gram_workspace(M, D), dev)
+            L.check(lib.bx_tcav_gram(_p(A), _p(mean), _p(gram), M, D, code, _p(ws), ws.numel(), _stream()), "bx_tcav_gram")
+        with _lap(profile, "fit"):
+            rows_d, labels_d, fit_d = (torch.from_numpy(a).to(dev) for a in (rows, labels, fit))
+            counts_d = torch.full((P,), NI, dtype=torch.int32, device=dev)
+            beta = torch.zeros(P, M, dtype=torch.float64, device=dev)
+            norms, lam = (torch.full((P,), float("nan"), dtype=torch.float64, device=dev) for _ in range(2))
+            decision = torch.full((P, NI), float("nan"), dtype=torch.float64, device=dev)
+            acc = torch.full((P, 2), float("nan"), dtype=torch.float64, device=dev)
+            status = torch.empty(P, dtype=torch.int32, device=dev)
+            ws = ops.workspace(lib.bx_tcav_fit_workspace(P, nf), dev)
+            L.check(lib.bx_tcav_fit(_p(gram), M, _p(rows_d), _p(labels_d), _p(fit_d), _p(counts_d), P, NI, nf, _TCAV_CLASSIFIERS[classifier], ridge,
+                                    _p(ws), ws.numel(), _p(beta), _p(norms), _p(lam), _p(status), _p(decision), _p(acc), _stream()), "bx_tcav_fit")
+            st = status.cpu()                                        # the one read of the problems' status
+            if bool((st != 0).any()):
+                bad = int((st != 0).nonzero()[0])
+                raise RuntimeError(f"brainxai.{who}: {_tcav_pair_name(names, problems, bad, R)} cannot be separated at {target}: "
+                                   f"{_TCAV_STATUS.get(int(st[bad]), 'status ' + str(int(st[bad])))}")
+        with _lap(profile, "vectors"):
+            V = torch.empty(P, D, dtype=torch.float32, device=dev)
+            L.check(lib.bx_tcav_vectors(_p(A), _p(mean), _p(beta), _p(norms), _p(status), _p(V), M, D, P, code, _stream()), "bx_tcav_vectors")
+    return CavSet(V, problems, names, acc[:, 0].contiguous(), acc[:, 1].contiguous(), norms, lam, decision, gram if keep_gram else None, target, input,
+                  tuple(shape), classifier, ridge, holdout, n)
+
+
+def tcav(model, eeg, spec, concepts=None, randoms=None, *, cavs=None, input="spec", target_layer=None, classifier="ridge", ridge=1e-2, holdout=0.0,
+         class_idx=None, max_batch=256, return_parts=False):
+    """Testing with Concept Activation Vectors (Kim et al., ICML 2018; Captum's concept.TCAV): does the model use a concept -- alpha
+    rhythm, delta slowing, a muscle artefact, given as example inputs -- when it decides for a class, and at which depth?  Every other
+    explanation of the package is a map of one sample; this one is a number per (concept, class) over a set of samples.
+        S_k(x; v) = grad_a F_k(x) . v        the directional derivative of class k's log-probability along the unit CAV v at the layer
+        score     = the share of the samples x explained for class k with S_k(x; v) > 0
+    computed against every random set (``train_cavs``) and averaged over them; the same scores of the null problems, random set against
+    random set, are what a concept has to beat: ``p_value`` is Welch's two-sided t-test of the R concept scores against the R null scores.
+
+    eeg, spec:    the samples to test, as for ``grad_cam``; a stand-alone branch takes None for the other input.
+    concepts, randoms / cavs: the example sets (``train_cavs`` runs first, with input, target_layer, classifier, ridge, holdout), or a
+                  ``CavSet`` trained before, which must fit input, target_layer and the activation's size.  One or the other.
+    class_idx:    None: a sample counts for its arg-max class (a class without samples scores NaN); an int c: every sample, explained for
+                  class c; one class per sample; 'all': every sample for every class.
+    The samples run as ``grad_cam``'s general path does -- capture, one forward and one backward pass per class seed, in passes of at
+    most max_batch samples; 'eeg_model.features' runs the EEG branch without autograd and differentiates the head alone.  The dot
+    products are fp64 sums in an order that depends on the activation's size alone (bx_tcav_sensitivity), the scores one launch
+    (bx_tcav_score); no bit of the result depends on max_batch.  The training flag and every requires_grad are restored on return.
+    Returns the scores fp64 [Q,K] on the device, or ``TcavResult`` with return_parts."""
+    return _tcav(model, eeg, spec, concepts, randoms, cavs, input, target_layer, classifier, ridge, holdout, class_idx, max_batch, return_parts)
+
+
+def _tcav(model, eeg, spec, concepts, randoms, cavs, input, target_layer, classifier, ridge, holdout, class_idx, max_batch, return_parts, profile=None):
+    """``tcav`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'activations', 'gram',
+    'fit', 'vectors' (``train_cavs``), 'gradients', 'sensitivity' -- device events around every phase (tools/tcav_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "tcav"
+    max_batch = _max_batch(who, max_batch)
+    if (cavs is None) == (concepts is None and randoms is None):
+        raise ValueError(f"{who}: pass either cavs= (a CavSet from train_cavs) or the example sets concepts and randoms, not both and not neither")
+    if cavs is not None and not isinstance(cavs, CavSet):
+        raise ValueError(f"{who}: cavs must be a CavSet from train_cavs, got {type(cavs).__name__}")
+    if cavs is not None and target_layer is None:
+        target_layer = cavs.target_layer
+    input_is_spec, _, net, target, where = _tcav_target(who, model, input, target_layer)
+    x = _input_tensor(who, input, eeg, spec)
+    B = _nonempty(who, x)
+    other = eeg if input_is_spec else spec
+    multimodal, K, _ = _target_model(who, model, x, other, input_is_spec)
+    if K > _RISE_MAX_K:
+        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
+    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    shape = _tcav_shape(who, net, where, tuple(x.shape[1:]))
+    D = int(np.prod(shape))
+    if cavs is None:
+        ridge, holdout = _tcav_options(who, classifier, ridge, holdout)
+        names, sets, n, nh, _ = _tcav_sets(who, concepts, randoms, input_is_spec, tuple(x.shape[1:]), holdout)
+        _tcav_fits_memory(who, model, net, where, sets, shape)
+    elif cavs.input != input or cavs.target_layer != target or int(cavs.vectors.shape[1]) != D:
+        raise ValueError(f"{who}: the CavSet was trained for input={cavs.input!r} at {cavs.target_layer} with {int(cavs.vectors.shape[1])} features; "
+                         f"this call explains input={input!r} at {target} with {D}")
+    _need_gpu(who, "the model and its inputs", model, eeg, spec)
+    if cavs is None:
+        cavs = _train_cavs(who, model, net, input, target, where, names, sets, n, nh, shape, classifier, ridge, holdout, max_batch, False, profile)
+    _need_gpu(who, "the CavSet", model, cavs.vectors)
+
+    lib = L.load()
+    dev = x.device
+    Kc = K if all_classes else 1
+    V = cavs.vectors.contiguous()
+    P = int(V.shape[0])
+    dt = getattr(net, "compute_dtype", torch.float32) if input_is_spec else torch.float32
+    cap = _row_cap(x, input, dt, max_batch)
+    with torch.cuda.device(dev), _eval_frozen(model):
+        xs = x.detach().to(torch.float32).contiguous()
+        xo = other.detach().to(torch.float32).contiguous() if multimodal else None
+        out = torch.empty(B, K, dtype=torch.float32, device=dev)
+        classes = None if all_classes else torch.empty(B, dtype=torch.int32, device=dev)
+        if cls_h is not None:
+            classes.copy_(torch.tensor(cls_h, dtype=torch.int32))
+        S = torch.empty(Kc, B, P, dtype=torch.float64, device=dev)
+        for b0 in range(0, B, cap):
+            nb = min(cap, B - b0)
+            with _lap(profile, "gradients"), contextlib.ExitStack() as stack:
+                if input_is_spec:
+                    leaf_in = xs[b0:b0 + nb].clone().requires_grad_(True)
+                    tgt = stack.enter_context(_SpecTarget(getattr(net, f"block{where[0]}"), where[1], want_input=True))
+                    y = model(xo[b0:b0 + nb], leaf_in) if multimodal else net(leaf_in)
+                    leaf, read = tgt.leaf, tgt.grad
+                else:
+                    with torch.no_grad():
+                        feat = ops.eeg_features_keep(net, xs[b0:b0 + nb])[0]
+                        s_out = model.spectrogram_model(xo[b0:b0 + nb]) if multimodal else None
+                    leaf = feat.detach().requires_grad_(True)
+                    with torch.enable_grad():
+                        y = _eeg_head(net, leaf)
+                        if multimodal:
+                            y = ops.FusionHeadFn.apply(y, s_out, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias)
+                    read = lambda g: g
+                yd = y.detach().float().contiguous()
+                out[b0:b0 + nb] = yd
+                if cls_h is None and not all_classes:
+                    classes[b0:b0 + nb] = yd.argmax(dim=1).to(torch.int32)
+                seed = torch.empty(nb, K, dtype=torch.float32, device=dev)
+                grads = []
+                for slot in range(Kc):
+                    L.check(lib.bx_expgrad_seed(None if all_classes else _p(classes[b0:b0 + nb]), slot if all_classes else -1, _p(seed), nb, 1, K, 0, nb,
+                                                _stream()), "bx_expgrad_seed")
+                    (g,) = torch.autograd.grad(y, leaf, grad_outputs=seed, retain_graph=slot + 1 < Kc)
+                    grads.append(read(g).contiguous())
+                    if grads[-1].dtype not in (torch.float32, torch.bfloat16):
+                        grads[-1] = grads[-1].float()
+                del y, leaf
+            with _lap(profile, "sensitivity"):
+                for slot, g in enumerate(grads):
+                    if g.numel() != nb * D:
+                        raise RuntimeError(f"brainxai.{who}: the gradient at {target} has {g.numel() // nb} values per sample, the CAVs {D}")
+                    L.check(lib.bx_tcav_sensitivity(_p(g), _p(V), _p(S[slot]), nb, D, P, b0, B, ops.bx_dtype(g.dtype), _stream()), "bx_tcav_sensitivity")
+            del grads
+        with _lap(profile, "sensitivity"):
+            sens = S.permute(1, 0, 2).contiguous() if all_classes else S[0]
+            score, mean_s, mean_abs = (torch.empty(P, K, dtype=torch.float64, device=dev) for _ in range(3))
+            counts = torch.empty(K, dtype=torch.int32, device=dev)
+            L.check(lib.bx_tcav_score(_p(sens), _p(classes), B * Kc, P, K, _p(score), _p(mean_s), _p(mean_abs), _p(counts), _stream()), "bx_tcav_score")
+    # ---- the host's share: the mean over the random sets and Welch's test, on [P,K] numbers ----
+    Q, R = cavs.Q, cavs.R
+    sc_h = score.cpu().numpy()
+    per_random, null = sc_h[:Q * R].reshape(Q, R, K), sc_h[Q * R:].reshape(-1, K)
+    scores_h = per_random.sum(axis=1) / R
+    if not return_parts:
+        return torch.from_numpy(scores_h).to(dev)
+    t, dof, pv = welch_t_test(per_random.transpose(0, 2, 1), null.T[None]) if R >= 2 else (np.full((Q, K), np.nan),) * 3
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return TcavResult(up(scores_h), up(per_random), up(null), up(pv), up(t), up(dof), mean_s[:Q * R].reshape(Q, R, K), mean_abs[:Q * R].reshape(Q, R, K), sens,
+                      None if classes is None else classes.long(), out, counts.long(), cavs)
