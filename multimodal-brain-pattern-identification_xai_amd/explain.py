@@ -1111,10 +1111,12 @@ def _faith_baseline(baseline, x, per_len, what):
     return _baseline_for("deletion_insertion", baseline, x, per_len, what)
 
 
-# ---- what the drivers that run rows through the model share: each driver keeps its own order of checks, built from the pieces below.
-# The perturb-and-predict drivers (deletion_insertion, rise, occlusion, kernel_shap, score_cam, spectral_occlusion, infidelity) keep
-# their own clean pass and send their rows through one _RowPass; the gradient drivers (gradient_shap, smooth_grad, blur_ig,
-# spectral_gradients by its sampled route; guided_ig, mask_explain by its per-row route) go through one _GradPass ----
+# ---- what the drivers that run rows through the model share: each driver keeps its own order of checks, built from the pieces below;
+# the checks every one of them makes -- the input, the tensors, the model, the classes, the GPU -- fill one record, _Call, and the
+# passes are built from it.  The perturb-and-predict drivers (deletion_insertion, rise, occlusion, kernel_shap, score_cam,
+# spectral_occlusion, infidelity) keep their own clean pass and send their rows through one _RowPass; the gradient drivers
+# (gradient_shap, smooth_grad, blur_ig, spectral_gradients by its sampled route; guided_ig, mask_explain by its per-row route) go
+# through one _GradPass ----
 @contextlib.contextmanager
 def _lap(profile, name):
     """Device events around a phase, appended to ``profile`` as (name, start, end); nothing when profile is None."""
@@ -1210,36 +1212,6 @@ def _need_gpu(who, what, model, *tensors):
         raise RuntimeError(f"brainxai.{who}: {what} must live on the GPU; there is no CPU path")
 
 
-def _input_tensor(who, input, eeg, spec):
-    """The tensor the rows are made of, [B,C,H,W] for input='spec' and [B,1,Chans,T] for 'eeg'."""
-    x = spec if input == "spec" else eeg
-    if x is None:
-        raise ValueError(f"{who}: input={input!r} but that tensor is None")
-    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (input == "eeg" and x.shape[1] != 1):
-        raise ValueError(f"{who}: the {input} input must be a tensor " + ("[B,C,H,W]" if input == "spec" else "[B,1,Chans,T]"))
-    return x
-
-
-def _target_model(who, model, x, other, input_is_spec):
-    """-> (multimodal, K, net): whether ``model`` has both branches (``other`` is then the input of the branch that does not read x),
-    its class count, and the branch that reads x.  score_cam words the two stand-alone refusals by target, the others by input."""
-    multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
-    if multimodal:
-        if not isinstance(other, torch.Tensor) or other.shape[0] != x.shape[0]:
-            raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
-        return True, int(model.fc2.out_features), model.spectrogram_model if input_is_spec else model.eeg_model
-    what = f"input={'spec' if input_is_spec else 'eeg'!r}"
-    if who == "score_cam":
-        what = "a spectrogram target" if input_is_spec else "an EEG target"
-    if input_is_spec:
-        if not (hasattr(model, "block1") and hasattr(model, "fc")):
-            raise ValueError(f"{who}: {what} needs a MultimodalModel or a Spectrogram_Model")
-        return False, int(model.fc.out_features), model
-    if not hasattr(model, "depthwiseConv"):
-        raise ValueError(f"{who}: {what} needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
-    return False, int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features), model
-
-
 def _explained_classes(who, class_idx, B, K, allow_all):
     """-> (cls_h, all_classes): one class per sample as a host list (None: the arg-max of the clean input, or every class)."""
     use, must = ("None, an int, one class per sample or 'all'", "None, an int, 'all' or") if allow_all else ("None, an int or one class per sample", "None, an int or")
@@ -1261,13 +1233,80 @@ def _explained_classes(who, class_idx, B, K, allow_all):
     return cls_h, False
 
 
-def _explained_model(who, model, x, other, input_is_spec, class_idx):
-    """-> (multimodal, K, net, cls_h, all_classes): ``_target_model``, the refusal of more than 32 classes, and ``_explained_classes``
-    with 'all' allowed -- the three checks most drivers make one after the other."""
-    multimodal, K, net = _target_model(who, model, x, other, input_is_spec)
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    return (multimodal, K, net) + _explained_classes(who, class_idx, int(x.shape[0]), K, allow_all=True)
+class _Call:
+    """The record of a checked call: what a driver establishes before its pass, and what the pass is then built from.  It is filled in
+    steps, each a refusal or two and the fields they make safe to read, because the drivers put checks of their own between them:
+      named(input)           'spec' or 'eeg'                                     -> input, input_is_spec
+      tensors(eeg, spec)     the explained tensor, [B,C,H,W] or [B,1,Chans,T]    -> x, other, B, per (the elements of a sample)
+      target()               the model and the other input                      -> multimodal, K, net, dt (the rows' storage dtype)
+      classes(class_idx)     at most 32 classes, then ``_explained_classes``     -> cls_h, all_classes, Kc (K for 'all', else 1)
+      need_gpu(what, *extra) the closing refusal: the model, x, the other input of a MultimodalModel and the driver's extras
+    ``explained`` is target and classes, which most drivers make one after the other.  Three drivers join late: spectral_gradients
+    and spectral_occlusion have no input to name (input='eeg' at construction), tcav resolves its input from the target (the same),
+    and score_cam, which words the tensors' refusals by target, hands in the tensors it checked (``given``).  sensitivity_max, which
+    explains a function, has no model: it stops after the tensors."""
+
+    def __init__(self, who, model, input=None):
+        self.who, self.model, self.input, self.input_is_spec = who, model, input, input == "spec"
+
+    def named(self, input):
+        if input not in _FAITH_INPUTS:
+            raise ValueError(f"{self.who}: unknown input {input!r}; use 'spec' or 'eeg'")
+        self.input, self.input_is_spec = input, input == "spec"
+        return self
+
+    def tensors(self, eeg, spec):
+        x, form = (spec, "[B,C,H,W]") if self.input_is_spec else (eeg, "[B,1,Chans,T]")
+        if x is None:
+            raise ValueError(f"{self.who}: input={self.input!r} but that tensor is None")
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or (not self.input_is_spec and x.shape[1] != 1):
+            raise ValueError(f"{self.who}: the {self.input} input must be a tensor {form}")
+        return self.given(x, eeg if self.input_is_spec else spec)
+
+    def given(self, x, other):
+        self.x, self.other, self.B = x, other, int(x.shape[0])
+        self.per = x.numel() // self.B if self.B else 0              # an empty batch is the driver's to refuse
+        return self
+
+    def target(self):
+        """Whether ``model`` has both branches (``other`` is then the input of the branch that does not read x), its class count, and
+        the branch that reads x.  score_cam words the two stand-alone refusals by target, the others by input."""
+        who, model = self.who, self.model
+        self.multimodal = hasattr(model, "spectrogram_model") and hasattr(model, "eeg_model")
+        what = f"input={self.input!r}"
+        if who == "score_cam":
+            what = "a spectrogram target" if self.input_is_spec else "an EEG target"
+        if self.multimodal:
+            if not isinstance(self.other, torch.Tensor) or self.other.shape[0] != self.x.shape[0]:
+                raise ValueError(f"{who}: a MultimodalModel needs both inputs with the same batch size")
+            self.K, self.net = int(model.fc2.out_features), model.spectrogram_model if self.input_is_spec else model.eeg_model
+        elif self.input_is_spec:
+            if not (hasattr(model, "block1") and hasattr(model, "fc")):
+                raise ValueError(f"{who}: {what} needs a MultimodalModel or a Spectrogram_Model")
+            self.K, self.net = int(model.fc.out_features), model
+        else:
+            if not hasattr(model, "depthwiseConv"):
+                raise ValueError(f"{who}: {what} needs a MultimodalModel, an EEGNet or an EEGNetAttentionDeep")
+            self.K, self.net = int(model.dense.out_features if hasattr(model, "dense") else model.dense2.out_features), model
+        self.dt = getattr(self.net, "compute_dtype", torch.float32) if self.input_is_spec else torch.float32
+        return self
+
+    def classes(self, class_idx, allow_all=True):
+        """One class per sample as a host list, or every class; the 32-class limit is that of the drivers that can explain every class."""
+        if allow_all and self.K > _RISE_MAX_K:
+            raise ValueError(f"{self.who}: {self.K} classes, supported 1..{_RISE_MAX_K}")
+        self.cls_h, self.all_classes = _explained_classes(self.who, class_idx, self.B, self.K, allow_all)
+        self.Kc = self.K if self.all_classes else 1
+        return self
+
+    def explained(self, class_idx):
+        return self.target().classes(class_idx)
+
+    def need_gpu(self, what, *extra):
+        _need_gpu(self.who, what, self.model, self.x, self.other if self.multimodal else None, *extra)
+
+    def row_cap(self, max_batch, beside=0):
+        return _row_cap(self.x, self.input, self.dt, max_batch, beside)
 
 
 def _row_cap(x, input, dt, max_batch, beside=0):
@@ -1317,20 +1356,36 @@ def _class_tensor(cls_h, all_classes, clean_scores, dev):
     return clean_scores.argmax(dim=1).to(torch.int32).contiguous()
 
 
-class _RowPass:
+class _Pass:
+    """What the row pass and the gradient pass are built from alike: a checked ``_Call``, whose facts they keep under their own names,
+    the device, the rows per forward pass (``_row_cap``), the unchanged branch's output ``fixed`` (None until ``fix_other`` and for a
+    stand-alone model) and the laps of ``profile``.  ``xs`` is the explained input, fp32 and contiguous inside ``open()``."""
+
+    def __init__(self, call, max_batch, profile, beside=0):
+        self.call, self.profile, self.fixed = call, profile, None
+        self.model, self.net, self.multimodal, self.K, self.input_is_spec = call.model, call.net, call.multimodal, call.K, call.input_is_spec
+        self.xs, self.dev, self.B, self.dt = call.x, call.x.device, call.B, call.dt
+        self.max_rows = call.row_cap(max_batch, beside)
+
+    def lap(self, name):
+        return _lap(self.profile, name)
+
+    def fix_other(self):
+        """Run the branch whose input does not change, once per sample (nothing for a stand-alone model); the lap is the caller's."""
+        if self.multimodal:
+            self.fixed = _fixed_branch(self.model, self.call.other, self.input_is_spec)
+
+
+class _RowPass(_Pass):
     """What the five drivers do alike once their arguments are checked: rows of perturbed samples, written in the model's layout, run
     through the branch that reads them, the other branch's per-sample output is repeated into the fusion head, and the scores of every
     class land in fp32 [B, N, K].  A driver brings its row writer and its clean pass; the chunking by max_batch, the layout, the repeat,
     the fusion and the 'perturb' / 'forward' laps of ``profile`` are here.  Inside ``open()``, ``xs`` is the explained input (fp32,
-    contiguous) and ``base`` the baseline on the device in its kind's shape; ``fixed`` is None until ``fix_other`` and for a
-    stand-alone model."""
+    contiguous) and ``base`` the baseline on the device in its kind's shape."""
 
-    def __init__(self, model, net, multimodal, K, x, other, input_is_spec, kind, base, max_batch, profile):
-        self.model, self.net, self.multimodal, self.K, self.other, self.input_is_spec = model, net, multimodal, K, other, input_is_spec
-        self.xs, self.kind, self.base, self.profile, self.fixed = x, kind, base, profile, None
-        self.dev, self.B = x.device, int(x.shape[0])
-        self.dt = getattr(net, "compute_dtype", torch.float32) if input_is_spec else torch.float32
-        self.max_rows = _row_cap(x, "spec" if input_is_spec else "eeg", self.dt, max_batch)
+    def __init__(self, call, kind, base, max_batch, profile):
+        super().__init__(call, max_batch, profile)
+        self.kind, self.base = kind, base
 
     @contextlib.contextmanager
     def open(self):
@@ -1339,14 +1394,6 @@ class _RowPass:
             self.xs = self.xs.detach().to(torch.float32).contiguous()
             self.base = self.base.to(self.dev, torch.float32).reshape(self.xs.shape if self.kind == 2 else (-1,)).contiguous()
             yield self
-
-    def lap(self, name):
-        return _lap(self.profile, name)
-
-    def fix_other(self):
-        """Run the branch whose input does not change, once per sample (nothing for a stand-alone model); the lap is the driver's."""
-        if self.multimodal:
-            self.fixed = _fixed_branch(self.model, self.other, self.input_is_spec)
 
     def groups(self):
         """(b0, nb): the samples in groups of at most max_rows, the groups of ``sweep``."""
@@ -1391,7 +1438,7 @@ def _sample_of(row0, rows, n, dev):
     return torch.div(torch.arange(row0, row0 + rows, dtype=torch.int64, device=dev), n, rounding_mode="floor")
 
 
-class _GradPass:
+class _GradPass(_Pass):
     """What the gradient drivers do alike once their arguments are checked: rows run through the branch that reads them with the other
     branch's per-sample output gathered into the fusion head, and backward passes from one-hot seeds (bx_expgrad_seed), in chunks of at
     most max_batch rows.  Two routes, one pass object:
@@ -1406,14 +1453,11 @@ class _GradPass:
     and ``result`` serve both.  Inside ``open()``, ``xs`` is the explained input (fp32, contiguous); ``clean`` sets ``out``, ``classes``
     and ``fixed`` (None for a stand-alone model).  Cc, HW: the channels and pixels a finish launch reduces over."""
 
-    def __init__(self, model, net, multimodal, K, x, other, input_is_spec, n, cls_h, all_classes, max_batch, profile, beside=0):
-        self.model, self.net, self.multimodal, self.K, self.other, self.input_is_spec = model, net, multimodal, K, other, input_is_spec
-        self.xs, self.n, self.cls_h, self.all_classes, self.profile, self.fixed = x, n, cls_h, all_classes, profile, None
-        self.dev, self.B = x.device, int(x.shape[0])
-        self.per, self.Kc, self.total = x.numel() // self.B, K if all_classes else 1, self.B * n
-        self.dt = getattr(net, "compute_dtype", torch.float32) if input_is_spec else torch.float32
-        self.max_rows = min(_row_cap(x, "spec" if input_is_spec else "eeg", self.dt, max_batch, beside), ((1 << 31) - 1) // self.per)
-        self.Cc, self.HW = (int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])) if input_is_spec else (1, self.per)
+    def __init__(self, call, n, max_batch, profile, beside=0):
+        super().__init__(call, max_batch, profile, beside)
+        self.n, self.cls_h, self.all_classes, self.per, self.Kc, self.total = n, call.cls_h, call.all_classes, call.per, call.Kc, call.B * n
+        self.max_rows = min(self.max_rows, ((1 << 31) - 1) // self.per)
+        self.Cc, self.HW = (int(call.x.shape[1]), int(call.x.shape[2]) * int(call.x.shape[3])) if self.input_is_spec else (1, self.per)
 
     @contextlib.contextmanager
     def open(self):
@@ -1422,14 +1466,10 @@ class _GradPass:
             self.xs = self.xs.detach().to(torch.float32).contiguous()
             yield self
 
-    def lap(self, name):
-        return _lap(self.profile, name)
-
     def clean(self):
         """The clean pass: the branch whose input does not change (once per sample), ``out`` fp32 [B,K] and the explained classes."""
         with torch.no_grad(), self.lap("forward"):
-            if self.multimodal:
-                self.fixed = _fixed_branch(self.model, self.other, self.input_is_spec)
+            self.fix_other()
             self.out = _fuse(self.model, self.multimodal, self.input_is_spec, self.net(self.xs), self.fixed).float().contiguous()
         self.classes = _class_tensor(self.cls_h, self.all_classes, self.out, self.dev)
 
@@ -1579,20 +1619,19 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
     'perturb', 'forward', 'curve' -- device events around every phase of the pass (tools/faithfulness_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "deletion_insertion"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     if mode not in _FAITH_MODES:
         raise ValueError(f"{who}: unknown mode {mode!r}; use one of " + ", ".join(f"'{m}'" for m in _FAITH_MODES))
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
     steps = int(steps)
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x = call.tensors(eeg, spec).x
     if not isinstance(attribution, torch.Tensor):
         raise ValueError(f"{who}: attribution must be a tensor")
-    B = int(x.shape[0])
-    per_len, what = _per_cell(who, x, input == "spec")
-    if input == "spec":
+    B = call.B
+    per_len, what = _per_cell(who, x, call.input_is_spec)
+    if call.input_is_spec:
         H, W = int(x.shape[2]), int(x.shape[3])
         if tuple(attribution.shape) != (B, H, W):
             raise ValueError(f"{who}: wrong map shape {tuple(attribution.shape)} for input='spec'; expected [B,H,W] = {(B, H, W)}")
@@ -1611,21 +1650,19 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
         raise ValueError(f"{who}: {N} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     if not 1 <= steps <= N:
         raise ValueError(f"{who}: steps = {steps} outside 1..N = {N}")
-    other = eeg if input == "spec" else spec
-    multimodal, K, net = _target_model(who, model, x, other, input == "spec")
-    cls_h, _ = _explained_classes(who, class_idx, B, K, allow_all=False)
+    K = call.target().classes(class_idx, allow_all=False).K
     kind, base = _baseline_for(who, baseline, x, per_len, what)
-    _need_gpu(who, "the model, its inputs and the attribution", model, x, attribution, other if multimodal else None)
+    call.need_gpu("the model, its inputs and the attribution", attribution)
 
     lib = L.load()
     dev = x.device
     P, per = steps + 1, -(-N // steps)
-    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
+    rp = _RowPass(call, kind, base, max_batch, profile)
 
     with rp.open():
         with rp.lap("rank"):
             ranks = attribution_ranks(attribution)
-        if multimodal:
+        if call.multimodal:
             with rp.lap("forward"):
                 rp.fix_other()
         logps = {}
@@ -1635,7 +1672,7 @@ def _deletion_insertion(model, eeg, spec, attribution, input, mode, steps, basel
                                     logprob=True)
         # there is no clean pass: the unperturbed input is a curve's first or last point
         unperturbed = logps["deletion"][:, 0] if "deletion" in logps else logps["insertion"][:, P - 1]
-        classes = _class_tensor(cls_h, False, unperturbed, dev)
+        classes = _class_tensor(call.cls_h, False, unperturbed, dev)
         res = {}
         with rp.lap("curve"):
             for m, logp in logps.items():
@@ -1787,8 +1824,7 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     'accumulate' -- device events around every phase of the pass (tools/rise_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "rise"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     if normalize not in _RISE_NORMALIZE:
         raise ValueError(f"{who}: unknown normalize {normalize!r}; use 'expected' or 'coverage'")
     if cells not in _RISE_CELLS:
@@ -1796,10 +1832,10 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     if cells == "time" and input != "eeg":
         raise ValueError(f"{who}: cells='time' masks time columns of the EEG input; input='spec' has no such map")
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
-    B = int(x.shape[0])
-    per_len, what = _per_cell(who, x, input == "spec")
-    if input == "spec":
+    x = call.tensors(eeg, spec).x
+    B = call.B
+    per_len, what = _per_cell(who, x, call.input_is_spec)
+    if call.input_is_spec:
         map_rows, Hm, Wm = None, int(x.shape[2]), int(x.shape[3])
     else:
         map_rows = 1 if cells == "time" else int(x.shape[2])
@@ -1807,18 +1843,17 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
     if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     geom = _rise_geometry(who, grid, Hm, Wm)
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
+    K, cls_h, all_classes = call.explained(class_idx).K, call.cls_h, call.all_classes
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     bits, shifts = _rise_mask_set(who, num_masks, geom, p1, seed, masks)
     N = int(bits.shape[0])
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
     dev = x.device
-    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
+    rp = _RowPass(call, kind, base, max_batch, profile)
 
     with rp.open():
         bits_d, shifts_d = torch.from_numpy(bits).to(dev), torch.from_numpy(shifts).to(dev)
@@ -1826,7 +1861,7 @@ def _rise(model, eeg, spec, input, num_masks, grid, p1, class_idx, baseline, nor
         with rp.lap("forward"):
             rp.fix_other()
             if cls_h is None and not all_classes:                   # the explained class: the arg-max on the unmasked input, one pass
-                clean = (model(eeg, spec) if multimodal else model(rp.xs)).float()
+                clean = (model(eeg, spec) if call.multimodal else model(rp.xs)).float()
         classes = _class_tensor(cls_h, all_classes, clean, dev)
         P = rp.sweep(N, lambda *chunk: _rise_perturb(rp.xs, bits_d, shifts_d, geom, rp.base, kind, *chunk, rp.dt, map_rows))
         with rp.lap("accumulate"):
@@ -1922,31 +1957,29 @@ def _occlusion(model, eeg, spec, input, window, stride, baseline, class_idx, sco
     'accumulate' -- device events around every phase of the pass (tools/occlusion_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "occlusion"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
-    B = int(x.shape[0])
+    x = call.tensors(eeg, spec).x
+    B = call.B
     Hm, Wm = int(x.shape[2]), int(x.shape[3])
-    per_len, what = _per_cell(who, x, input == "spec")
+    per_len, what = _per_cell(who, x, call.input_is_spec)
     if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     geom = _occlusion_geometry(who, window, stride, Hm, Wm)
     ny, nx = geom[4:]
     N = ny * nx
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
+    K, cls_h, all_classes = call.explained(class_idx).K, call.cls_h, call.all_classes
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * K * Hm * Wm = {B * K * Hm * Wm} beyond 32-bit offsets; use fewer samples per call")
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
     dev = x.device
     use_logprob = score == "logprob"
-    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
+    rp = _RowPass(call, kind, base, max_batch, profile)
 
     with rp.open():
         with rp.lap("forward"):
@@ -2153,40 +2186,38 @@ def _kernel_shap(model, eeg, spec, input, segments, num_samples, baseline, class
     'fit' -- device events around every phase of the pass (tools/kernel_shap_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "kernel_shap"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
-    B = int(x.shape[0])
+    x = call.tensors(eeg, spec).x
+    B = call.B
     Hd, Wd = int(x.shape[2]), int(x.shape[3])
-    per_len, what = _per_cell(who, x, input == "spec")
+    per_len, what = _per_cell(who, x, call.input_is_spec)
     if B < 1 or not 1 <= Hd * Wd <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hd * Wd} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
     seg, M = _shap_segments(who, segments, input, Hd, Wd)
     Hm, Wm = seg.shape
-    map_rows = None if input == "spec" else Hm
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
+    map_rows = None if call.input_is_spec else Hm
+    K, cls_h, all_classes = call.explained(class_idx).K, call.cls_h, call.all_classes
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     Z, weights, exact = _shap_coalitions(who, M, 2 * M + 2048 if num_samples is None else num_samples, seed, coalitions)
     N = int(Z.shape[0])
     if B * N * K >= 1 << 31 or B * K * Hm * Wm >= 1 << 31 or N * M >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K}, B * K * Hm * Wm = {B * K * Hm * Wm} or N * M = {N * M} beyond 32-bit offsets; "
                          "use fewer samples per call")
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
     dev = x.device
     use_logprob = score == "logprob"
-    rp = _RowPass(model, net, multimodal, K, x, other, input == "spec", kind, base, max_batch, profile)
+    rp = _RowPass(call, kind, base, max_batch, profile)
 
     with rp.open():
         seg_d, Z_d, w_d = torch.from_numpy(seg).to(dev), torch.from_numpy(Z).to(dev), torch.from_numpy(weights).to(dev)
         none_d = torch.zeros(1, M, dtype=torch.uint8, device=dev)      # the empty coalition: the baseline itself
         clean, empty = (torch.empty(B, K, dtype=torch.float32, device=dev) for _ in range(2))
-        if multimodal:
+        if call.multimodal:
             with rp.lap("forward"):
                 rp.fix_other()
         # v(1) and v(0): the unperturbed input and the baseline take the path of the coalition rows, in chunks of the same size
@@ -2324,9 +2355,8 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
         raise ValueError(f"{who}: target {target_layer!r} reads the {'EEG' if eeg_target else 'spectrogram'} input, but that tensor is None")
     if not isinstance(x, torch.Tensor) or x.dim() != 4 or (eeg_target and x.shape[1] != 1):
         raise ValueError(f"{who}: the {'EEG' if eeg_target else 'spectrogram'} input must be a tensor " + ("[B,1,Chans,T]" if eeg_target else "[B,C,H,W]"))
-    B = int(x.shape[0])
-    other = spec if eeg_target else eeg
-    multimodal, K, net = _target_model(who, model, x, other, not eeg_target)
+    call = _Call(who, model, "eeg" if eeg_target else "spec").given(x, spec if eeg_target else eeg).target()
+    B, K, net, multimodal = call.B, call.K, call.net, call.multimodal
     if eeg_target:
         from .models import EEGNet, EEGNetAttentionDeep
         if not isinstance(net, (EEGNet, EEGNetAttentionDeep)):
@@ -2342,16 +2372,14 @@ def _score_cam(model, eeg, spec, target_layer, class_idx, weights, baseline, ups
     per_len, what = _per_cell(who, x, not eeg_target)
     if B < 1 or not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per sample (B = {B}), supported 1..{_FAITH_MAX_N}")
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    cls_h, all_classes = call.classes(class_idx).cls_h, call.all_classes
     kind, base = _baseline_for(who, baseline, x, per_len, what)
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
     dev = x.device
-    nm = K if all_classes else 1
-    rp = _RowPass(model, net, multimodal, K, x, other, not eeg_target, kind, base, max_batch, profile)
+    nm = call.Kc
+    rp = _RowPass(call, kind, base, max_batch, profile)
 
     with rp.open():
         xs = rp.xs
@@ -2470,10 +2498,9 @@ def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, see
     'backward', 'accumulate', 'finish' -- device events around every phase of the pass (tools/gradient_shap_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "gradient_shap"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     n, max_batch = _draw_count(who, nsamples), _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x = call.tensors(eeg, spec).x
     B = _nonempty(who, x)
     if not isinstance(background, torch.Tensor) or background.dim() != 4 or tuple(background.shape[1:]) != tuple(x.shape[1:]):
         got = tuple(background.shape) if isinstance(background, torch.Tensor) else type(background).__name__
@@ -2481,17 +2508,14 @@ def _gradient_shap(model, eeg, spec, background, input, nsamples, class_idx, see
     Nb = int(background.shape[0])
     if Nb < 1:
         raise ValueError(f"{who}: empty background (Nb = 0)")
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
-    Kc = K if all_classes else 1
-    per = x.numel() // B
+    Kc, per = call.explained(class_idx).Kc, call.per
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or Nb * per >= 1 << 31:
         raise ValueError(f"{who}: B * n = {B * n}, B * Kc * per = {B * Kc * per} or Nb * per = {Nb * per} beyond 32-bit offsets; use fewer samples per call")
     idx, alpha = _gradshap_draws(who, B, Nb, n, seed, draws)
-    _need_gpu(who, "the model, its inputs and the background", model, x, background, other if multimodal else None)
+    call.need_gpu("the model, its inputs and the background", background)
 
     lib = L.load()
-    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", n, cls_h, all_classes, max_batch, profile)
+    gp = _GradPass(call, n, max_batch, profile)
 
     with gp.open():
         xs = gp.xs
@@ -2635,24 +2659,20 @@ def _smooth_grad(model, eeg, spec, input, nsamples, noise_level, stdev, kind, cl
     'forward', 'backward', 'accumulate', 'finish' -- device events around every phase of the pass (tools/smooth_grad_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "smooth_grad"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     if not isinstance(kind, str) or kind not in _SMOOTHGRAD_KINDS:
         raise ValueError(f"{who}: unknown kind {kind!r}; use 'smoothgrad', 'smoothgrad_sq' or 'vargrad'")
     n, seed, max_batch = _draw_count(who, nsamples), _stream_seed(who, seed), _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x = call.tensors(eeg, spec).x
     B = _nonempty(who, x)
     level, sd = _level_or_absolute(who, B, "noise_level", noise_level, "stdev", stdev, 0.15, True)
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
-    Kc = K if all_classes else 1
-    per = x.numel() // B
+    Kc, per = call.explained(class_idx).Kc, call.per
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or B * Kc > 65535:
         raise ValueError(f"{who}: B * n = {B * n} or B * Kc * per = {B * Kc * per} beyond 32-bit offsets, or B * Kc = {B * Kc} > 65535; use fewer samples per call")
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
-    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", n, cls_h, all_classes, max_batch, profile)
+    gp = _GradPass(call, n, max_batch, profile)
 
     with gp.open():
         xs = gp.xs
@@ -2883,17 +2903,13 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
     'backward', 'accumulate', 'finish' -- device events around every phase of the pass (tools/blur_ig_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "blur_ig"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
-    axes = _blur_axes(who, axes, input == "eeg")
+    call = _Call(who, model).named(input)
+    axes = _blur_axes(who, axes, not call.input_is_spec)
     n, max_sigma, sqrt, eps = _blur_steps(who, steps, max_sigma, sqrt, grad_step)
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x = call.tensors(eeg, spec).x
     B = _nonempty(who, x)
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
-    Kc = K if all_classes else 1
-    per = x.numel() // B
+    Kc, per = call.explained(class_idx).Kc, call.per
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31 or B * Kc > 65535:
         raise ValueError(f"{who}: B * n = {B * n} or B * Kc * per = {B * Kc * per} beyond 32-bit offsets, or B * Kc = {B * Kc} > 65535; use fewer samples per call")
     sigmas = blur_sigmas(n, max_sigma, sqrt)
@@ -2901,10 +2917,10 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
     end_taps, end_radius = blur_taps(sigmas[n:])
     _blur_fits(who, x, axes, max(taps.shape[2], end_taps.shape[2]) // 2, True)
     w = np.array([-(sigmas[i + 1] - sigmas[i]) for i in range(n)], dtype=np.float64)
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
-    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", n, cls_h, all_classes, max_batch, profile, beside=per * 4)
+    gp = _GradPass(call, n, max_batch, profile, beside=per * 4)
 
     with gp.open():
         xs = gp.xs
@@ -2926,7 +2942,7 @@ def _blur_ig(model, eeg, spec, input, steps, max_sigma, sqrt, grad_step, axes, c
             last = torch.empty_like(xs)                             # the end of the path: x blurred with sigma_n
             _blur_rows(lib, xs, torch.from_numpy(end_taps).to(gp.dev), torch.from_numpy(end_radius).to(gp.dev), end_taps.shape[2], last, None, 1, axes, 0, 0, B)
             with torch.no_grad():
-                endpoint = _fuse(model, multimodal, gp.input_is_spec, net(last), gp.fixed).float().contiguous()
+                endpoint = _fuse(model, call.multimodal, gp.input_is_spec, call.net(last), gp.fixed).float().contiguous()
             delta = gp.completeness(values, per, endpoint)
     return gp.result(return_parts, BlurIGResult, amap, values, endpoint, delta, sigmas, n, max_sigma, sqrt, eps, axes)
 
@@ -2999,30 +3015,27 @@ def _guided_ig(model, eeg, spec, input, steps, fraction, max_dist, baseline, cla
     'step', 'finish' -- device events around every phase of the pass (tools/guided_ig_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "guided_ig"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     n, fraction, max_dist = _guided_steps(who, steps, fraction, max_dist)
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x = call.tensors(eeg, spec).x
     B = _nonempty(who, x)
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
-    Kc = K if all_classes else 1
-    per, R = x.numel() // B, B * Kc
+    Kc, per = call.explained(class_idx).Kc, call.per
+    R = B * Kc
     if per > _GUIDED_MAX_CELLS:
         raise ValueError(f"{who}: {per} cells per sample, supported 1..{_GUIDED_MAX_CELLS}")
     if R * n >= 1 << 31 or R * per >= 1 << 31 or R > 65535:
         raise ValueError(f"{who}: B * Kc * steps = {R * n} or B * Kc * per = {R * per} beyond 32-bit offsets, or B * Kc = {R} > 65535; use fewer samples per call")
-    per_len, what = _per_cell(who, x, input == "spec")
+    per_len, what = _per_cell(who, x, call.input_is_spec)
     kind, base = _baseline_for(who, baseline, x, per_len, what)
     k, cap = guided_ig_passes(per, fraction)
     if cap > _GUIDED_MAX_PASSES:
         raise ValueError(f"{who}: fraction = {fraction!r} is too small for an input of {per} cells: a step could take {cap} passes, "
                          f"supported up to {_GUIDED_MAX_PASSES}")
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
-    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", 1, cls_h, all_classes, max_batch, profile)
+    gp = _GradPass(call, 1, max_batch, profile)
     with gp.open():
         xs, dev, trail = gp.xs, gp.dev, tuple(gp.xs.shape[1:])
         xb = gp.baseline_rows(kind, base)
@@ -3149,8 +3162,7 @@ def _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, t
     'backward', 'step', 'finish' -- device events around every phase of the pass (tools/mask_explain_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "mask_explain"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     if mode not in _MASKOPT_MODES:
         raise ValueError(f"{who}: unknown mode {mode!r}; use 'deletion' or 'preservation'")
     if score not in _MASKOPT_SCORES:
@@ -3161,10 +3173,10 @@ def _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, t
         raise ValueError(f"{who}: cells='time' masks time columns of the EEG input; input='spec' has no such map")
     n, lr, l1, tv, tv_beta, b1, b2, eps = _maskopt_settings(who, iterations, lr, l1, tv, tv_beta, betas, eps)
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x = call.tensors(eeg, spec).x
     B = _nonempty(who, x)
-    per_len, what = _per_cell(who, x, input == "spec")
-    if input == "spec":
+    per_len, what = _per_cell(who, x, call.input_is_spec)
+    if call.input_is_spec:
         map_rows, Hm, Wm = 0, int(x.shape[2]), int(x.shape[3])
     else:
         map_rows = 1 if cells == "time" else int(x.shape[2])
@@ -3172,18 +3184,16 @@ def _mask_explain(model, eeg, spec, input, mode, grid, iterations, lr, l1, tv, t
     if not 1 <= Hm * Wm <= _FAITH_MAX_N:
         raise ValueError(f"{who}: {Hm * Wm} cells per mask, supported 1..{_FAITH_MAX_N}")
     gh, gw = _maskopt_grid(who, grid, Hm, Wm)
-    other = eeg if input == "spec" else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, input == "spec", class_idx)
-    Kc = K if all_classes else 1
-    per, R = x.numel() // B, B * Kc
+    K, Kc, per, all_classes = call.explained(class_idx).K, call.Kc, call.per, call.all_classes
+    R = B * Kc
     if R * per >= 1 << 31 or R * n * 3 >= 1 << 31 or R * Hm * Wm >= 1 << 31 or (keep_path and R * n * per >= 1 << 31) or R > _MASKOPT_MAX_ROWS:
         raise ValueError(f"{who}: B * Kc * per = {R * per}, B * Kc * iterations * 3 = {R * n * 3}" + (f", B * Kc * iterations * per = {R * n * per} (keep_path)" if keep_path else "")
                          + f" beyond 32-bit offsets, or B * Kc = {R} > {_MASKOPT_MAX_ROWS}; use fewer samples per call")
     kind, base = _baseline_for(who, baseline, x, per_len, what)
-    _need_gpu(who, "the model and its inputs", model, x, other if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
-    gp = _GradPass(model, net, multimodal, K, x, other, input == "spec", 1, cls_h, all_classes, max_batch, profile)
+    gp = _GradPass(call, 1, max_batch, profile)
     code_mode, code_score = _MASKOPT_MODES[mode], _MASKOPT_SCORES[score]
     Cc, Hh, Ww = (int(v) for v in x.shape[1:])
     with gp.open():
@@ -3422,20 +3432,18 @@ def _spectral_gradients(model, eeg, spec, kind, steps, fs, bands, class_idx, max
     if n < 1:
         raise ValueError(f"{who}: steps = {n} < 1")
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, "eeg", eeg, spec)
-    B, Chans, T, F = _spectral_shape(who, x)
+    call = _Call(who, model, "eeg").tensors(eeg, spec)
+    B, Chans, T, F = _spectral_shape(who, call.x)
     fs = _spectral_fs(who, fs)
     band_bins = None if bands is None else spectral_band_bins(bands, T, fs, who)
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, spec, False, class_idx)
-    Kc = K if all_classes else 1
-    per = Chans * T
+    Kc, per, all_classes = call.explained(class_idx).Kc, call.per, call.all_classes
     if B * n >= 1 << 31 or B * Kc * per >= 1 << 31:
         raise ValueError(f"{who}: B * n = {B * n} or B * Kc * per = {B * Kc * per} beyond 32-bit offsets; use fewer samples per call")
-    _need_gpu(who, "the model and its inputs", model, x, spec if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
     alpha, w = (np.ones(1), np.ones(1)) if n == 1 else ig_nodes(n)
-    gp = _GradPass(model, net, multimodal, K, x, spec, False, n, cls_h, all_classes, max_batch, profile)
+    gp = _GradPass(call, n, max_batch, profile)
 
     with gp.open():
         xs, dev = gp.xs, gp.dev
@@ -3467,8 +3475,8 @@ def _spectral_gradients(model, eeg, spec, kind, steps, fs, bands, class_idx, max
         delta = None
         if n > 1 and kind == "gradient_x_amplitude":
             with torch.no_grad():                                   # F(0): EEGNet in eval mode treats every row alike, one row serves all samples
-                at_zero = net(torch.zeros_like(xs[:1]))
-                at_zero = _fuse(model, multimodal, False, at_zero.expand(B, -1).contiguous(), gp.fixed).float()
+                at_zero = call.net(torch.zeros_like(xs[:1]))
+                at_zero = _fuse(model, call.multimodal, False, at_zero.expand(B, -1).contiguous(), gp.fixed).float()
             delta = gp.completeness(amap, Chans * F, at_zero)
         if not all_classes:
             amap, gradient = amap[:, 0], gradient[:, 0]
@@ -3505,20 +3513,20 @@ def _spectral_occlusion(model, eeg, spec, bands, fs, cells, class_idx, score, ma
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
     max_batch = _max_batch(who, max_batch)
-    x = _input_tensor(who, "eeg", eeg, spec)
-    B, Chans, T, F = _spectral_shape(who, x)
+    call = _Call(who, model, "eeg").tensors(eeg, spec)
+    B, Chans, T, F = _spectral_shape(who, call.x)
     band_bins = spectral_band_bins(bands, T, fs, who)
     nb = len(band_bins)
     N = nb if cells == "band" else nb * Chans
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, spec, False, class_idx)
+    K, cls_h, all_classes = call.explained(class_idx).K, call.cls_h, call.all_classes
     if B * N * K >= 1 << 31 or B * Chans * T >= 1 << 31:
         raise ValueError(f"{who}: B * N * K = {B * N * K} or B * Chans * T = {B * Chans * T} beyond 32-bit offsets; use fewer samples per call")
-    _need_gpu(who, "the model and its inputs", model, x, spec if multimodal else None)
+    call.need_gpu("the model and its inputs")
 
     lib = L.load()
-    dev = x.device
+    dev = call.x.device
     use_logprob = score == "logprob"
-    rp = _RowPass(model, net, multimodal, K, x, spec, False, 0, torch.zeros(1), max_batch, profile)
+    rp = _RowPass(call, 0, torch.zeros(1), max_batch, profile)
 
     with rp.open():
         xs = rp.xs
@@ -3637,31 +3645,27 @@ def _infidelity(model, eeg, spec, attribution, input, nsamples, noise_level, std
     'forward', 'dot', 'finish' -- device events around every phase of the pass (tools/infidelity_bench.py sums them)."""
     # ---- everything that can be refused is refused here, before the library is touched ----
     who = "infidelity"
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    call = _Call(who, model).named(input)
     if score not in _FAITH_SCORES:
         raise ValueError(f"{who}: unknown score {score!r}; use 'prob' or 'logprob'")
     n, seed, max_batch = _draw_count(who, nsamples), _stream_seed(who, seed), _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x = call.tensors(eeg, spec).x
     if not isinstance(attribution, torch.Tensor):
         raise ValueError(f"{who}: attribution must be a tensor")
     B = _nonempty(who, x)
-    is_spec = input == "spec"
+    is_spec = call.input_is_spec
     _per_cell(who, x, is_spec)
     level, sd = _level_or_absolute(who, B, "noise_level", noise_level, "stdev", stdev, 0.15, True)
-    other = eeg if is_spec else spec
-    multimodal, K, net, cls_h, all_classes = _explained_model(who, model, x, other, is_spec, class_idx)
+    K, Kc, per, cls_h, all_classes = call.explained(class_idx).K, call.Kc, call.per, call.cls_h, call.all_classes
     grouped, cells = _infidelity_cells(who, attribution, x, is_spec, all_classes, K)
-    Kc = K if all_classes else 1
-    per = x.numel() // B
     if B * n * K >= 1 << 31 or B * Kc * cells >= 1 << 31 or B * per >= 1 << 31:
         raise ValueError(f"{who}: B * n * K = {B * n * K}, B * Kc * cells = {B * Kc * cells} or B * per = {B * per} beyond 32-bit offsets; use fewer samples per call")
-    _need_gpu(who, "the model, its inputs and the attribution", model, x, attribution, other if multimodal else None)
+    call.need_gpu("the model, its inputs and the attribution", attribution)
 
     lib = L.load()
     dev = x.device
     use_logprob = score == "logprob"
-    rp = _RowPass(model, net, multimodal, K, x, other, is_spec, 0, torch.zeros(1), max_batch, profile)
+    rp = _RowPass(call, 0, torch.zeros(1), max_batch, profile)
 
     with rp.open():
         with rp.lap("sigma"):
@@ -3726,16 +3730,14 @@ def sensitivity_max(explain, eeg, spec, *, input="spec", nsamples=10, radius=Non
     who = "sensitivity_max"
     if not callable(explain):
         raise ValueError(f"{who}: explain must be a callable (eeg_rows, spec_rows, sample) -> tensor, got {type(explain).__name__}")
-    if input not in _FAITH_INPUTS:
-        raise ValueError(f"{who}: unknown input {input!r}; use 'spec' or 'eeg'")
+    record = _Call(who, None).named(input)                          # a function is explained: there is no model to check
     n, seed, max_batch = _draw_count(who, nsamples), _stream_seed(who, seed), _max_batch(who, max_batch)
-    x = _input_tensor(who, input, eeg, spec)
+    x, other = record.tensors(eeg, spec).x, record.other
     B = _nonempty(who, x)
     level, rad = _level_or_absolute(who, B, "radius_level", radius_level, "radius", radius, 0.02, False)
-    other = eeg if input == "spec" else spec
     if other is not None and (not isinstance(other, torch.Tensor) or other.shape[0] != B):
         raise ValueError(f"{who}: the other input must be None or a tensor with the same batch size")
-    per = x.numel() // B
+    per = record.per
     if B * n >= 1 << 31 or B * per >= 1 << 31:
         raise ValueError(f"{who}: B * n = {B * n} or B * per = {B * per} beyond 32-bit offsets; use fewer samples per call")
     if not (x.is_cuda and (other is None or other.is_cuda)):
@@ -4783,13 +4785,10 @@ def _tcav(model, eeg, spec, concepts, randoms, cavs, input, target_layer, classi
     if cavs is not None and target_layer is None:
         target_layer = cavs.target_layer
     input_is_spec, _, net, target, where = _tcav_target(who, model, input, target_layer)
-    x = _input_tensor(who, input, eeg, spec)
-    B = _nonempty(who, x)
-    other = eeg if input_is_spec else spec
-    multimodal, K, _ = _target_model(who, model, x, other, input_is_spec)
-    if K > _RISE_MAX_K:
-        raise ValueError(f"{who}: {K} classes, supported 1..{_RISE_MAX_K}")
-    cls_h, all_classes = _explained_classes(who, class_idx, B, K, allow_all=True)
+    call = _Call(who, model, input).tensors(eeg, spec)
+    x, B = call.x, _nonempty(who, call.x)
+    K, Kc, cls_h, all_classes = call.explained(class_idx).K, call.Kc, call.cls_h, call.all_classes
+    multimodal, other = call.multimodal, call.other
     shape = _tcav_shape(who, net, where, tuple(x.shape[1:]))
     D = int(np.prod(shape))
     if cavs is None:
@@ -4799,18 +4798,16 @@ def _tcav(model, eeg, spec, concepts, randoms, cavs, input, target_layer, classi
     elif cavs.input != input or cavs.target_layer != target or int(cavs.vectors.shape[1]) != D:
         raise ValueError(f"{who}: the CavSet was trained for input={cavs.input!r} at {cavs.target_layer} with {int(cavs.vectors.shape[1])} features; "
                          f"this call explains input={input!r} at {target} with {D}")
-    _need_gpu(who, "the model and its inputs", model, eeg, spec)
+    call.need_gpu("the model and its inputs", other)               # the other input wherever it is given, beside a stand-alone branch too
     if cavs is None:
         cavs = _train_cavs(who, model, net, input, target, where, names, sets, n, nh, shape, classifier, ridge, holdout, max_batch, False, profile)
-    _need_gpu(who, "the CavSet", model, cavs.vectors)
+    call.need_gpu("the CavSet", cavs.vectors)
 
     lib = L.load()
     dev = x.device
-    Kc = K if all_classes else 1
     V = cavs.vectors.contiguous()
     P = int(V.shape[0])
-    dt = getattr(net, "compute_dtype", torch.float32) if input_is_spec else torch.float32
-    cap = _row_cap(x, input, dt, max_batch)
+    cap = call.row_cap(max_batch)
     with torch.cuda.device(dev), _eval_frozen(model):
         xs = x.detach().to(torch.float32).contiguous()
         xo = other.detach().to(torch.float32).contiguous() if multimodal else None
