@@ -1283,6 +1283,68 @@ int bx_tcav_sensitivity(const void* G, const float* V, double* S, int rows, int 
  * of |S[r,p]|; NaN for a class without rows.  counts[k] = the number of rows of class k. */
 int bx_tcav_score(const double* S, const int* classes, int rows, int P, int K, double* score, double* mean, double* mean_abs, int* counts,
                   bxStream stream);
+/* ---- TracIn: training-data influence and self-influence (Pruthi et al., NeurIPS 2020; Captum's influence.TracInCPFast) through the
+ * model's Linear layers -- fc2, fc1, eeg_model.dense, spectrogram_model.fc, in that order -- whose per-example gradients are outer
+ * products delta (x) a, so that a gradient dot product is (delta_i . delta_j)(a_i . a_j + 1) and no per-example backward pass runs.
+ * Loss of one row: KLDivLoss(reduction="sum"), l = sum_k t_k (log t_k - logp_k) with 0 log 0 = 0; t is the row's target distribution or
+ * the one-hot of an integer label (then l = -logp_c).  With T = sum_k t_k, p = exp(logp), h = hidden, e / s the EEG / spectrogram
+ * branch's log-probabilities, all in fp64 from the fp32 tensors of bx_mm_head_fwd:
+ *     fc2                   delta_2 = T p - t                        [K]    a_2 = h                 [Hd]
+ *     fc1                   delta_1 = (W2^T delta_2) (.) [h > 0]     [Hd]   a_1 = cat(e, s)         [2K]
+ *                           v = W1^T delta_1                         [2K]   v_e = v[:K], v_s = v[K:]
+ *     eeg_model.dense       delta_e = v_e - exp(e) sum(v_e)          [K]    a_e = the EEG features  [F]
+ *     spectrogram_model.fc  delta_s = v_s - exp(s) sum(v_s)          [K]    a_s = gap_out           [C]
+ * A stand-alone branch has its one layer: delta = T p - t, a = gap_out / the features.
+ *     S[i,j]  = sum_c eta_c sum_l (delta_l,i . delta_l,j)(a_l,i . a_l,j + 1)        positive: a gradient step on i lowers j's loss
+ *     self[i] = sum_c eta_c sum_l |delta_l,i|^2 (|a_l,i|^2 + 1)
+ * Order of arithmetic (the file is built with -ffp-contract=off): every sum -- T, l, a dot product, W2^T delta_2 over the rows of W2,
+ * W1^T delta_1 over the rows of W1, sum(v_e) -- is sequential in fp64 over ascending index from +0; each product is rounded once (the
+ * product of two fp32 activations is exact); a layer's term is dd * (aa + 1); the terms of the selected layers are added from +0 in
+ * layer order; the first checkpoint stores eta * sum, a later one adds it.  The gate [h > 0] selects +0.  exp and log are these
+ * sequences of fp64 operations, Horner forms evaluated as p = p * x + c from the last coefficient:
+ *     exp(x): NaN for NaN, 0 below -708, inf above 709; n = rint(x * 1.4426950408889634);
+ *             r = (x - n * 0.6931471803691238) - n * 1.9082149292705877e-10;  ldexp(sum_{i=0..13} r^i / i!, n)   (1 / i! rounded to fp64)
+ *     log(x): (m, q) = frexp(x), doubled with q - 1 when m < 0.7071067811865476;  f = m - 1, s = f / (2 + f), z = s * s,
+ *             P = sum_{i=0..10} z^i / (2 i + 3);  q * 0.6931471803691238 + ((2 s + 2 s * (z * P)) + q * 1.9082149292705877e-10)
+ * So no bit of a factor or a score depends on how the rows were cut into passes, blocks or launches.  No floating-point atomics.
+ * Limits: K <= 32, Hd <= 256, a layer's delta <= 256 and activation <= 4096 wide, 1 <= M <= 4096 test rows, at most 65536 training rows
+ * in a launch, N M < 2^31, 1 <= k <= 256; beyond them BX_EUNSUPPORTED (BX_EINVAL for a malformed call) before any pointer is touched. */
+enum { BX_TRACIN_MULTIMODAL = 0, BX_TRACIN_SINGLE = 1 };
+enum { BX_TRACIN_OK = 0, BX_TRACIN_NONFINITE = 1, BX_TRACIN_BAD_TARGET = 2 };
+typedef struct {
+  int layers;              /* 1..4, in the order above */
+  int dwidth[4];           /* width of every layer's delta; a row of the delta array holds them side by side */
+  int awidth[4];           /* width of every layer's activation */
+} bxTracinShape;
+typedef struct {
+  const double* delta;     /* fp64 [rows, sum of dwidth] */
+  const float* act[4];     /* fp32 [rows, awidth[l]]; may be NULL for a layer the mask leaves out */
+  int rows;
+} bxTracinSide;
+/* logp, target, eeg_logp, spec_logp fp32 [rows,K]; labels i32 [rows] in place of target (exactly one of the two is given); hidden fp32
+ * [rows,Hd]; w1 fp32 [Hd,2K], w2 fp32 [K,Hd].  BX_TRACIN_MULTIMODAL: delta fp64 [rows, K + Hd + K + K] = delta_2 | delta_1 | delta_e |
+ * delta_s.  BX_TRACIN_SINGLE: delta fp64 [rows,K]; hidden, eeg_logp, spec_logp, w1, w2 and Hd are not read.  loss fp64 [rows].  status
+ * i32 [rows]: BX_TRACIN_BAD_TARGET for a negative entry, T <= 0 or a label outside 0..K-1, else BX_TRACIN_NONFINITE for a non-finite
+ * input or result, else 0; the factors and the loss of a flagged row are unspecified. */
+int bx_tracin_factors(const float* logp, const float* target, const int* labels, const float* hidden, const float* eeg_logp,
+                      const float* spec_logp, const float* w1, const float* w2, double* delta, double* loss, int* status, int rows, int K,
+                      int Hd, int mode, bxStream stream);
+/* S fp64 [N,M], M = test->rows: S[row0 + i, j] = eta * sum (store != 0) or S[row0 + i, j] + eta * sum, for the train->rows rows of the
+ * block; the other rows of S are not touched.  layer_mask: bit l selects layer l.  A workgroup owns a 64 x 64 tile of pairs, both
+ * sides' features stream through LDS 32 at a time and every pair's running sums stay in its thread's registers. */
+int bx_tracin_scores(const bxTracinSide* train, const bxTracinSide* test, const bxTracinShape* shape, double* S, int N, int row0, double eta,
+                     int store, int layer_mask, bxStream stream);
+/* self fp64 [N]: self[row0 + i] = eta * sum or self[row0 + i] + eta * sum; bit-equal to the diagonal of bx_tracin_scores of the block
+ * against itself.  One workgroup per row; the widths of all layers together: delta <= 352, activations <= 5440. */
+int bx_tracin_self(const bxTracinSide* side, const bxTracinShape* shape, double* self, int N, int row0, double eta, int store, int layer_mask,
+                   bxStream stream);
+/* For every column j of S fp64 [N,M] the k rows with the largest (largest = 1) or smallest (0) values: idx i32 [M,k], val fp64 [M,k] =
+ * S[idx, j], sorted by value (descending for the largest), ties by ascending row; -0.0 equals +0.0, NaN ranks last.  Exact: a radix
+ * select over the 12 bytes (order-preserving 64-bit key, row) of the column, read from a transposed copy of the keys in the workspace
+ * (N M 8 bytes, 8-byte aligned), then a rank sort of the k survivors.  k <= N. */
+size_t bx_tracin_topk_workspace(int N, int M);
+int bx_tracin_topk(const double* S, int N, int M, int k, int largest, int* idx, double* val, void* workspace, size_t workspace_bytes,
+                   bxStream stream);
 /* attribution seeds: seed fp32 [rows,N], row r = onehot(class of sample r % B); class_mode >= 0: that class, -1: arg-max of
  * logp fp32 [B,N] (first maximum).  Replaces the reference's output[0, argmax] indexing (XAI_Multimodality.py:3110-3111). */
 int bx_class_seed(const float* logp, float* seed, int rows, int B, int N, int class_mode, bxStream stream);

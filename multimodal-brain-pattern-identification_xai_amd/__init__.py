@@ -19,7 +19,8 @@ from .explain import (GradCamSweep, expected_gradients, generate_saliency_maps, 
                       InfidelityResult, infidelity, SensitivityResult, sensitivity_max,
                       MapSimilarityResult, map_similarity, agreement_matrix, RandomizationResult, randomization_test, randomization_layers,
                       FusionVotes, FusionShapResult, fusion_shap, fusion_votes, shapley_weights, modality_importance,
-                      CavSet, TcavResult, train_cavs, tcav, welch_t_test, regularized_incomplete_beta)
+                      CavSet, TcavResult, train_cavs, tcav, welch_t_test, regularized_incomplete_beta,
+                      TracInResult, SelfInfluenceResult, tracin, self_influence)
 from .data import (EEGStacker, stack_eeg, EEGMontageStacker, stack_eeg_montage,          # noqa: F401
                    SpectrogramPreprocessor, preprocess_spectrograms, SpectrogramRegionStacker, stack_spectrogram_regions, StagingRing)                                        # noqa: F401
 from .train import (FlatAdamW, DataParallel, GraphedTrainStep, AsyncCheckpointer, train_and_validate_combined, train_and_validate_eeg_distributed,   # noqa: F401

@@ -33,6 +33,8 @@ BX_MASKOPT_DELETION, BX_MASKOPT_PRESERVATION = 0, 1
 BX_MASKOPT_PROB, BX_MASKOPT_LOGPROB = 0, 1
 BX_TCAV_RIDGE, BX_TCAV_MEAN_DIFFERENCE = 0, 1
 BX_TCAV_MAX_M = 8192
+BX_TRACIN_MULTIMODAL, BX_TRACIN_SINGLE = 0, 1
+BX_TRACIN_OK, BX_TRACIN_NONFINITE, BX_TRACIN_BAD_TARGET = 0, 1, 2
 
 vp, i32, i64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -81,6 +83,14 @@ class WgradGroupLayer(C.Structure):
 class PackJob(C.Structure):
     _fields_ = [("w_oihw", vp), ("packed_mfma", vp), ("Cout", i32), ("Cin", i32), ("I_p", i32), ("O_p", i32),
                 ("transpose_flip", i32), ("block_begin", i32)]
+
+
+class TracinShape(C.Structure):
+    _fields_ = [("layers", i32), ("dwidth", i32 * 4), ("awidth", i32 * 4)]
+
+
+class TracinSide(C.Structure):
+    _fields_ = [("delta", vp), ("act", vp * 4), ("rows", i32)]
 
 
 class EegGrads(C.Structure):
@@ -260,6 +270,11 @@ SIGNATURES = {
     "bx_tcav_vectors": (i32, [vp] * 6 + [i32] * 4 + [vp]),
     "bx_tcav_sensitivity": (i32, [vp, vp, vp] + [i32] * 6 + [vp]),
     "bx_tcav_score": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "bx_tracin_factors": (i32, [vp] * 11 + [i32] * 4 + [vp]),
+    "bx_tracin_scores": (i32, [P(TracinSide), P(TracinSide), P(TracinShape), vp, i32, i32, C.c_double, i32, i32, vp]),
+    "bx_tracin_self": (i32, [P(TracinSide), P(TracinShape), vp, i32, i32, C.c_double, i32, i32, vp]),
+    "bx_tracin_topk_workspace": (sz, [i32, i32]),
+    "bx_tracin_topk": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "bx_param_uniform": (i32, [vp, sz, f32, C.c_uint64, u32, u32, vp]),
     "bx_class_seed": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "bx_seed_next": (i32, [vp, vp, vp]),

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbrainxai.so")
-SOURCES = ["core.hip", "conv3x3.hip", "conv3x3_mfma.hip", "conv3x3_split.hip", "tail.hip", "heads.hip", "eeg.hip", "eeg_generic.hip", "eeg_mfma.hip", "eeg_collapse.hip", "eeg_deep.hip", "eeg_cam.hip", "attrib.hip", "montage.hip", "specprep.hip", "lime.hip", "faith.hip", "rise.hip", "scorecam.hip", "occlusion.hip", "shap.hip", "expgrad.hip", "smoothgrad.hip", "infidelity.hip", "blurig.hip", "spectral.hip", "similarity.hip", "guided_ig.hip", "fusion_shap.hip", "maskopt.hip", "tcav.hip"]
+SOURCES = ["core.hip", "conv3x3.hip", "conv3x3_mfma.hip", "conv3x3_split.hip", "tail.hip", "heads.hip", "eeg.hip", "eeg_generic.hip", "eeg_mfma.hip", "eeg_collapse.hip", "eeg_deep.hip", "eeg_cam.hip", "attrib.hip", "montage.hip", "specprep.hip", "lime.hip", "faith.hip", "rise.hip", "scorecam.hip", "occlusion.hip", "shap.hip", "expgrad.hip", "smoothgrad.hip", "infidelity.hip", "blurig.hip", "spectral.hip", "similarity.hip", "guided_ig.hip", "fusion_shap.hip", "maskopt.hip", "tcav.hip", "tracin.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # No packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32), round 3.  Found with the EEG branch running beside the
@@ -29,8 +29,8 @@ if os.environ.get("BX_PACKED_FP32", "0") != "1":
 # x + gamma * (X_max - x) and its attr += (x - x_old) * g likewise; Fusion SHAP names every fmaf of the head, and the Shapley sum's
 # w * (v(S + i) - v(S)) and its running sum are separate fp64 roundings; the optimised masks' up-sampling, base + M * (x - base), the
 # fp64 footprint sums w * t, the regularisers and every operation of the Adam step likewise; TCAV's fits, vectors and dot products round every
-# product and sum on their own and its Gram matrix names its fma
-EXTRA_FLAGS = {"tcav.hip": ["-ffp-contract=off"], "fusion_shap.hip": ["-ffp-contract=off"], "maskopt.hip": ["-ffp-contract=off"],
+# product and sum on their own and its Gram matrix names its fma; TracIn's factors, its exp and log and its pairwise sums likewise
+EXTRA_FLAGS = {"tracin.hip": ["-ffp-contract=off"], "tcav.hip": ["-ffp-contract=off"], "fusion_shap.hip": ["-ffp-contract=off"], "maskopt.hip": ["-ffp-contract=off"],
 "montage.hip": ["-ffp-contract=off"], "specprep.hip": ["-ffp-contract=off"], "rise.hip": ["-ffp-contract=off"],
                "scorecam.hip": ["-ffp-contract=off"], "expgrad.hip": ["-ffp-contract=off"], "smoothgrad.hip": ["-ffp-contract=off"],
                "infidelity.hip": ["-ffp-contract=off"], "blurig.hip": ["-ffp-contract=off"], "spectral.hip": ["-ffp-contract=off"],

@@ -96,6 +96,13 @@
                                  workgroup per problem (bx_tcav_fit) -- the CAVs (bx_tcav_vectors), fp64 directional derivatives
                                  against all of them in a fixed order (bx_tcav_sensitivity) and the scores (bx_tcav_score);
                                  ``welch_t_test`` is the host's significance test against the null problems.
+* ``tracin`` / ``self_influence`` -- TracIn (Pruthi et al., NeurIPS 2020; Captum's influence.TracInCPFast; not in the reference): which
+                                 training examples made the model decide as it does on a test example, and which training labels
+                                 the model fights against, from the checkpoints the training loop writes.  Through the four Linear
+                                 layers a per-example gradient is an outer product, so the forward passes' activations and the
+                                 closed-form factors (bx_tracin_factors) suffice; the pairwise fp64 sums of a block of training rows
+                                 against all test rows are one tiled launch (bx_tracin_scores), the diagonal bx_tracin_self, the
+                                 top proponents and opponents an exact radix select (bx_tracin_topk).
 """
 from __future__ import annotations
 
@@ -4870,3 +4877,467 @@ def _tcav(model, eeg, spec, concepts, randoms, cavs, input, target_layer, classi
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     return TcavResult(up(scores_h), up(per_random), up(null), up(pv), up(t), up(dof), mean_s[:Q * R].reshape(Q, R, K), mean_abs[:Q * R].reshape(Q, R, K), sens,
                       None if classes is None else classes.long(), out, counts.long(), cavs)
+
+
+# ------------------------------------------------------------------------------------------------
+# TracIn: training-data influence and self-influence through the model's Linear layers.  The definition is pinned in
+# include/brainxai.h; tests/tracin_ref.py restates it.
+_TRACIN_LAYERS = ("fc2", "fc1", "eeg_model.dense", "spectrogram_model.fc")
+_TRACIN_MAX_M, _TRACIN_MAX_BLOCK, _TRACIN_MAX_TOP = 4096, 65536, 256
+_TRACIN_STATUS = {L.BX_TRACIN_NONFINITE: "a non-finite activation, target or factor",
+                  L.BX_TRACIN_BAD_TARGET: "a target with a negative entry or no mass, or a label outside the classes"}
+TracInResult = collections.namedtuple("TracInResult", "proponents proponent_scores opponents opponent_scores scores train_losses test_losses layers "
+                                                      "learning_rates N")
+TracInResult.__doc__ = """What ``tracin(..., return_parts=True)`` returns: ``proponents`` / ``opponents`` int64 [M,top] (the training examples with the largest /
+smallest scores per test example, best first; what the plain call returns), ``proponent_scores`` / ``opponent_scores`` fp64 [M,top], ``scores``
+fp64 [N,M] (None without keep_scores), ``train_losses`` fp64 [C,N] and ``test_losses`` fp64 [C,M] (KLDivLoss(reduction='sum') per example at
+every checkpoint), all on the device; ``layers`` (the layers summed, in the library's order), ``learning_rates`` (one per checkpoint) and ``N``."""
+SelfInfluenceResult = collections.namedtuple("SelfInfluenceResult", "self_influence top top_scores train_losses layers learning_rates N")
+SelfInfluenceResult.__doc__ = """What ``self_influence(..., return_parts=True)`` returns: ``self_influence`` fp64 [N], ``top`` int64 [top] and ``top_scores`` fp64 [top]
+(the most self-influential examples, the mislabel candidates; None without top), ``train_losses`` fp64 [C,N], on the device; ``layers``,
+``learning_rates`` and ``N``."""
+
+
+def _tracin_model(who, model):
+    """-> the layers of the model as the library sees them: kind, K, Hd, names, dwidth, awidth.  Anything else is refused."""
+    from .models import EEGNet, EEGNetAttentionDeep, Spectrogram_Model
+    lin = torch.nn.Linear
+    ns = collections.namedtuple("_TracinPlan", "kind K Hd names dwidth awidth")
+
+    def limits(K, Hd, Cc, F):
+        if not (1 <= K <= 32 and 1 <= Hd <= 256 and 1 <= Cc <= 1024 and 1 <= F <= 4096):
+            raise ValueError(f"{who}: K = {K} classes, Hd = {Hd} hidden units, C = {Cc} channels, F = {F} EEG features; "
+                             f"supported K <= 32, Hd <= 256, C <= 1024, F <= 4096")
+
+    if hasattr(model, "eeg_model") and hasattr(model, "spectrogram_model"):
+        em, sm = model.eeg_model, model.spectrogram_model
+        if isinstance(em, EEGNetAttentionDeep):
+            raise ValueError(f"{who}: an EEGNetAttentionDeep branch is out of scope; the EEG branch must be an EEGNet")
+        if not all(isinstance(m, lin) for m in (getattr(model, "fc1", None), getattr(model, "fc2", None), getattr(em, "dense", None), getattr(sm, "fc", None))):
+            raise ValueError(f"{who}: needs a MultimodalModel with the Linear layers fc2, fc1, eeg_model.dense and spectrogram_model.fc")
+        K, Hd, F, Cc = int(model.fc2.out_features), int(model.fc1.out_features), int(em.dense.in_features), int(sm.fc.in_features)
+        limits(K, Hd, Cc, F)
+        if not (hasattr(model, "_fusable") and model._fusable()):
+            raise ValueError(f"{who}: needs the un-hooked reference MultimodalModel (EEGNet, Spectrogram_Model, head Linear(2K,Hd) -> ReLU -> Linear(Hd,K) "
+                             f"with Hd * 2K <= 4096): its activations come from the fused head")
+        return ns("multimodal", K, Hd, _TRACIN_LAYERS, (K, Hd, K, K), (Hd, 2 * K, F, Cc))
+    if type(model) is Spectrogram_Model:
+        K, Cc = int(model.fc.out_features), int(model.fc.in_features)
+        limits(K, 1, Cc, 1)
+        return ns("spec", K, 0, ("fc",), (K,), (Cc,))
+    if type(model) is EEGNet:
+        K, F = int(model.dense.out_features), int(model.dense.in_features)
+        limits(K, 1, 1, F)
+        return ns("eeg", K, 0, ("dense",), (K,), (F,))
+    raise ValueError(f"{who}: needs a MultimodalModel, a Spectrogram_Model or an EEGNet, got {type(model).__name__}")
+
+
+def _tracin_layers(who, plan, layers):
+    """-> (mask, names): bit l of mask selects the plan's layer l."""
+    names = plan.names
+    if isinstance(layers, str):
+        if layers == "all":
+            layers = names
+        elif layers == "head" and plan.kind == "multimodal":
+            layers = ("fc2", "fc1")
+        else:
+            layers = (layers,)
+    try:
+        layers = list(layers)
+    except TypeError:
+        raise ValueError(f"{who}: layers must be 'all', 'head' or a sequence of layer names, got {type(layers).__name__}") from None
+    if not layers:
+        raise ValueError(f"{who}: layers is empty")
+    mask = 0
+    for name in layers:
+        if name not in names:
+            raise ValueError(f"{who}: unknown layer {name!r}; use 'all'{', ' + repr('head') if plan.kind == 'multimodal' else ''} or any of {names}")
+        mask |= 1 << names.index(name)
+    return mask, tuple(n for l, n in enumerate(names) if mask >> l & 1)
+
+
+def _tracin_checkpoints(who, checkpoints, learning_rates):
+    """-> (the checkpoints as a list, one finite learning rate per checkpoint)."""
+    import os
+    if isinstance(checkpoints, (str, bytes, dict, os.PathLike)) or not hasattr(checkpoints, "__len__") or not hasattr(checkpoints, "__getitem__"):
+        raise ValueError(f"{who}: checkpoints must be a sequence of state dicts, dicts with a 'state_dict' key or paths, got {type(checkpoints).__name__}")
+    cks = list(checkpoints)
+    if not cks:
+        raise ValueError(f"{who}: checkpoints is empty")
+    for c, ck in enumerate(cks):
+        if not isinstance(ck, (dict, str, os.PathLike)):
+            raise ValueError(f"{who}: checkpoint {c} must be a state dict, a dict with a 'state_dict' key or a path, got {type(ck).__name__}")
+    if learning_rates is None:
+        return cks, [1.0] * len(cks)
+    try:
+        rates = list(learning_rates)
+    except TypeError:
+        raise ValueError(f"{who}: learning_rates must be None or one number per checkpoint, got {type(learning_rates).__name__}") from None
+    if len(rates) != len(cks):
+        raise ValueError(f"{who}: {len(rates)} learning rates for {len(cks)} checkpoints")
+    for c, r in enumerate(rates):
+        if isinstance(r, bool) or not isinstance(r, numbers.Real) or not math.isfinite(float(r)):
+            raise ValueError(f"{who}: learning rate {c} must be a finite number, got {r!r}")
+    return cks, [float(r) for r in rates]
+
+
+def _tracin_int(who, name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= int(v) <= hi:
+        raise ValueError(f"{who}: {name} = {v!r} outside {lo}..{hi}")
+    return int(v)
+
+
+def _tracin_form(plan):
+    return {"multimodal": "(eeg [n,1,Chans,T], spec [n,C,H,W], target)", "eeg": "(x, target) with x [n,1,Chans,T]",
+            "spec": "(x, target) with x [n,C,H,W]"}[plan.kind]
+
+
+def _tracin_batch(who, plan, batch, what):
+    """-> n: one batch in tensor form, (eeg, spec, target) for a MultimodalModel, (x, target) for a stand-alone branch."""
+    form = _tracin_form(plan)
+    want = 3 if plan.kind == "multimodal" else 2
+    if not (isinstance(batch, (tuple, list)) and len(batch) == want and all(isinstance(t, torch.Tensor) for t in batch)):
+        raise ValueError(f"{who}: {what} must be the tensors {form}")
+    *xs, target = batch
+    ok = all(x.dim() == 4 for x in xs) and (plan.kind == "spec" or xs[0].shape[1] == 1)
+    if not ok:
+        raise ValueError(f"{who}: {what} must be the tensors {form}")
+    n = int(xs[0].shape[0])
+    if any(int(x.shape[0]) != n for x in xs):
+        raise ValueError(f"{who}: {what} hold {int(xs[0].shape[0])} EEG and {int(xs[1].shape[0])} spectrogram samples")
+    if n < 1 or any(x.numel() == 0 for x in xs):
+        raise ValueError(f"{who}: {what} are empty")
+    is_dist = target.dtype == torch.float32 and tuple(target.shape) == (n, plan.K)
+    is_label = target.dtype in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8) and tuple(target.shape) == (n,)
+    if not (is_dist or is_label):
+        raise ValueError(f"{who}: the target of {what} must be fp32 [{n}, {plan.K}] or an integer tensor [{n}], got {target.dtype} {tuple(target.shape)}")
+    return n
+
+
+def _tracin_data(who, plan, data, what, tensors_only):
+    """-> (n or None, batches): ``data`` in tensor form is one batch (n known); anything else re-iterable is a stream of batches."""
+    if isinstance(data, (tuple, list)) and data and all(isinstance(t, torch.Tensor) for t in data):
+        return _tracin_batch(who, plan, data, what), None
+    if tensors_only or isinstance(data, (str, bytes, dict, torch.Tensor)) or not hasattr(data, "__iter__") or iter(data) is data:
+        more = "" if tensors_only else ", or a re-iterable of such batches (a one-shot iterator cannot be walked once per checkpoint)"
+        raise ValueError(f"{who}: {what}{more} must be the tensors {_tracin_form(plan)}")
+    return None, data
+
+
+class _TracinWalk:
+    """The checkpoints' walk: the model's parameters and buffers are copied on the device on entry and put back bit for bit on exit;
+    ``load(c)`` writes checkpoint c's weights, ``passes(data)`` runs the data through the model in passes of at most max_batch rows and
+    yields every pass's activations, factors, losses and status words."""
+
+    def __init__(self, who, model, plan, checkpoints, max_batch, profile):
+        self.who, self.model, self.plan, self.checkpoints, self.max_batch, self.profile = who, model, plan, checkpoints, max_batch, profile
+        self.dev = next(model.parameters()).device
+        self.lib = L.load()
+        self.ld = sum(plan.dwidth)
+        shape = L.TracinShape()
+        shape.layers = len(plan.names)
+        for l, (dw, aw) in enumerate(zip(plan.dwidth, plan.awidth)):
+            shape.dwidth[l], shape.awidth[l] = dw, aw
+        self.shape = shape
+
+    def __enter__(self):
+        self.saved = [(t, t.detach().clone()) for t in list(self.model.parameters()) + list(self.model.buffers())]
+        return self
+
+    def __exit__(self, *exc):
+        _rand_restore(self.saved)
+
+    def load(self, c):
+        who, ck = self.who, self.checkpoints[c]
+        if not isinstance(ck, dict):
+            ck = torch.load(ck, map_location="cpu", weights_only=False)
+            if not isinstance(ck, dict):
+                raise ValueError(f"{who}: checkpoint {c} holds a {type(ck).__name__}, not a state dict")
+        sd = ck["state_dict"] if isinstance(ck.get("state_dict"), dict) else ck
+        own = self.model.state_dict()
+        missing, extra = sorted(set(own) - set(sd)), sorted(set(sd) - set(own))
+        if missing or extra:
+            raise ValueError(f"{who}: checkpoint {c}: its keys are not the model's (missing {missing[:3]}, unexpected {extra[:3]})")
+        with torch.no_grad():
+            self.model.load_state_dict(sd, strict=True)
+        ops.bump_param_epoch()
+        if self.plan.kind == "multimodal":
+            self.w1, self.w2 = (t.detach().to(torch.float32).contiguous() for t in (self.model.fc1.weight, self.model.fc2.weight))
+
+    def side(self, delta, acts, rows):
+        s = L.TracinSide()
+        s.delta, s.rows = _p(delta), rows
+        for l, a in enumerate(acts):
+            s.act[l] = _p(a)
+        return s
+
+    def _batches(self, data, what):
+        if isinstance(data, (tuple, list)) and all(isinstance(t, torch.Tensor) for t in data):
+            yield data
+            return
+        for batch in data:
+            _tracin_batch(self.who, self.plan, batch, f"a batch of {what}")
+            yield tuple(t.to(self.dev) for t in batch)
+
+    def passes(self, data, what):
+        """-> (n, acts, delta, loss, status) per pass, the rows in the data's order."""
+        plan, model, lib, dev = self.plan, self.model, self.lib, self.dev
+        K, Hd = plan.K, plan.Hd
+        for batch in self._batches(data, what):
+            *xs, target = batch
+            xs = [x.detach().to(torch.float32).contiguous() for x in xs]
+            dist = target.dtype == torch.float32
+            target = target.detach().contiguous() if dist else target.detach().to(torch.int32).contiguous()
+            if plan.kind == "multimodal":
+                cap = min(_row_cap(xs[1], "spec", getattr(model.spectrogram_model, "compute_dtype", torch.float32), self.max_batch),
+                          _row_cap(xs[0], "eeg", torch.float32, self.max_batch))
+            else:
+                cap = _row_cap(xs[0], plan.kind, getattr(model, "compute_dtype", torch.float32) if plan.kind == "spec" else torch.float32, self.max_batch)
+            for b0 in range(0, int(xs[0].shape[0]), cap):
+                n = min(cap, int(xs[0].shape[0]) - b0)
+                tgt = target[b0:b0 + n]
+                logp = torch.empty(n, K, dtype=torch.float32, device=dev)
+                with _lap(self.profile, "forward"):
+                    if plan.kind == "multimodal":
+                        em, sm = model.eeg_model, model.spectrogram_model
+                        ef = em.features(xs[0][b0:b0 + n]).float().contiguous()
+                        feat = sm.features(xs[1][b0:b0 + n]).permute(0, 2, 3, 1).contiguous()
+                        Cc, F = int(feat.shape[3]), int(ef.shape[1])
+                        if (Hd, 2 * K, F, Cc) != tuple(plan.awidth):
+                            raise RuntimeError(f"brainxai.{self.who}: the branches emit {F} EEG features and {Cc} channels, the layers expect "
+                                               f"{plan.awidth[2]} and {plan.awidth[3]} (Samples mismatch)")
+                        gap = torch.empty(n, Cc, dtype=torch.float32, device=dev)
+                        votes = torch.empty(2, n, K, dtype=torch.float32, device=dev)           # the EEG branch's, then the spectrogram branch's
+                        hidden = torch.empty(n, Hd, dtype=torch.float32, device=dev)
+                        p = [t.detach() for t in (sm.fc.weight, sm.fc.bias, em.dense.weight, em.dense.bias, model.fc1.weight, model.fc1.bias,
+                                                  model.fc2.weight, model.fc2.bias)]
+                        L.check(lib.bx_mm_head_fwd(_p(feat), _p(ef), *[_p(t) for t in p], _p(gap), _p(votes[1]), _p(votes[0]), _p(hidden), _p(logp), n,
+                                                   int(feat.shape[1]) * int(feat.shape[2]), Cc, F, K, Hd, ops.bx_dtype(feat.dtype), _stream()), "bx_mm_head_fwd")
+                        acts = [hidden, torch.cat([votes[0], votes[1]], dim=1), ef, gap]
+                    elif plan.kind == "spec":
+                        feat = model.features(xs[0][b0:b0 + n]).permute(0, 2, 3, 1).contiguous()
+                        Cc = int(feat.shape[3])
+                        if Cc != plan.awidth[0]:
+                            raise RuntimeError(f"brainxai.{self.who}: block5 emits {Cc} channels, fc expects {plan.awidth[0]}")
+                        gap = torch.empty(n, Cc, dtype=torch.float32, device=dev)
+                        L.check(lib.bx_gap_fc_lsm_fwd(_p(feat), _p(model.fc.weight.detach()), _p(model.fc.bias.detach()), _p(gap), _p(logp), n,
+                                                      int(feat.shape[1]) * int(feat.shape[2]), Cc, K, ops.bx_dtype(feat.dtype), _stream()), "bx_gap_fc_lsm_fwd")
+                        acts = [gap]
+                    else:
+                        ef = model.features(xs[0][b0:b0 + n]).float().contiguous()
+                        if int(ef.shape[1]) != plan.awidth[0]:
+                            raise RuntimeError(f"brainxai.{self.who}: EEGNet emits {int(ef.shape[1])} features, dense expects {plan.awidth[0]} (Samples mismatch)")
+                        L.check(lib.bx_linear_lsm_fwd(_p(ef), _p(model.dense.weight.detach()), _p(model.dense.bias.detach()), _p(logp), n, int(ef.shape[1]), K,
+                                                      _stream()), "bx_linear_lsm_fwd")
+                        acts = [ef]
+                with _lap(self.profile, "factors"):
+                    delta = torch.empty(n, self.ld, dtype=torch.float64, device=dev)
+                    loss = torch.empty(n, dtype=torch.float64, device=dev)
+                    status = torch.empty(n, dtype=torch.int32, device=dev)
+                    multi = plan.kind == "multimodal"
+                    L.check(lib.bx_tracin_factors(_p(logp), _p(tgt) if dist else None, None if dist else _p(tgt), _p(hidden) if multi else None,
+                                                  _p(votes[0]) if multi else None, _p(votes[1]) if multi else None, _p(self.w1) if multi else None,
+                                                  _p(self.w2) if multi else None, _p(delta), _p(loss), _p(status), n, K, Hd,
+                                                  L.BX_TRACIN_MULTIMODAL if multi else L.BX_TRACIN_SINGLE, _stream()), "bx_tracin_factors")
+                yield n, acts, delta, loss, status
+
+    def check(self, c, status, what):
+        """The status words of a checkpoint's rows, read once: raises naming the first flagged example."""
+        st = torch.cat(status).cpu().numpy()
+        bad = np.flatnonzero(st)
+        if bad.size:
+            raise ValueError(f"{self.who}: checkpoint {c}: {what} example {int(bad[0])} has {_TRACIN_STATUS.get(int(st[bad[0]]), 'a bad status')}")
+
+
+def _tracin_common(who, model, checkpoints, layers, learning_rates, top, max_batch, block_rows, top_default):
+    plan = _tracin_model(who, model)
+    mask, names = _tracin_layers(who, plan, layers)
+    cks, rates = _tracin_checkpoints(who, checkpoints, learning_rates)
+    max_batch = _max_batch(who, max_batch)
+    block_rows = min(_tracin_int(who, "block_rows", block_rows, 1, 1 << 30), _TRACIN_MAX_BLOCK)
+    if top is not None or not top_default:
+        top = _tracin_int(who, "top", top, 1, _TRACIN_MAX_TOP)
+    return plan, mask, names, cks, rates, max_batch, block_rows, top
+
+
+def _tracin_top(who, top, N):
+    if top is not None and top > N:
+        raise ValueError(f"{who}: top = {top} outside 1..{min(_TRACIN_MAX_TOP, N)}")
+
+
+def _tracin_topk(lib, S, N, M, k, largest):
+    """-> (idx int64 [M,k], val fp64 [M,k]) of S fp64 [N,M]."""
+    dev = S.device
+    ws = torch.empty(max(int(lib.bx_tracin_topk_workspace(N, M)), 8) // 8, dtype=torch.int64, device=dev)
+    idx = torch.empty(M, k, dtype=torch.int32, device=dev)
+    val = torch.empty(M, k, dtype=torch.float64, device=dev)
+    L.check(lib.bx_tracin_topk(_p(S), N, M, k, largest, _p(idx), _p(val), _p(ws), ws.numel() * 8, _stream()), "bx_tracin_topk")
+    return idx.long(), val
+
+
+def tracin(model, checkpoints, train, test, *, layers="all", learning_rates=None, top=10, max_batch=256, block_rows=16384, keep_scores=False,
+           return_parts=False):
+    """Which training examples made the model decide as it does on the test examples: TracIn (Pruthi et al., NeurIPS 2020; Captum's
+    influence.TracInCPFast) through the model's last Linear layers, from checkpoints the training loop already writes.
+        S[i,j] = sum_c eta_c sum_l (delta_l,i . delta_l,j)(a_l,i . a_l,j + 1)
+    the gradient dot product of KLDivLoss(reduction='sum') of training example i and test example j with respect to the weights and
+    biases of fc2, fc1, eeg_model.dense and spectrogram_model.fc, exactly: their per-example gradients are outer products, so no
+    per-example backward pass runs.  A positive score marks a proponent (a gradient step on i lowers j's loss), a negative one an opponent.
+
+    model:          a MultimodalModel (the un-hooked reference architecture with an EEGNet branch), a Spectrogram_Model or an EEGNet.
+    checkpoints:    a non-empty sequence; every entry a state_dict, a dict with a 'state_dict' key (what ``save_checkpoint`` writes) or a
+                    path to one (loaded as ``load_checkpoint`` does).  The keys must be the model's.
+    train:          (eeg, spec, target) for a MultimodalModel, (x, target) for a stand-alone branch, on the model's device; or a re-iterable
+                    of such batches (a DataLoader), walked once per checkpoint, every batch moved to the device.  target: fp32 [n,K]
+                    distributions, or integer labels [n].
+    test:           the same tensor form, M <= 4096 examples.
+    layers:         'all'; 'head' (fc1 and fc2); a sequence out of 'fc2', 'fc1', 'eeg_model.dense', 'spectrogram_model.fc'; 'fc' / 'dense' is
+                    the one layer of a stand-alone branch.
+    learning_rates: None (all 1) or one finite number per checkpoint.
+    top:            proponents and opponents returned per test example, 1..min(256, N).
+    max_batch:      rows per forward pass; block_rows: training rows per score launch.  No bit of the result depends on either.
+    Eval mode without autograd; forward passes through the model's own kernels, then the factors in closed form (bx_tracin_factors), one
+    tiled fp64 launch per block of training rows against all test rows (bx_tracin_scores) and an exact radix select per test example
+    (bx_tracin_topk).  Every parameter and buffer of the model is copied on the device first and restored bit for bit in a ``finally``;
+    the training flag and every requires_grad likewise.  Returns (proponents, opponents), int64 [M,top] each, or ``TracInResult`` with
+    return_parts."""
+    return _tracin(model, checkpoints, train, test, layers, learning_rates, top, max_batch, block_rows, keep_scores, return_parts)
+
+
+def _tracin(model, checkpoints, train, test, layers, learning_rates, top, max_batch, block_rows, keep_scores, return_parts, profile=None):
+    """``tracin`` itself.  profile: None, or a list that receives (phase, start event, end event) with phase in 'forward', 'factors',
+    'scores', 'topk' -- device events around every phase (tools/tracin_bench.py sums them)."""
+    # ---- everything that can be refused is refused here, before the library is touched ----
+    who = "tracin"
+    plan, mask, names, cks, rates, max_batch, block_rows, top = _tracin_common(who, model, checkpoints, layers, learning_rates, top, max_batch, block_rows, False)
+    N, train_iter = _tracin_data(who, plan, train, "train", False)
+    M, _ = _tracin_data(who, plan, test, "test", True)
+    if M > _TRACIN_MAX_M:
+        raise ValueError(f"{who}: {M} test examples, supported 1..{_TRACIN_MAX_M}")
+    if N is not None:
+        _tracin_top(who, top, N)
+        if N * M >= 1 << 31:
+            raise ValueError(f"{who}: N * M = {N * M} scores, supported below 2^31; use fewer test examples per call")
+    _need_gpu(who, "the model, train and test", model, *test, *(train if train_iter is None else ()))
+
+    dev = next(model.parameters()).device
+    Cn = len(cks)
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad(), _TracinWalk(who, model, plan, cks, max_batch, profile) as walk:
+        lib = walk.lib
+        S = None if N is None else torch.empty(N, M, dtype=torch.float64, device=dev)
+        train_losses, test_losses = [], []
+        for c in range(Cn):
+            walk.load(c)
+            parts = list(walk.passes(test, "test"))
+            t_acts = [torch.cat([p[1][l] for p in parts]) for l in range(len(plan.names))]
+            t_delta, t_status = torch.cat([p[2] for p in parts]), [p[4] for p in parts]
+            test_losses.append(torch.cat([p[3] for p in parts]))
+            t_side = walk.side(t_delta, t_acts, M)
+            blocks, pend, npend, row0, losses, status = [], [], 0, 0, [], []
+
+            def flush():
+                nonlocal pend, npend, row0
+                acts = [torch.cat([p[0][l] for p in pend]) for l in range(len(plan.names))]
+                delta = torch.cat([p[1] for p in pend])
+                out, n_all, r0 = (S, N, row0) if S is not None else (torch.empty(npend, M, dtype=torch.float64, device=dev), npend, 0)
+                with _lap(profile, "scores"):
+                    L.check(lib.bx_tracin_scores(C.byref(walk.side(delta, acts, npend)), C.byref(t_side), C.byref(walk.shape), _p(out), n_all, r0, rates[c],
+                                                 1 if c == 0 else 0, mask, _stream()), "bx_tracin_scores")
+                if S is None:
+                    blocks.append(out)
+                row0 += npend
+                pend, npend = [], 0
+
+            for n, acts, delta, loss, st in walk.passes(train if train_iter is None else train_iter, "train"):
+                losses.append(loss)
+                status.append(st)
+                o = 0
+                while o < n:
+                    take = min(n - o, block_rows - npend)
+                    if N is not None and row0 + npend + take > N:
+                        raise ValueError(f"{who}: train yields more than the {N} examples of its first pass at checkpoint {c}")
+                    pend.append(([a[o:o + take] for a in acts], delta[o:o + take]))
+                    npend += take
+                    o += take
+                    if npend == block_rows:
+                        flush()
+            if npend:
+                flush()
+            if S is None:
+                if not blocks:
+                    raise ValueError(f"{who}: train yields no batches")
+                S = torch.cat(blocks)
+                N = int(S.shape[0])
+                _tracin_top(who, top, N)
+                if N * M >= 1 << 31:
+                    raise ValueError(f"{who}: N * M = {N * M} scores, supported below 2^31; use fewer test examples per call")
+            elif row0 != N:
+                raise ValueError(f"{who}: train yields {row0} examples at checkpoint {c}, {N} in its first pass")
+            train_losses.append(torch.cat(losses))
+            walk.check(c, t_status, "test")
+            walk.check(c, status, "training")
+        with _lap(profile, "topk"):
+            pro, pro_s = _tracin_topk(lib, S, N, M, top, 1)
+            opp, opp_s = _tracin_topk(lib, S, N, M, top, 0)
+    if not return_parts:
+        return pro, opp
+    return TracInResult(pro, pro_s, opp, opp_s, S if keep_scores else None, torch.stack(train_losses), torch.stack(test_losses), names, tuple(rates), N)
+
+
+def self_influence(model, checkpoints, train, *, layers="all", learning_rates=None, top=None, max_batch=256, block_rows=16384, return_parts=False):
+    """The influence of every training example on itself, self[i] = sum_c eta_c sum_l |delta_l,i|^2 (|a_l,i|^2 + 1): ``tracin``'s score of
+    (i, i), bit for bit.  Examples the model fights against -- mislabelled ones first -- have the largest values.  The arguments are
+    ``tracin``'s (block_rows is accepted for symmetry; a row needs no partner).  Returns fp64 [N] on the device; with ``top`` also the
+    indices int64 [top] of the most self-influential examples (bx_tracin_topk), as (self_influence, top); ``SelfInfluenceResult`` with
+    return_parts."""
+    return _self_influence(model, checkpoints, train, layers, learning_rates, top, max_batch, block_rows, return_parts)
+
+
+def _self_influence(model, checkpoints, train, layers, learning_rates, top, max_batch, block_rows, return_parts, profile=None):
+    who = "self_influence"
+    plan, mask, names, cks, rates, max_batch, block_rows, top = _tracin_common(who, model, checkpoints, layers, learning_rates, top, max_batch, block_rows, True)
+    N, train_iter = _tracin_data(who, plan, train, "train", False)
+    if N is not None:
+        _tracin_top(who, top, N)
+        if N >= 1 << 31:
+            raise ValueError(f"{who}: N = {N} examples, supported below 2^31")
+    _need_gpu(who, "the model and train", model, *(train if train_iter is None else ()))
+
+    dev = next(model.parameters()).device
+    with torch.cuda.device(dev), _eval_frozen(model), torch.no_grad(), _TracinWalk(who, model, plan, cks, max_batch, profile) as walk:
+        lib = walk.lib
+        out = None if N is None else torch.empty(N, dtype=torch.float64, device=dev)
+        train_losses = []
+        for c in range(len(cks)):
+            walk.load(c)
+            row0, chunks, losses, status = 0, [], [], []
+            for n, acts, delta, loss, st in walk.passes(train if train_iter is None else train_iter, "train"):
+                losses.append(loss)
+                status.append(st)
+                if out is not None and row0 + n > N:
+                    raise ValueError(f"{who}: train yields more than the {N} examples of its first pass at checkpoint {c}")
+                dst, n_all, r0 = (out, N, row0) if out is not None else (torch.empty(n, dtype=torch.float64, device=dev), n, 0)
+                with _lap(profile, "scores"):
+                    L.check(lib.bx_tracin_self(C.byref(walk.side(delta, acts, n)), C.byref(walk.shape), _p(dst), n_all, r0, rates[c], 1 if c == 0 else 0, mask,
+                                               _stream()), "bx_tracin_self")
+                if out is None:
+                    chunks.append(dst)
+                row0 += n
+            if out is None:
+                if not chunks:
+                    raise ValueError(f"{who}: train yields no batches")
+                out = torch.cat(chunks)
+                N = int(out.shape[0])
+                _tracin_top(who, top, N)
+            elif row0 != N:
+                raise ValueError(f"{who}: train yields {row0} examples at checkpoint {c}, {N} in its first pass")
+            train_losses.append(torch.cat(losses))
+            walk.check(c, status, "training")
+        idx = val = None
+        if top is not None:
+            with _lap(profile, "topk"):
+                idx, val = _tracin_topk(lib, out, N, 1, top, 1)
+                idx, val = idx[0], val[0]
+    if return_parts:
+        return SelfInfluenceResult(out, idx, val, torch.stack(train_losses), names, tuple(rates), N)
+    return out if top is None else (out, idx)
