@@ -298,6 +298,18 @@ int bx_mm_head_bwd(const float* dlogp, const float* logp, const float* hidden, c
                    float* d_fc_w, float* d_fc_b, float* d_dense_w, float* d_dense_b, float* dw1, float* db1, float* dw2,
                    float* db2, void* workspace, size_t workspace_bytes, int B, int HW, int C, int K, int N, int Hd,
                    int dtype, bxStream stream);
+/* The training head: bx_mm_head_fwd, bx_kldiv_fwd_bwd(logp, target, reduction, grad_scale) and bx_mm_head_bwd(dlogp) as TWO launches,
+ * bit for bit what the three entries compute.  Launch 1, one workgroup per sample: the forward (all five outputs of bx_mm_head_fwd are
+ * written), dlogp [B,N] = -target * grad_scale / denom (may be NULL) and the input half of the backward (dfeat / d_eeg_feat, may be
+ * NULL, and the workspace).  Launch 2: the parameter gradients (written when non-NULL) and, in one more workgroup, loss[1] (may be
+ * NULL).  target fp32 [B,N]; workspace as bx_mm_head_bwd; the gradients are those of the loss itself (upstream gradient 1). */
+int bx_mm_head_train(const void* feat, const float* eeg_feat, const float* fc_w, const float* fc_b, const float* dense_w,
+                     const float* dense_b, const float* w1, const float* b1, const float* w2, const float* b2,
+                     const float* target, float* gap_out, float* spec_logp, float* eeg_logp, float* hidden, float* logp,
+                     float* loss, float* dlogp, void* dfeat, float* d_eeg_feat, float* d_fc_w, float* d_fc_b,
+                     float* d_dense_w, float* d_dense_b, float* dw1, float* db1, float* dw2, float* db2, void* workspace,
+                     size_t workspace_bytes, int B, int HW, int C, int K, int N, int Hd, int reduction, float grad_scale,
+                     int dtype, bxStream stream);
 /* nn.KLDivLoss on log-prob input / prob target (NB:1989,1599): loss[1] and dlogp = -t/denom.
  * reduction: 0 'mean' (denom B*N), 1 'batchmean' (denom B), 2 'sum'.  grad_scale multiplies dlogp. */
 int bx_kldiv_fwd_bwd(const float* logp, const float* target, float* loss, float* dlogp, int B, int N,

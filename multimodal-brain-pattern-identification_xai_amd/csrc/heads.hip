@@ -324,8 +324,9 @@ extern "C" int bx_fusion_head_bwd(const float* dlogp, const float* logp, const f
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_kldiv(const float* __restrict__ logp, const float* __restrict__ target, float* __restrict__ loss,
-                                                float* __restrict__ dlogp, int n, float inv_denom, float gscale) {
+// loss = sum t (log t - logp) * inv_denom by one workgroup of 256 threads (fixed order of adds); dlogp = -t * inv_denom * gscale when asked for
+__device__ __forceinline__ void kldiv_body(const float* __restrict__ logp, const float* __restrict__ target, float* __restrict__ loss,
+                                           float* __restrict__ dlogp, int n, float inv_denom, float gscale) {
   __shared__ float part[4];
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) {
@@ -338,11 +339,16 @@ __global__ __launch_bounds__(256) void k_kldiv(const float* __restrict__ logp, c
   __syncthreads();
   if (threadIdx.x == 0 && loss) loss[0] = (part[0] + part[1] + part[2] + part[3]) * inv_denom;
 }
+__global__ __launch_bounds__(256) void k_kldiv(const float* __restrict__ logp, const float* __restrict__ target, float* __restrict__ loss,
+                                                float* __restrict__ dlogp, int n, float inv_denom, float gscale) {
+  kldiv_body(logp, target, loss, dlogp, n, inv_denom, gscale);
+}
+static float kldiv_denom(int reduction, int B, int N) { return reduction == 0 ? (float)B * N : reduction == 1 ? (float)B : 1.f; }
 extern "C" int bx_kldiv_fwd_bwd(const float* logp, const float* target, float* loss, float* dlogp, int B, int N,
                                 int reduction, float grad_scale, bxStream stream) {
   BX_REQUIRE(logp && target && B > 0 && N > 0, "bx_kldiv_fwd_bwd: bad arguments");
   BX_REQUIRE(reduction >= 0 && reduction <= 2, "bx_kldiv_fwd_bwd: reduction must be 0 (mean), 1 (batchmean) or 2 (sum)");
-  const float denom = reduction == 0 ? (float)B * N : reduction == 1 ? (float)B : 1.f;
+  const float denom = kldiv_denom(reduction, B, N);
   hipLaunchKernelGGL(k_kldiv, dim3(1), dim3(256), 0, (hipStream_t)stream, logp, target, loss, dlogp, B * N, 1.f / denom, grad_scale);
   BX_CHECK_LAUNCH("bx_kldiv_fwd_bwd");
   return BX_OK;
@@ -374,16 +380,22 @@ __device__ __forceinline__ float mmh_wave_dot(const float* __restrict__ wrow, co
 
 // FAST (2N <= 12, i.e. N <= 6, K <= 1024, C <= 1024: three [dense ; fc] rows per wave, 12 fc1 entries per thread): every weight a thread will need is loaded into registers at kernel start,
 // together with the feature loads, so the chain gap -> logits -> hidden -> logits costs one memory round trip instead of six.
-template <typename T, bool FAST>
-__global__ __launch_bounds__(256) void k_mm_head_fwd(const T* __restrict__ feat, const float* __restrict__ ef, const float* __restrict__ fcw,
-    const float* __restrict__ fcb, const float* __restrict__ dw_, const float* __restrict__ db_, const float* __restrict__ w1,
-    const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ gap_out,
-    float* __restrict__ s_logp, float* __restrict__ e_logp, float* __restrict__ hidden, float* __restrict__ logp, int HW, int C, int K, int N, int Hd) {
-  __shared__ float gs[MMH_MAXC], es[MMH_MAXK], hs[MMH_MAXHD], lg[2 * HEAD_MAX_N], z[2 * HEAD_MAX_N], lo[HEAD_MAX_N];
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const float inv_hw = 1.f / (float)HW;
-  // FAST: register copies of this thread's weights (rows q = wave + 4r of [dense ; fc], row tid of fc1, rows wave, wave+4 of fc2)
-  float wq[FAST ? 3 : 1][FAST ? 16 : 1], bq[FAST ? 3 : 1], w1r[FAST ? 12 : 1], b1r = 0.f, w2r[FAST ? 2 : 1][FAST ? 4 : 1], b2r[FAST ? 2 : 1];
+// The forward and the input half of the backward are each a load step (everything the workgroup will read from global memory,
+// requested at kernel start) and a body over registers and LDS: k_mm_head_fwd and k_mm_head_bwd_in run one pair each,
+// k_mm_head_train runs both load steps first and then both bodies, so that the arithmetic exists once.
+// FAST: register copies of this thread's weights (rows q = wave + 4r of [dense ; fc], row tid of fc1, rows wave, wave+4 of fc2)
+template <bool FAST>
+struct MmhFwdRegs { float wq[FAST ? 3 : 1][FAST ? 16 : 1], bq[FAST ? 3 : 1], w1r[FAST ? 12 : 1], b1r, w2r[FAST ? 2 : 1][FAST ? 4 : 1], b2r[FAST ? 2 : 1], efr[FAST ? 4 : 1]; };
+// after the body: z = [eeg_logp ; spec_logp], hs = hidden, lg[0..N) = logp
+struct MmhFwdLds { float gs[MMH_MAXC], es[MMH_MAXK], hs[MMH_MAXHD], lg[2 * HEAD_MAX_N], z[2 * HEAD_MAX_N], lo[HEAD_MAX_N]; };
+
+template <bool FAST>
+__device__ __forceinline__ void mmh_fwd_load(MmhFwdRegs<FAST>& rg, const float* __restrict__ ef, const float* __restrict__ fcw, const float* __restrict__ fcb,
+    const float* __restrict__ dw_, const float* __restrict__ db_, const float* __restrict__ w1, const float* __restrict__ b1,
+    const float* __restrict__ w2, const float* __restrict__ b2, int C, int K, int N, int Hd) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  auto& wq = rg.wq; auto& bq = rg.bq; auto& w1r = rg.w1r; auto& b1r = rg.b1r; auto& w2r = rg.w2r; auto& b2r = rg.b2r;
+  b1r = 0.f;
   if (FAST) {
 #pragma unroll
     // (clamped indices + selects, never `cond ? p[i] : 0`: each conditional load became an exec-mask branch, ~75 of them in a row)
@@ -411,22 +423,43 @@ __global__ __launch_bounds__(256) void k_mm_head_fwd(const T* __restrict__ feat,
       for (int u = 0; u < 4; ++u) { const int j = lane + 64 * u; const float v = w2[(size_t)nc * Hd + (j < Hd ? j : 0)]; w2r[r][u] = j < Hd ? v : 0.f; }
       b2r[r] = b2[nc];
     }
+    // this sample's EEG features (K <= 1024): requested with the weights, stored to LDS behind the pooling loop -- after it they
+    // would be one more round trip
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { const int i = tid + 256 * u; rg.efr[u] = ef[(size_t)blockIdx.x * K + (i < K ? i : K - 1)]; }
   }
+}
+
+template <typename T, bool FAST>
+__device__ __forceinline__ void mmh_fwd_body(const MmhFwdRegs<FAST>& rg, MmhFwdLds& sm, const T* __restrict__ feat, const float* __restrict__ ef,
+    const float* __restrict__ fcw, const float* __restrict__ fcb, const float* __restrict__ dw_, const float* __restrict__ db_,
+    const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+    float* __restrict__ gap_out, float* __restrict__ s_logp, float* __restrict__ e_logp, float* __restrict__ hidden, float* __restrict__ logp,
+    int HW, int C, int K, int N, int Hd) {
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float inv_hw = 1.f / (float)HW;
+  auto& wq = rg.wq; auto& bq = rg.bq; auto& w1r = rg.w1r; const float b1r = rg.b1r; auto& w2r = rg.w2r; auto& b2r = rg.b2r;
+  float* gs = sm.gs; float* es = sm.es; float* hs = sm.hs; float* lg = sm.lg; float* z = sm.z; float* lo = sm.lo;
   for (int c = tid; c < C; c += 256) {
     float s = 0.f;
     const T* fp = feat + (size_t)b * HW * C + c;
-    for (int p0 = 0; p0 < HW; p0 += 16) {
-      float v[16];
+    for (int p0 = 0; p0 < HW; p0 += 32) {                     // 32 pixel loads in flight (the shipped 4x8 map in one trip), added in pixel order
+      float v[32];
 #pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = ldf(fp, (size_t)(p0 + u < HW ? p0 + u : 0) * C);
+      for (int u = 0; u < 32; ++u) v[u] = ldf(fp, (size_t)(p0 + u < HW ? p0 + u : 0) * C);
 #pragma unroll
-      for (int u = 0; u < 16; ++u) s += p0 + u < HW ? v[u] : 0.f;
+      for (int u = 0; u < 32; ++u) s += p0 + u < HW ? v[u] : 0.f;
     }
     s *= inv_hw;
     gs[c] = s;
     gap_out[(size_t)b * C + c] = s;
   }
-  lds_fill<4>(es, K, [&](int i) { return ef[(size_t)b * K + i]; });
+  if (FAST) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { const int i = tid + 256 * u; if (i < K) es[i] = rg.efr[u]; }
+  } else {
+    lds_fill<4>(es, K, [&](int i) { return ef[(size_t)b * K + i]; });
+  }
   __syncthreads();
   if (FAST) {
 #pragma unroll
@@ -497,21 +530,35 @@ __global__ __launch_bounds__(256) void k_mm_head_fwd(const T* __restrict__ feat,
   if (tid < N) logp[(size_t)b * N + tid] = lg[tid];
 }
 
+template <typename T, bool FAST>
+__global__ __launch_bounds__(256) void k_mm_head_fwd(const T* __restrict__ feat, const float* __restrict__ ef, const float* __restrict__ fcw,
+    const float* __restrict__ fcb, const float* __restrict__ dw_, const float* __restrict__ db_, const float* __restrict__ w1,
+    const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ gap_out,
+    float* __restrict__ s_logp, float* __restrict__ e_logp, float* __restrict__ hidden, float* __restrict__ logp, int HW, int C, int K, int N, int Hd) {
+  __shared__ MmhFwdLds sm;
+  MmhFwdRegs<FAST> rg;
+  mmh_fwd_load<FAST>(rg, ef, fcw, fcb, dw_, db_, w1, b1, w2, b2, C, K, N, Hd);
+  mmh_fwd_body<T, FAST>(rg, sm, feat, ef, fcw, fcb, dw_, db_, w1, b1, w2, b2, gap_out, s_logp, e_logp, hidden, logp, HW, C, K, N, Hd);
+}
+
 // backward 1: per sample, gradients w.r.t. the two feature inputs; the per-sample logit / pre-activation gradients go to
 // the workspace ([B][N] dl2 | [B][Hd] dpre | [B][N] dle | [B][N] dls) for the parameter-gradient kernel
-template <typename T>
-__global__ __launch_bounds__(256) void k_mm_head_bwd_in(const float* __restrict__ dlogp, const float* __restrict__ logp, const float* __restrict__ hidden,
-    const float* __restrict__ s_logp, const float* __restrict__ e_logp, const float* __restrict__ fcw, const float* __restrict__ dw_,
-    const float* __restrict__ w1, const float* __restrict__ w2, T* __restrict__ dfeat, float* __restrict__ def, float* __restrict__ ws,
-    int B, int HW, int C, int K, int N, int Hd) {
-  __shared__ float w1s[MMH_MAXHD * 2 * HEAD_MAX_N / 4];      // Hd * 2N <= 4096 floats (checked by the launcher)
-  __shared__ float dl2[HEAD_MAX_N], dpre[MMH_MAXHD], dz[2 * HEAD_MAX_N], dbr[2 * HEAD_MAX_N];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  // everything this thread will read from global memory is requested up front (one round trip for the whole kernel)
-  constexpr int PN = 8, PK = 4;                               // register prefetch covers N <= 8, K <= 1024, C <= 256, Hd <= 256
-  const bool pre = N <= PN && K <= 256 * PK && C <= 256 && Hd <= 256;
-  float w2c[PN], hid = 0.f, fcc[PN], dwc[PK][PN];
-  if (pre) {
+constexpr int MMH_PN = 8, MMH_PK = 4;                         // register prefetch covers N <= 8, K <= 1024, C <= 256, Hd <= 256
+struct MmhBwdRegs { float w2c[MMH_PN], fcc[MMH_PN], dwc[MMH_PK][MMH_PN], w1v[8]; };
+struct MmhBwdLds {
+  float w1s[MMH_MAXHD * 2 * HEAD_MAX_N / 4];                  // Hd * 2N <= 4096 floats (checked by the launcher)
+  float dl2[HEAD_MAX_N], dpre[MMH_MAXHD], dz[2 * HEAD_MAX_N], dbr[2 * HEAD_MAX_N];
+};
+__device__ __forceinline__ bool mmh_bwd_pre(int C, int K, int N, int Hd) { return N <= MMH_PN && K <= 256 * MMH_PK && C <= 256 && Hd <= 256; }
+
+// everything this thread will read from global memory is requested up front (one round trip for the whole kernel); `hidden`, which
+// the fused kernel still holds in LDS, is the caller's
+__device__ __forceinline__ void mmh_bwd_load(MmhBwdRegs& rg, const float* __restrict__ fcw, const float* __restrict__ dw_,
+    const float* __restrict__ w1, const float* __restrict__ w2, int C, int K, int N, int Hd) {
+  constexpr int PN = MMH_PN, PK = MMH_PK;
+  const int tid = threadIdx.x;
+  auto& w2c = rg.w2c; auto& fcc = rg.fcc; auto& dwc = rg.dwc;
+  if (mmh_bwd_pre(C, K, N, Hd)) {
 #pragma unroll
     for (int n = 0; n < PN; ++n) {                              // clamped indices + selects: no branch per load
       const int nc = n < N ? n : 0;
@@ -520,10 +567,32 @@ __global__ __launch_bounds__(256) void k_mm_head_bwd_in(const float* __restrict_
 #pragma unroll
       for (int u = 0; u < PK; ++u) { const int k = tid + 256 * u; dwc[u][n] = dw_[(size_t)nc * K + (k < K ? k : 0)]; }
     }
-    hid = hidden[(size_t)b * Hd + (tid < Hd ? tid : 0)];
   }
-  lds_fill<8>(w1s, Hd * 2 * N, [&](int i) { return w1[i]; });
-  if (tid == 0) bx_lsm_bwd(dlogp + (size_t)b * N, logp + (size_t)b * N, N, dl2);
+  const int n1 = Hd * 2 * N;                                    // fc1's weights go to LDS: the first 8 per thread wait in registers
+#pragma unroll
+  for (int u = 0; u < 8; ++u) { const int i = tid + 256 * u; rg.w1v[u] = w1[i < n1 ? i : n1 - 1]; }
+}
+// second step of fc1's weights to LDS: stores the eight values mmh_bwd_load left in registers (and loads what lies beyond them).
+// An LDS store waits for every global load requested before it, so the fused kernel calls this behind the forward body.
+__device__ __forceinline__ void mmh_bwd_w1_store(const MmhBwdRegs& rg, MmhBwdLds& sm, const float* __restrict__ w1, int N, int Hd) {
+  const int n1 = Hd * 2 * N, tid = threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) { const int i = tid + 256 * u; if (i < n1) sm.w1s[i] = rg.w1v[u]; }
+  if (n1 > 2048) lds_fill<8>(sm.w1s + 2048, n1 - 2048, [&](int i) { return w1[2048 + i]; });
+}
+
+// dlogp / logp / hidden / s_logp / e_logp: this sample's rows, in global memory or LDS; hid: hidden[tid] on the prefetch path
+template <typename T>
+__device__ __forceinline__ void mmh_bwd_body(const MmhBwdRegs& rg, MmhBwdLds& sm, float hid, const float* dlogp, const float* logp,
+    const float* hidden, const float* s_logp, const float* e_logp, const float* __restrict__ fcw, const float* __restrict__ dw_,
+    const float* __restrict__ w2, T* __restrict__ dfeat, float* __restrict__ def, float* __restrict__ ws,
+    int B, int HW, int C, int K, int N, int Hd) {
+  constexpr int PN = MMH_PN, PK = MMH_PK;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const bool pre = mmh_bwd_pre(C, K, N, Hd);
+  auto& w2c = rg.w2c; auto& fcc = rg.fcc; auto& dwc = rg.dwc;
+  float* w1s = sm.w1s; float* dl2 = sm.dl2; float* dpre = sm.dpre; float* dz = sm.dz; float* dbr = sm.dbr;
+  if (tid < N) dl2[tid] = bx_lsm_bwd_at(dlogp, logp, N, tid);     // one thread per class: bx_lsm_bwd's row in the time of one entry
   __syncthreads();
   float* ws_dl2 = ws; float* ws_dpre = ws + (size_t)B * N; float* ws_dle = ws_dpre + (size_t)B * Hd; float* ws_dls = ws_dle + (size_t)B * N;
   if (tid < N) ws_dl2[(size_t)b * N + tid] = dl2[tid];
@@ -544,7 +613,7 @@ __global__ __launch_bounds__(256) void k_mm_head_bwd_in(const float* __restrict_
       float s = 0.f;
 #pragma unroll
       for (int n = 0; n < HEAD_MAX_N; ++n) if (n < N) s = fmaf(dl2[n], wv[n], s);
-      s = hidden[(size_t)b * Hd + j] > 0.f ? s : 0.f;
+      s = hidden[j] > 0.f ? s : 0.f;
       dpre[j] = s;
       ws_dpre[(size_t)b * Hd + j] = s;
     }
@@ -556,9 +625,9 @@ __global__ __launch_bounds__(256) void k_mm_head_bwd_in(const float* __restrict_
     dz[tid] = s;
   }
   __syncthreads();
-  if (tid < 2) {                                               // log-softmax backward of the two branch outputs
-    const float* lp = (tid == 0 ? e_logp : s_logp) + (size_t)b * N;
-    bx_lsm_bwd(dz + tid * N, lp, N, dbr + tid * N);
+  if (tid < 2 * N) {                                           // log-softmax backward of the two branch outputs, one thread per entry
+    const bool eeg = tid < N;
+    dbr[tid] = bx_lsm_bwd_at(dz + (eeg ? 0 : N), eeg ? e_logp : s_logp, N, eeg ? tid : tid - N);
   }
   __syncthreads();
   if (tid < 2 * N) (tid < N ? ws_dle : ws_dls)[(size_t)b * N + (tid < N ? tid : tid - N)] = dbr[tid];
@@ -607,10 +676,64 @@ __global__ __launch_bounds__(256) void k_mm_head_bwd_in(const float* __restrict_
   }
 }
 
-// backward 2: every parameter-gradient entry is a batch sum  sum_b A[b][m] * V[b][n]  (V = 1 for biases); one thread per entry
+template <typename T>
+__global__ __launch_bounds__(256) void k_mm_head_bwd_in(const float* __restrict__ dlogp, const float* __restrict__ logp, const float* __restrict__ hidden,
+    const float* __restrict__ s_logp, const float* __restrict__ e_logp, const float* __restrict__ fcw, const float* __restrict__ dw_,
+    const float* __restrict__ w1, const float* __restrict__ w2, T* __restrict__ dfeat, float* __restrict__ def, float* __restrict__ ws,
+    int B, int HW, int C, int K, int N, int Hd) {
+  __shared__ MmhBwdLds sm;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  MmhBwdRegs rg;
+  mmh_bwd_load(rg, fcw, dw_, w1, w2, C, K, N, Hd);
+  mmh_bwd_w1_store(rg, sm, w1, N, Hd);
+  const float hid = mmh_bwd_pre(C, K, N, Hd) ? hidden[(size_t)b * Hd + (tid < Hd ? tid : 0)] : 0.f;
+  mmh_bwd_body<T>(rg, sm, hid, dlogp + (size_t)b * N, logp + (size_t)b * N, hidden + (size_t)b * Hd, s_logp + (size_t)b * N,
+                  e_logp + (size_t)b * N, fcw, dw_, w2, dfeat, def, ws, B, HW, C, K, N, Hd);
+}
+
+// The training head: k_mm_head_fwd, the loss gradient dlogp = -target * inv_denom * gscale (k_kldiv's, which needs no forward value)
+// and k_mm_head_bwd_in as ONE chain per sample.  Both halves' global reads are requested before anything is waited for, and the
+// backward reads logp, hidden and the two branch outputs from the forward's LDS instead of from memory: the step's turn from forward
+// to backward costs one kernel's round trips, not three kernels'.  The loss VALUE is a sum over the batch and rides in the
+// parameter-gradient launch that follows (k_mm_head_bwd_w's extra workgroup).
+template <typename T, bool FAST>
+__global__ __launch_bounds__(256) void k_mm_head_train(const T* __restrict__ feat, const float* __restrict__ ef, const float* __restrict__ fcw,
+    const float* __restrict__ fcb, const float* __restrict__ dw_, const float* __restrict__ db_, const float* __restrict__ w1,
+    const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ target,
+    float* __restrict__ gap_out, float* __restrict__ s_logp, float* __restrict__ e_logp, float* __restrict__ hidden, float* __restrict__ logp,
+    float* __restrict__ dlogp, T* __restrict__ dfeat, float* __restrict__ def, float* __restrict__ ws, float inv_denom, float gscale,
+    int B, int HW, int C, int K, int N, int Hd) {
+  __shared__ MmhFwdLds fs;
+  __shared__ MmhBwdLds bs;
+  __shared__ float dlp[HEAD_MAX_N];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  MmhFwdRegs<FAST> fr;
+  MmhBwdRegs br;
+  mmh_fwd_load<FAST>(fr, ef, fcw, fcb, dw_, db_, w1, b1, w2, b2, C, K, N, Hd);
+  mmh_bwd_load(br, fcw, dw_, w1, w2, C, K, N, Hd);
+  const float t = target[(size_t)b * N + (tid < N ? tid : 0)];
+  mmh_fwd_body<T, FAST>(fr, fs, feat, ef, fcw, fcb, dw_, db_, w1, b1, w2, b2, gap_out, s_logp, e_logp, hidden, logp, HW, C, K, N, Hd);
+  if (tid < N) {
+    const float d = -t * inv_denom * gscale;
+    dlp[tid] = d;
+    if (dlogp) dlogp[(size_t)b * N + tid] = d;
+  }
+  mmh_bwd_w1_store(br, bs, w1, N, Hd);
+  __syncthreads();
+  const float hid = mmh_bwd_pre(C, K, N, Hd) ? fs.hs[tid < Hd ? tid : 0] : 0.f;
+  mmh_bwd_body<T>(br, bs, hid, dlp, fs.lg, fs.hs, fs.z + N, fs.z, fcw, dw_, w2, dfeat, def, ws, B, HW, C, K, N, Hd);
+}
+
+// backward 2: every parameter-gradient entry is a batch sum  sum_b A[b][m] * V[b][n]  (V = 1 for biases); one thread per entry.
+// With kl.loss set, workgroup kl.block (one past the entries) computes the KL-divergence loss of the whole batch instead.
 struct MmHeadSeg { const float* A; const float* V; const float* V2; float* out; int M, Nn, sa, sv, split; };   // V2: second half of a concatenated V
 struct MmHeadJobs { MmHeadSeg seg[8]; int start[9]; };
-__global__ __launch_bounds__(256) void k_mm_head_bwd_w(MmHeadJobs jobs, int B) {
+struct MmHeadLoss { const float* logp; const float* target; float* loss; int n, block; float inv_denom; };
+__global__ __launch_bounds__(256) void k_mm_head_bwd_w(MmHeadJobs jobs, int B, MmHeadLoss kl) {
+  if (kl.loss && (int)blockIdx.x == kl.block) {
+    kldiv_body(kl.logp, kl.target, kl.loss, nullptr, kl.n, kl.inv_denom, 0.f);
+    return;
+  }
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= jobs.start[8]) return;
   int si = 0;
@@ -642,6 +765,29 @@ static int mm_head_check(const char* who, int B, int HW, int C, int K, int N, in
              who, HEAD_MAX_N, MMH_MAXHD, MMH_MAXHD * 2 * HEAD_MAX_N / 4);
   return BX_OK;
 }
+static bool mm_head_fast(int C, int K, int N) { return 2 * N <= 12 && N <= 8 && K <= 1024 && C <= 1024; }
+// the parameter-gradient launch over the workspace of the input half; with kl.loss set, one more workgroup for the loss
+static int mm_head_launch_w(const char* who, const float* ws, const float* hidden, const float* spec_logp, const float* eeg_logp, const float* gap,
+                            const float* eeg_feat, float* d_fc_w, float* d_fc_b, float* d_dense_w, float* d_dense_b, float* dw1, float* db1,
+                            float* dw2, float* db2, MmHeadLoss kl, int B, int C, int K, int N, int Hd, hipStream_t s) {
+  const bool grads = d_fc_w || d_fc_b || d_dense_w || d_dense_b || dw1 || db1 || dw2 || db2;
+  if (!grads && !kl.loss) return BX_OK;
+  const float* dl2 = ws; const float* dpre = ws + (size_t)B * N; const float* dle = dpre + (size_t)B * Hd; const float* dls = dle + (size_t)B * N;
+  MmHeadJobs j;
+  const MmHeadSeg segs[8] = {
+      {dl2, hidden, nullptr, dw2, N, Hd, N, Hd, 0},            {dl2, nullptr, nullptr, db2, N, 1, N, 0, 0},
+      {dpre, eeg_logp, spec_logp, dw1, Hd, 2 * N, Hd, N, N},   {dpre, nullptr, nullptr, db1, Hd, 1, Hd, 0, 0},
+      {dle, eeg_feat, nullptr, d_dense_w, N, K, N, K, 0},      {dle, nullptr, nullptr, d_dense_b, N, 1, N, 0, 0},
+      {dls, gap, nullptr, d_fc_w, N, C, N, C, 0},              {dls, nullptr, nullptr, d_fc_b, N, 1, N, 0, 0}};
+  int acc = 0;
+  for (int q = 0; q < 8; ++q) { j.seg[q] = segs[q]; j.start[q] = acc; acc += segs[q].M * segs[q].Nn; }
+  j.start[8] = acc;
+  const int wblocks = grads ? bx_ceil_div(acc, 256) : 0;
+  kl.block = wblocks;
+  hipLaunchKernelGGL(k_mm_head_bwd_w, dim3(wblocks + (kl.loss ? 1 : 0)), dim3(256), 0, s, j, B, kl);
+  BX_CHECK_LAUNCH(who);
+  return BX_OK;
+}
 extern "C" int bx_mm_head_fwd(const void* feat, const float* eeg_feat, const float* fc_w, const float* fc_b, const float* dense_w,
                               const float* dense_b, const float* w1, const float* b1, const float* w2, const float* b2, float* gap_out,
                               float* spec_logp, float* eeg_logp, float* hidden, float* logp, int B, int HW, int C, int K, int N, int Hd,
@@ -651,7 +797,7 @@ extern "C" int bx_mm_head_fwd(const void* feat, const float* eeg_feat, const flo
   BX_DTYPE_OK(dtype);
   const int rc = mm_head_check("bx_mm_head_fwd", B, HW, C, K, N, Hd);
   if (rc) return rc;
-  const bool fast = 2 * N <= 12 && N <= 8 && K <= 1024 && C <= 1024;
+  const bool fast = mm_head_fast(C, K, N);
   BX_DISPATCH_DTYPE(dtype, T,
     if (fast) hipLaunchKernelGGL((k_mm_head_fwd<T, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const T*)feat, eeg_feat, fc_w, fc_b, dense_w,
                                  dense_b, w1, b1, w2, b2, gap_out, spec_logp, eeg_logp, hidden, logp, HW, C, K, N, Hd);
@@ -676,19 +822,36 @@ extern "C" int bx_mm_head_bwd(const float* dlogp, const float* logp, const float
     hipLaunchKernelGGL((k_mm_head_bwd_in<T>), dim3(B), dim3(256), 0, s, dlogp, logp, hidden, spec_logp, eeg_logp, fc_w, dense_w, w1, w2, (T*)dfeat,
                        d_eeg_feat, ws, B, HW, C, K, N, Hd));
   BX_CHECK_LAUNCH("bx_mm_head_bwd(inputs)");
-  if (d_fc_w || d_fc_b || d_dense_w || d_dense_b || dw1 || db1 || dw2 || db2) {
-    const float* dl2 = ws; const float* dpre = ws + (size_t)B * N; const float* dle = dpre + (size_t)B * Hd; const float* dls = dle + (size_t)B * N;
-    MmHeadJobs j;
-    const MmHeadSeg segs[8] = {
-        {dl2, hidden, nullptr, dw2, N, Hd, N, Hd, 0},            {dl2, nullptr, nullptr, db2, N, 1, N, 0, 0},
-        {dpre, eeg_logp, spec_logp, dw1, Hd, 2 * N, Hd, N, N},   {dpre, nullptr, nullptr, db1, Hd, 1, Hd, 0, 0},
-        {dle, eeg_feat, nullptr, d_dense_w, N, K, N, K, 0},      {dle, nullptr, nullptr, d_dense_b, N, 1, N, 0, 0},
-        {dls, gap, nullptr, d_fc_w, N, C, N, C, 0},              {dls, nullptr, nullptr, d_fc_b, N, 1, N, 0, 0}};
-    int acc = 0;
-    for (int q = 0; q < 8; ++q) { j.seg[q] = segs[q]; j.start[q] = acc; acc += segs[q].M * segs[q].Nn; }
-    j.start[8] = acc;
-    hipLaunchKernelGGL(k_mm_head_bwd_w, dim3(bx_ceil_div(acc, 256)), dim3(256), 0, s, j, B);
-    BX_CHECK_LAUNCH("bx_mm_head_bwd(weights)");
-  }
-  return BX_OK;
+  return mm_head_launch_w("bx_mm_head_bwd(weights)", ws, hidden, spec_logp, eeg_logp, gap, eeg_feat, d_fc_w, d_fc_b, d_dense_w, d_dense_b, dw1, db1,
+                          dw2, db2, MmHeadLoss{}, B, C, K, N, Hd, s);
+}
+extern "C" int bx_mm_head_train(const void* feat, const float* eeg_feat, const float* fc_w, const float* fc_b, const float* dense_w,
+                                const float* dense_b, const float* w1, const float* b1, const float* w2, const float* b2, const float* target,
+                                float* gap_out, float* spec_logp, float* eeg_logp, float* hidden, float* logp, float* loss, float* dlogp,
+                                void* dfeat, float* d_eeg_feat, float* d_fc_w, float* d_fc_b, float* d_dense_w, float* d_dense_b, float* dw1,
+                                float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes, int B, int HW, int C, int K, int N,
+                                int Hd, int reduction, float grad_scale, int dtype, bxStream stream) {
+  BX_REQUIRE(feat && eeg_feat && fc_w && fc_b && dense_w && dense_b && w1 && b1 && w2 && b2 && target && gap_out && spec_logp && eeg_logp &&
+             hidden && logp, "bx_mm_head_train: null pointer");
+  BX_DTYPE_OK(dtype);
+  BX_REQUIRE(reduction >= 0 && reduction <= 2, "bx_mm_head_train: reduction must be 0 (mean), 1 (batchmean) or 2 (sum)");
+  const int rc = mm_head_check("bx_mm_head_train", B, HW, C, K, N, Hd);
+  if (rc) return rc;
+  if (!workspace || workspace_bytes < bx_mm_head_workspace(B, N, Hd)) BX_FAIL(BX_EWORKSPACE, "bx_mm_head_train: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)workspace;
+  const float inv_denom = 1.f / kldiv_denom(reduction, B, N);
+  const bool fast = mm_head_fast(C, K, N);
+  BX_DISPATCH_DTYPE(dtype, T,
+    if (fast) hipLaunchKernelGGL((k_mm_head_train<T, true>), dim3(B), dim3(256), 0, s, (const T*)feat, eeg_feat, fc_w, fc_b, dense_w, dense_b, w1, b1,
+                                 w2, b2, target, gap_out, spec_logp, eeg_logp, hidden, logp, dlogp, (T*)dfeat, d_eeg_feat, ws, inv_denom,
+                                 grad_scale, B, HW, C, K, N, Hd);
+    else hipLaunchKernelGGL((k_mm_head_train<T, false>), dim3(B), dim3(256), 0, s, (const T*)feat, eeg_feat, fc_w, fc_b, dense_w, dense_b, w1, b1,
+                            w2, b2, target, gap_out, spec_logp, eeg_logp, hidden, logp, dlogp, (T*)dfeat, d_eeg_feat, ws, inv_denom,
+                            grad_scale, B, HW, C, K, N, Hd));
+  BX_CHECK_LAUNCH("bx_mm_head_train");
+  // same stream: logp and the workspace are complete when this launch runs
+  const MmHeadLoss kl = {logp, target, loss, B * N, 0, inv_denom};
+  return mm_head_launch_w("bx_mm_head_train(weights, loss)", ws, hidden, spec_logp, eeg_logp, gap_out, eeg_feat, d_fc_w, d_fc_b, d_dense_w,
+                          d_dense_b, dw1, db1, dw2, db2, kl, B, C, K, N, Hd, s);
 }

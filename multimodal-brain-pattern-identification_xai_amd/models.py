@@ -329,58 +329,69 @@ class MultimodalModel(nn.Module):
     def forward(self, eeg_data, spectrogram_data, cut=None):
         """``cut``: see Spectrogram_Model.features (build extension used by the overlapped data-parallel step; the reference's
         signature is the two positional inputs, XAI_Multimodality.py:1095)."""
-        if cut is not None:
-            if not self._fusable():
-                raise RuntimeError("brainxai MultimodalModel: cut= needs the un-hooked reference architecture (fused head path)")
-            em, sm = self.eeg_model, self.spectrogram_model
-            ss = se = packed = None
-            if self.training and em.dropout.p > 0 and any(getattr(sm, f"block{i}").dropout.p > 0 for i in range(1, 6)):
-                xi, ss, se = sm._pack_all(spectrogram_data, seed_pair=True)
-                packed = (xi,)
-            if eeg_data.is_cuda and ops.OVERLAP_EEG_DDP and ops.overlap_eeg_now():      # (opt-in; see the fused path below and ops.overlap_eeg_now)
-                cur, side = ops.fork_eeg(eeg_data.device, se, eeg_data)
-                with torch.cuda.stream(side):
-                    ef = em.features(eeg_data, seed=se)
-                sf = sm.features(spectrogram_data, seed=ss, cut=cut, packed=packed)
-                cur.wait_stream(side)
-                ef.record_stream(cur)
-            else:
-                ef = em.features(eeg_data, seed=se)
-                sf = sm.features(spectrogram_data, seed=ss, cut=cut, packed=packed)
-            return ops.MultimodalHeadFn.apply(sf.permute(0, 2, 3, 1), ef, sm.fc.weight, sm.fc.bias, em.dense.weight, em.dense.bias,
-                                              self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+        if cut is not None and not self._fusable():
+            raise RuntimeError("brainxai MultimodalModel: cut= needs the un-hooked reference architecture (fused head path)")
         if self._fusable():
             # one launch for GAP+fc, dense and the fusion head (same arithmetic as the three separate ops below)
-            em, sm = self.eeg_model, self.spectrogram_model
-            ss = se = packed = None
-            if self.training and em.dropout.p > 0 and any(getattr(sm, f"block{i}").dropout.p > 0 for i in range(1, 6)):
-                # both branches' dropout seeds ride in the weight-packing launch, which therefore opens the step
-                xi, ss, se = sm._pack_all(spectrogram_data, seed_pair=True)
-                packed = (xi,)
-            if eeg_data.is_cuda and ops.overlap_eeg_now():
-                # Round 3: the EEG branch (twenty small-grid, latency-bound launches, ~180 us of the step) runs on a side stream beside
-                # the spectrogram branch -- ONE fork after the packing launch (its seeds feed both branches) and one join in front of
-                # the head; autograd replays the branch's backward on the stream its forward ran on, so the backward overlaps the same
-                # way.  Inside a captured step these are two parallel chains of the graph.
-                cur, side = ops.fork_eeg(eeg_data.device, se, eeg_data)
-                with torch.cuda.stream(side):
-                    ef = em.features(eeg_data, seed=se)
-                sf = sm.features(spectrogram_data, seed=ss, packed=packed)
-                cur.wait_stream(side)
-                ef.record_stream(cur)
-            else:
-                ef = em.features(eeg_data, seed=se)
-                sf = sm.features(spectrogram_data, seed=ss, packed=packed)
-            if ef.shape[1] != em.dense.in_features:
-                raise RuntimeError(f"EEGNet: {ef.shape[1]} features but dense expects {em.dense.in_features} (Samples mismatch)")
-            return ops.MultimodalHeadFn.apply(sf.permute(0, 2, 3, 1), ef, sm.fc.weight, sm.fc.bias, em.dense.weight, em.dense.bias,
-                                              self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+            return ops.MultimodalHeadFn.apply(*self._head_args(eeg_data, spectrogram_data, cut))
         else:
             e = self.eeg_model(eeg_data)
             s = self.spectrogram_model(spectrogram_data)
         if e.shape[1] != s.shape[1]:
             raise RuntimeError("MultimodalModel: both branches must emit the same number of classes")
         return ops.FusionHeadFn.apply(e, s, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+
+    def forward_loss(self, eeg_data, spectrogram_data, target, criterion, cut=None):
+        """(loss, log-probabilities) of a training step: forward(), ``criterion`` and the head's backward in two launches
+        (ops.MultimodalTrainHeadFn) where ``criterion(self(eeg, spec), target)`` takes four.  ``loss.backward()`` then
+        starts at the block-5 map and the EEG features.  Only where can_forward_loss(criterion) holds.
+
+        Two things differ from ``criterion(self(eeg, spec), target)`` and are the caller's to know (can_forward_loss cannot see them):
+        * the head's eight parameter gradients are written by THIS call, not by ``backward()`` -- with FlatAdamW straight into the
+          optimizer's gradient arena.  The step forms call zero_grad -> forward_loss -> backward -> step; a second forward_loss
+          between ``backward()`` and ``optimizer.step()`` (a logging forward in training mode, say) would overwrite the head's
+          gradients of the step in flight: use ``self(eeg, spec)`` for such a forward.
+        * the returned log-probabilities are not part of the autograd graph (their gradient is already accounted for): a tensor
+          hook or ``retain_grad()`` on them never fires."""
+        if not self.can_forward_loss(criterion):
+            raise RuntimeError("brainxai MultimodalModel: forward_loss needs training mode, gradients, brainxai.KLDivLoss and the un-hooked fused head")
+        return ops.MultimodalTrainHeadFn.apply(*self._head_args(eeg_data, spectrogram_data, cut), target, criterion.reduction, 1.0)
+
+    def can_forward_loss(self, criterion) -> bool:
+        """The fused training head replaces the head's and the loss's own launches: not in evaluation, not without gradients, for no
+        other loss, and not where a hook on the head's modules or on the loss expects their forward() or backward() to run."""
+        if not (ops.HEAD_FUSED and self.training and torch.is_grad_enabled() and type(criterion) is KLDivLoss and self._fusable()):
+            return False
+        return not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks
+                       for m in (self, self.fc1, self.fc2, self.log_softmax, criterion))
+
+    def _head_args(self, eeg_data, spectrogram_data, cut=None):
+        """Both branches' features and the eight head parameters, in the argument order of ops.MultimodalHeadFn."""
+        em, sm = self.eeg_model, self.spectrogram_model
+        ss = se = packed = None
+        if self.training and em.dropout.p > 0 and any(getattr(sm, f"block{i}").dropout.p > 0 for i in range(1, 6)):
+            # both branches' dropout seeds ride in the weight-packing launch, which therefore opens the step
+            xi, ss, se = sm._pack_all(spectrogram_data, seed_pair=True)
+            packed = (xi,)
+        # the data-parallel cut form overlaps only by opt-in (ops.OVERLAP_EEG_DDP; see ops.overlap_eeg_now)
+        if eeg_data.is_cuda and (cut is None or ops.OVERLAP_EEG_DDP) and ops.overlap_eeg_now():
+            # Round 3: the EEG branch (twenty small-grid, latency-bound launches, ~180 us of the step) runs on a side stream beside
+            # the spectrogram branch -- ONE fork after the packing launch (its seeds feed both branches) and one join in front of
+            # the head; autograd replays the branch's backward on the stream its forward ran on, so the backward overlaps the same
+            # way.  Inside a captured step these are two parallel chains of the graph.
+            cur, side = ops.fork_eeg(eeg_data.device, se, eeg_data)
+            with torch.cuda.stream(side):
+                ef = em.features(eeg_data, seed=se)
+            sf = sm.features(spectrogram_data, seed=ss, cut=cut, packed=packed)
+            cur.wait_stream(side)
+            ef.record_stream(cur)
+        else:
+            ef = em.features(eeg_data, seed=se)
+            sf = sm.features(spectrogram_data, seed=ss, cut=cut, packed=packed)
+        if ef.shape[1] != em.dense.in_features:
+            raise RuntimeError(f"EEGNet: {ef.shape[1]} features but dense expects {em.dense.in_features} (Samples mismatch)")
+        return (sf.permute(0, 2, 3, 1), ef, sm.fc.weight, sm.fc.bias, em.dense.weight, em.dense.bias,
+                self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
 
     def _fusable(self) -> bool:
         """The fused head skips the branch modules' own forward(): only when nobody hooked them and the sizes fit its kernels."""

@@ -992,6 +992,72 @@ class KLDivFn(torch.autograd.Function):
         return out, None, None, None
 
 
+# The training step's head, loss and head backward as two launches instead of four (BX_HEAD_FUSED=0: the separate
+# MultimodalHeadFn + KLDivFn launches everywhere).  Same device functions, same bits (tests/test_gpu_head_train.py).
+HEAD_FUSED = _os.environ.get("BX_HEAD_FUSED", "1") == "1"
+
+
+class MultimodalTrainHeadFn(torch.autograd.Function):
+    """MultimodalHeadFn, KLDivFn and both their backwards in one native call (bx_mm_head_train): returns (loss, logp).
+    The gradients of the loss are complete when forward() returns -- the loss gradient -target / denom needs no forward
+    value -- and backward() hands them out; for an upstream gradient other than the cached unit_gradient it first scales
+    dlogp (bx_scale_dev, as KLDivFn does) and reruns the head's backward into the same buffers.
+    Because the kernels write the parameter gradients during forward() -- into the optimizer's arena slices where FlatAdamW
+    registered them (new_grad) -- a forward() between another step's backward() and its optimizer.step() overwrites that
+    step's head gradients, and logp is returned outside the graph (MultimodalModel.forward_loss says so to its callers)."""
+
+    @staticmethod
+    def forward(ctx, feat, efeat, fcw, fcb, dw, db, w1, b1, w2, b2, target, reduction, grad_scale):
+        B, H, W, Cc = feat.shape
+        K, N, Hd = efeat.shape[1], fcw.shape[0], w1.shape[0]
+        dev = feat.device
+        lib = L.load()
+        efeat = efeat.contiguous()
+        target_c = target.contiguous().float()
+        gap = torch.empty(B, Cc, dtype=torch.float32, device=dev)
+        slp, elp, logp, dlogp = (torch.empty(B, N, dtype=torch.float32, device=dev) for _ in range(4))
+        hidden = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        dfeat = torch.empty(B, H, W, Cc, dtype=feat.dtype, device=dev) if need[0] else None
+        defeat = torch.empty_like(efeat) if need[1] else None
+        gl = [new_grad(t) if nd else None for t, nd in zip((fcw, fcb, dw, db, w1, b1, w2, b2), need[2:10])]
+        ws = workspace(lib.bx_mm_head_workspace(B, N, Hd), dev)
+        L.check(lib.bx_mm_head_train(_p(feat), _p(efeat), _p(fcw), _p(fcb), _p(dw), _p(db), _p(w1), _p(b1), _p(w2), _p(b2), _p(target_c),
+                                     _p(gap), _p(slp), _p(elp), _p(hidden), _p(logp), _p(loss), _p(dlogp), _p(dfeat), _p(defeat),
+                                     *[_p(t) for t in gl], _p(ws), ws.numel(), B, H * W, Cc, K, N, Hd, _REDUCTIONS[reduction],
+                                     float(grad_scale), bx_dtype(feat.dtype), _stream()), "bx_mm_head_train")
+        ctx.shape, ctx.dt, ctx.grads = (B, H, W, Cc), feat.dtype, (dfeat, defeat, *gl)
+        ctx.save_for_backward(gap, slp, elp, hidden, logp, dlogp, efeat, fcw, dw, w1, w2)
+        ctx.mark_non_differentiable(logp)
+        ctx.set_materialize_grads(False)             # no zero-fill launch for logp's absent gradient
+        return loss, logp
+
+    @staticmethod
+    def backward(ctx, g, _dlogp):
+        if g is None:
+            return (None,) * 13
+        grads, ctx.grads = ctx.grads, None
+        if grads is None:
+            raise RuntimeError("brainxai: the fused training head's gradients were already handed out (a second backward)")
+        gap, slp, elp, hidden, logp, dlogp, efeat, fcw, dw, w1, w2 = ctx.saved_tensors
+        one = _ONES.get(gap.device.index if gap.device.index is not None else torch.cuda.current_device())
+        if one is None or g.data_ptr() != one.data_ptr():
+            # any other upstream gradient: KLDivFn's multiply, then the head's backward over the same buffers (what the separate
+            # launches compute for it, bit for bit)
+            B, H, W, Cc = ctx.shape
+            K, N, Hd = efeat.shape[1], fcw.shape[0], w1.shape[0]
+            lib = L.load()
+            g = g.contiguous()
+            scaled = torch.empty_like(dlogp)
+            L.check(lib.bx_scale_dev(_p(dlogp), _p(g), _p(scaled), dlogp.numel(), _stream()), "bx_scale_dev")
+            ws = workspace(lib.bx_mm_head_workspace(B, N, Hd), gap.device)
+            L.check(lib.bx_mm_head_bwd(_p(scaled), _p(logp), _p(hidden), _p(slp), _p(elp), _p(gap), _p(efeat), _p(fcw), _p(dw), _p(w1), _p(w2),
+                                       *[_p(t) for t in grads], _p(ws), ws.numel(), B, H * W, Cc, K, N, Hd, bx_dtype(ctx.dt), _stream()),
+                    "bx_mm_head_bwd")
+        return (*grads, None, None, None)
+
+
 def _eeg_forward(x, c1w, bn1w, bn1b, dww, bn2w, bn2b, sepw, bn3w, bn3b, bufs, cfg, needs_input_grad):
     """One bx_eeg_features_fwd launch (EegFeaturesFn.forward and eeg_features_keep): returns (x as read, feat, saved arena, desc,
     params, seed).  ``needs_input_grad``: autograd's flags for (x, the nine parameters)."""

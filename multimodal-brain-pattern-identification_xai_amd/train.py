@@ -330,6 +330,19 @@ def create_ddp_model(model, device_ids=None, output_device=None):
 
 
 # ------------------------------------------------------------------------------------------------
+def forward_and_loss(model, criterion, inputs, labels, cut=None):
+    """(outputs, loss) of one training forward.  A model with ``forward_loss`` (MultimodalModel) whose ``can_forward_loss(criterion)``
+    holds -- training mode, gradients on, brainxai.KLDivLoss, no hook on the head or the loss, BX_HEAD_FUSED not 0 -- computes head,
+    loss and the head's backward in one native call; anything else is ``criterion(model(*inputs), labels)``."""
+    kw = {} if cut is None else {"cut": cut}
+    can = getattr(model, "can_forward_loss", None)
+    if can is not None and len(inputs) == 2 and can(criterion):
+        loss, out = model.forward_loss(*inputs, labels, criterion, **kw)
+        return out, loss
+    out = model(*inputs, **kw)
+    return out, criterion(out, labels)
+
+
 def train_step_overlapped(model, optimizer, eeg, spec, labels, criterion, ddp, plan=None):
     """The data-parallel step with the gradient exchange overlapped with backward (DDP's bucketing, done with two buckets of the
     flat arena): autograd is cut after spectrogram stage 2; ``loss.backward()`` yields the gradients of stages 3-5, the heads
@@ -341,8 +354,7 @@ def train_step_overlapped(model, optimizer, eeg, spec, labels, criterion, ddp, p
     k, pidx, off = plan
     cut = _Cut()
     optimizer.zero_grad()
-    out = model(eeg, spec, cut=(k, cut))
-    loss = criterion(out, labels)
+    out, loss = forward_and_loss(model, criterion, (eeg, spec), labels, cut=(k, cut))
     loss.backward(ops.unit_gradient(loss.device) if loss.is_cuda and loss.dim() == 0 else None)
     optimizer.gather_grads(pidx, None)
     r1 = ddp.reduce_async(optimizer.flat_g.narrow(0, off, optimizer.n - off))
@@ -360,8 +372,7 @@ def train_step(model, optimizer, eeg, spec, labels, criterion, ddp=None):
     """zero_grad -> forward -> loss -> backward -> (all-reduce) -> step (reference NB:1597-1601).
     Returns (loss, outputs) as device tensors; nothing here synchronises with the host."""
     optimizer.zero_grad()
-    out = model(eeg, spec)
-    loss = criterion(out, labels)
+    out, loss = forward_and_loss(model, criterion, (eeg, spec), labels)
     loss.backward(ops.unit_gradient(loss.device) if loss.is_cuda and loss.dim() == 0 else None)
     if ddp is not None:
         ddp.sync_gradients(optimizer)
@@ -430,8 +441,7 @@ class GraphedTrainStep:
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1):
             self.opt.zero_grad()
-            out = self.model(*static_in, cut=(k, cut))
-            loss = self.crit(out, static_lab)
+            out, loss = forward_and_loss(self.model, self.crit, static_in, static_lab, cut=(k, cut))
             loss.backward(ops.unit_gradient(loss.device) if loss.is_cuda and loss.dim() == 0 else None)
             self.opt.gather_grads(pidx, None)
         with torch.cuda.graph(g2, pool=g1.pool()):          # always replayed right after g1: one memory pool
@@ -451,8 +461,7 @@ class GraphedTrainStep:
             if self.plan is not None and len(static_in) == 2:
                 k, pidx, off = self.plan
                 cut = _Cut()
-                out = self.model(*static_in, cut=(k, cut))
-                loss = self.crit(out, static_lab)
+                out, loss = forward_and_loss(self.model, self.crit, static_in, static_lab, cut=(k, cut))
                 loss.backward(ops.unit_gradient(loss.device) if loss.is_cuda and loss.dim() == 0 else None)
                 self.opt.gather_grads(pidx, None)
                 r1 = self.ddp.reduce_async(self.opt.flat_g.narrow(0, off, self.opt.n - off))
@@ -463,8 +472,7 @@ class GraphedTrainStep:
                     if r is not None:
                         r.wait()
             else:
-                out = self.model(*static_in)
-                loss = self.crit(out, static_lab)
+                out, loss = forward_and_loss(self.model, self.crit, static_in, static_lab)
                 loss.backward(ops.unit_gradient(loss.device) if loss.is_cuda and loss.dim() == 0 else None)
                 self.ddp.sync_gradients(self.opt)
             self.opt.step(gathered=True)
@@ -496,8 +504,7 @@ class GraphedTrainStep:
 
     def _eager(self, inputs, labels):
         self.opt.zero_grad()
-        out = self.model(*inputs)
-        loss = self.crit(out, labels)
+        out, loss = forward_and_loss(self.model, self.crit, inputs, labels)
         loss.backward(ops.unit_gradient(loss.device) if loss.is_cuda and loss.dim() == 0 else None)
         if self.ddp is not None:
             self._finish()
@@ -542,8 +549,7 @@ class GraphedTrainStep:
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         self.opt.zero_grad()
-                        out = self.model(*static_in)
-                        loss = self.crit(out, static_lab)
+                        out, loss = forward_and_loss(self.model, self.crit, static_in, static_lab)
                         loss.backward(ops.unit_gradient(loss.device) if loss.is_cuda and loss.dim() == 0 else None)
                         if self.ddp is None:
                             self.opt.step()
